@@ -8,7 +8,13 @@ scans already resident in HBM: voxelise → PFN → scatter+LN → Swin → pixe
 → Hungarian-matched loss → backward (gradient all-reduce overlapped for N > 1) → AdamW step.
 Rank 0 prints ONE JSON line (metric of BASELINE.json: LiDAR scans/s fwd+bwd, whole job).
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value`, `unit`, `n_gpus`, `steps`,
+`warmup`, `ms_per_step`, `higher_is_better`, `scaling`, `vs_baseline`, `dtype`, `data` and `config`.  Everything else
+the benchmark measures or checks (below) runs only with ``--full``; ``--detail-out`` and ``--aten-detail`` imply it.
+``--dump-outputs DIR`` writes what the timed step computed in its last step, right after the timed region
+(`dump_outputs`): the inputs and the initial parameters are seeded, so two builds can be compared output for output.
+
+Extra objects on the line of a ``--full`` run:
   roofline      roofline of the kernel of this repository that costs the most time per step (launches x average
                 duration): algorithmic bytes (HBM-bound) or flops (MFMA-bound) of one launch over its average launch
                 duration, measured live with HIP events on the stream the kernel is launched on.  K3's kernels and
@@ -77,7 +83,16 @@ def parse():
                          'default gpurun_out/bench_detail.json — the printed line carries the summary only')
     ap.add_argument('--switch', action='append', default=[], metavar='NAME=VALUE',
                     help='A/B runs: set a path selector of mask_bev_amd/switches.py (recorded in config.switches)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: the per-family roofline table '
+                         '(instrumented eager steps), the fp32 step, the CPU baseline, the data-parallel replica check '
+                         'and the full record behind --detail-out')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)')
+    args = ap.parse_args()
+    if args.detail_out or args.aten_detail:
+        args.full = True            # both files are records of the full run
+    return args
 
 
 def free_port() -> int:
@@ -508,6 +523,58 @@ def write_detail(full: dict, path=None):
         return None
 
 
+def collectives_schedule(last, world: int) -> dict:
+    """Host-side launch schedule of the last step: (mark, ms after the first graph replay was issued, MB reduced)."""
+    t0m = last[0][1]
+    total = sum(nb for _, _, nb in last)
+    return dict(
+        backend=os.environ.get('MBV_DIST_BACKEND', 'nccl'), world_size=world, bytes_per_step=total,
+        schedule=[dict(mark=name, ms=round((t - t0m) * 1e3, 3), mb=round(nb / 1e6, 2)) for name, t, nb in last],
+        note='host launch times: a piece is launched as soon as the host has issued the work that completes its '
+             'gradients; on the device it waits for that work through stream order (the comm stream waits for '
+             'the compute stream at launch)')
+
+
+def _flush_c_stdio(needed: bool) -> None:
+    """RCCL prints its version banner through C stdio, which is fully buffered on a pipe: push it out before the JSON
+    line, so that the line stays the LAST line of stdout."""
+    if not needed:
+        return
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+
+
+DUMP_SAMPLE = 1 << 22      # model-state values kept by `dump_outputs`: 16 MB of float32
+
+
+def dump_outputs(out_dir: str, model, loss) -> None:
+    """What a caller of the timed step holds after its last step — the loss the step returns and the model state its
+    AdamW update leaves — as float32 / float64 ``.npy`` files in `out_dir` (< 20 MB in all):
+
+      loss.npy          float32 (1,)   the loss of the last timed step
+      state_sums.npy    float64 (T, 2) sum and sum of |x| of every floating tensor of ``model.state_dict()``, in its order
+      state_sample.npy  float32 (S,)   the values at DUMP_SAMPLE fixed positions (seed 0, ascending) of those tensors
+                                       flattened and concatenated in the same order (all of them if there are fewer)
+
+    The inputs and the initial state are the same in every run with the same arguments, but the step is not bit-exact
+    from process to process (some gradients meet through f32 atomics): two runs of one build agree to a tolerance
+    (bench workload, 25 steps: the loss within ≈ 0.5 %), not bit for bit."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    state = [t.detach() for t in model.state_dict().values() if t.is_floating_point()]
+    np.save(os.path.join(out_dir, 'loss.npy'), np.asarray([float(loss.detach())], dtype=np.float32))
+    sums = torch.stack([torch.stack([t.double().sum(), t.double().abs().sum()]) for t in state])
+    np.save(os.path.join(out_dir, 'state_sums.npy'), sums.cpu().numpy().astype(np.float64))
+    flat = torch.cat([t.reshape(-1).float() for t in state])
+    if flat.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, 'state_sample.npy'), flat.cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
     from mask_bev_amd import switches
@@ -605,7 +672,7 @@ def main():
     if args.dry_run_collectives and graphed is not None:
         graphed.trace = []
     ops.TIMER.reset()
-    ops.TIMER.enabled = True
+    ops.TIMER.enabled = args.full           # the in-region events of the roofline table
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -623,6 +690,34 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)      # before anything else runs a step on the model
+    w = synthetic.WORKLOADS[args.workload]
+    nx = int((w['x_range'][1] - w['x_range'][0]) / w['voxel_size'])
+    ny = int((w['y_range'][1] - w['y_range'][0]) / w['voxel_size'])
+    k3_fused = bool(graphed is not None and getattr(graphed, '_k3_fused', False))
+    line = dict(
+        # BASELINE.json's metric on its own workload; the other BASELINE configs name their shape in the same form
+        metric=('LiDAR scans/sec fwd+bwd, 120k-pt 512x512 BEV 100q' if args.workload == 'semantic_kitti_512' else
+                f'LiDAR scans/sec fwd+bwd, {w["points"] // 1000}k-pt {ny}x{nx} BEV {w["num_queries"]}q'),
+        value=args.batch * world * args.steps / dt,
+        unit='scans/s', n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3,
+        higher_is_better=True, scaling='weak', vs_baseline=None, dtype=args.dtype, data='synthetic' if args.distribution == 'lidar' else 'synthetic (uniform x/y points)',
+        config=dict(workload=f'{args.workload}: {w["points"]} pts/scan, {ny}x{nx} BEV, {w["num_queries"]} queries',
+                    scans_per_gpu=args.batch, global_batch=args.batch * world, parallelism=f'dp{world}',
+                    step='fwd + Hungarian loss + bwd + AdamW; inputs device-resident', launch='eager' if args.no_graph else 'hip-graph', tuned_gemm_table=tuned, grad_wire=(args.grad_wire if (world > 1 or force) else None),
+                    forced_reducer=True if force else None, replica_param_checksum_spread=None,
+                    final_loss=final_loss, k3_adam_fused=k3_fused or None,
+                    switches={k: v for k, v in switches._values.items() if v != switches.defaults()[k]}))
+    if not args.full:
+        if rank == 0:
+            if args.dry_run_collectives and graphed is not None and graphed.trace:
+                line['collectives'] = collectives_schedule(graphed.trace[-1], world)
+            _flush_c_stdio(world > 1 or force)
+            print(json.dumps(_short(line)), flush=True)
+        if world > 1 or force:
+            dist.destroy_process_group()
+        return
     profile = {}
     if world == 1 and not args.no_kernel_profile:
         profile = kernel_profile(model, opt, pool[0], detail_file=args.aten_detail)
@@ -643,9 +738,6 @@ def main():
         replica_spread = float((hi - lo).item())
 
     if rank == 0:
-        w = synthetic.WORKLOADS[args.workload]
-        nx = int((w['x_range'][1] - w['x_range'][0]) / w['voxel_size'])
-        ny = int((w['y_range'][1] - w['y_range'][0]) / w['voxel_size'])
         c = kw['encoder_feat_channels'][-1]
         times = ops.TIMER.summary_ms()
         # algorithmic HBM bytes per launch: fwd reads weight+bias once per batch and writes the
@@ -660,7 +752,6 @@ def main():
         # parameter it reads param + 2 moments and writes them + the 16-bit shadow (26 B) instead of the gradient round
         # trip; the optimizer pass proper covers the other parameters, in however many launches it took (the family's
         # bytes PER LAUNCH = the pass's bytes / launches per step)
-        k3_fused = bool(graphed is not None and getattr(graphed, '_k3_fused', False))
         adam_launches = max(1.0, len(times.get('k_adamw') or []) / max(1, args.steps))
         adam_params = n_params - (2 * c * cells if k3_fused else 0)
         algo = {'k_ln_apply': 2 * c * cells * 4.0 + args.batch * c * cells * io,
@@ -704,19 +795,8 @@ def main():
                              frac_mfma=0.97 * sps / 2500.0, bytes_per_scan=bytes_scan,
                              achieved_gbs=bytes_scan * sps / 1e9, hbm_peak_gbs=8000.0,
                              frac_hbm=bytes_scan * sps / 1e9 / 8000.0)
-        line = dict(
-            # BASELINE.json's metric on its own workload; the other BASELINE configs name their shape in the same form
-            metric=('LiDAR scans/sec fwd+bwd, 120k-pt 512x512 BEV 100q' if args.workload == 'semantic_kitti_512' else
-                    f'LiDAR scans/sec fwd+bwd, {w["points"] // 1000}k-pt {ny}x{nx} BEV {w["num_queries"]}q'),
-            value=args.batch * world * args.steps / dt,
-            unit='scans/s', n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3,
-            higher_is_better=True, scaling='weak', vs_baseline=None, dtype=args.dtype, data='synthetic' if args.distribution == 'lidar' else 'synthetic (uniform x/y points)',
-            config=dict(workload=f'{args.workload}: {w["points"]} pts/scan, {ny}x{nx} BEV, {w["num_queries"]} queries',
-                        scans_per_gpu=args.batch, global_batch=args.batch * world, parallelism=f'dp{world}',
-                        step='fwd + Hungarian loss + bwd + AdamW; inputs device-resident', launch='eager' if args.no_graph else 'hip-graph', tuned_gemm_table=tuned, grad_wire=(args.grad_wire if (world > 1 or force) else None),
-                        forced_reducer=True if force else None, replica_param_checksum_spread=replica_spread,
-                        final_loss=final_loss, k3_adam_fused=k3_fused or None,
-                        switches={k: v for k, v in switches._values.items() if v != switches.defaults()[k]}),
+        line['config']['replica_param_checksum_spread'] = replica_spread
+        line.update(
             roofline=dominant, roofline_all=ranked, roofline_traffic_source=traffic_file if traffic else None,
             # share of the step the table prices: sum of the families' time per step over the measured step time
             roofline_coverage=sum(r['total_ms_per_step'] for r in ranked) / (dt / args.steps * 1e3) if ranked else None,
@@ -724,16 +804,7 @@ def main():
         if fp32_line is not None:
             line['fp32'] = fp32_line
         if args.dry_run_collectives and graphed is not None and graphed.trace:
-            # host-side launch schedule of the last step: (mark, ms after the first graph replay was issued, MB reduced)
-            last = graphed.trace[-1]
-            t0m = last[0][1]
-            total = sum(nb for _, _, nb in last)
-            line['collectives'] = dict(
-                backend=os.environ.get('MBV_DIST_BACKEND', 'nccl'), world_size=world, bytes_per_step=total,
-                schedule=[dict(mark=name, ms=round((t - t0m) * 1e3, 3), mb=round(nb / 1e6, 2)) for name, t, nb in last],
-                note='host launch times: a piece is launched as soon as the host has issued the work that completes its '
-                     'gradients; on the device it waits for that work through stream order (the comm stream waits for '
-                     'the compute stream at launch)')
+            line['collectives'] = collectives_schedule(graphed.trace[-1], world)
         if not args.no_cpu_baseline and world == 1:
             try:
                 line['cpu_baseline'] = cpu_baseline(args.workload, model, args.cpu_baseline_budget_s)
@@ -741,14 +812,7 @@ def main():
                 line['cpu_baseline'] = dict(value=None, unit='scans/s', cores=os.cpu_count(), kind='port',
                                             sample=f'failed: {type(e).__name__}: {e}')
         detail_path = write_detail(line, args.detail_out)
-        if world > 1 or force:
-            # RCCL prints its version banner through C stdio, which is fully buffered on a pipe: push it out now so that
-            # the JSON line stays the LAST line of stdout
-            try:
-                import ctypes
-                ctypes.CDLL(None).fflush(None)
-            except Exception:
-                pass
+        _flush_c_stdio(world > 1 or force)
         print(json.dumps(compact_line(line, detail_path)), flush=True)
     if world > 1 or force:
         dist.destroy_process_group()

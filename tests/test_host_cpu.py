@@ -478,6 +478,45 @@ def test_bench_line_fits_the_drivers_tail_and_keeps_the_contract():
     assert line['roofline']['frac'] > 0 and line['cpu_baseline']['value'] > 0
 
 
+def test_bench_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is the plain run (headline only); the roofline table, the fp32 step and
+    the CPU baseline need `--full`, which the two options that write records of the full run imply."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    args = bench.parse()
+    assert (args.gpus, args.steps, args.warmup, args.full, args.dump_outputs) == (1, 7, 2, False, None)
+    for extra in (['--full'], ['--detail-out', 'd.json'], ['--aten-detail', 'a.json']):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '7'] + extra)
+        assert bench.parse().full, extra
+
+
+def test_bench_dump_outputs_is_seeded_float_and_bounded(tmp_path):
+    """`bench.dump_outputs`: float32 / float64 .npy files, < 64 MB in all, the same positions sampled on every call."""
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(1000, 5000), torch.nn.BatchNorm1d(5000))      # 5 M values > the sample
+    loss = torch.tensor(1.5)
+    bench.dump_outputs(str(tmp_path / 'a'), model, loss)
+    bench.dump_outputs(str(tmp_path / 'b'), model, loss)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['loss.npy', 'state_sample.npy', 'state_sums.npy']
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += os.path.getsize(tmp_path / 'a' / n)
+    assert total < 64 << 20
+    assert np.load(tmp_path / 'a' / 'loss.npy').tolist() == [1.5]
+    sample = np.load(tmp_path / 'a' / 'state_sample.npy')
+    assert sample.shape == (bench.DUMP_SAMPLE,)
+    flat = torch.cat([t.reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()]).numpy()
+    assert np.isin(sample, flat).all()
+    sums = np.load(tmp_path / 'a' / 'state_sums.npy')
+    assert sums.shape == (6, 2) and np.allclose(sums[0], [model[0].weight.double().sum().item(),
+                                                          model[0].weight.double().abs().sum().item()])
+
+
 def test_level_inputs_node_equals_the_plain_ops():
     """ops.level_inputs (one autograd node for flatten + level-embedding add + positional add + casts,
     mask2former_head.py:518-527) against the four plain ops, values and gradients (CPU: the non-arena branch)."""
