@@ -1114,6 +1114,35 @@ int mbv_gemm32s_nn_act(const float* g, const float* w, float* out, const float* 
                        int64_t m, int64_t n, int64_t k, int64_t ldg, int64_t ldw, int64_t ldo, int64_t ldpre,
                        const uint32_t* amax_g, const uint32_t* amax_w, uint32_t* amax_out, int32_t act, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K21 — instances of one decoder output at inference (csrc/instances.hip).
+ * Replaces the host loops `c = cls.argmax(); if c > 0: sigmoid(F.interpolate(mask, (ny, nx), 'bilinear',
+ * align_corners=False)) > 0.5` of mask_bev/evaluation/kitti_eval.py:27-44 and mask_bev/mask_bev_module.py:286-294, with no
+ * (B, Q, ny, nx) intermediate.  Class convention: index 0 = empty, > 0 = object.
+ *
+ * mbv_select_queries: cls (rows, classes) in f32 / bf16 / fp16 (cls_dtype: MBV_DT_*), classes <= 256.  Per row, in f32:
+ *   label = first argmax (torch's tie rule), score = softmax(cls)[label] (max-subtracted),
+ *   keep = label > 0 && score >= score_threshold.  label (rows) i32, score (rows) f32, keep (rows) u8 {0, 1}.
+ *
+ * mbv_extract_masks: logits (batch, num_queries, h, w) f32, score / keep (batch * num_queries) as above; BEV grid H x W with
+ *   H*W <= 1024*1024.  Every pixel is interpolated with upsample_bilinear2d's align_corners=False arithmetic (as K15);
+ *   a pixel is SET when v > 0 (sigmoid(v) > 0.5).  Outputs, each may be NULL:
+ *   masks_packed (batch * num_queries, mbv_packed_mask_words(H, W)) u32: every map, mbv_pack_binary_masks layout;
+ *   areas (batch, num_queries) i32: set pixels;  mask_scores (batch, num_queries) f32: mean of sigmoid(v) over the set
+ *   pixels, 0 for an empty mask;  instance_map (batch, H, W) i32: the kept query with a set bit maximising
+ *   score[q] * sigmoid(v_q), ties to the smaller q, -1 where there is none.
+ *   areas / mask_scores need `workspace` (mbv_extract_masks_workspace_bytes; per-tile partial sums, reduced in a second
+ *   launch in a fixed order: deterministic).  No memset, no atomics on floats: every output element is written by a kernel.
+ *   batch * num_queries == 0 returns MBV_OK before any pointer is checked (with batch > 0 and num_queries == 0 a non-NULL
+ *   instance_map is filled with -1); MBV_ERR_UNSUPPORTED when a tile's logit rows
+ *   exceed 64 KB of LDS (w > 8192). */
+int mbv_select_queries(const void* cls, int32_t cls_dtype, int64_t rows, int32_t classes, float score_threshold,
+                       int32_t* label, float* score, uint8_t* keep, void* stream);
+size_t mbv_extract_masks_workspace_bytes(int32_t batch, int32_t num_queries, int32_t h, int32_t w, int32_t H, int32_t W);
+int mbv_extract_masks(const float* logits, const float* score, const uint8_t* keep, int32_t batch, int32_t num_queries,
+                      int32_t h, int32_t w, int32_t H, int32_t W, uint32_t* masks_packed, int32_t* areas,
+                      float* mask_scores, int32_t* instance_map, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ from typing import Dict, List, Tuple
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libmaskbev_hip.so')
 
-ABI_VERSION = 58
+ABI_VERSION = 59
 
 
 class MaskBevHipError(RuntimeError):
@@ -183,6 +183,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_patch_embed32_bwd_weight': (ctypes.c_int, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, c_size_t, _P]),
     'mbv_gemm32s_tn_acc': (ctypes.c_int, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, c_size_t, _P]),
     'mbv_gemm16_tn_group': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, c_size_t, _P]),
+    'mbv_select_queries': (ctypes.c_int, [_P, _I, _L, _I, _F, _P, _P, _P, _P]),
+    'mbv_extract_masks_workspace_bytes': (c_size_t, [_I, _I, _I, _I, _I, _I]),
+    'mbv_extract_masks': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

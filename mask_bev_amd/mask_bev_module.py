@@ -295,6 +295,18 @@ class MaskBevModule(_Base):
     def validation_step(self, val_batch, batch_idx):
         return self._step(val_batch, batch_idx, 'val')
 
+    # ------------------------------------------------------------------ inference (build extension, predict.py)
+    def predict(self, scans, score_threshold: float = 0.0):
+        """Instances of a list of device scans: eager forward in eval mode under no_grad (the previous mode is restored),
+        then K21 on the last decoder output → :class:`~mask_bev_amd.predict.Predictions`."""
+        from .predict import predict
+        return predict(self, scans, score_threshold)
+
+    def predict_step(self, batch, batch_idx=0):
+        """Lightning's name: ``batch`` is a list of scans or a ``(scans, targets[, metadata])`` batch."""
+        scans = batch[0] if isinstance(batch, tuple) and len(batch) in (2, 3) and not torch.is_tensor(batch[0]) else batch
+        return self.predict(scans)
+
     def enable_metrics(self, layers=(9,), train: bool = True, val: bool = True, mask_map: bool = False):
         """Build extension: attach the GPU-native classification / mIoU metrics (mask_bev_amd/metrics.py) to the
         given decoder layers, in the reference's ``{layer: (cls_metric, map_metric, miou_metric)}`` layout

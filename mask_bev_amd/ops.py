@@ -13,6 +13,7 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_msda       K5 / K16 multi-scale deformable attention
     ops_norm       K12 add + LayerNorm, bias + activation, K18 GroupNorm, patch merging
     ops_loss       K8 point sampling, K9 Hungarian, K10 importance sampling, K13 loss rows / costs
+    ops_instances  K21 query selection + BEV mask / instance-map extraction at inference
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403
@@ -22,3 +23,4 @@ from .ops_attention import *       # noqa: F401,F403
 from .ops_msda import *            # noqa: F401,F403
 from .ops_norm import *            # noqa: F401,F403
 from .ops_loss import *            # noqa: F401,F403
+from .ops_instances import *       # noqa: F401,F403

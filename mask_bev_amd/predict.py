@@ -1,0 +1,205 @@
+"""Inference: scans → instances, eager or replayed from a HIP graph.
+
+The head's last decoder output — class logits (B, Q, K+1) and mask logits (B, Q, ny/4, nx/4) — is turned into instances
+on the device by K21 (csrc/instances.hip, ops_instances.py): query selection (first argmax, softmax score, keep =
+label > 0 and score >= threshold; SURVEY.md §8a: class 0 = empty) and the BEV masks at the encoder's (ny, nx) grid,
+interpolated on the fly with upsample_bilinear2d's align_corners=False arithmetic (set where the logit is > 0, i.e.
+sigmoid > 0.5), bit-packed, with areas, mask scores and a per-pixel instance map.  No (B, Q, ny, nx) tensor is made.
+
+:class:`GraphedPredictStep` runs the encoder eagerly (pillar counts are dynamic) into a static input buffer — the same
+hand-off as :class:`~mask_bev_amd.graph.GraphedTrainStep` — and replays backbone + head + K21 as one captured graph.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, fields
+from typing import List, Optional, Tuple
+
+import torch
+
+from . import ops
+from ._lib import MaskBevHipError
+
+
+def unpack_bits(words: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """Bit-packed maps (N, words) int32 in the mbv_pack_binary_masks layout (pixel y*w + x at bit (y*w + x) % 32 of word
+    (y*w + x) // 32) → (N, h, w) bool, on the words' device."""
+    n = words.shape[0]
+    shifts = torch.arange(32, dtype=torch.int32, device=words.device)
+    bits = (words.to(torch.int32).unsqueeze(-1) >> shifts) & 1
+    return bits.reshape(n, -1)[:, :h * w].reshape(n, h, w).bool()
+
+
+@dataclass
+class Predictions:
+    """K21's outputs for a batch of B scans and Q queries, on the device (or on the host after :meth:`cpu`).
+
+    labels (B, Q) int32 — first argmax of the class logits (0 = empty);  scores (B, Q) f32 — softmax probability of that
+    label;  keep (B, Q) bool — label > 0 and score >= the threshold;  masks — :class:`ops.PackedMasks` of the B*Q maps at
+    (H, W) (row b*Q + q), or None;  areas (B, Q) int32 — set pixels;  mask_scores (B, Q) f32 — mean sigmoid over the set
+    pixels (0 for an empty mask);  instance_map (B, H, W) int32 — per pixel the kept query with a set bit maximising
+    score * sigmoid, -1 for none (or None)."""
+    labels: torch.Tensor
+    scores: torch.Tensor
+    keep: torch.Tensor
+    masks: Optional[ops.PackedMasks]
+    areas: Optional[torch.Tensor]
+    mask_scores: Optional[torch.Tensor]
+    instance_map: Optional[torch.Tensor]
+    grid_hw: Tuple[int, int]
+
+    def _map(self, fn) -> 'Predictions':
+        vals = {}
+        for f in fields(self):
+            v = getattr(self, f.name)
+            if isinstance(v, ops.PackedMasks):
+                v = ops.PackedMasks(fn(v.words), v.h, v.w)
+            elif torch.is_tensor(v):
+                v = fn(v)
+            vals[f.name] = v
+        return Predictions(**vals)
+
+    def clone(self) -> 'Predictions':
+        """A copy that the next replay of a :class:`GraphedPredictStep` does not overwrite."""
+        return self._map(lambda t: t.clone())
+
+    def cpu(self) -> 'Predictions':
+        return self._map(lambda t: t.cpu())
+
+    def instances(self, b: int) -> List[dict]:
+        """The kept queries of scan ``b`` in query order: ``{'query', 'label', 'score', 'mask_score', 'area', 'mask'}``,
+        ``mask`` the dense (H, W) bool map unpacked on demand (None without masks).  Synchronises with the device."""
+        q = self.labels.shape[1]
+        idx = torch.nonzero(self.keep[b]).flatten().tolist()
+        rows = torch.tensor([b * q + i for i in idx], dtype=torch.long, device=self.labels.device)
+        dense = (unpack_bits(self.masks.words.index_select(0, rows.to(self.masks.words.device)), self.masks.h, self.masks.w)
+                 if self.masks is not None and idx else None)
+        labels, scores = self.labels[b].tolist(), self.scores[b].tolist()
+        areas = self.areas[b].tolist() if self.areas is not None else None
+        ms = self.mask_scores[b].tolist() if self.mask_scores is not None else None
+        out = []
+        for j, i in enumerate(idx):
+            out.append(dict(query=i, label=labels[i], score=scores[i], mask_score=None if ms is None else ms[i],
+                            area=None if areas is None else areas[i], mask=None if dense is None else dense[j]))
+        return out
+
+
+def extract_instances(cls: torch.Tensor, mask_logits: torch.Tensor, grid_hw, score_threshold: float = 0.0,
+                      masks: bool = True, instance_map: bool = True) -> Predictions:
+    """K21a + K21b on one decoder output: cls (B, Q, K+1) f32 / bf16 / fp16 and mask_logits (B, Q, h, w) f32 on the device,
+    grid_hw = (H, W) the BEV grid.  ``masks=False`` skips the packed masks, areas and mask scores; ``instance_map=False``
+    the map.  Device tensors only (a CPU tensor raises MaskBevHipError)."""
+    ops._need_gpu(cls, mask_logits)
+    if cls.dim() != 3 or mask_logits.dim() != 4 or tuple(cls.shape[:2]) != tuple(mask_logits.shape[:2]):
+        raise MaskBevHipError(f'extract_instances: cls (B, Q, K+1) and mask logits (B, Q, h, w) expected, got '
+                              f'{tuple(cls.shape)} and {tuple(mask_logits.shape)}')
+    labels, scores, keep = ops.select_queries(cls, score_threshold)
+    out = ops.extract_masks(mask_logits, scores, keep, grid_hw, masks=masks, instance_map=instance_map)
+    return Predictions(labels, scores, keep, out['masks'], out['areas'], out['mask_scores'], out['instance_map'],
+                       (int(grid_hw[0]), int(grid_hw[1])))
+
+
+def grid_hw(module) -> Tuple[int, int]:
+    """The module's BEV grid (ny, nx): the size of the encoder's pseudo-image and of the ground-truth masks."""
+    enc = module._encoder
+    return enc._num_voxel_y, enc._num_voxel_x
+
+
+class _EvalMode:
+    """Eval mode (the voxeliser's test-time max_voxels, the PFN's running statistics) for the duration, then the previous
+    mode back."""
+
+    def __init__(self, module):
+        self.m = module
+
+    def __enter__(self):
+        self.was = self.m.training
+        self.m.train(False)
+
+    def __exit__(self, *exc):
+        self.m.train(self.was)
+        return False
+
+
+def predict(module, scans, score_threshold: float = 0.0, masks: bool = True, instance_map: bool = True) -> Predictions:
+    """Eager inference on a list of (N_i, pc_dim) device scans: forward in eval mode under no_grad, K21 on the last
+    decoder output (MaskBevModule.predict)."""
+    with _EvalMode(module), torch.no_grad():
+        cls, mk, _ = module(scans)
+        return extract_instances(cls[-1], mk[-1], grid_hw(module), score_threshold, masks, instance_map)
+
+
+class GraphedPredictStep:
+    """``step(scans) -> Predictions`` with backbone + head + K21 replayed from one HIP graph.
+
+    The encoder runs eagerly in eval mode and writes into the graph's static input (the 16-bit patch rows of
+    ``module._patch_handoff()``, or the f32 map with its registered absmax record in fp32 compute).  The returned
+    :class:`Predictions` are the graph's static outputs: the NEXT replay overwrites them (``.clone()`` to keep them).
+    The batch size is fixed at construction.  Weights are read at replay time, so in-place parameter updates (optimizer
+    steps on the parameters or on a parameter arena and its 16-bit shadow) are followed; the decoder's weight copies are
+    refreshed by a launch inside the graph.  May live beside a :class:`~mask_bev_amd.graph.GraphedTrainStep` (validation
+    during training).  Construct it before any eager backward on the default stream, like the training graph."""
+
+    def __init__(self, module, example_scans, score_threshold: float = 0.0, masks: bool = True,
+                 instance_map: bool = True, warmup_iters: int = 2):
+        m = self.m = module
+        self.batch = len(example_scans)
+        self.score_threshold = float(score_threshold)
+        self._flags = (masks, instance_map)
+        self._grid = grid_hw(m)
+        dev = example_scans[0].device
+        with _EvalMode(m), torch.no_grad():
+            self._patch = m._patch_handoff()
+            with m._autocast():
+                x = m._encoder(example_scans, patch=self._patch)
+            rows = x.rows if isinstance(x, ops.PatchTokens) else x
+            self.x_static = torch.zeros_like(rows)
+            self._x_in = (ops.PatchTokens(self.x_static, x.channels, x.patch) if isinstance(x, ops.PatchTokens)
+                          else self.x_static)
+            static_rec = None
+            if not isinstance(x, ops.PatchTokens) and self.x_static.dtype == torch.float32 and ops.static_amax_wanted():
+                # fp32 compute: K3 leaves the map's absmax record at a fixed address for the captured patch projection
+                static_rec = ops.static_amax_register(self.x_static)
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.x_static.copy_(rows)
+                if static_rec is not None:
+                    static_rec.copy_(ops.f32_absmax([self.x_static.view(-1, self.x_static.shape[-1])]))
+                for _ in range(warmup_iters):
+                    self._forward()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            ops.amax_new_capture()        # records made inside an earlier capture (a training graph) are not this graph's
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.out = self._forward()
+            torch.cuda.synchronize()
+
+    def _forward(self) -> Predictions:
+        m = self.m
+        dt = m._compute_dtype
+        with torch.autocast('cuda', dtype=dt or torch.bfloat16, enabled=dt is not None, cache_enabled=False):
+            feats = m._backbone(self._x_in)
+            cls, mk, _ = m._panoptic_head(feats)
+        return extract_instances(cls[-1], mk[-1], self._grid, self.score_threshold, *self._flags)
+
+    def step(self, scans) -> Predictions:
+        if self.graph is None:
+            raise MaskBevHipError('GraphedPredictStep: closed')
+        if len(scans) != self.batch:
+            raise MaskBevHipError(f'GraphedPredictStep: captured for {self.batch} scans, got {len(scans)}')
+        m = self.m
+        with _EvalMode(m), torch.no_grad():
+            with m._autocast():                        # eager: K1 → K2 → K3 into the static buffer
+                m._encoder(scans, patch=self._patch, out=self.x_static)
+            self.graph.replay()
+        return self.out
+
+    __call__ = step
+
+    def close(self):
+        """Release the graph and its memory pool (the returned Predictions die with it)."""
+        self.graph = None
+        self.out = None
+        self._x_in = None
+        self.x_static = None
