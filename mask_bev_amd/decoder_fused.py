@@ -443,8 +443,10 @@ class _DecA(torch.autograd.Function):
         # 26 backward, 14 -> 8 forward, for 100 x 100 scores per head — like the per-op path's
         qkv = torch.empty((3, m, e), dtype=lc.dt, device=dev)
         w_o, w_i = lc.w(wo), lc.w(w_in)
-        # three workgroups per row block: each one of the q / k / v projections and a share of the stores
-        P = Program(m, lc.q, lc.eps, lc.wdt, 'A.fwd', split=spread(3))
+        # three workgroups per row block: each one of the q / k / v projections and a share of the stores (every workgroup
+        # repeats the stages they depend on — a 128 KB weight block is ~2 us of one CU's L2 bandwidth, a store stage
+        # ~1.2 us, and 231 CUs are idle)
+        P = Program(m, lc.q, lc.eps, lc.wdt, 'A.fwd', split=3)
         P.load(0, o1, e)
         o1f = o1
         if o1.dtype != torch.float32:         # an f32 copy for the weight gradient of the output projection (one STORE
@@ -502,7 +504,7 @@ class _DecA(torch.autograd.Function):
         g_o1 = torch.empty((m, e), dtype=ctx.o1_dtype, device=dev)
         tw = lc.tw
         # two workgroups per row block: one takes the last product, the other the column sums and the stores
-        P = Program(m, lc.q, lc.eps, lc.wdt, 'A.bwd', split=spread(2))
+        P = Program(m, lc.q, lc.eps, lc.wdt, 'A.bwd', split=2)
         P.load(0, g_qkv[0], e)
         with P.only(1):
             P.colsum(0, part_b, e, 0)
@@ -579,7 +581,7 @@ class _DecB(torch.autograd.Function):
         oc = head.mlp[2][0].shape[0]
         me = torch.empty((m, oc), dtype=head.mask_feature.dtype, device=dev)
         w_o, w_1, w_2 = lc.w(wo), lc.w(w1), lc.w(w2)
-        fused_ffn = lc.wdt != torch.float32 and f % 256 == 0 and e % 32 == 0 and switches.get('rc_ffn')
+        fused_ffn = lc.wdt != torch.float32 and f % 256 == 0 and e % 32 == 0
         # The MLP's 2 x 1 MB of weights behind ONE workgroup per 16 rows is 30 us of dependent loads on 25 CUs.  Split form:
         # f / 256 workgroups per row block each take 256 hidden units (launch 1: the cheap stages before the MLP run in all
         # of them), a second launch adds the parts and finishes the layer with its three independent branches (next
@@ -717,7 +719,7 @@ class _DecB(torch.autograd.Function):
         ds3, ds2 = torch.empty((m, e), **f32), torch.empty((m, e), **f32)
         dh = torch.empty((m, f), **f32)
         g_o2 = torch.empty((m, e), dtype=ctx.o2_dtype, device=dev)
-        fused_ffn = lc.wdt != torch.float32 and f % 256 == 0 and e % 32 == 0 and switches.get('rc_ffn')
+        fused_ffn = lc.wdt != torch.float32 and f % 256 == 0 and e % 32 == 0
         S = ffn_split(f, e, lc.wdt)
         split = S > 1
         P = Program(m, lc.q, lc.eps, lc.wdt, 'B1.bwd' if split else 'B.bwd', split=S)
@@ -747,7 +749,7 @@ class _DecB(torch.autograd.Function):
             P.ffn(1, 0, 2, w2t, w1t, e, f, hid, backward=True, d_hid=dh, partial=part_b, partial_col0=3 * e, sliced=True)
             P.store_part(1, parts, e)
             P.run()
-            P = Program(m, lc.q, lc.eps, lc.wdt, 'B2.bwd', split=spread(2))
+            P = Program(m, lc.q, lc.eps, lc.wdt, 'B2.bwd', split=2)
             P.sum_parts(1, parts, e)
             P.load(0, ds3, e)
         elif fused_ffn:
@@ -788,18 +790,10 @@ class _DecB(torch.autograd.Function):
                 gb3, gnw, gnb)
 
 
-def spread(n: int) -> int:
-    """Workgroups per row block of the programs WITHOUT a sliced stage (``n`` asked for): stores, column sums and
-    independent products move to different workgroups of the block, every workgroup repeating the stages they depend
-    on — a 128 KB weight block is ~2 us of one CU's L2 bandwidth, a store stage ~1.2 us, and 231 CUs are idle.
-    MBV_RC_SPREAD=0: one workgroup per block (A/B)."""
-    return n if switches.get('rc_spread') else 1
-
-
 def ffn_split(f: int, e: int, dt: torch.dtype) -> int:
     """Workgroups per row block of the decoder MLP's split launches (1: the one-workgroup stage / the staged f32 form)."""
-    fused = dt != torch.float32 and f % 256 == 0 and e % 32 == 0 and switches.get('rc_ffn')
-    return f // 256 if (fused and switches.get('rc_split')) else 1
+    fused = dt != torch.float32 and f % 256 == 0 and e % 32 == 0
+    return f // 256 if fused else 1
 
 
 def enabled(dtype: torch.dtype = torch.bfloat16) -> bool:

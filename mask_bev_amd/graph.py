@@ -37,7 +37,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops, switches
+from . import ops
 from .ddp import RangeReady
 from .mask_bev_module import MaskBevModule
 
@@ -66,7 +66,7 @@ class GraphedTrainStep:
     """``step(batch) -> loss`` with the static-shape part of the step replayed from a HIP graph."""
 
     def __init__(self, module: MaskBevModule, optimizer: torch.optim.Optimizer, example_batch, warmup_iters: int = 3,
-                 reducer=None, overlap_matcher: bool = True):
+                 reducer=None):
         self.m = module
         self.opt = optimizer
         self.reducer = reducer
@@ -74,9 +74,6 @@ class GraphedTrainStep:
         scans, labels, masks, _ = module._unpack(example_batch)
         dev = labels.device
         head = module._panoptic_head._panoptic_head
-        self._overlap_prev = head.overlap_matcher
-        # the matcher's side-stream fork / join is captured as a parallel branch of the graph
-        head.overlap_matcher = overlap_matcher
         # the encoder writes its result (the (B, C, ny, nx) map, or the backbone's bf16 patch rows) straight into the
         # graph's static input buffer
         self._patch = module._patch_handoff()
@@ -107,7 +104,7 @@ class GraphedTrainStep:
         # One GPU: the AdamW update of the encoder's (C, ny, nx) LayerNorm affine happens inside K3's backward (one backward
         # per step here by construction); a data-parallel step needs the all-reduced gradient and keeps the plain form
         self._k3_fused = False
-        if (reducer is None and switches.get('k3_adam') and getattr(module, '_arena', None) is not None
+        if (reducer is None and getattr(module, '_arena', None) is not None
                 and hasattr(optimizer, 'fuse_layernorm_affine')):
             ln = module._encoder._layer_norm
             self._k3_fused = optimizer.fuse_layernorm_affine(ln.weight, ln.bias)
@@ -141,20 +138,9 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss_static = self._forward_backward_head()
-        # A/B switch `switches.tn_overlap` (one GPU only): the grouped weight-gradient launch of the early stages (≈ 0.65 ms,
-        # nobody's input inside the graph) is taken out of the capture and issued after the replay on a side stream,
-        # beside the eager encoder backward; the captured operands stay alive in the graph's pool (held here), so their
-        # addresses are the replay's.  MEASURED SLOWER — 28.3 vs 27.7 ms: the MFMA / L2-heavy launch slows the
-        # latency-bound per-pillar walks it runs beside by more than it hides (as the optimizer pass did).
-        self._late_tn = [] if (reducer is None and switches.get('tn_overlap')) else None
-        self._tn_stream = torch.cuda.Stream(device=dev) if self._late_tn is not None else None
         self.graph_late = torch.cuda.CUDAGraph()
-        ops.set_tn_sink(self._late_tn)
-        try:
-            with torch.cuda.graph(self.graph_late, pool=self.graph.pool()):
-                self._backward_early_stages()
-        finally:
-            ops.set_tn_sink(None)
+        with torch.cuda.graph(self.graph_late, pool=self.graph.pool()):
+            self._backward_early_stages()
         torch.cuda.synchronize()
         self._ranges_head, self._ranges_late = self._arena_ranges()
 
@@ -266,14 +252,7 @@ class GraphedTrainStep:
             self.reducer.finish_arena(self.arena, handles, self.opt)
             mark('optimizer')
         else:
-            if self._late_tn:                              # the early stages' weight gradients, beside the encoder backward
-                main = torch.cuda.current_stream()
-                self._tn_stream.wait_stream(main)
-                with torch.cuda.stream(self._tn_stream):
-                    ops.launch_tn_group(self._late_tn)
             x.backward(self.x_static.grad)                 # eager: backward of K3 / K2
-            if self._late_tn:
-                torch.cuda.current_stream().wait_stream(self._tn_stream)
             if self.reducer is not None:
                 self.reducer.reduce_all()
         self.opt.step()
@@ -285,7 +264,6 @@ class GraphedTrainStep:
         return self.loss_static
 
     def close(self):
-        self.m._panoptic_head._panoptic_head.overlap_matcher = self._overlap_prev
         if self._k3_fused:
             self.opt.fuse_layernorm_affine(None)
             self._k3_fused = False

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, switches
+from . import ops
 
 
 def trunc_normal_(t: torch.Tensor, std: float = 0.02) -> torch.Tensor:
@@ -53,12 +53,9 @@ class LayerNorm(nn.LayerNorm):
             if (gemm_input and torch.is_autocast_enabled('cuda')
                     and torch.get_autocast_dtype('cuda') in ops._LO_DTYPES):
                 out_dtype = torch.get_autocast_dtype('cuda')
-            if fanout and not switches.get('ln_fanout'):
-                y = ops.add_layernorm(x, residual, self.weight, self.bias, self.eps, out_dtype, branch_bias=residual_bias)
-                return y, y
             branch_dtype = None
             if (fanout and branch_gemm and torch.is_autocast_enabled('cuda')
-                    and torch.get_autocast_dtype('cuda') in ops._LO_DTYPES and switches.get('ln_branch_lowp')):
+                    and torch.get_autocast_dtype('cuda') in ops._LO_DTYPES):
                 branch_dtype = torch.get_autocast_dtype('cuda')
             return ops.add_layernorm(x, residual, self.weight, self.bias, self.eps, out_dtype, return_sum,
                                      branch_bias=residual_bias, fanout=fanout, branch_dtype=branch_dtype)
@@ -186,8 +183,7 @@ def conv1x1(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     fp16 (MIOpen's fp16 solver for the mask-feature projection was measured to change its result from call to call,
     which made every decoder layer after it — and the gradients — irreproducible)."""
     b, c, h, w = x.shape
-    if (not x.is_contiguous() and x.is_cuda and x.permute(0, 2, 3, 1).is_contiguous()
-            and switches.get('conv1x1_tokens')):
+    if not x.is_contiguous() and x.is_cuda and x.permute(0, 2, 3, 1).is_contiguous():
         # a channels-last map (the backbone's stage outputs are (B, H, W, C) tokens seen through a permute): the GEMM
         # reads the token matrix as its transposed operand and writes NCHW; its backward returns token-major gradients
         y = ops.conv1x1_tokens(x.permute(0, 2, 3, 1).reshape(b, h * w, c), conv.weight.view(conv.weight.shape[0], c),
@@ -354,7 +350,7 @@ class MultiScaleDeformableAttention(nn.Module):
         h, l, p = self.num_heads, self.num_levels, self.num_points
         if (spatial_shapes is not None and query.is_cuda and query.dtype == torch.float32
                 and query_pos.shape[0] == 1 and sum(hh * ww for hh, ww in spatial_shapes) == n
-                and ops.msda_prepare_supported(l, p) and switches.get('msda_fused')):
+                and ops.msda_prepare_supported(l, p)):
             out = ops.msda_query_side(query, query_pos, reference_points, self.value_proj, self.sampling_offsets,
                                       self.attention_weights, h, l, p, spatial_shapes, shapes_t, level_start,
                                       pos_share=pos_share, pos_share_index=pos_share_index, wcat=wcat)

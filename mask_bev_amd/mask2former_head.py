@@ -13,7 +13,6 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import ops, switches
 from .layers import ConvGN, FFN, conv1x1, LayerNorm, Linear, MultiScaleDeformableAttention, MultiheadAttention, sine_positional_encoding
@@ -132,11 +131,11 @@ class MSDeformAttnPixelDecoder(nn.Module):
         q_branch = None
         nlay = len(self.encoder.layers)
         # one d(pos) product for the chain of layers instead of one per layer (ops.PosGradShare)
-        share = (ops.PosGradShare(nlay) if (q.is_cuda and torch.is_grad_enabled() and qpos.requires_grad and nlay > 1
-                                            and switches.get('pos_share')) else None)
+        share = (ops.PosGradShare(nlay) if (q.is_cuda and torch.is_grad_enabled() and qpos.requires_grad and nlay > 1)
+                 else None)
         # the layers' stacked projection weights [Wv; Wo; Wa] in the compute dtype: 18 pieces, one launch
         wcats = None
-        if q.is_cuda and q.dtype == torch.float32 and switches.get('msda_fused'):
+        if q.is_cuda and q.dtype == torch.float32:
             cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else q.dtype
             wcats = ops.msda_weight_stacks([l.self_attn for l in self.encoder.layers], cdt)
         for li, layer in enumerate(self.encoder.layers):
@@ -177,7 +176,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         return mask_feature, tail[:self.num_outs]
 
     def _tail_stream(self, device):
-        if device.type != 'cuda' or not torch.is_grad_enabled() or not switches.get('tail_stream'):
+        if device.type != 'cuda' or not torch.is_grad_enabled():
             return None
         st = self._tail_streams.get(device)
         if st is None:
@@ -350,7 +349,7 @@ class _DeferredHeads(torch.autograd.Function):
         # handed over through the layer context, the producer's backward program adds it while it loads that gradient — not
         # autograd with a launch per layer.  Output 0 is the query parameter, output D - 1 has no other consumer.
         stash = getattr(head, '_gq_stash', None)
-        if stash is not None and nd > 2 and switches.get('gq_stash'):
+        if stash is not None and nd > 2:
             box = stash.setdefault('gq', {})
             for i in range(1, nd - 1):
                 box[i] = gq[i]
@@ -413,7 +412,6 @@ class Mask2FormerHead(nn.Module):
         self.point_seed: Optional[int] = None          # tests set this to share points with the oracle
         self._iota_cache: Dict = {}
         self._side_streams: Dict = {}
-        self.overlap_matcher = switches.get('overlap_matcher')
         # GT masks are float32 {0, 1} by the reference's batch contract (semantic_kitti_transforms.py:77-81);
         # set False to sample arbitrary-valued maps through the generic f32 path
         self.binary_gt_masks = True
@@ -491,7 +489,7 @@ class Mask2FormerHead(nn.Module):
         # training on the GPU: the heads run layer by layer WITHOUT a graph and get one batched backward (_DeferredHeads)
         deferred = (stack is not None and self.training and torch.is_grad_enabled()
                     and switches.get('deferred_heads'))
-        if deferred and switches.get('stack_grad_sink'):
+        if deferred:
             # K8's backward writes the stacked logit gradient where and how _DeferredHeads reads it (ops.StackGradSink)
             self._stack_sink = ops.StackGradSink(nd, bs, self.num_queries, mask_features.dtype, mask_features.device)
         feats_q = [query_feat]
@@ -560,7 +558,7 @@ class Mask2FormerHead(nn.Module):
         # GEMM stage (<= 256 classes); the MLP is ONE stage in its fused form (16-bit weights, f % 256 == 0, at most 64
         # slices) and f / 256 chunks of 3 forward / 5 backward stages otherwise — beyond 2048 hidden units that form
         # does not fit beside the layer's other ~20 stages, and such a head takes the per-op path.
-        fused_ffn = dt != torch.float32 and f % 256 == 0 and e % 32 == 0 and switches.get('rc_ffn')
+        fused_ffn = dt != torch.float32 and f % 256 == 0 and e % 32 == 0
         if self.cls_embed.out_features > 256 or (f > 16384 if fused_ffn else f > 2048):
             return False
         return (DF.enabled(dt) and mask_features.is_cuda and all(s is not None for s in shared)
@@ -660,7 +658,7 @@ class Mask2FormerHead(nn.Module):
         """Per problem, the count K of real ground-truth columns for K9's padded mode (None: solve the square problem).  The
         dataset pads the instance list to num_queries with all-zero masks of label 0; a column counts as padding only if it
         has label 0 AND an empty mask AND every later column is padding too."""
-        if not (nq == ng <= 320 and isinstance(gt_flat, ops.PackedMasks) and switches.get('k9_padded')):
+        if not (nq == ng <= 320 and isinstance(gt_flat, ops.PackedMasks)):
             return None
         dev = labels_gt.device
         # "the packed mask holds a set bit" in TWO reduction stages of <= 128 words per output: a one-stage reduction of 8 192
@@ -761,33 +759,17 @@ class Mask2FormerHead(nn.Module):
         mp = ops.point_sample(masks_flat, self._iota(d * b * nq, dev), match_coords,
                               self._iota(d * b * nq, dev, div=nq)).view(d, b, nq, -1)            # (D, B, Q, P)
         gp = gp.view(d, b, ng, -1)                                                               # (D, B, G, P)
-        if (cls.is_cuda and switches.get('loss_glue') and switches.get('match_fused')
-                and ops.match_products_supported(nq, ng, mp.shape[-1])):
+        if ops.match_products_supported(nq, ng, mp.shape[-1]):
             # K13c: the products x·t, sigmoid(x)·t and every row sum from one kernel (terms evaluated per 32-point chunk,
             # split into half pairs, contracted on MFMA) — the (DB, 3Q + 1, P) term planes and the f32 GEMM are gone
             prod, neg = ops.match_products(mp.reshape(d * b, nq, -1), gp.reshape(d * b, ng, -1))
             return ops.match_cost_split(cls, labels_gt, prod, neg, self.num_points)
         gpt = gp.reshape(d * b, ng, -1).transpose(1, 2)                                       # (DB, P, G)
-        if cls.is_cuda and switches.get('loss_glue'):
-            # K13: the cost terms with an all-ones row behind them — ONE batched GEMM against the sampled ground truth then
-            # gives the three cost matrices AND the targets' row sums — and one launch that turns the products, the class
-            # logits and the labels into the cost matrices (was: softmax, gather, a 200 MB row reduction, ~ 20 ATen launches)
-            terms, sums = ops.match_cost_terms(mp.reshape(d * b, nq, -1), ones_row=True)      # (DB, 3Q + 1, P), (DB, Q, 2)
-            return ops.match_cost(cls, labels_gt, torch.matmul(terms, gpt), sums, self.num_points)
-        prob = cls.softmax(-1)
-        lab = labels_gt.view(1, b, 1, ng).expand(d, b, nq, ng)
-        cls_cost = -torch.gather(prob, 3, lab) * 2.0                                            # (D, B, Q, G)
-        # K13: softplus(-x), softplus(x), sigmoid(x) and two row sums in one pass over the sampled logits; the three
-        # cost matrices come from ONE batched GEMM against the sampled ground truth
-        terms, sums = ops.match_cost_terms(mp.reshape(d * b, nq, -1))                         # (DB, 3Q, P), (DB, Q, 2)
-        prod = torch.matmul(terms, gpt).view(d, b, 3, nq, ng)
-        pos_gp, neg_gp, sig_gp = prod[:, :, 0], prod[:, :, 1], prod[:, :, 2]
-        sums = sums.view(d, b, nq, 2)
-        # BCE against 1 on the GT pixels + against 0 elsewhere: neg·(1 - gp) = Σ neg - neg·gp
-        bce = (pos_gp + sums[..., 0:1] - neg_gp) / self.num_points
-        den = sums[..., 1:2] + gp.sum(-1)[..., None, :]
-        dice = 1 - (2 * sig_gp + 1.0) / (den + 1.0)
-        return (cls_cost + 5.0 * bce + 5.0 * dice).flatten(0, 1)                               # (D*B, Q, G)
+        # K13: the cost terms with an all-ones row behind them — ONE batched GEMM against the sampled ground truth then
+        # gives the three cost matrices AND the targets' row sums — and one launch that turns the products, the class
+        # logits and the labels into the cost matrices (was: softmax, gather, a 200 MB row reduction, ~ 20 ATen launches)
+        terms, sums = ops.match_cost_terms(mp.reshape(d * b, nq, -1), ones_row=True)          # (DB, 3Q + 1, P), (DB, Q, 2)
+        return ops.match_cost(cls, labels_gt, torch.matmul(terms, gpt), sums, self.num_points)
 
     def loss(self, all_cls_scores, all_mask_preds, gt_labels_list, gt_masks_list, img_metas=None, heights_pred=None,
              heights_gt=None) -> Dict[str, torch.Tensor]:
@@ -850,7 +832,7 @@ class Mask2FormerHead(nn.Module):
         # K9 is latency-bound (one wavefront per problem) and the cost kernels in front of it are short.  When every query
         # gets matched (G >= Q, the dataset's padding convention) nothing of the importance sampling below depends on the
         # assignment, so the whole matcher — sampling the logits at its points, K13c, K9 — runs on a side stream underneath it.
-        overlap = m == nq and self.overlap_matcher and cls.is_cuda
+        overlap = m == nq and cls.is_cuda
         if overlap:
             side = self._stream_for('matcher', dev)
             # every buffer the side stream's result lives in is allocated on the main stream and outlives the join below,
@@ -895,32 +877,22 @@ class Mask2FormerHead(nn.Module):
         # kept for the metrics path (mask_bev_amd/metrics.py), which the reference feeds by running the matcher again
         self.last_assignment = assigned.detach()
         self.last_gt_packed = gt_flat if isinstance(gt_flat, ops.PackedMasks) else None
-        glue = cls.is_cuda and switches.get('loss_glue')
         with torch.no_grad():
-            if m == nq and glue:
+            if m == nq:
                 # every query is matched and `qsel` is the identity: the ground-truth row of (d, b, q) is b * G + assigned —
                 # two launches on the int32 assignment instead of compare / clamp / cast / gather / multiply / add / cast
                 boff = self._iota(d * b * nq, dev, div=nq, mod=b, mul=ng).view(d, b, nq)
                 gt_index = (assigned.clamp(min=0) + boff).flatten()
             else:
-                if overlap:
-                    matched = assigned >= 0
-                    safe = assigned.clamp(min=0).long()
                 bsel = self._iota(b, dev).long().view(1, b, 1)
                 gt_index = (bsel * ng + torch.gather(safe, 2, qsel)).flatten().to(torch.int32)   # rows of gt_flat
             tgt = self._sample_gt(gt_flat, gt_index, coords, rows)                               # (D*g, P)
 
         # classification loss (class-weighted CE, avg_factor = sum of the class weights of the targets)
         class_weight = self._const(dev, self.class_weight)
-        if cls.is_cuda and switches.get('loss_glue'):
-            # K13: labels from the assignment, weighted cross entropy and its normaliser per decoder output in one launch
-            # (and one for the gradient) instead of where / gather / log_softmax / nll_loss / index / sums
-            loss_cls = ops.cls_loss(cls, assigned, labels_gt, class_weight, self.loss_cls_weight, eps)
-        else:
-            labels = torch.where(matched, torch.gather(labels_gt.view(1, b, ng).expand(d, b, ng), 2, safe),
-                                 torch.full_like(safe, self.num_classes))
-            ce = F.cross_entropy(cls.flatten(0, 2), labels.flatten(), weight=class_weight, reduction='none').view(d, -1)
-            loss_cls = self.loss_cls_weight * ce.sum(1) / (class_weight[labels].view(d, -1).sum(1) + eps)
+        # K13: labels from the assignment, weighted cross entropy and its normaliser per decoder output in one launch
+        # (and one for the gradient) instead of where / gather / log_softmax / nll_loss / index / sums
+        loss_cls = ops.cls_loss(cls, assigned, labels_gt, class_weight, self.loss_cls_weight, eps)
 
         # MaskPseudoSampler: avg_factor = num_pos + num_neg = Q per image; reduce_mean over ranks (:388) is the
         # identity for equal per-rank batches (drop_last=True), see ddp.py
@@ -931,17 +903,11 @@ class Mask2FormerHead(nn.Module):
         else:
             num_total_masks = self.world_size_fn(self._const(dev, [float(b * nq)])).clamp(min=1.0)[0]
 
-        if pred.is_cuda and switches.get('loss_node'):
-            # K13's row sums (Σ σ·t, Σ σ, Σ t, Σ bce in one pass) and the dice / BCE algebra on them as one autograd node
-            with torch.no_grad():
-                c_dice = self.loss_dice_weight / (num_total_masks + eps)
-                c_mask = self.loss_mask_weight / (num_total_masks * p + eps)
-            loss_dice, loss_mask = ops.mask_dice_bce(pred, tgt, d, c_dice, c_mask)
-        else:
-            sums = ops.mask_loss_rows(pred, tgt)              # K13: (D*g, 4) = Σ σ·t, Σ σ, Σ t, Σ bce in one pass
-            dice = (2 * sums[:, 0] + 1.0) / (sums[:, 1] + sums[:, 2] + 1.0)
-            loss_dice = self.loss_dice_weight * (1 - dice).view(d, g).sum(1) / (num_total_masks + eps)
-            loss_mask = self.loss_mask_weight * sums[:, 3].view(d, g).sum(1) / (num_total_masks * p + eps)
+        # K13's row sums (Σ σ·t, Σ σ, Σ t, Σ bce in one pass) and the dice / BCE algebra on them as one autograd node
+        with torch.no_grad():
+            c_dice = self.loss_dice_weight / (num_total_masks + eps)
+            c_mask = self.loss_mask_weight / (num_total_masks * p + eps)
+        loss_dice, loss_mask = ops.mask_dice_bce(pred, tgt, d, c_dice, c_mask)
 
         out = LossDict(loss_cls=loss_cls[-1], loss_mask=loss_mask[-1], loss_dice=loss_dice[-1], loss_height=0)
         for i in range(d - 1):

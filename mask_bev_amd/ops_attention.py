@@ -273,8 +273,7 @@ class _SharedKVProject(torch.autograd.Function):
         # and a multi-tensor add: 9 launches of 5-20 us.
         def _arena(p):
             return getattr(p, '_mbv_arena', False) and p.grad is not None and p.grad.dtype == torch.float32
-        if (switches.get('skv_direct')
-                and all(_arena(ctx.params[i]) and ctx.needs_input_grad[3 + i] for i in range(2 * n))):
+        if all(_arena(ctx.params[i]) and ctx.needs_input_grad[3 + i] for i in range(2 * n)):
             for j in range(n):
                 w, b_ = ctx.params[2 * j], ctx.params[2 * j + 1]
                 for g2, x2, r0 in ((dk2, key2, e), (dv2, val2, 2 * e)):
@@ -524,7 +523,7 @@ class _MaskLogits(torch.autograd.Function):
             check(lib.mbv_gemm16_nn(_ptr(e), _ptr(f), _ptr(out), None, None, q, c, hw, c, hw, hw, 0, _GEMM16_DT[dt],
                                     1 if out.dtype == torch.float32 else 0, 0, b, q * c, c * hw, q * hw, None, 0, _stream()),
                   'mbv_gemm16_nn')
-        elif dt == torch.float32 and switches.get('k7_f32_library'):
+        elif dt == torch.float32:
             # f32: the library's batched product (0.76 of the f32 MFMA peak on this shape); K7's own exact-f32 form streams
             # E through L2 per 128-pixel slab and sits at 0.07 of HBM — 179 against ≈ 35 us per launch in the fp32 step
             # (through .data: like the raw-pointer launches around it, the store must not count as an in-place update of the

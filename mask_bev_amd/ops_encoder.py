@@ -173,7 +173,7 @@ class _PillarFeatureNet(torch.autograd.Function):
         # the host's time per launch is step time); every tensor of the pass is a piece of one workspace, cut into views only
         # when the backward asks for them.
         units = [int(params[5 * l].shape[0]) for l in range(n_layers)]
-        if (switches.get('pfn_one_call') and switches.get('pfn_skinny') and rows.dtype == torch.float32 and rows.is_contiguous()
+        if (switches.get('pfn_one_call') and rows.dtype == torch.float32 and rows.is_contiguous()
                 and k > 0 and v > 0 and n_layers <= 8 and int(rows.shape[1]) <= 128
                 and all(u % 32 == 0 and 32 <= u <= 128 for u in units)
                 and all(t.dtype == torch.float32 and t.is_contiguous() for t in params)
@@ -311,7 +311,7 @@ def _pfn_mm(x: torch.Tensor, w: torch.Tensor, weight_is_nk: bool, stream=None) -
     n = int(w.shape[0] if weight_is_nk else w.shape[1])
     if (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and m >= _PFN_SKINNY_MIN_ROWS
             and x.is_contiguous() and w.stride(1) == 1 and (w.shape[1] if weight_is_nk else w.shape[0]) == c
-            and 1 <= c <= 128 and 32 <= n <= 128 and n % 32 == 0 and switches.get('pfn_skinny')):
+            and 1 <= c <= 128 and 32 <= n <= 128 and n % 32 == 0):
         y = torch.empty((m, n), dtype=torch.float32, device=x.device)
         check(_lib.load().mbv_skinny_gemm_f32(_ptr(x), _ptr(w), _ptr(y), m, c, n, int(w.stride(0)),
                                               1 if weight_is_nk else 0, stream if stream is not None else _stream()),

@@ -521,7 +521,7 @@ class _Conv3x3K17(torch.autograd.Function):
 def conv3x3_16_ok(x: torch.Tensor, conv) -> bool:
     """A 16-bit compute mode (autocast to bf16 / fp16, or 16-bit tensors), a 3 x 3 stride-1 padding-1 convolution without bias
     whose channel counts K17 takes."""
-    if not (switches.get('conv3x3_k17') and gemm16_enabled() and x.is_cuda and x.dim() == 4):
+    if not (gemm16_enabled() and x.is_cuda and x.dim() == 4):
         return False
     dt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else x.dtype
     return bool(dt in _GEMM16_DT and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
@@ -709,16 +709,6 @@ def _defer_tn32_wgrad(g2: torch.Tensor, x2: torch.Tensor, acc: torch.Tensor, ama
     return True
 
 
-_TN_SINK: Optional[list] = None
-
-
-def set_tn_sink(sink: Optional[list]) -> None:
-    """While a list is installed, the end-of-pass flush appends the pass's ``(g, x, acc)`` weight-gradient products to it
-    instead of launching them (``None`` restores the launch)."""
-    global _TN_SINK
-    _TN_SINK = sink
-
-
 def launch_tn_group(items) -> None:
     """The grouped launch(es) for a pass's products: deepest token sums first (their work items are the longest of a
     launch), one call per 16-bit dtype."""
@@ -822,11 +812,6 @@ def flush_deferred_grads(task_id: Optional[int] = None) -> None:
     for st in {it[-1] for it in wg + cs + tn + tn32}:
         if st != cur:
             cur.wait_stream(st)
-    if tn and _TN_SINK is not None:
-        # the caller (graph.py, while it captures a backward pass) takes the pass's weight-gradient products over and
-        # issues them itself — after the replay, on a side stream, underneath the eager encoder backward
-        _TN_SINK.extend(it[:3] for it in tn)
-        tn = []
     if tn:
         launch_tn_group([it[:3] for it in tn])
     if wg and switches.get('gemm32s') and switches.get('tn32_group'):

@@ -54,13 +54,10 @@ class _MSDeformAttn(torch.autograd.Function):
         return g_value, None, None, g_loc, g_attn, None
 
 
-_MSDA_SIDE = {}
-
-
 def msda_value_packed_ok(dims, host) -> bool:
     """Whether d(value) of this shape can take the packed fixed-point form (mbv_ms_deform_attn_bwd_value_packed)."""
     b, nv, nh, d, nl, nq, npnt = dims
-    return bool(host is not None and switches.get('msda_packed')
+    return bool(host is not None
                 and _lib.load().mbv_ms_deform_attn_bwd_value_packed_supported(d, nl, npnt, nq, host))
 
 
@@ -85,28 +82,13 @@ def _msda_backward(lib, g_out, value, shapes_t, level_start, loc, attn, dims, ho
 
 
 def _msda_backward_f64(lib, g_out, value, shapes_t, level_start, loc, attn, dims, host, g_value, g_loc, g_attn):
-    """K5 backward.  The no-atomics form has two independent parts — d(value), bound by the LDS f64-atomic rate, and
-    d(location) / d(weight), bound by L2 gathers.  `switches.msda_bwd_overlap` puts them on two streams; measured inside the
-    HIP-graph step the fork / join edges cost more than the overlap returns (34.17 vs 33.88 ms per step), so the
-    default is one stream.  The side stream only touches buffers that were allocated on the current stream and
-    outlive the join."""
-    import os
+    """K5 backward: d(value), bound by the LDS f64-atomic rate, and d(location) / d(weight), bound by L2 gathers, in one
+    call (mode 3).  On two streams the fork / join edges inside the HIP-graph step cost more than the overlap returns
+    (34.17 vs 33.88 ms per step)."""
     b, nv, nh, d, nl, nq, npnt = dims
-    args = (_ptr(g_out), _ptr(value), _ptr(shapes_t), _ptr(level_start), _ptr(loc), _ptr(attn), b, nv, nh, d, nl, nq,
-            npnt, host, _ptr(g_value), _ptr(g_loc), _ptr(g_attn))
-    split = host is not None and lib.mbv_ms_deform_attn_bwd_split(d, nl, host)
-    if not split or not switches.get('msda_bwd_overlap'):
-        check(lib.mbv_ms_deform_attn_bwd(*args, 3, _stream()), 'mbv_ms_deform_attn_bwd')
-        return
-    main = torch.cuda.current_stream()
-    side = _MSDA_SIDE.get(g_out.device)
-    if side is None:
-        side = _MSDA_SIDE[g_out.device] = torch.cuda.Stream(device=g_out.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        check(lib.mbv_ms_deform_attn_bwd(*args, 2, _stream()), 'mbv_ms_deform_attn_bwd')      # d(location), d(weight)
-    check(lib.mbv_ms_deform_attn_bwd(*args, 1, _stream()), 'mbv_ms_deform_attn_bwd')          # d(value)
-    main.wait_stream(side)
+    check(lib.mbv_ms_deform_attn_bwd(_ptr(g_out), _ptr(value), _ptr(shapes_t), _ptr(level_start), _ptr(loc), _ptr(attn),
+                                     b, nv, nh, d, nl, nq, npnt, host, _ptr(g_value), _ptr(g_loc), _ptr(g_attn), 3,
+                                     _stream()), 'mbv_ms_deform_attn_bwd')
 
 
 class _MSDAPrepare(torch.autograd.Function):
@@ -246,7 +228,7 @@ class _MSDAQuerySide(torch.autograd.Function):
                     # forward and its location / weight gradient are bound by the bytes of their bilinear taps, 128 B per
                     # (tap, head) in f32.  Needs the packed value gradient (its f64 alternative wants an f32 map), head dim 32.
                     host_b = (ctypes.c_int64 * (2 * levels))(*[int(v) for hw in shapes_host for v in hw])
-                    lo_value = bool(switches.get('msda_value_lowp') and d == 32 and (e + lo + la) % 2 == 0
+                    lo_value = bool(d == 32 and (e + lo + la) % 2 == 0
                                     and msda_value_packed_ok((b, n, heads, d, levels, n, points), host_b))
                     value = gemm16_nt(xb.view(b * n, e), wvc, bvf,
                                       out_dtype=None if lo_value else torch.float32).view(b, n, e)

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, switches
+from . import ops
 from .layers import FFN, LayerNorm, Linear, PatchEmbed, PatchMerging, trunc_normal_
 
 
@@ -177,7 +177,7 @@ class CustomSwinTransformer(nn.Module):
                 ape = F.interpolate(ape, size=(h, w), mode='bicubic', align_corners=False)
             # the reference flattens the (rows, cols) map row-major into the token axis, whatever h, w are
             # (made contiguous first: the broadcast add of the transposed view ran at 1.8 TB/s, 84 us per step)
-            if (x.is_cuda and ape is self.absolute_pos_embed and switches.get('pos_fused') and len(self.stages[0].blocks) > 0
+            if (x.is_cuda and ape is self.absolute_pos_embed and len(self.stages[0].blocks) > 0
                     and (cut is None or cut['stage'] > 0) and ops.add_layernorm_supported(e)):
                 # the add rides on the first block's LayerNorm launch; the gradient takes one transposing pass (ops.pos_tokens)
                 pos_pending = ops.pos_tokens(ape, b, h, w)
@@ -195,10 +195,10 @@ class CustomSwinTransformer(nn.Module):
             # it (seen as NaNs in lateral_convs.0's weight gradient).  It stays f32; its cast is the tail stream's own tensor.
             x, out = stage(x, getattr(self, f'norm{i}') if i in self.out_indices else None,
                            pending=pos_pending if i == 0 else None,
-                           out_gemm_input=bool(i > 0 and switches.get('stage_out_lowp')))
+                           out_gemm_input=i > 0)
             if i in self.out_indices:
                 # (B, C, H, W) as the reference returns it, but as a VIEW of the channels-last map: the head's 1 x 1
                 # convolutions read it as tokens (layers.conv1x1), so no NCHW copy is made — forward or backward
-                outs.append(out.permute(0, 3, 1, 2) if out.is_cuda and switches.get('conv1x1_tokens')
+                outs.append(out.permute(0, 3, 1, 2) if out.is_cuda
                             else out.permute(0, 3, 1, 2).contiguous())
         return outs
