@@ -248,8 +248,11 @@ class _MSDAQuerySide(torch.autograd.Function):
         loc = torch.empty((b, n, heads, levels, points, 2), dtype=torch.float32, device=x.device)
         attn = torch.empty((b, n, heads, levels, points), dtype=torch.float32, device=x.device)
         esz = ol.element_size()
+        # f32 biases held by name until the launch: were both temporaries, the first could be freed and its block refilled
+        # with the second before the kernel runs
+        bo32, ba32 = bo.float().contiguous(), ba.float().contiguous()
         check(lib.mbv_msda_prepare_fwd_ld(_ptr(ol), lo + la, ctypes.c_void_p(ol.data_ptr() + lo * esz), lo + la,
-                                          _ptr(bo.float().contiguous()), _ptr(ba.float().contiguous()), _dt_flag(dt),
+                                          _ptr(bo32), _ptr(ba32), _dt_flag(dt),
                                           _ptr(ref32), host, b, n, heads, levels, points, _ptr(loc), _ptr(attn), _stream()),
               'mbv_msda_prepare_fwd_ld')
         del ol
