@@ -1143,6 +1143,55 @@ int mbv_extract_masks(const float* logits, const float* score, const uint8_t* ke
                       int32_t h, int32_t w, int32_t H, int32_t W, uint32_t* masks_packed, int32_t* areas,
                       float* mask_scores, int32_t* instance_map, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K22 — SemanticKITTI scene → instance-id map (csrc/rasterize.hip): the input of K14, made on the device.
+ * Replaces: SemanticKittiRasterizer.get_mask_around (mask_bev/datasets/semantic_kitti/semantic_kitti_rasterizer.py:41-94;
+ * numpy + one cv2.morphologyEx pair per instance on the host) and with it the reference's `.npy` mask cache.
+ *
+ * points        (n_points, stride) f32 (points_f64 = 0) or f64 (points_f64 = 1), x, y, z first, stride 3 or 4; scans
+ *               concatenated.  f64 is the reference's aggregated scene in the world frame, passed through as it is.
+ * inst          (n_points) i32 instance id per point, 0 = no instance; valid ids are 1 … 65535 (SemanticKITTI's 16 bits)
+ * scan_offsets  (n_scans + 1) i32; transforms (n_scans, 4, 4) f64 row-major, scan → centre-scan frame, last row 0 0 0 1
+ *               (the caller checks it; only the upper 3 x 4 block is read)
+ * centre_inst   (n_centre) i32.  n_centre < 0 (`remove_unseen = False`, :80): the present instances are the ids with at
+ *               least one kept point.  n_centre >= 0 (:73-78): they are the non-zero ids with >= max(min_points, 1) labels in
+ *               the whole centre scan; a present instance with no kept point paints nothing.
+ * geometry      a point is KEPT iff lo < c < hi strictly on all three axes of the transformed point (:59-61; NaN / inf
+ *               never are); cell ix = floor((x - x_lo) / voxel_size), iy likewise (:66-67), all in f64 with one rounding
+ *               per operation (the transform is ((m0 x + m1 y) + m2 z) + m3, no contraction).  nx, ny are the caller's
+ *               int((hi - lo) / voxel_size); a kept point whose cell index reaches nx or ny is dropped.
+ * morph_kernel  odd, 1 … 31: every present instance's occupancy is closed, then opened, with a k x k square (:71, :87-88).
+ *               Border rule (cv2 BORDER_CONSTANT with morphologyDefaultBorderValue): outside the grid a cell counts as
+ *               set for an erosion and as clear for a dilation.
+ * instance_map  (nx, ny) i32, 0 = background: the layout of the reference's mask cache and of K14's input.
+ *               OVERLAPS: the reference paints in the iteration order of a Python set of numpy.uint32 (hash order, neither
+ *               ascending nor stable); here THE HIGHEST ID WINS on a cell that several closed-and-opened instances
+ *               claim, independent of point order.  Where no two instances share a cell the map equals the reference's.
+ * status        device i32, written by phase 1: bit 0 = more than max_instances present instances (the max_instances
+ *               smallest ids are rasterised), bit 1 = an id outside 0 … 65535 was met (those points are skipped).
+ * phases        bit 0 = K22a (id table, occupancy bits and cell bounding boxes into `workspace`), bit 1 = K22b
+ *               (morphology + paint from `workspace`); 3 = the whole call.  Split only for measurements.
+ * workspace     mbv_rasterize_workspace_bytes(nx, ny, max_instances) bytes, 256-byte aligned; 0 = bad geometry
+ *               (nx, ny >= 1, nx * ny <= 2^26, 1 <= max_instances <= 65535).  MBV_ERR_UNSUPPORTED when a row band of
+ *               the widest window cannot hold its halo: 8192 / ceil(ny / 32) - 8 * (k / 2) < 1 (ny > 2176 with k = 31).
+ *               `inst` must be 16-byte aligned.
+ *
+ * mbv_rasterize_paint is K22b alone on caller-given data: occupancy (n_slots_max, nx, ceil(ny / 32)) u32, bit b of word w
+ * of row ix = cell (ix, 32 w + b), bits at iy >= ny clear; bbox (n_slots_max, 4) i32 = inclusive cell bounds xmin, ymin,
+ * xmax, ymax of the set bits (xmax < 0: nothing to paint); slot_ids (n_slots_max) i32 > 0; *n_slots (device i32) <=
+ * n_slots_max slots are painted.  It zeroes instance_map first.
+ */
+size_t mbv_rasterize_workspace_bytes(int32_t nx, int32_t ny, int32_t max_instances);
+int mbv_rasterize(const void* points, int32_t points_f64, int32_t stride, const int32_t* inst, int64_t n_points,
+                  const int32_t* scan_offsets, int32_t n_scans, const double* transforms, const int32_t* centre_inst,
+                  int64_t n_centre, double x_lo, double x_hi, double y_lo, double y_hi, double z_lo, double z_hi,
+                  double voxel_size, int32_t nx, int32_t ny, int32_t morph_kernel, int32_t min_points,
+                  int32_t max_instances, int32_t phases, int32_t* instance_map, int32_t* status, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int mbv_rasterize_paint(const uint32_t* occupancy, const int32_t* bbox, const int32_t* slot_ids, const int32_t* n_slots,
+                        int32_t n_slots_max, int32_t nx, int32_t ny, int32_t morph_kernel, int32_t* instance_map,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ _P = c_void_p
 _F = c_float
 _I = c_int32
 _L = c_int64
+_D = c_double
 
 # symbol -> (restype, argtypes); mirrors include/maskbev_hip.h one to one
 SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
@@ -186,6 +187,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_select_queries': (ctypes.c_int, [_P, _I, _L, _I, _F, _P, _P, _P, _P]),
     'mbv_extract_masks_workspace_bytes': (c_size_t, [_I, _I, _I, _I, _I, _I]),
     'mbv_extract_masks': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'mbv_rasterize_workspace_bytes': (c_size_t, [_I, _I, _I]),
+    'mbv_rasterize': (ctypes.c_int, [_P, _I, _I, _P, _L, _P, _I, _P, _P, _L, _D, _D, _D, _D, _D, _D, _D, _I, _I, _I, _I, _I, _I,
+                                     _P, _P, _P, c_size_t, _P]),
+    'mbv_rasterize_paint': (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

@@ -147,3 +147,41 @@ class InstanceMapCollate:
         if len(batch[0]) > 2:
             return pcs, (labels, masks), [s[2] for s in batch]
         return pcs, (labels, masks)
+
+
+class SceneCollate:
+    """Collate of ``(point_cloud (N, pc_dim) f32 array/tensor, scene[, metadata])`` samples with ``scene = (points list,
+    inst list, transforms (S, 4, 4) f64, centre_inst or None)`` — the labelled scans around the sample's scan and the
+    transforms that take them into its frame — into the batch ``MaskBevModule.training_step`` takes.  Beside
+    :class:`InstanceMapCollate`: instead of a cached instance map, the scene is rasterised on ``device`` (K22,
+    ``rasterize.SemanticKittiRasterizer``) and the maps go to K14, so no mask cache is needed and a point-level
+    augmentation of the scene can come first."""
+
+    def __init__(self, rasterizer, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False):
+        self.rasterizer, self.num_queries, self.device = rasterizer, num_queries, torch.device(device)
+        self.min_num_inst_pixels, self.packed = min_num_inst_pixels, packed
+
+    def _up(self, t, dtype=None):
+        t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t)
+        if dtype is not None:
+            t = t.to(dtype)
+        elif t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float32)
+        return t.to(self.device, non_blocking=True)
+
+    def __call__(self, batch: Sequence):
+        pcs = [torch.as_tensor(s[0], dtype=torch.float32).to(self.device, non_blocking=True) for s in batch]
+        scenes = []
+        for s in batch:
+            points, inst, transforms, centre = s[1]
+            scenes.append(([self._up(p) for p in points],
+                           [self._up(np.asarray(i).astype(np.int64) if not isinstance(i, torch.Tensor) else i, torch.int32)
+                            for i in inst], transforms,
+                           None if centre is None else
+                           self._up(np.asarray(centre).astype(np.int64) if not isinstance(centre, torch.Tensor) else centre,
+                                    torch.int32)))
+        maps = self.rasterizer.rasterize_batch(scenes)
+        labels, masks = instance_targets(maps, self.num_queries, self.min_num_inst_pixels, self.packed)
+        if len(batch[0]) > 2:
+            return pcs, (labels, masks), [s[2] for s in batch]
+        return pcs, (labels, masks)

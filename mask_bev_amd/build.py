@@ -27,6 +27,8 @@ COMMON_FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-fa
 FILE_FLAGS = {
     'voxelize.hip': ['-ffp-contract=off'],
     'scatter_layernorm.hip': ['-ffp-contract=off'],
+    # K22's f64 transform and `(x - lo) / vs` decide a cell index: one rounding per operation, as numpy does them
+    'rasterize.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }
