@@ -1192,6 +1192,74 @@ int mbv_rasterize_paint(const uint32_t* occupancy, const int32_t* bbox, const in
                         int32_t n_slots_max, int32_t nx, int32_t ny, int32_t morph_kernel, int32_t* instance_map,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K23 — training augmentations of scans and instance maps (csrc/augment.hip).
+ * Replaces: Flip, ShufflePoints, RandomRotate, DecimatePoints, JitterPoints, RandomDropPoints of
+ * mask_bev/augmentations/semantic_kitti_mask_augmentations.py:44-161 (numpy + cv2.warpAffine on the host, per sample).
+ * The per-sample decisions (which transforms fire, the angle, the seed) are drawn on the host; the device runs them.
+ *
+ * points        (n_points, dim) f32, dim 3 or 4 (x, y, z[, intensity]); the scans of a batch concatenated
+ * scan_offsets  (batch + 1) i32, ascending, scan_offsets[batch] = n_points; 1 <= batch <= 4096, n_points < 2^28
+ * records       (batch) records of 656 bytes, 8-byte aligned, one per scan, little endian, no padding beyond what is named:
+ *                 u32 seed_lo, u32 seed_hi   the sample's 64-bit seed
+ *                 i32 n_ops                  0 ... 8 ops, run in order
+ *                 i32 flags                  bit 0: the scan's output order is that of the order hash (a shuffle or a
+ *                                            decimate was drawn); otherwise the scan keeps its input order
+ *                 8 x op (80 bytes each):    i32 code, u32 arg, f64 p[9]
+ *               op codes: 0 none; 1 linear, p[0..3] = a00 a01 a10 a11; 2 jitter, p[0] = magnitude, p[1..4] = std of
+ *               x y z intensity, p[5..8] = max_delta of x y z intensity (+inf = no clip); 3 drop, arg = T;
+ *               4 shuffle (sets nothing on a point: flags bit 0 carries it); 5 decimate, arg = k >= 1.
+ * the ops       The value of a point lives in f32 between ops.  f64 arithmetic has one rounding per operation, no
+ *               contraction.
+ *                 linear   x' = (f32)(a00 * (f64)x + a01 * (f64)y), y' = (f32)(a10 * (f64)x + a11 * (f64)y), both from the
+ *                          old x, y; z, intensity untouched.
+ *                 jitter   per component c < dim: d = std_c * (f64)n_c, clipped to [-max_delta_c, max_delta_c];
+ *                          v_c = (f32)((f64)v_c + magnitude * d); then, dim = 4, intensity clamped to [0, 1] in f32.
+ *                 drop     the point is kept iff (draw(slot, idx, 0, 0) >> 8) >= T, T = ceil(p * 2^24) clamped to 0 ... 2^24.
+ * the draws     with pcg(v): s = v * 747796405 + 2891336453; w = ((s >> ((s >> 28) + 4)) ^ s) * 277803737;
+ *               pcg = (w >> 22) ^ w (all u32, wrapping):
+ *                 stream(slot)            = pcg(seed_lo ^ pcg(seed_hi + slot * 0x9E3779B9))
+ *                 draw(slot, idx, c, j)   = pcg(stream(slot) + (idx * 8 + c * 2 + j))
+ *               slot = the op's position in the list (0 ... 7; 8 = the order hash), idx = the point's ORIGINAL index within
+ *               its scan, c = component, j = 0 / 1.  A result therefore depends neither on the launch shape nor on what
+ *               other scans share the batch.  The standard normal of (slot, idx, c), all in f32 with the full-precision
+ *               logf / sqrtf / cosf:  u1 = ((draw(.., 0) >> 8) + 1) * 2^-24, u2 = (draw(.., 1) >> 8) * 2^-24,
+ *               n = sqrtf(-2 * logf(u1)) * cosf(6.283185307179586f * u2);  |n| <= 5.77.
+ * mode          0: no point is removed or moved; drop / shuffle / decimate ops are ignored; no workspace needed.
+ *               1: drops only: the kept points of every scan in input order (count, scan, scatter: stable compaction).
+ *               2: order and selection by one stable radix sort (batch <= 63 and n_points < 2^26 are required).  Key of
+ *                  a kept point = scan << 26 | (draw(8, idx, 0, 0) >> 6) when flags bit 0 is set, else scan << 26 | idx; a
+ *                  dropped point has the key batch << 26.  Ties keep input order: a shuffle is uniform up to the
+ *                  ~n^2 / 2^27 expected pairs of equal 26-bit hashes (107 at 120 000 points), which stay in input order.
+ *                  The key's hash bits do not depend on the batch, so a scan comes out the same alone or beside others.  Of the m
+ *                  survivors of a scan the first keep are written, keep = m passed through ceil(keep / k) once per
+ *                  decimate op, in op order: a uniform random subset in random order, the reference's pc[randperm][::k]
+ *                  in distribution.  A drop counts wherever it stands in the list: all drops act before the decimates.
+ *               The caller passes the smallest mode that covers the ops of the batch.
+ * out           (n_points, dim) f32: the output scans concatenated, the first out_offsets[batch] rows are written
+ * out_offsets   (batch + 1) i32, out_counts (batch) i32: written on the device in every mode
+ * workspace     mbv_augment_workspace_bytes(n_points, batch, mode) bytes (0 = bad arguments), 256-byte aligned.
+ * MBV_ERR_UNSUPPORTED: n_points >= 2^28, or mode 2 with n_points >= 2^26 or batch > 63.  No atomics: the output is a pure function of
+ * the inputs.
+ *
+ * mbv_warp_instance_maps — the cached-map path: maps (batch, nx, ny) i32 → out (batch, nx, ny) i32 (out != maps), mats
+ * (batch, 4) f64 = a00 a01 a10 a11 of every sample's composed matrix A (flips and rotations in op order, original →
+ * augmented; orthogonal, so its inverse is its transpose); cx = -x_lo / voxel_size, cy = -y_lo / voxel_size: the cell
+ * coordinate of the origin.  For every output cell, in f64, one rounding per operation:
+ *   du = (ix + 0.5) - cx;  dv = (iy + 0.5) - cy;  su = (a00 * du + a10 * dv) + cx;  sv = (a01 * du + a11 * dv) + cy;
+ *   out[ix, iy] = maps[floor(su), floor(sv)], 0 where that lies outside the grid.
+ * A flip on a symmetric range is exactly the reference's mask[::-1, :] / mask[:, ::-1] (:52, :55); on an asymmetric range
+ * it mirrors about the origin's cell, as the flipped points do, and cells from outside the grid arrive as 0.  A rotation is
+ * nearest-neighbour about the origin; the reference's cv2.warpAffine(INTER_NEAREST) turns about (sx / 2, sy / 2) in
+ * integer-centred pixel coordinates, half a cell away: parity with OpenCV is not pinned by any test.
+ */
+size_t mbv_augment_workspace_bytes(int64_t n_points, int32_t batch, int32_t mode);
+int mbv_augment_points(const float* points, int32_t dim, int64_t n_points, const int32_t* scan_offsets, int32_t batch,
+                       const void* records, int32_t mode, float* out, int32_t* out_offsets, int32_t* out_counts,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int mbv_warp_instance_maps(const int32_t* maps, const double* mats, int32_t batch, int32_t nx, int32_t ny, double cx,
+                           double cy, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,16 +133,22 @@ def instance_targets(instance_maps: torch.Tensor, num_queries: int, min_num_inst
 class InstanceMapCollate:
     """Collate of ``(point_cloud (N, pc_dim) f32 array/tensor, instance_map (nx, ny) int array/tensor[, metadata])``
     samples into the batch ``MaskBevModule.training_step`` takes — the reference's ``MaskListCollate[Height]``
-    (semantic_kitti_transforms.py:98-121) with the masks built on ``device`` by K14."""
+    (semantic_kitti_transforms.py:98-121) with the masks built on ``device`` by K14.  ``augmentation``: an
+    ``augment.DeviceAugmentation`` (built with the grid's ranges and voxel size) applied on the device to the scans and,
+    through K23c, to the maps before the targets are made; ``None``: none."""
 
-    def __init__(self, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False):
+    def __init__(self, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False, augmentation=None):
         self.num_queries, self.device = num_queries, torch.device(device)
         self.min_num_inst_pixels, self.packed = min_num_inst_pixels, packed
+        self.augmentation = augmentation
 
     def __call__(self, batch: Sequence):
         pcs = [torch.as_tensor(s[0], dtype=torch.float32).to(self.device, non_blocking=True) for s in batch]
         maps = torch.stack([torch.as_tensor(np.asarray(s[1])).to(torch.int32) for s in batch]).to(self.device,
                                                                                                    non_blocking=True)
+        if self.augmentation is not None:
+            aug = self.augmentation.apply(pcs, instance_maps=maps)
+            pcs, maps = aug.scans, aug.instance_maps
         labels, masks = instance_targets(maps, self.num_queries, self.min_num_inst_pixels, self.packed)
         if len(batch[0]) > 2:
             return pcs, (labels, masks), [s[2] for s in batch]
@@ -155,11 +161,15 @@ class SceneCollate:
     transforms that take them into its frame — into the batch ``MaskBevModule.training_step`` takes.  Beside
     :class:`InstanceMapCollate`: instead of a cached instance map, the scene is rasterised on ``device`` (K22,
     ``rasterize.SemanticKittiRasterizer``) and the maps go to K14, so no mask cache is needed and a point-level
-    augmentation of the scene can come first."""
+    augmentation of the scene can come first: ``augmentation`` (an ``augment.DeviceAugmentation``, ``None``: none) runs on
+    the scans (K23a / b) and its flips and rotations are folded into the scene's transforms, ``diag(A, 1, 1) @ tf``, so the
+    map is rasterised from the rotated scene itself and no map is warped."""
 
-    def __init__(self, rasterizer, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False):
+    def __init__(self, rasterizer, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False,
+                 augmentation=None):
         self.rasterizer, self.num_queries, self.device = rasterizer, num_queries, torch.device(device)
         self.min_num_inst_pixels, self.packed = min_num_inst_pixels, packed
+        self.augmentation = augmentation
 
     def _up(self, t, dtype=None):
         t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t)
@@ -171,9 +181,13 @@ class SceneCollate:
 
     def __call__(self, batch: Sequence):
         pcs = [torch.as_tensor(s[0], dtype=torch.float32).to(self.device, non_blocking=True) for s in batch]
+        scene_tfs = [s[1][2] for s in batch]
+        if self.augmentation is not None:
+            aug = self.augmentation.apply(pcs, scene_transforms=scene_tfs)
+            pcs, scene_tfs = aug.scans, aug.scene_transforms
         scenes = []
-        for s in batch:
-            points, inst, transforms, centre = s[1]
+        for s, transforms in zip(batch, scene_tfs):
+            points, inst, _, centre = s[1]
             scenes.append(([self._up(p) for p in points],
                            [self._up(np.asarray(i).astype(np.int64) if not isinstance(i, torch.Tensor) else i, torch.int32)
                             for i in inst], transforms,

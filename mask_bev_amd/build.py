@@ -29,6 +29,8 @@ FILE_FLAGS = {
     'scatter_layernorm.hip': ['-ffp-contract=off'],
     # K22's f64 transform and `(x - lo) / vs` decide a cell index: one rounding per operation, as numpy does them
     'rasterize.hip': ['-ffp-contract=off'],
+    # K23's f64 linear op, jitter sum and map warp: one rounding per operation, as the numpy restatement does them
+    'augment.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

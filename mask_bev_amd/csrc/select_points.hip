@@ -10,6 +10,7 @@
 // The SET of selected points equals top-k's; their order differs, which no consumer depends on (the loss sums).
 #include "common.hpp"
 #include "bilinear.hpp"
+#include "rng.hpp"
 
 namespace {
 
@@ -133,11 +134,7 @@ constexpr int kFusedWaves = kFusedThreads / 64;
 // RNG = true the candidate coordinates are generated where they are consumed — once for sampling, once more in
 // the compaction — instead of being drawn by torch.rand into a 1.2 GB tensor, read, and read again.  The same
 // generator filled into a tensor by mbv_uniform_points gives the tests an exact two-kernel reference.
-__device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
-  const uint32_t s = v * 747796405u + 2891336453u;
-  const uint32_t w = ((s >> ((s >> 28u) + 4u)) ^ s) * 277803737u;
-  return (w >> 22u) ^ w;
-}
+// (pcg_hash: rng.hpp)
 __device__ __forceinline__ uint32_t row_stream(int64_t seed, int64_t row) {
   return pcg_hash((uint32_t)seed ^ pcg_hash((uint32_t)(seed >> 32) + (uint32_t)row * 0x9E3779B9u + (uint32_t)(row >> 32)));
 }

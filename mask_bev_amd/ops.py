@@ -15,6 +15,7 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_loss       K8 point sampling, K9 Hungarian, K10 importance sampling, K13 loss rows / costs
     ops_instances  K21 query selection + BEV mask / instance-map extraction at inference
     ops_rasterize  K22 SemanticKITTI scene -> instance-id map (binning, close + open, paint)
+    ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403
@@ -26,3 +27,4 @@ from .ops_norm import *            # noqa: F401,F403
 from .ops_loss import *            # noqa: F401,F403
 from .ops_instances import *       # noqa: F401,F403
 from .ops_rasterize import *       # noqa: F401,F403
+from .ops_augment import *         # noqa: F401,F403

@@ -2,11 +2,11 @@
 ``SemanticKittiRasterizer`` (mask_bev/datasets/semantic_kitti/semantic_kitti_rasterizer.py) does on the host with numpy
 and one OpenCV call pair per instance, and therefore caches on disk.  The map is the input of ``batch.instance_targets``
 (K14), so a training step needs neither the reference's cache nor OpenCV, and a scene can be rasterised after a
-point-level augmentation.
+point-level augmentation: ``augment.DeviceAugmentation`` (K23) folds its flips and rotations into ``transforms``.
 
 Where two closed-and-opened instances claim one cell the HIGHEST ID wins (the reference paints in the hash order of a
 Python set); everywhere else the map equals the reference's.  Not covered: the KITTI / Waymo box rasterisers
-(``cv2.drawContours``), the approximate scene branch, the mask augmentations.
+(``cv2.drawContours``), the approximate scene branch.
 """
 from __future__ import annotations
 

@@ -447,6 +447,13 @@ MODELS: Dict[str, Callable[[tuple], Work]] = {
     'mbv_groupnorm_bwd': lambda a: _groupnorm(a, True),
     'mbv_merge_layernorm_fwd': lambda a: _merge_ln(a, False),
     'mbv_merge_layernorm_bwd': lambda a: _merge_ln(a, True),
+    # K23 (points, dim, n, offsets, batch, records, mode, ...): points read and written once; mode 1 / 2 stage them (one more
+    # write + read) beside 8 B of flags and their scan per point; mode 2 sorts 8 B pairs in four passes (read + write each)
+    'mbv_augment_points': lambda a: ('k_augment_points', 'hbm',
+                                     _i(a[2]) * (_i(a[1]) * 4.0 * (2.0 if _i(a[6]) == 0 else 4.0)
+                                                 + (0.0, 12.0, 12.0 + 8.0 * (1 + 2 * 4))[_i(a[6])]), 0.0),
+    # K23c (maps, mats, batch, nx, ny, ...): every cell read and written once
+    'mbv_warp_instance_maps': lambda a: ('k_warp_maps', 'hbm', _i(a[2]) * _i(a[3]) * _i(a[4]) * 8.0, 0.0),
     'mbv_colsum_accum': lambda a: ('k_colsum', 'hbm', _i(a[2]) * _i(a[3]) * (2.0 if _i(a[1]) else 4.0), 0.0),
     'mbv_match_cost_terms': lambda a: ('k_match_cost_terms', 'hbm', _i(a[1]) * _i(a[2]) * _i(a[3]) * 16.0, 0.0),
     'mbv_match_cost': lambda a: ('k_match_cost', 'hbm',

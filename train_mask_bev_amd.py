@@ -18,7 +18,8 @@ Data (the reference's DataModules, /root/reference: train_mask_bev.py:68-83, are
 ``dataset: synthetic`` (or ``--synthetic``) draws SemanticKITTI-shaped scans and box masks on the GPU
 (mask_bev_amd/synthetic.py); ``dataset: semantic-kitti`` reads ``<root>/sequences/SS/velodyne/*.bin`` with the
 instance-map cache ``<root>/sequences/SS/mask_cache/*.npy`` the reference's mask dataset writes
-(semantic_kitti_mask_dataset.py:121-137) and builds the (labels, masks) targets on the GPU (batch.py, K14).
+(semantic_kitti_mask_dataset.py:121-137) and builds the (labels, masks) targets on the GPU (batch.py, K14).  The config's
+``augmentations:`` list is applied to the training batches on the GPU (mask_bev_amd/augment.py, K23), never to validation.
 """
 from __future__ import annotations
 
@@ -72,12 +73,26 @@ class SyntheticBatches:
         return scans, (labels, masks)
 
 
-class SemanticKittiCacheBatches:
-    """``.bin`` scans + the reference's ``.npy`` instance-map cache; targets are expanded on the GPU (K14)."""
+def build_augmentation(config):
+    """The config's ``augmentations:`` list (the reference's SemanticKITTI configurations carry one) as an on-device
+    augmentation (K23), ``None`` without one."""
+    spec = config.get('augmentations')
+    if not spec:
+        return None
+    from mask_bev_amd.augment import DeviceAugmentation, make_semantic_kitti_augmentation_list
+    return DeviceAugmentation(make_semantic_kitti_augmentation_list(spec), int(config.get('seed', 420)),
+                              config['x_range'], config['y_range'], config['voxel_size'])
 
-    def __init__(self, config, device, rank, world, root, sequences):
+
+class SemanticKittiCacheBatches:
+    """``.bin`` scans + the reference's ``.npy`` instance-map cache; targets are expanded on the GPU (K14).  ``augment``:
+    apply the config's ``augmentations:`` (training batches only), seeded from (seed, rank, epoch, batch index)."""
+
+    def __init__(self, config, device, rank, world, root, sequences, augment=False):
         from mask_bev_amd import batch as B
         self.B, self.device = B, device
+        self.rank, self.seed = rank, int(config.get('seed', 420))
+        self.augmentation = build_augmentation(config) if augment else None
         files = []
         for seq in sequences:
             d = pathlib.Path(root) / 'sequences' / f'{int(seq):02d}'
@@ -92,7 +107,7 @@ class SemanticKittiCacheBatches:
         self.files = files[rank:usable:world]
         self.bsz = bsz
         self.collate = B.InstanceMapCollate(int(config['num_queries']), device,
-                                            int(config.get('min_num_inst_pixels', 0)))
+                                            int(config.get('min_num_inst_pixels', 0)), augmentation=self.augmentation)
         self.shuffle = bool(config.get('shuffle_train', True))
 
     def __len__(self):
@@ -109,6 +124,8 @@ class SemanticKittiCacheBatches:
             pc = torch.from_numpy(self.B.read_velodyne_bin(self.files[j][0]))
             pc = pc[torch.randperm(pc.shape[0])]                     # ShufflePointCloud (semantic_kitti_transforms.py:58-61)
             samples.append((pc, self.B.read_mask_cache(self.files[j][1])))
+        if self.augmentation is not None:
+            self.augmentation.reseed(self.seed, self.rank, epoch, i)
         return self.collate(samples)
 
 
@@ -190,7 +207,7 @@ def main(argv=None):
         val = None
     elif dataset_name == 'semantic-kitti':
         data = SemanticKittiCacheBatches(config, device, rank, world, args.data_root,
-                                         config.get('train_sequences', [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]))
+                                         config.get('train_sequences', [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]), augment=True)
         val = SemanticKittiCacheBatches(dict(config, shuffle_train=False), device, rank, world, args.data_root,
                                         config.get('val_sequences', [8])) if limit_val_batches > 0 else None
     else:
