@@ -1208,7 +1208,8 @@ int mbv_rasterize_paint(const uint32_t* occupancy, const int32_t* bbox, const in
  *                 8 x op (80 bytes each):    i32 code, u32 arg, f64 p[9]
  *               op codes: 0 none; 1 linear, p[0..3] = a00 a01 a10 a11; 2 jitter, p[0] = magnitude, p[1..4] = std of
  *               x y z intensity, p[5..8] = max_delta of x y z intensity (+inf = no clip); 3 drop, arg = T;
- *               4 shuffle (sets nothing on a point: flags bit 0 carries it); 5 decimate, arg = k >= 1.
+ *               4 shuffle (sets nothing on a point: flags bit 0 carries it); 5 decimate, arg = k >= 1;
+ *               6 global noise, p[0] = scale, p[1..3] = translation of x y z (kitti_mask_augmentations.py:196-217).
  * the ops       The value of a point lives in f32 between ops.  f64 arithmetic has one rounding per operation, no
  *               contraction.
  *                 linear   x' = (f32)(a00 * (f64)x + a01 * (f64)y), y' = (f32)(a10 * (f64)x + a11 * (f64)y), both from the
@@ -1216,6 +1217,7 @@ int mbv_rasterize_paint(const uint32_t* occupancy, const int32_t* bbox, const in
  *                 jitter   per component c < dim: d = std_c * (f64)n_c, clipped to [-max_delta_c, max_delta_c];
  *                          v_c = (f32)((f64)v_c + magnitude * d); then, dim = 4, intensity clamped to [0, 1] in f32.
  *                 drop     the point is kept iff (draw(slot, idx, 0, 0) >> 8) >= T, T = ceil(p * 2^24) clamped to 0 ... 2^24.
+ *                 global noise   v_c = (f32)((f64)v_c * scale + t_c) for c = x, y, z; intensity untouched.
  * the draws     with pcg(v): s = v * 747796405 + 2891336453; w = ((s >> ((s >> 28) + 4)) ^ s) * 277803737;
  *               pcg = (w >> 22) ^ w (all u32, wrapping):
  *                 stream(slot)            = pcg(seed_lo ^ pcg(seed_hi + slot * 0x9E3779B9))
@@ -1259,6 +1261,37 @@ int mbv_augment_points(const float* points, int32_t dim, int64_t n_points, const
                        void* workspace, size_t workspace_bytes, void* stream);
 int mbv_warp_instance_maps(const int32_t* maps, const double* mats, int32_t batch, int32_t nx, int32_t ny, double cx,
                            double cy, int32_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K24 — KITTI / Waymo box tables → instance-id maps (csrc/box_rasterize.hip): the input of K14 for the box datasets.
+ * Replaces: the paint loop of KittiRasterizer.get_mask (mask_bev/datasets/kitti/kitti_rasterizer.py:45-56) and of
+ * WaymoRasterizer.get_mask (mask_bev/datasets/waymo/waymo_rasterizer.py:38-45): one cv2.drawContours(..., -1) per box on
+ * the host.  The corners are made on the host (rasterize.box_vertices: the reference's f64 expressions and np.intp).
+ *
+ * vertices      (n_boxes, 4, 2) i32, 16-byte aligned: v0 .. v3 of every box in cell coordinates (px, py), px along x.
+ *               |coordinate| <= 2^20; a box with a vertex beyond that paints nothing.
+ * ids           (n_boxes) i32: the value a box paints
+ * frame_offsets (batch + 1) i32 on the device, ascending from 0; frame b owns rows frame_offsets[b] .. frame_offsets[b + 1]
+ *               - 1, frame_offsets[batch] = n_boxes.  An empty frame is valid.  Rows outside 0 .. frame_offsets[batch]
+ *               are never read.
+ * maps          (batch, nx, ny) i32, ny contiguous: the layout of K14's input.  EVERY cell is written: 0 where no box of
+ *               the frame holds it, else the id of the LAST box in table order that does (the reference's overwrite).
+ * the fill rule A cell (px, py) belongs to a box iff it is in I or in L; cells outside the grid are dropped.
+ *                 I  the integer point lies inside or on the closed quadrilateral: on an edge (cross product 0, inside
+ *                    the edge's bounding box), or a ray towards +x crosses an odd number of edges: edge a → b is crossed
+ *                    iff (ay > py) != (by > py) and cross = (bx - ax)(py - ay) - (by - ay)(px - ax) is > 0 for by > ay,
+ *                    < 0 for by < ay.  64-bit products; either vertex order; a folded quadrilateral fills even-odd.
+ *                 L  the point is on the line between two consecutive vertices (v3 → v0 included): dx = bx - ax,
+ *                    dy = by - ay, n = max(|dx|, |dy|), the points (ax + floor((2 i dx + n) / (2 n)),
+ *                    ay + floor((2 i dy + n) / (2 n))), i = 0 .. n; n = 0: the single point.
+ *               All arithmetic is integer: the map is a pure function of the table.  Parity with OpenCV's fill is NOT
+ *               pinned by any test: drawContours draws the outline with its own line iterator and fills spans in 16-bit
+ *               fixed point, so tie cells on an edge may differ.
+ * One launch, no workspace, no host synchronisation, nothing to pre-zero.  MBV_ERR_BAD_ARG: a null pointer, batch outside
+ * 1 .. 65535, nx or ny < 1, nx * ny > 2^26, nx > 16 * 65535, vertices not 16-byte aligned; nothing is launched.
+ */
+int mbv_rasterize_boxes(const int32_t* vertices, const int32_t* ids, const int32_t* frame_offsets, int32_t batch,
+                        int32_t nx, int32_t ny, int32_t* maps, void* stream);
 
 #ifdef __cplusplus
 }

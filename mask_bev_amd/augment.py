@@ -1,6 +1,6 @@
-"""Training augmentations of SemanticKITTI samples on the device (K23, csrc/augment.hip): the reference's
-``mask_bev/augmentations/semantic_kitti_mask_augmentations.py`` — same names, same keyword arguments, same magnitude rules
-— with the per-sample decisions (which transform fires, the angle, one 64-bit seed) drawn on the host from a seeded
+"""Training augmentations of SemanticKITTI, KITTI and Waymo samples on the device (K23, csrc/augment.hip): the reference's
+``mask_bev/augmentations/semantic_kitti_mask_augmentations.py``, ``kitti_mask_augmentations.py`` and
+``waymo_mask_augmentations.py`` — same names, same keyword arguments, same magnitude rules — with the per-sample decisions (which transform fires, the angle, one 64-bit seed) drawn on the host from a seeded
 generator and everything per point or per cell done by three kernels.
 
     aug = DeviceAugmentation(make_semantic_kitti_augmentation_list(config['augmentations']), seed=420,
@@ -8,6 +8,13 @@ generator and everything per point or per cell done by three kernels.
     aug.reseed(seed, rank, epoch, batch_index)
     out = aug.apply(scans, instance_maps=maps)            # cached maps: warped by K23c
     out = aug.apply(scans, scene_transforms=[tf, ...])    # scenes: diag(A, 1, 1) @ tf, rasterised afterwards (K22)
+    out = aug.apply(scans, boxes=[(n, 7) f64, ...])       # box tables: moved on the host, rasterised afterwards (K24)
+
+Boxes [cx, cy, cz, l, w, h, theta] follow the points: a linear op acts on the centre; theta changes as the reference changes
+``rotation_y`` / ``heading`` — a rotation adds its angle, the KITTI y-flip negates it, the Waymo y-flip LEAVES the heading
+as it is (waymo_mask_augmentations.py:54-59 mirrors ``center_y`` only; restated, not repaired); ``global_noise`` scales
+centre and dimensions and shifts the centre.  ``object_sample`` (needs the dataset's ``samples.pkl``) and ``object_noise``
+(mmdet3d's numba collision search) are not provided and raise ``NotImplementedError``.
 
 Differences from the reference: a rotated map turns about the origin's cell, not about OpenCV's
 (sx / 2, sy / 2) pixel; flips mirror about the origin also on an asymmetric range; a shuffle orders points by a 26-bit hash
@@ -27,7 +34,7 @@ from . import ops_augment
 from ._lib import MaskBevHipError
 
 MAX_OPS = 8
-OP_LINEAR, OP_JITTER, OP_DROP, OP_SHUFFLE, OP_DECIMATE = 1, 2, 3, 4, 5
+OP_LINEAR, OP_JITTER, OP_DROP, OP_SHUFFLE, OP_DECIMATE, OP_GLOBAL_NOISE = 1, 2, 3, 4, 5, 6
 
 # one scan's record as the kernels read it (include/maskbev_hip.h, K23): 656 bytes
 OP_DTYPE = np.dtype([('code', '<i4'), ('arg', '<u4'), ('p', '<f8', (9,))])
@@ -39,6 +46,19 @@ class Op(NamedTuple):
     code: int
     arg: int = 0
     p: Tuple[float, ...] = ()
+
+
+class LinearOp(Op):
+    """A linear ``Op`` — the same 3-tuple to records, comparisons and unpacking — that also says, on the host only, what it
+    does to a box's theta: theta' = heading[0] * theta + heading[1] (a rotation: (1, angle); a mirror: (-1, 0) or (-1, pi);
+    the Waymo y-flip: (1, 0)).  A plain linear ``Op`` turns theta with the mapped direction vector."""
+    heading: Tuple[float, float] = (1., 0.)
+
+
+def linear_op(p, heading) -> LinearOp:
+    op = LinearOp(OP_LINEAR, 0, tuple(p))
+    op.heading = (float(heading[0]), float(heading[1]))
+    return op
 
 
 def drop_threshold(p: float) -> int:
@@ -58,10 +78,37 @@ class Flip:
     def draw(self, rng: np.random.Generator, magnitude: float = 1) -> List[Op]:
         ops = []
         if rng.uniform(0, 1) < self._prob_flip_x * magnitude:
-            ops.append(Op(OP_LINEAR, 0, (-1., 0., 0., 1.)))
+            ops.append(linear_op((-1., 0., 0., 1.), (-1., math.pi)))
         if rng.uniform(0, 1) < self._prob_flip_y * magnitude:
-            ops.append(Op(OP_LINEAR, 0, (1., 0., 0., -1.)))
+            ops.append(linear_op((1., 0., 0., -1.), self._heading_flip_y))
         return ops
+
+    _heading_flip_y = (-1., 0.)
+
+
+class KittiFlip(Flip):
+    """kitti_mask_augmentations.py:55-71: y only; ``rotation_y`` is negated.  One uniform is drawn."""
+
+    def __init__(self, prob_flip_x: float = 0, prob_flip_y: float = 0.5):
+        if prob_flip_x != 0:
+            raise ValueError('Cannot flip in x')
+        super().__init__(0, prob_flip_y)
+
+    def draw(self, rng, magnitude: float = 1) -> List[Op]:
+        if rng.uniform(0, 1) < self._prob_flip_y * magnitude:
+            return [linear_op((1., 0., 0., -1.), self._heading_flip_y)]
+        return []
+
+
+class WaymoFlip(Flip):
+    """waymo_mask_augmentations.py:38-59: y only, two uniforms drawn (the first decides nothing), ``center_y`` mirrored and
+    the heading left as it is."""
+    _heading_flip_y = (1., 0.)
+
+    def __init__(self, prob_flip_x: float = 0, prob_flip_y: float = 0.5):
+        if prob_flip_x != 0:
+            raise ValueError('Cannot flip in x')
+        super().__init__(0, prob_flip_y)
 
 
 class ShufflePoints:
@@ -88,7 +135,7 @@ class RandomRotate:
 
 def rotation_op(theta_deg: float) -> Op:
     c, s = float(np.cos(np.deg2rad(theta_deg))), float(np.sin(np.deg2rad(theta_deg)))
-    return Op(OP_LINEAR, 0, (c, -s, s, c))
+    return linear_op((c, -s, s, c), (1., float(np.deg2rad(theta_deg))))
 
 
 class DecimatePoints:
@@ -139,6 +186,19 @@ class RandomDropPoints:
         return [Op(OP_DROP, drop_threshold(self._per_point_drop_prob * magnitude))]
 
 
+class GlobalNoise:
+    """kitti_mask_augmentations.py:196-217: ALWAYS applied (``prob_aug`` is stored and never read there); one N(0,
+    ``trans_std``) translation of x, y, z, then one scale in ``1 ± scale_delta``, drawn in that order."""
+
+    def __init__(self, prob_aug: float, trans_std: float = 0.2, scale_delta: float = 0.05):
+        self._prob_aug, self._trans_std, self._scale_delta = prob_aug, trans_std, scale_delta
+
+    def draw(self, rng, magnitude: float = 1) -> List[Op]:
+        noise = rng.standard_normal((3,)) * self._trans_std
+        scale = rng.uniform(1 - self._scale_delta, 1 + self._scale_delta)
+        return [Op(OP_GLOBAL_NOISE, 0, (float(scale),) + tuple(float(v) for v in noise))]
+
+
 class RandAugment:
     """``num_augments`` of ``transforms`` drawn with replacement, each run at ``magnitude`` (rand_augment.py)."""
 
@@ -156,22 +216,69 @@ _CONSTRUCTORS = {'flip': Flip, 'shuffle': ShufflePoints, 'rotate': RandomRotate,
                  'jitter': JitterPoints, 'drop': RandomDropPoints}
 
 
-def make_augmentation(args: Dict):
+_KITTI_CONSTRUCTORS = dict(_CONSTRUCTORS, flip=KittiFlip, global_noise=GlobalNoise)
+_WAYMO_CONSTRUCTORS = dict(_CONSTRUCTORS, flip=WaymoFlip)
+_NOT_PROVIDED = {
+    'cut_pc': 'cut_pc is not implemented (in the reference it calls a tuple: a dead path)',
+    'object_sample': 'object_sample is not implemented: it pastes objects from the dataset\'s samples.pkl, which this package '
+                     'neither reads nor writes',
+    'object_noise': 'object_noise is not implemented: it is mmdet3d\'s numba collision search (noise_per_object_v3_)',
+}
+
+
+def make_augmentation(args: Dict, constructors: Optional[Dict] = None, rand_augment: bool = True):
+    constructors = _CONSTRUCTORS if constructors is None else constructors
     name = args.get('name')
     if name == 'rand_augment':
-        return RandAugment(args.get('num_augments'), make_semantic_kitti_augmentation_list(args.get('transforms')),
-                           args.get('magnitude'))
-    if name == 'cut_pc':
-        raise NotImplementedError('cut_pc is not implemented (in the reference it calls a tuple: a dead path)')
-    if name not in _CONSTRUCTORS:
+        if not rand_augment:
+            raise NotImplementedError('rand augment')                 # waymo_mask_augmentations.py:25-26
+        return RandAugment(args.get('num_augments'),
+                           [make_augmentation(a, constructors) for a in args.get('transforms')], args.get('magnitude'))
+    if name in _NOT_PROVIDED and name not in constructors:
+        raise NotImplementedError(_NOT_PROVIDED[name])
+    if name not in constructors:
         raise NotImplementedError(f'{name} is not implemented')
     kwargs = copy.copy(args)
     kwargs.pop('name')
-    return _CONSTRUCTORS[name](**kwargs)
+    return constructors[name](**kwargs)
 
 
 def make_semantic_kitti_augmentation_list(augmentations: List[Dict]) -> List:
     return [make_augmentation(aug) for aug in augmentations]
+
+
+def make_kitti_augmentation_list(augmentations: List[Dict]) -> List:
+    """kitti_mask_augmentations.py:19-52: the SemanticKITTI names with the y-only ``flip``, plus ``global_noise``."""
+    return [make_augmentation(aug, _KITTI_CONSTRUCTORS) for aug in augmentations]
+
+
+def make_waymo_augmentation_list(augmentations: List[Dict]) -> List:
+    """waymo_mask_augmentations.py:11-35: the six point transforms with the y-only ``flip`` that keeps the heading; no
+    ``rand_augment``, no magnitudes."""
+    return [make_augmentation(aug, _WAYMO_CONSTRUCTORS, rand_augment=False) for aug in augmentations]
+
+
+def transform_boxes(boxes, ops: Sequence[Op]) -> np.ndarray:
+    """One sample's ``boxes`` (n, 7) f64 [cx, cy, cz, l, w, h, theta] under its ``ops``, in op order, as the reference moves
+    its labels (kitti_mask_augmentations.py:67-71,118-123,209-214): a linear op maps the centre's x, y and sets theta by
+    the op's ``heading`` rule (``LinearOp``); global noise scales centre and dimensions, then shifts the centre.  Other ops act on points
+    only."""
+    boxes = np.array(boxes, dtype=np.float64).reshape(-1, 7)
+    for op in ops:
+        if op.code == OP_LINEAR:
+            a = np.array(op.p[:4], dtype=np.float64).reshape(2, 2)
+            c, s = np.cos(boxes[:, 6]), np.sin(boxes[:, 6])
+            x, y = boxes[:, 0].copy(), boxes[:, 1].copy()
+            boxes[:, 0], boxes[:, 1] = a[0, 0] * x + a[0, 1] * y, a[1, 0] * x + a[1, 1] * y
+            heading = getattr(op, 'heading', None)
+            if heading is not None:
+                boxes[:, 6] = heading[0] * boxes[:, 6] + heading[1]
+            else:
+                boxes[:, 6] = np.arctan2(a[1, 0] * c + a[1, 1] * s, a[0, 0] * c + a[0, 1] * s)
+        elif op.code == OP_GLOBAL_NOISE:
+            boxes[:, :6] *= op.p[0]
+            boxes[:, :3] += np.array(op.p[1:4], dtype=np.float64)
+    return boxes
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -226,6 +333,7 @@ class AugmentedBatch(NamedTuple):
     draws: List[SampleDraw]
     offsets: torch.Tensor                           # (B + 1) i32 on the device
     synced: bool
+    boxes: Optional[List[np.ndarray]] = None        # per sample (n, 7) f64, moved with the points
 
 
 class DeviceAugmentation:
@@ -253,7 +361,8 @@ class DeviceAugmentation:
 
     @torch.no_grad()
     def apply(self, scans: Sequence[torch.Tensor], instance_maps: Optional[torch.Tensor] = None,
-              scene_transforms: Optional[Sequence] = None, draws: Optional[Sequence[SampleDraw]] = None) -> AugmentedBatch:
+              scene_transforms: Optional[Sequence] = None, draws: Optional[Sequence[SampleDraw]] = None,
+              boxes: Optional[Sequence] = None) -> AugmentedBatch:
         scans = list(scans)
         if len(scans) == 0:
             raise ValueError('empty batch')
@@ -267,6 +376,12 @@ class DeviceAugmentation:
         draws = self.draw(len(scans)) if draws is None else list(draws)
         if len(draws) != len(scans):
             raise ValueError(f'{len(draws)} draws for {len(scans)} scans')
+        if boxes is not None and len(boxes) != len(scans):
+            raise ValueError('one (n, 7) box table per scan expected')
+        if (instance_maps is not None or scene_transforms is not None) and \
+                any(op.code == OP_GLOBAL_NOISE for d in draws for op in d.ops):
+            raise ValueError('global_noise is not a linear map about the origin: it cannot be applied to instance maps or '
+                             'scene transforms (use box tables)')
         dev = scans[0].device
         counts = [int(s.shape[0]) for s in scans]
         offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
@@ -300,11 +415,14 @@ class DeviceAugmentation:
                 a4 = np.eye(4)
                 a4[:2, :2] = m
                 tfs.append(a4 @ tf.reshape(-1, 4, 4))                        # the last row stays 0 0 0 1
-        return AugmentedBatch(views, maps, tfs, list(draws), out_offsets, bool(mode))
+        moved = None if boxes is None else [transform_boxes(b, d.ops) for b, d in zip(boxes, draws)]
+        return AugmentedBatch(views, maps, tfs, list(draws), out_offsets, bool(mode), moved)
 
     __call__ = apply
 
 
-__all__ = ['make_augmentation', 'make_semantic_kitti_augmentation_list', 'DeviceAugmentation', 'AugmentedBatch', 'SampleDraw',
+__all__ = ['make_augmentation', 'make_semantic_kitti_augmentation_list', 'make_kitti_augmentation_list',
+           'make_waymo_augmentation_list', 'KittiFlip', 'WaymoFlip', 'GlobalNoise', 'LinearOp', 'linear_op', 'transform_boxes', 'OP_GLOBAL_NOISE',
+           'DeviceAugmentation', 'AugmentedBatch', 'SampleDraw',
            'Op', 'Flip', 'ShufflePoints', 'RandomRotate', 'DecimatePoints', 'JitterPoints', 'RandomDropPoints', 'RandAugment',
            'rotation_op', 'drop_threshold', 'pack_records', 'batch_mode', 'RECORD_DTYPE', 'MAX_OPS']

@@ -4,7 +4,9 @@ with the target construction moved to the GPU (K14, csrc/instance_masks.hip).
 
 Reference: mask_bev/datasets/semantic_kitti/semantic_kitti_dataset.py (``.bin`` / ``.label`` readers),
 semantic_kitti_mask_dataset.py:121-137 (``.npy`` mask cache), semantic_kitti_transforms.py:11-26,66-81,98-121
-(FilterSmallMasks, MaskToLabelInstanceMasks, MaskListCollate[Height]).
+(FilterSmallMasks, MaskToLabelInstanceMasks, MaskListCollate[Height]); for the box datasets
+mask_bev/datasets/kitti/kitti_dataset.py (``label_2`` / ``calib`` readers, camera → velodyne labels) and kitti_transforms.py
+(difficulty and range filters, FrameMaskListCollate), with the box table rasterised on the GPU (K24) in front of K14.
 
 What crosses PCIe per scan is the point cloud (1.9 MB) and the (nx, ny) int32 instance map (1 MB) instead of the
 dense (Q, ny, nx) f32 masks (105 MB).
@@ -82,6 +84,89 @@ def read_mask_cache(path) -> np.ndarray:
     semantic_kitti_mask_dataset.py:121-137)."""
     with open(str(path), 'rb') as f:
         return np.load(f)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# host readers of the KITTI object distribution (plain numpy; kitti_dataset.py)
+# ---------------------------------------------------------------------------------------------------------
+def read_kitti_label(path) -> dict:
+    """``label_2/NNNNNN.txt`` → the camera-frame labels as arrays over the n objects that are not DontCare
+    (kitti_dataset.py:157-176): ``type`` (n) int64 KittiType codes (indices into ``rasterize.KITTI_TYPES``), ``truncated``
+    (n), ``occluded`` (n) int64, ``alpha`` (n), ``bbox`` (n, 4), ``dimensions`` (n, 3) in the file's order, ``location``
+    (n, 3) in the camera frame, ``rotation_y`` (n)."""
+    from .rasterize import KITTI_TYPES
+    rows, types = [], []
+    with open(str(path), 'r') as f:
+        for line in f:
+            content = line.strip().split(' ')
+            if content == ['']:
+                continue
+            if content[0] not in KITTI_TYPES:
+                raise ValueError(f'{path}: unknown object type {content[0]!r}')
+            if content[0] == 'DontCare':
+                continue
+            types.append(KITTI_TYPES.index(content[0]))
+            rows.append([float(v) for v in content[1:15]])
+    a = np.array(rows, dtype=np.float64).reshape(-1, 14)
+    return {'type': np.array(types, dtype=np.int64), 'truncated': a[:, 0], 'occluded': a[:, 1].astype(np.int64),
+            'alpha': a[:, 2], 'bbox': a[:, 3:7], 'dimensions': a[:, 7:10], 'location': a[:, 10:13], 'rotation_y': a[:, 13]}
+
+
+def read_kitti_calib(path) -> dict:
+    """``calib/NNNNNN.txt`` → ``{'P0' … 'P3', 'R0_rect', 'Tr_velo_to_cam', 'Tr_imu_to_velo'}``, every matrix completed
+    to 4 x 4 as kitti_dataset.py:122-155 completes it (a last row 0 0 0 1; ``R0_rect`` in the upper-left 3 x 3)."""
+    calib = {}
+    with open(str(path), 'r') as f:
+        for line in f:
+            if ':' not in line:
+                continue
+            k, v = line.split(':', 1)
+            vals = np.array(v.split(), dtype=np.float64)
+            m = np.eye(4)
+            if k.strip() == 'R0_rect':
+                m[:3, :3] = vals[:9].reshape(3, 3)
+            else:
+                m[:3, :] = vals[:12].reshape(3, 4)
+            calib[k.strip()] = m
+    return calib
+
+
+def kitti_labels_to_velodyne(labels: dict, calib: dict) -> dict:
+    """Camera-frame labels → velodyne-frame labels (kitti_dataset.py:181-195): ``dimensions[[2, 0, 1]]`` = length, width,
+    height; location through ``inv(Tr_velo_to_cam)``; ``yaw = -rotation_y - pi / 2`` wrapped with ``arctan2``.  The result
+    keeps the other fields and adds ``boxes`` (n, 7) f64 [x, y, z, l, w, h, yaw], the rasteriser's table."""
+    c2v = np.linalg.inv(np.asarray(calib['Tr_velo_to_cam'], dtype=np.float64))
+    n = labels['location'].shape[0]
+    dimensions = labels['dimensions'][:, [2, 0, 1]]
+    location = np.zeros((n, 3))
+    yaw = np.zeros((n,))
+    for k in range(n):
+        tx, ty, tz = labels['location'][k]
+        location[k] = (c2v @ np.array([tx, ty, tz, 1]).T)[:3]
+        y = -labels['rotation_y'][k] - np.pi / 2
+        yaw[k] = np.arctan2(np.sin(y), np.cos(y))
+    out = dict(labels, dimensions=dimensions, location=location, rotation_y=yaw)
+    out['boxes'] = np.concatenate([location, dimensions, yaw[:, None]], axis=1).reshape(-1, 7)
+    return out
+
+
+def is_difficulty_valid(occluded, truncated) -> np.ndarray:
+    """kitti_transforms.py:48-61 over arrays: fully visible and truncated < 0.15, partly occluded and <= 0.3, or largely
+    occluded and <= 0.5."""
+    occ, trunc = np.asarray(occluded), np.asarray(truncated)
+    return ((occ == 0) & (trunc < 0.15)) | ((occ == 1) & (trunc <= 0.3)) | ((occ == 2) & (trunc <= 0.5))
+
+
+def object_range_mask(boxes, x_range, y_range) -> np.ndarray:
+    """``ObjectRangeFilter`` (kitti_transforms.py:199-219): the boxes whose centre lies in the closed x and y ranges."""
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 7)
+    return (x_range[0] <= boxes[:, 0]) & (boxes[:, 0] <= x_range[1]) & (y_range[0] <= boxes[:, 1]) & \
+           (boxes[:, 1] <= y_range[1])
+
+
+def select_labels(labels: dict, keep) -> dict:
+    """The labels of a frame where ``keep`` (a boolean mask or an index array) says so, field by field."""
+    return {k: v[keep] for k, v in labels.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -195,6 +280,41 @@ class SceneCollate:
                            self._up(np.asarray(centre).astype(np.int64) if not isinstance(centre, torch.Tensor) else centre,
                                     torch.int32)))
         maps = self.rasterizer.rasterize_batch(scenes)
+        labels, masks = instance_targets(maps, self.num_queries, self.min_num_inst_pixels, self.packed)
+        if len(batch[0]) > 2:
+            return pcs, (labels, masks), [s[2] for s in batch]
+        return pcs, (labels, masks)
+
+
+class BoxCollate:
+    """Collate of ``(point_cloud (N, pc_dim) f32 array/tensor, boxes (n, 7) f64 [cx, cy, cz, l, w, h, theta][, metadata])``
+    samples into the batch ``MaskBevModule.training_step`` takes — the reference's ``FrameMaskListCollate``
+    (kitti_transforms.py:117-128) behind ``FrameScanToMask`` and ``FrameMasksToLabelInstanceMasks``, with the boxes
+    rasterised on ``device`` (K24; ``rasterizer``: a ``rasterize.KittiRasterizer`` or ``WaymoRasterizer``, every box of a
+    sample counts as a vehicle) and the maps expanded by K14.  Every real instance gets the label ``CAR`` = 1:
+    ``KittiType.Car + 1`` there, ``TYPE_VEHICLE`` for Waymo.  ``augmentation`` (an ``augment.DeviceAugmentation``, ``None``:
+    none) runs on the scans (K23) and moves the boxes on the host before they are rasterised.  ``object_range`` =
+    ``(x_range, y_range)`` drops the boxes whose centre has left the closed ranges AFTER the augmentation, where the
+    reference's pipeline has its ObjectRangeFilter (kitti_data_module.py:84-86); ``None``: no such filter."""
+
+    def __init__(self, rasterizer, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False,
+                 augmentation=None, object_range=None):
+        self.rasterizer, self.num_queries, self.device = rasterizer, num_queries, torch.device(device)
+        self.min_num_inst_pixels, self.packed = min_num_inst_pixels, packed
+        self.augmentation, self.object_range = augmentation, object_range
+        if getattr(rasterizer, 'device', None) is None:
+            rasterizer.device = self.device
+
+    def __call__(self, batch: Sequence):
+        pcs = [torch.as_tensor(s[0], dtype=torch.float32).to(self.device, non_blocking=True) for s in batch]
+        boxes = [np.asarray(s[1].detach().cpu().numpy() if isinstance(s[1], torch.Tensor) else s[1],
+                            dtype=np.float64).reshape(-1, 7) for s in batch]
+        if self.augmentation is not None:
+            aug = self.augmentation.apply(pcs, boxes=boxes)
+            pcs, boxes = aug.scans, aug.boxes
+        if self.object_range is not None:
+            boxes = [b[object_range_mask(b, *self.object_range)] for b in boxes]
+        maps = self.rasterizer.rasterize_batch(boxes)
         labels, masks = instance_targets(maps, self.num_queries, self.min_num_inst_pixels, self.packed)
         if len(batch[0]) > 2:
             return pcs, (labels, masks), [s[2] for s in batch]

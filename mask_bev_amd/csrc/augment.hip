@@ -1,7 +1,8 @@
 // K23 — training augmentations of scans and instance maps on the device.
 //
 // Replaces mask_bev/augmentations/semantic_kitti_mask_augmentations.py:44-161 (Flip, ShufflePoints, RandomRotate,
-// DecimatePoints, JitterPoints, RandomDropPoints: numpy on the host, one sample at a time, cv2.warpAffine for the mask).
+// DecimatePoints, JitterPoints, RandomDropPoints: numpy on the host, one sample at a time, cv2.warpAffine for the mask) and
+// the point half of kitti_mask_augmentations.py:196-217 (GlobalNoise: one scale and one translation per sample).
 //
 // K23a, the per-point program.  The y dimension of the grid walks the scans, so a workgroup's op record (656 bytes, built on
 // the host) is the same for all its lanes: it is read through uniform loads, and the op switch does not diverge.  A point's
@@ -32,12 +33,13 @@ constexpr int kMaxBatch = 4096;
 constexpr int kLowBits = 26;           // mode 2: key = scan << 26 | 26 bits of order hash or index (the same for every batch size)
 constexpr int kMaxSortBatch = 63;      // ... so that the invalid key, batch << 26, fits 32 bits
 
-enum : int32_t { OP_NONE = 0, OP_LINEAR = 1, OP_JITTER = 2, OP_DROP = 3, OP_SHUFFLE = 4, OP_DECIMATE = 5 };
+enum : int32_t { OP_NONE = 0, OP_LINEAR = 1, OP_JITTER = 2, OP_DROP = 3, OP_SHUFFLE = 4, OP_DECIMATE = 5, OP_GLOBAL_NOISE = 6 };
 
 struct AugOp {                         // 80 bytes
   int32_t code;
   uint32_t arg;                        // drop: T; decimate: k
-  double p[9];                         // linear: a00 a01 a10 a11; jitter: magnitude, std x y z i, max_delta x y z i
+  double p[9];                         // linear: a00 a01 a10 a11; jitter: magnitude, std x y z i, max_delta x y z i;
+                                       // global noise: scale, tx, ty, tz
 };
 struct AugRecord {                     // 656 bytes
   uint32_t seed_lo, seed_hi;
@@ -99,6 +101,8 @@ __global__ void __launch_bounds__(256) k_program(const float* __restrict__ point
       } else if (code == OP_DROP) {
         const uint32_t h = aug_draw(aug_stream(seed_lo, seed_hi, (uint32_t)s), idx, 0u, 0u);
         keep = keep && (h >> 8) >= op.arg;
+      } else if (code == OP_GLOBAL_NOISE) {
+        for (int c = 0; c < 3; ++c) v[c] = (float)((double)v[c] * op.p[0] + op.p[1 + c]);
       }
     }
     float* o = dst + i * dim;

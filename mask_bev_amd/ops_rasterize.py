@@ -1,10 +1,14 @@
 """K22 — SemanticKITTI scene → instance-id map (csrc/rasterize.hip): binning of the labelled points of a scene into
 per-instance bit images (K22a), close + open with a k x k square in LDS and painting (K22b).  Where two closed-and-opened
-instances claim one cell the highest id wins (the reference paints in the hash order of a Python set)."""
+instances claim one cell the highest id wins (the reference paints in the hash order of a Python set).
+
+K24 — KITTI / Waymo box tables → instance-id maps (csrc/box_rasterize.hip): integer box corners in, one launch for a batch,
+the fill rule of include/maskbev_hip.h; the last box in table order wins a cell, as in the reference's paint loop."""
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -81,4 +85,43 @@ def rasterize_paint(occupancy: torch.Tensor, bbox: torch.Tensor, slot_ids: torch
     return out
 
 
-__all__ = ['rasterize_scene', 'rasterize_paint']
+@torch.no_grad()
+def rasterize_boxes(vertices: torch.Tensor, ids: torch.Tensor, frame_offsets: Union[torch.Tensor, Sequence[int]], nx: int,
+                    ny: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K24: vertices (N, 4, 2) i32 cell coordinates (|c| <= 2^20), ids (N) i32, frame_offsets (B + 1) → maps (B, nx, ny) i32,
+    every cell written (``out`` needs no zeroing).  ``frame_offsets`` as a host sequence is checked here (ascending from 0 to
+    N) and uploaded; as a device i32 tensor it is taken as it is, and the kernel reads no row beyond its last entry."""
+    lib = _lib.load()
+    _need_gpu(vertices, ids)
+    n = ids.numel()
+    if (vertices.dtype != torch.int32 or ids.dtype != torch.int32 or vertices.numel() != n * 8
+            or (n > 0 and tuple(vertices.shape[-2:]) != (4, 2))):
+        raise MaskBevHipError('rasterize_boxes: vertices (N, 4, 2) i32 and ids (N) i32 expected')
+    dev = vertices.device
+    if isinstance(frame_offsets, torch.Tensor):
+        _need_gpu(frame_offsets)
+        if frame_offsets.dtype != torch.int32:
+            raise MaskBevHipError('rasterize_boxes: frame_offsets must be i32')
+        offs = frame_offsets.contiguous()
+    else:
+        host = np.asarray(frame_offsets, dtype=np.int64).reshape(-1)
+        if host.size < 2 or host[0] != 0 or host[-1] != n or np.any(np.diff(host) < 0):
+            raise ValueError(f'rasterize_boxes: frame_offsets must ascend from 0 to {n}, got {host.tolist()}')
+        offs = torch.from_numpy(host.astype(np.int32)).to(dev, non_blocking=True)
+    b = offs.numel() - 1
+    if b < 1:
+        raise ValueError('rasterize_boxes: empty batch')
+    if n == 0:                                    # no box at all: the entry point still wants non-null tables
+        vertices = torch.zeros((1, 4, 2), dtype=torch.int32, device=dev)
+        ids = torch.zeros((1,), dtype=torch.int32, device=dev)
+    vertices, ids = _aligned(vertices), ids.contiguous()
+    if out is None:
+        out = torch.empty((b, nx, ny), dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (b, nx, ny) or not out.is_contiguous() or not out.is_cuda:
+        raise MaskBevHipError(f'rasterize_boxes: out must be a contiguous ({b}, {nx}, {ny}) i32 device tensor')
+    check(lib.mbv_rasterize_boxes(_ptr(vertices), _ptr(ids), _ptr(offs), b, int(nx), int(ny), _ptr(out), _stream()),
+          'mbv_rasterize_boxes')
+    return out
+
+
+__all__ = ['rasterize_scene', 'rasterize_paint', 'rasterize_boxes']

@@ -5,8 +5,16 @@ and one OpenCV call pair per instance, and therefore caches on disk.  The map is
 point-level augmentation: ``augment.DeviceAugmentation`` (K23) folds its flips and rotations into ``transforms``.
 
 Where two closed-and-opened instances claim one cell the HIGHEST ID wins (the reference paints in the hash order of a
-Python set); everywhere else the map equals the reference's.  Not covered: the KITTI / Waymo box rasterisers
-(``cv2.drawContours``), the approximate scene branch.
+Python set); everywhere else the map equals the reference's.  Not covered: the approximate scene branch.
+
+KITTI / Waymo box tables → instance-id maps (K24, csrc/box_rasterize.hip): ``KittiRasterizer`` and ``WaymoRasterizer``
+(mask_bev/datasets/kitti/kitti_rasterizer.py, mask_bev/datasets/waymo/waymo_rasterizer.py).  The corners of the few dozen
+boxes of a frame are made on the host by ``box_vertices`` — the reference's f64 expressions and its ``np.intp``
+truncation, so identical to the last bit — and one launch paints the whole batch by the fill rule of
+include/maskbev_hip.h: a cell belongs to a box iff its integer point lies inside or on the closed quadrilateral of the
+truncated corners, or on the integer line between two consecutive corners; a later box overwrites an earlier one.
+Equality with ``cv2.drawContours(..., -1)`` is NOT pinned by any test: OpenCV draws the outline with its own line iterator
+and fills spans in 16-bit fixed point, so tie cells on an edge may differ — boundary cells of a target mask only.
 """
 from __future__ import annotations
 
@@ -153,4 +161,158 @@ class SemanticKittiRasterizer:
                               centre)
 
 
-__all__ = ['SemanticKittiRasterizer', 'scans_in_range']
+# ---------------------------------------------------------------------------------------------------------
+# K24: box tables
+# ---------------------------------------------------------------------------------------------------------
+KITTI_TYPES = ('Car', 'Van', 'Truck', 'Pedestrian', 'Person_sitting', 'Cyclist', 'Tram', 'Misc', 'DontCare')   # KittiType
+KITTI_CAR, KITTI_CAR_LIKE = 0, (0, 1, 2)         # Car; Car, Van, Truck: all painted as Car (kitti_rasterizer.py:28-34)
+WAYMO_TYPE_VEHICLE = 1                           # torch_waymo's Type.TYPE_VEHICLE
+MAX_VERTEX = 1 << 20                             # |cell coordinate| the kernel's 64-bit products are sized for
+
+
+def box_vertices(boxes, x_range, y_range, nx: int, ny: int) -> np.ndarray:
+    """``boxes`` (n, 7) f64 [cx, cy, cz, l, w, h, theta] → (n, 4, 2) int32 corners in cell coordinates (x-cell, y-cell):
+    ``_box_to_points``, ``_map_to`` and the ``np.intp`` truncation toward zero of kitti_rasterizer.py:49-52,60-80
+    (waymo_rasterizer.py has the identical lines), expression by expression in f64, one box at a time as there."""
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 7)
+    if not np.all(np.isfinite(boxes)):
+        raise ValueError('box_vertices: a box has a non-finite entry')
+    out = np.zeros((boxes.shape[0], 4, 2), dtype=np.int32)
+    for k, (cx, cy, _, l, w, _, theta) in enumerate(boxes):
+        points = np.zeros((4, 2))
+        dl, dw = l / 2, w / 2
+        d = np.array([np.cos(theta), np.sin(theta)])
+        phi = theta + np.pi / 2
+        d_bar = np.array([np.cos(phi), np.sin(phi)])
+        points[0, :] = d * dl + d_bar * dw
+        points[1, :] = - d * dl + d_bar * dw
+        points[2, :] = - d * dl - d_bar * dw
+        points[3, :] = d * dl - d_bar * dw
+        points += [cx, cy]
+        points[:, 0] = (points[:, 0] - x_range[0]) / (x_range[1] - x_range[0]) * (nx - 0) + 0
+        points[:, 1] = (points[:, 1] - y_range[0]) / (y_range[1] - y_range[0]) * (ny - 0) + 0
+        if not np.all(np.abs(points) <= MAX_VERTEX):                 # also catches the NaN of a zero-width range
+            raise ValueError(f'box_vertices: box {k} has a corner beyond ±2^20 cells')
+        out[k] = np.intp(points)
+    return out
+
+
+class _BoxRasterizer:
+    """What the two box rasterisers share: the reference's constructor keywords and grid sizes, the upload and the launch."""
+
+    def __init__(self, x_range, y_range, z_range, voxel_size: float, remove_unseen: bool = False, min_points: int = 1,
+                 device=None):
+        if not voxel_size > 0:
+            raise ValueError('voxel_size must be positive')
+        self.x_range, self.y_range, self.z_range = tuple(x_range), tuple(y_range), tuple(z_range)
+        self.voxel_size = voxel_size
+        self.nx = int((x_range[1] - x_range[0]) / voxel_size)          # the reference's expression (:23-24)
+        self.ny = int((y_range[1] - y_range[0]) / voxel_size)
+        if self.nx < 1 or self.ny < 1:
+            raise ValueError('empty grid')
+        self.remove_unseen, self.min_points = bool(remove_unseen), int(min_points)
+        self.device = None if device is None else torch.device(device)
+
+    def _device(self) -> torch.device:
+        dev = self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        if dev.type != 'cuda':
+            raise MaskBevHipError(f'{type(self).__name__} needs a ROCm device (no CPU fallback), got {dev}')
+        return dev
+
+    def _paint(self, frames: Sequence) -> torch.Tensor:
+        """``frames``: per frame ``(boxes (k, 7), ids (k))`` of the boxes to paint, in paint order → (B, nx, ny) int32."""
+        if len(frames) == 0:
+            raise ValueError('empty batch')
+        dev = self._device()
+        verts = np.concatenate([box_vertices(b, self.x_range, self.y_range, self.nx, self.ny) for b, _ in frames])
+        ids = np.concatenate([np.asarray(i, dtype=np.int32).reshape(-1) for _, i in frames])
+        offsets = np.concatenate([[0], np.cumsum([len(i) for _, i in frames])])
+        return ops_rasterize.rasterize_boxes(torch.from_numpy(verts).to(dev, non_blocking=True),
+                                             torch.from_numpy(ids).to(dev, non_blocking=True), offsets, self.nx, self.ny)
+
+    @staticmethod
+    def _rows(boxes) -> np.ndarray:
+        if isinstance(boxes, torch.Tensor):
+            boxes = boxes.detach().cpu().numpy()
+        return np.asarray(boxes, dtype=np.float64).reshape(-1, 7)
+
+
+class KittiRasterizer(_BoxRasterizer):
+    """mask_bev/datasets/kitti/kitti_rasterizer.py.  Car, Van and Truck labels are painted (all as Car); a label's id is its
+    index among those labels plus 1, counted BEFORE the range skip.  The range skip is the reference's line (:46-48) as it
+    stands: it tests ``x_range[0] <= cx``, ``y_range[0] <= cy`` and the TRUTHINESS of the two upper bounds — a centre beyond
+    an upper bound is still painted where it reaches the grid, and an upper bound of 0 skips every box (SURVEY.md
+    Appendix B).  ``remove_unseen`` and ``min_points`` are accepted and unused, as there."""
+
+    def _select(self, boxes, types=None):
+        boxes = self._rows(boxes)
+        if types is not None:
+            types = np.asarray(types).reshape(-1)
+            if types.shape[0] != boxes.shape[0]:
+                raise ValueError('one type per box expected')
+            boxes = boxes[np.isin(types, KITTI_CAR_LIKE)]
+        ids = np.arange(1, boxes.shape[0] + 1, dtype=np.int32)
+        keep = np.array([bool(self.x_range[0] <= b[0] and self.x_range[1] and self.y_range[0] <= b[1] and self.y_range[1])
+                         for b in boxes], dtype=bool).reshape(-1)
+        return boxes[keep], ids[keep]
+
+    @torch.no_grad()
+    def rasterize_batch(self, boxes: Sequence, types: Optional[Sequence] = None) -> torch.Tensor:
+        """``boxes``: per frame an (n_b, 7) f64 array [cx, cy, cz, l, w, h, theta] in the velodyne frame (n_b = 0: an all-zero
+        map); ``types``: per frame the (n_b) KittiType codes (indices into ``KITTI_TYPES``), ``None``: every box is car-like.
+        → (B, nx, ny) int32 on the device, ready for ``batch.instance_targets``."""
+        if types is not None and len(types) != len(boxes):
+            raise ValueError('one type array per frame expected')
+        return self._paint([self._select(b, None if types is None else types[k]) for k, b in enumerate(boxes)])
+
+    def get_mask(self, frame) -> dict:
+        """The reference's call, for drop-in use: ``frame.labels`` with ``type``, ``location``, ``dimensions`` and
+        ``rotation_y`` → ``{KittiType.Car: (ny, nx) int32 device tensor}`` (a view of the (nx, ny) map)."""
+        labels = list(frame.labels)
+        boxes = np.array([[*l.location, *l.dimensions, l.rotation_y] for l in labels], dtype=np.float64).reshape(-1, 7)
+        types = np.array([int(l.type) for l in labels], dtype=np.int64)
+        return {KITTI_CAR: self.rasterize_batch([boxes], [types])[0].t()}
+
+
+class WaymoRasterizer(_BoxRasterizer):
+    """mask_bev/datasets/waymo/waymo_rasterizer.py: the ``TYPE_VEHICLE`` labels with ``num_lidar_points_in_box >=
+    min_points``, in label order, id = index among them plus 1; no range skip.  Cells are indexed [y-cell][x-cell] as the
+    reference's ``drawContours`` call indexes them.  The reference allocates that image as (nx, ny), which only fits a
+    square grid; here the map always has the KITTI layout — (nx, ny) for K14, (ny, nx) from ``get_mask`` — so a non-square
+    grid works too."""
+
+    def _select(self, boxes, types=None, num_points=None):
+        boxes = self._rows(boxes)
+        keep = np.ones(boxes.shape[0], dtype=bool)
+        if types is not None:
+            keep &= np.asarray(types).reshape(-1) == WAYMO_TYPE_VEHICLE
+        boxes = boxes[keep]
+        if num_points is not None:
+            boxes = boxes[np.asarray(num_points).reshape(-1)[keep] >= self.min_points]
+        return boxes, np.arange(1, boxes.shape[0] + 1, dtype=np.int32)
+
+    @torch.no_grad()
+    def rasterize_batch(self, boxes: Sequence, types: Optional[Sequence] = None,
+                        num_points: Optional[Sequence] = None) -> torch.Tensor:
+        """``boxes``: per frame (n_b, 7) f64 [center_x, center_y, center_z, length, width, height, heading]; ``types`` /
+        ``num_points``: per frame the (n_b) label types and ``num_lidar_points_in_box`` (``None``: every box is a vehicle /
+        has enough points) → (B, nx, ny) int32 on the device."""
+        for extra in (types, num_points):
+            if extra is not None and len(extra) != len(boxes):
+                raise ValueError('one type / point-count array per frame expected')
+        return self._paint([self._select(b, None if types is None else types[k],
+                                         None if num_points is None else num_points[k]) for k, b in enumerate(boxes)])
+
+    def get_mask(self, frame) -> dict:
+        """``frame.laser_labels`` with ``type``, ``num_lidar_points_in_box`` and ``box`` → ``{TYPE_VEHICLE: (ny, nx) int32
+        device tensor}``."""
+        labels = list(frame.laser_labels)
+        boxes = np.array([[l.box.center_x, l.box.center_y, l.box.center_z, l.box.length, l.box.width, l.box.height,
+                           l.box.heading] for l in labels], dtype=np.float64).reshape(-1, 7)
+        types = np.array([int(l.type) for l in labels], dtype=np.int64)
+        counts = np.array([l.num_lidar_points_in_box for l in labels], dtype=np.int64)
+        return {WAYMO_TYPE_VEHICLE: self.rasterize_batch([boxes], [types], [counts])[0].t()}
+
+
+__all__ = ['SemanticKittiRasterizer', 'scans_in_range', 'box_vertices', 'KittiRasterizer', 'WaymoRasterizer',
+           'KITTI_TYPES', 'KITTI_CAR', 'KITTI_CAR_LIKE', 'WAYMO_TYPE_VEHICLE']

@@ -18,7 +18,12 @@ Data (the reference's DataModules, /root/reference: train_mask_bev.py:68-83, are
 ``dataset: synthetic`` (or ``--synthetic``) draws SemanticKITTI-shaped scans and box masks on the GPU
 (mask_bev_amd/synthetic.py); ``dataset: semantic-kitti`` reads ``<root>/sequences/SS/velodyne/*.bin`` with the
 instance-map cache ``<root>/sequences/SS/mask_cache/*.npy`` the reference's mask dataset writes
-(semantic_kitti_mask_dataset.py:121-137) and builds the (labels, masks) targets on the GPU (batch.py, K14).  The config's
+(semantic_kitti_mask_dataset.py:121-137) and builds the (labels, masks) targets on the GPU (batch.py, K14);
+``dataset: kitti`` reads the KITTI object distribution as the reference's KittiDataset lays it out
+(``<root>/data_object_velodyne/training/velodyne/*.bin``, ``data_object_label_2/training/label_2/*.txt``,
+``data_object_calib/training/calib/*.txt``, ``train.txt`` / ``val.txt``) and rasterises each frame's Car / Van / Truck
+boxes on the GPU (rasterize.KittiRasterizer, K24) in front of K14.  ``dataset: waymo`` is not read here (``torch_waymo``
+frames); ``rasterize.WaymoRasterizer`` with ``batch.BoxCollate`` makes its batches from box tables.  The config's
 ``augmentations:`` list is applied to the training batches on the GPU (mask_bev_amd/augment.py, K23), never to validation.
 """
 from __future__ import annotations
@@ -129,6 +134,80 @@ class SemanticKittiCacheBatches:
         return self.collate(samples)
 
 
+def build_kitti_augmentation(config):
+    """The ``augmentations:`` list of a KITTI configuration (kitti_mask_augmentations.py's names).  ``object_sample`` and
+    ``object_noise`` need files and libraries this package does not have: training goes on without them after one line."""
+    spec = config.get('augmentations')
+    if not spec:
+        return None
+    from mask_bev_amd.augment import DeviceAugmentation, make_kitti_augmentation_list
+    left_out = [a.get('name') for a in spec if a.get('name') in ('object_sample', 'object_noise')]
+    if left_out:
+        print(f'warning: training without {", ".join(left_out)} (not provided: samples.pkl / mmdet3d collision search)',
+              flush=True)
+    spec = [a for a in spec if a.get('name') not in ('object_sample', 'object_noise')]
+    return DeviceAugmentation(make_kitti_augmentation_list(spec), int(config.get('seed', 420)),
+                              config['x_range'], config['y_range'], config['voxel_size']) if spec else None
+
+
+class KittiObjectBatches:
+    """KITTI object frames (kitti_dataset.py, kitti_data_module.py:53-105): ``.bin`` scan, ``label_2`` and ``calib`` of the
+    frames listed in ``<root>/<split>.txt``; labels taken to the velodyne frame, optionally filtered by difficulty
+    (``filter_difficulty``), Car / Van / Truck boxes rasterised on the GPU (K24) and expanded to targets (K14).  The
+    range filter acts after the augmentation, as there."""
+
+    def __init__(self, config, device, rank, world, root, split, augment=False):
+        from mask_bev_amd import batch as B
+        from mask_bev_amd.rasterize import KITTI_CAR_LIKE, KittiRasterizer
+        import numpy as np
+        self.B, self.np, self.device, self.car_like = B, np, device, KITTI_CAR_LIKE
+        self.rank, self.seed = rank, int(config.get('seed', 420))
+        self.augmentation = build_kitti_augmentation(config) if augment else None
+        root = pathlib.Path(root).expanduser()
+        with open(root / f'{split}.txt', 'r') as f:
+            frames = [int(line.strip()) for line in f if line.strip()]
+        self.dirs = {k: root / f'data_object_{k}' / 'training' / d
+                     for k, d in (('velodyne', 'velodyne'), ('label_2', 'label_2'), ('calib', 'calib'))}
+        if not frames:
+            raise ValueError(f'{root / (split + ".txt")} lists no frame')
+        bsz = int(config.get('batch_size', 1))
+        usable = len(frames) - len(frames) % (world * bsz)           # drop_last, equal work per rank
+        self.frames, self.bsz = frames[rank:usable:world], bsz
+        self.filter_difficulty = bool(config.get('filter_difficulty', False))
+        rasterizer = KittiRasterizer(config['x_range'], config['y_range'], config['z_range'], config['voxel_size'],
+                                     bool(config.get('remove_unseen', False)), int(config.get('min_num_points', 1)),
+                                     device=device)
+        self.collate = B.BoxCollate(rasterizer, int(config['num_queries']), device,
+                                    int(config.get('min_num_inst_pixels', 0)), augmentation=self.augmentation,
+                                    object_range=(config['x_range'], config['y_range']))
+        self.shuffle = bool(config.get('shuffle_train', True))
+
+    def __len__(self):
+        return len(self.frames) // self.bsz
+
+    def sample(self, frame):
+        B, np = self.B, self.np
+        name = f'{frame:06d}'
+        pc = torch.from_numpy(B.read_velodyne_bin(self.dirs['velodyne'] / f'{name}.bin'))
+        pc = pc[torch.randperm(pc.shape[0])]                         # ShufflePointCloud (kitti_transforms.py:35-38)
+        labels = B.kitti_labels_to_velodyne(B.read_kitti_label(self.dirs['label_2'] / f'{name}.txt'),
+                                            B.read_kitti_calib(self.dirs['calib'] / f'{name}.txt'))
+        keep = np.isin(labels['type'], self.car_like)
+        if self.filter_difficulty:
+            keep &= B.is_difficulty_valid(labels['occluded'], labels['truncated'])
+        return pc, labels['boxes'][keep]
+
+    def batch(self, epoch, i):
+        order = list(range(len(self.frames)))
+        if self.shuffle:
+            g = torch.Generator().manual_seed(epoch)
+            order = torch.randperm(len(order), generator=g).tolist()
+        samples = [self.sample(self.frames[j]) for j in order[i * self.bsz:(i + 1) * self.bsz]]
+        if self.augmentation is not None:
+            self.augmentation.reseed(self.seed, self.rank, epoch, i)
+        return self.collate(samples)
+
+
 def save_checkpoint(model, optimizer, path, epoch, metric_name, metric):
     torch.save({'state_dict': model.state_dict(), 'hyper_parameters': dict(getattr(model, 'hparams', {})),
                 'optimizer_states': [optimizer.state_dict()], 'epoch': epoch, metric_name: metric}, path)
@@ -141,7 +220,7 @@ def main(argv=None):
     parser.add_argument('--test', '-e', action='store_true', help='Test the model')
     # extensions of this launcher
     parser.add_argument('--synthetic', action='store_true', help='synthetic scans instead of a dataset on disk')
-    parser.add_argument('--data-root', default='data/SemanticKITTI')
+    parser.add_argument('--data-root', default=None, help='default: data/SemanticKITTI, data/KITTI for dataset: kitti')
     parser.add_argument('--max-epochs', type=int, default=1000)
     parser.add_argument('--max-steps', type=int, default=-1, help='stop after this many optimizer steps (-1: no limit)')
     parser.add_argument('--steps-per-epoch', type=int, default=100, help='synthetic data: batches per epoch')
@@ -206,10 +285,19 @@ def main(argv=None):
         data = SyntheticBatches(config, device, rank, args.steps_per_epoch)
         val = None
     elif dataset_name == 'semantic-kitti':
+        args.data_root = args.data_root or 'data/SemanticKITTI'
         data = SemanticKittiCacheBatches(config, device, rank, world, args.data_root,
                                          config.get('train_sequences', [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]), augment=True)
         val = SemanticKittiCacheBatches(dict(config, shuffle_train=False), device, rank, world, args.data_root,
                                         config.get('val_sequences', [8])) if limit_val_batches > 0 else None
+    elif dataset_name == 'kitti':
+        args.data_root = args.data_root or 'data/KITTI'
+        data = KittiObjectBatches(config, device, rank, world, args.data_root, 'train', augment=True)
+        val = KittiObjectBatches(dict(config, shuffle_train=False), device, rank, world, args.data_root,
+                                 'val') if limit_val_batches > 0 else None
+    elif dataset_name == 'waymo':
+        raise NotImplementedError('dataset: waymo is not read by this launcher (torch_waymo frames); build batches from '
+                                  'box tables with mask_bev_amd.rasterize.WaymoRasterizer and mask_bev_amd.batch.BoxCollate')
     else:
         raise NotImplementedError(dataset_name)
 
