@@ -1293,6 +1293,80 @@ int mbv_warp_instance_maps(const int32_t* maps, const double* mats, int32_t batc
 int mbv_rasterize_boxes(const int32_t* vertices, const int32_t* ids, const int32_t* frame_offsets, int32_t batch,
                         int32_t nx, int32_t ny, int32_t* maps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K25 — oriented box of a bit-packed BEV mask (csrc/box_fit.hip).
+ * Stands where mask_to_pred (mask_bev/evaluation/kitti_eval.py:27-45) takes cv2.minAreaRect of the largest contour on the
+ * host.  Here ALL set cells of a mask count and the box is the MOMENT-AXIS box; equality with minAreaRect is not pinned
+ * by any test (OpenCV is not a dependency).
+ *
+ * packed        (num_maps, mbv_packed_mask_words(H, W)) u32, mbv_pack_binary_masks layout: pixel y * W + x; H * W <= 2^20.
+ *               Bits at and beyond H * W are not read as cells.
+ * rows          (num_rows) i32: the maps to fit; a row outside 0 .. num_maps - 1 counts as an empty mask.
+ * n             (num_rows) i32: set cells.
+ * moments       (num_rows, 5) i64: Σx, Σy, Σx², Σy², Σxy over the set cells, x and y the integer cell indices; exact.
+ * boxes         (num_rows, 5) f32: cx, cy, dx, dy, theta in cell units; all 0 for a row with n == 0.
+ *                 cx = Σx / n, cy = Σy / n (the centroid).
+ *                 theta = atan2(2 m11, m20 - m02) / 2 with m20 = n Σx² - (Σx)², m02 = n Σy² - (Σy)², m11 = n Σxy - Σx Σy
+ *                 formed in i64 (exact) and only then converted to f64; theta = 0 when m11 = 0 and m20 = m02.
+ *                 dx = max u - min u + |cos theta| + |sin theta| with u = x cos theta + y sin theta over the set cells,
+ *                 dy the same with v = y cos theta - x sin theta: the extent of the cells' centres plus the support of
+ *                 the unit cell, so an axis-aligned a x b block of cells gives exactly (a, b).
+ *               f64 arithmetic, one rounding per operation, one rounding to f32 at the store.
+ * One workgroup per row, two sweeps over its words; integer sums and min / max only, so the result is deterministic.
+ * MBV_ERR_BAD_ARG: a null pointer (with num_rows > 0), H or W < 1, H * W > 2^20, num_maps < 1 with rows to fit.
+ */
+int mbv_fit_boxes(const uint32_t* packed, int64_t num_maps, int32_t H, int32_t W, const int32_t* rows, int32_t num_rows,
+                  int32_t* n, int64_t* moments, float* boxes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K26 — rotated-box overlap over ragged frames (csrc/rotate_iou.hip).
+ * Stands where rotate_iou_gpu_eval (mask_bev/evaluation/rotate_iou.py) is called per part of the validation set.
+ *
+ * boxes         (n_boxes, 5) f32, qboxes (n_qboxes, 5) f32: x, y, dx, dy, angle.  The corners are those of
+ *               rasterize.box_vertices: centre ± (dx / 2) d ± (dy / 2) d_bar, d = (cos angle, sin angle),
+ *               d_bar = (-sin angle, cos angle): the angle turns COUNTER-clockwise (the reference's kernel turns clockwise).
+ * box_offsets, qbox_offsets   (frames + 1) i32 on the device, ascending from 0 to n_boxes / n_qboxes.
+ * pair_offsets  (frames + 1) i64 on the device: pair_offsets[f + 1] - pair_offsets[f] = n_f * k_f, pair_offsets[frames] =
+ *               total_pairs.
+ * criterion     -1: intersection / union; 0: intersection / area of the box; 1: / area of the query box; 2: the intersection.
+ * overlaps      (total_pairs) f32: frame f's (n_f, k_f) matrix, k_f contiguous, at pair_offsets[f].  Exactly 0 where the
+ *               rectangles do not meet in a polygon of positive area.
+ * One thread per pair: the first rectangle, expressed in the second one's axes, is clipped against its four half-planes
+ * (Sutherland-Hodgman), then the shoelace area.  f32 throughout.  Offsets that point outside the tables read nothing.
+ * MBV_ERR_BAD_ARG: a null pointer, frames < 1, a criterion outside -1 .. 2; MBV_ERR_UNSUPPORTED: more than 2^39 pairs.
+ */
+int mbv_rotate_iou(const float* boxes, int64_t n_boxes, const float* qboxes, int64_t n_qboxes, const int32_t* box_offsets,
+                   const int32_t* qbox_offsets, const int64_t* pair_offsets, int32_t frames, int64_t total_pairs,
+                   int32_t criterion, float* overlaps, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K27 — KITTI statistics of all frames and score thresholds (csrc/kitti_stats.hip): the protocol's inner loop,
+ * compute_statistics_jit / fused_compute_statistics of mask_bev/evaluation/kitti_eval.py:266-443 for metric == 1 (BEV).
+ * DontCare regions and the orientation score (AOS) belong to the image-box metric: out of scope.
+ *
+ * overlaps      K26's output with the DETECTIONS as the first table: frame f's (d_f, g_f) matrix at pair_offsets[f].
+ * dt_offsets, gt_offsets (frames + 1) i32, pair_offsets (frames + 1) i64, on the device.
+ * ignored_gt    (n_gt) i32: 0 counted, 1 ignored at this difficulty (or a neighbouring class), -1 another class.
+ * ignored_dt    (n_dt) i32: 0 counted, 1 ignored, -1 another class.  dt_scores (n_dt) f32.
+ * min_overlap   a match needs (double)overlap > min_overlap.
+ * thresholds    (num_thresholds) f32; with compute_fp a detection with score < threshold does not exist.
+ * compute_fp    0: the highest-scoring candidate is matched, no false positives are counted (the pass that collects the
+ *               scores get_thresholds consumes: num_thresholds = 1); 1: the candidate of largest overlap is matched, ignored
+ *               detections only as a last resort, false positives counted.  The rules are written out in the kernel file.
+ * stats         (num_thresholds, 3) i64: tp, fp, fn summed over the frames; zeroed by the call, exact.
+ * tp_scores     (n_gt) f32 and tp_flags (n_gt) i32, both or neither: for threshold 0, per ground truth whether it was a
+ *               true positive and the score of its detection (0 otherwise); every entry of a well-formed frame is written.
+ * workspace     mbv_kitti_statistics_workspace_bytes(n_dt, num_thresholds) bytes: the per-thread "assigned" flags.
+ * One thread per (frame, threshold), a serial greedy loop; integer atomics on `stats`.  A frame whose offsets point outside
+ * the tables is left out.  MBV_ERR_BAD_ARG: a null pointer, frames < 1, num_thresholds outside 1 .. 65535.
+ */
+size_t mbv_kitti_statistics_workspace_bytes(int64_t n_dt, int32_t num_thresholds);
+int mbv_kitti_statistics(const float* overlaps, const int64_t* pair_offsets, const int32_t* dt_offsets,
+                         const int32_t* gt_offsets, int32_t frames, int64_t n_dt, int64_t n_gt, int64_t n_pairs,
+                         const int32_t* ignored_gt, const int32_t* ignored_dt, const float* dt_scores, double min_overlap,
+                         const float* thresholds, int32_t num_thresholds, int32_t compute_fp, int64_t* stats,
+                         float* tp_scores, int32_t* tp_flags, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_instances  K21 query selection + BEV mask / instance-map extraction at inference
     ops_rasterize  K22 SemanticKITTI scene -> instance-id map (binning, close + open, paint)
     ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp
+    ops_eval       K25 oriented box of a packed mask, K26 rotated-box overlap over ragged frames, K27 KITTI tp / fp / fn
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403
@@ -28,3 +29,4 @@ from .ops_loss import *            # noqa: F401,F403
 from .ops_instances import *       # noqa: F401,F403
 from .ops_rasterize import *       # noqa: F401,F403
 from .ops_augment import *         # noqa: F401,F403
+from .ops_eval import *            # noqa: F401,F403

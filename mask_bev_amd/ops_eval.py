@@ -1,0 +1,157 @@
+"""K25 — oriented box of a bit-packed mask (csrc/box_fit.hip); K26 — rotated-box overlap over ragged frames
+(csrc/rotate_iou.hip); K27 — KITTI tp / fp / fn of all frames and score thresholds (csrc/kitti_stats.hip).  The three
+kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``; the definitions are in include/maskbev_hip.h."""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import MaskBevHipError, check
+from .ops_core import _need_gpu, _ptr, _stream, _workspace
+from .ops_loss import PackedMasks
+
+Offsets = Union[torch.Tensor, Sequence[int], np.ndarray]
+
+
+@torch.no_grad()
+def fit_boxes(masks: PackedMasks, rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """masks: the R maps at (H, W) of a :class:`PackedMasks`; rows (r) integer device tensor, the maps to fit →
+    ``(n (r) int32, moments (r, 5) int64 = Σx Σy Σx² Σy² Σxy, boxes (r, 5) f32 = cx cy dx dy theta)`` in cell units: the
+    moment-axis box of ALL set cells (K25); a row with ``n == 0`` gets a box of zeros.  No host synchronisation."""
+    lib = _lib.load()
+    words = masks.words
+    _need_gpu(words, rows)
+    h, w = int(masks.h), int(masks.w)
+    if h < 1 or w < 1 or h * w > 1024 * 1024:
+        raise MaskBevHipError(f'fit_boxes: grid {h}x{w} outside 1 <= H*W <= 1024*1024')
+    if words.dim() != 2 or words.dtype != torch.int32 or words.shape[1] != lib.mbv_packed_mask_words(h, w):
+        raise MaskBevHipError(f'fit_boxes: words must be (R, {lib.mbv_packed_mask_words(h, w)}) int32 for a {h}x{w} grid')
+    if rows.dim() != 1 or rows.dtype not in (torch.int32, torch.int64) or rows.device != words.device:
+        raise MaskBevHipError('fit_boxes: rows must be a 1-d int32 / int64 tensor on the masks\' device')
+    words, rows = words.contiguous(), rows.to(torch.int32).contiguous()
+    r, dev = rows.numel(), words.device
+    n = torch.empty((r,), dtype=torch.int32, device=dev)
+    moments = torch.empty((r, 5), dtype=torch.int64, device=dev)
+    boxes = torch.empty((r, 5), dtype=torch.float32, device=dev)
+    if r > 0:
+        if words.shape[0] == 0:
+            raise MaskBevHipError('fit_boxes: rows to fit but no map')
+        check(lib.mbv_fit_boxes(_ptr(words), words.shape[0], h, w, _ptr(rows), r, _ptr(n), _ptr(moments), _ptr(boxes),
+                                _stream()), 'mbv_fit_boxes')
+    return n, moments, boxes
+
+
+def _host_offsets(offsets: Offsets, total: int, what: str) -> np.ndarray:
+    """Per-frame offsets as a checked host array.  A device tensor is copied back (one synchronisation): pass host
+    sequences where the frame sizes are known on the host, as ``kitti_eval`` does."""
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.detach().cpu().numpy()
+    host = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if host.size < 2 or host[0] != 0 or host[-1] != total or np.any(np.diff(host) < 0):
+        raise ValueError(f'{what}: offsets must ascend from 0 to {total}, got {host.tolist()[:8]} ...')
+    if total >= 2 ** 31:
+        raise ValueError(f'{what}: more than 2^31 - 1 rows')
+    return host
+
+
+class FrameOffsets:
+    """The per-frame offsets of two ragged tables and of their per-frame (n_f, k_f) pair matrices, on the host (``a``, ``b``,
+    ``pairs``: int64 arrays of frames + 1 entries) and on the device (``a_dev``, ``b_dev`` int32, ``pairs_dev`` int64)."""
+
+    def __init__(self, a: Offsets, n_a: int, b: Offsets, n_b: int, device):
+        self.a, self.b = _host_offsets(a, n_a, 'first table'), _host_offsets(b, n_b, 'second table')
+        if self.a.size != self.b.size:
+            raise ValueError('the two tables have different numbers of frames')
+        self.frames = self.a.size - 1
+        self.pairs = np.concatenate([[0], np.cumsum(np.diff(self.a) * np.diff(self.b))]).astype(np.int64)
+        self.total = int(self.pairs[-1])
+        dev = torch.device(device)
+        self.a_dev = torch.from_numpy(self.a.astype(np.int32)).to(dev, non_blocking=True)
+        self.b_dev = torch.from_numpy(self.b.astype(np.int32)).to(dev, non_blocking=True)
+        self.pairs_dev = torch.from_numpy(self.pairs).to(dev, non_blocking=True)
+
+
+def _box_table(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 5:
+        raise MaskBevHipError(f'{what} must be (N, 5) f32 [x, y, dx, dy, angle], got {tuple(t.shape)} {t.dtype}')
+    return t.contiguous()
+
+
+@torch.no_grad()
+def rotate_iou(boxes: torch.Tensor, qboxes: torch.Tensor, box_offsets: Offsets = None, qbox_offsets: Offsets = None,
+               criterion: int = -1, offsets: Optional[FrameOffsets] = None) -> Tuple[torch.Tensor, FrameOffsets]:
+    """boxes (N, 5), qboxes (K, 5) f32 device tables [x, y, dx, dy, angle] (corners as ``rasterize.box_vertices`` makes
+    them: the angle turns counter-clockwise) with per-frame offsets (F + 1; ``None``: one frame) → ``(overlaps, offsets)``:
+    the F per-frame (n_f, k_f) matrices concatenated in one f32 device tensor, frame f at ``offsets.pairs[f]``.
+    ``criterion``: -1 IoU, 0 intersection over the first box's area, 1 over the second's, 2 the intersection.  One K26 launch;
+    no host synchronisation when the offsets are host sequences (or a :class:`FrameOffsets` from an earlier call)."""
+    lib = _lib.load()
+    _need_gpu(boxes, qboxes)
+    boxes, qboxes = _box_table(boxes, 'rotate_iou: boxes'), _box_table(qboxes, 'rotate_iou: qboxes')
+    if boxes.device != qboxes.device:
+        raise MaskBevHipError('rotate_iou: tables on different devices')
+    if criterion not in (-1, 0, 1, 2):
+        raise ValueError(f'rotate_iou: criterion must be -1, 0, 1 or 2, got {criterion}')
+    n, k, dev = boxes.shape[0], qboxes.shape[0], boxes.device
+    if offsets is None:
+        offsets = FrameOffsets([0, n] if box_offsets is None else box_offsets, n,
+                               [0, k] if qbox_offsets is None else qbox_offsets, k, dev)
+    elif offsets.a[-1] != n or offsets.b[-1] != k:
+        raise ValueError('rotate_iou: offsets of other tables')
+    out = torch.empty((offsets.total,), dtype=torch.float32, device=dev)
+    if offsets.total > 0:
+        check(lib.mbv_rotate_iou(_ptr(boxes), n, _ptr(qboxes), k, _ptr(offsets.a_dev), _ptr(offsets.b_dev),
+                                 _ptr(offsets.pairs_dev), offsets.frames, offsets.total, int(criterion), _ptr(out),
+                                 _stream()), 'mbv_rotate_iou')
+    return out, offsets
+
+
+@torch.no_grad()
+def kitti_statistics(overlaps: torch.Tensor, offsets: FrameOffsets, ignored_gt: torch.Tensor, ignored_dt: torch.Tensor,
+                     dt_scores: torch.Tensor, min_overlap: float, thresholds: Optional[torch.Tensor] = None,
+                     compute_fp: bool = True, collect_scores: bool = False):
+    """K27 on K26's overlaps with the detections as the FIRST table (``offsets.a``: detections, ``offsets.b``: ground truth):
+    ``ignored_gt`` (n_gt) / ``ignored_dt`` (n_dt) int32 codes -1, 0, 1, ``dt_scores`` (n_dt) f32, ``thresholds`` (T) f32
+    (``None``: the single threshold 0) → ``stats`` (T, 3) int64 = tp, fp, fn over all frames.  ``collect_scores`` (T = 1,
+    the pass in front of ``get_thresholds``) also returns ``(tp_scores (n_gt) f32, tp_flags (n_gt) int32)``: per ground
+    truth whether it was matched as a true positive, and by which score.  Device tensors in, device tensors out, no host
+    synchronisation."""
+    lib = _lib.load()
+    _need_gpu(overlaps, ignored_gt, ignored_dt, dt_scores, thresholds)
+    dev = overlaps.device
+    n_dt, n_gt = int(offsets.a[-1]), int(offsets.b[-1])
+    if overlaps.dtype != torch.float32 or overlaps.numel() != offsets.total:
+        raise MaskBevHipError(f'kitti_statistics: overlaps must hold {offsets.total} f32 values')
+    if (ignored_gt.dtype != torch.int32 or ignored_gt.numel() != n_gt or ignored_dt.dtype != torch.int32
+            or ignored_dt.numel() != n_dt or dt_scores.dtype != torch.float32 or dt_scores.numel() != n_dt):
+        raise MaskBevHipError(f'kitti_statistics: ignored_gt ({n_gt}) i32, ignored_dt ({n_dt}) i32 and dt_scores ({n_dt}) f32 '
+                              'expected')
+    if thresholds is None:
+        thresholds = torch.zeros((1,), dtype=torch.float32, device=dev)
+    if thresholds.dtype != torch.float32 or thresholds.dim() != 1 or not 1 <= thresholds.numel() <= 65535:
+        raise MaskBevHipError('kitti_statistics: thresholds must be (T) f32 with 1 <= T <= 65535')
+    t = thresholds.numel()
+    if collect_scores and t != 1:
+        raise ValueError('kitti_statistics: collect_scores needs a single threshold')
+    for x in (ignored_gt, ignored_dt, dt_scores, thresholds):
+        if x.device != dev:
+            raise MaskBevHipError('kitti_statistics: tensors on different devices')
+    overlaps, ignored_gt, ignored_dt = overlaps.contiguous(), ignored_gt.contiguous(), ignored_dt.contiguous()
+    dt_scores, thresholds = dt_scores.contiguous(), thresholds.contiguous()
+    stats = torch.empty((t, 3), dtype=torch.int64, device=dev)
+    tp_scores = torch.empty((n_gt,), dtype=torch.float32, device=dev) if collect_scores else None
+    tp_flags = torch.empty((n_gt,), dtype=torch.int32, device=dev) if collect_scores else None
+    nbytes = lib.mbv_kitti_statistics_workspace_bytes(n_dt, t)
+    ws = _workspace(nbytes, dev)
+    check(lib.mbv_kitti_statistics(_ptr(overlaps), _ptr(offsets.pairs_dev), _ptr(offsets.a_dev), _ptr(offsets.b_dev),
+                                   offsets.frames, n_dt, n_gt, offsets.total, _ptr(ignored_gt), _ptr(ignored_dt),
+                                   _ptr(dt_scores), float(min_overlap), _ptr(thresholds), t, int(bool(compute_fp)),
+                                   _ptr(stats), _ptr(tp_scores), _ptr(tp_flags), _ptr(ws), ws.numel(), _stream()),
+          'mbv_kitti_statistics')
+    return (stats, tp_scores, tp_flags) if collect_scores else stats
+
+
+__all__ = ['fit_boxes', 'rotate_iou', 'kitti_statistics', 'FrameOffsets']

@@ -82,6 +82,46 @@ class Predictions:
                             area=None if areas is None else areas[i], mask=None if dense is None else dense[j]))
         return out
 
+    def _grid_ranges(self, x_range, y_range, voxel_size):
+        if y_range is None and hasattr(x_range, 'x_range'):              # a rasteriser (or anything with its attributes)
+            r = x_range
+            x_range, y_range, voxel_size = r.x_range, r.y_range, r.voxel_size
+        if y_range is None or voxel_size is None:
+            raise ValueError('boxes: pass x_range, y_range and voxel_size, or a rasteriser')
+        h, w = self.masks.h, self.masks.w
+        nx, ny = int((x_range[1] - x_range[0]) / voxel_size), int((y_range[1] - y_range[0]) / voxel_size)
+        if (ny, nx) != (h, w):
+            raise ValueError(f'boxes: the ranges make a {ny}x{nx} (ny, nx) grid, the masks are {h}x{w}')
+        return x_range, y_range, nx, ny
+
+    def boxes(self, x_range, y_range=None, voxel_size=None) -> dict:
+        """Oriented BEV boxes of the kept queries (K25, ``ops.fit_boxes``: the moment-axis box of all set cells of a mask),
+        in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a rasteriser (``KittiRasterizer``) in place of
+        ``x_range``.  A kept query whose mask is empty yields no box.  Returns, for the R remaining rows in (scan, query)
+        order, ``boxes`` (R, 5) f32 [x, y, l, w, yaw] (velodyne frame, the yaw of ``rasterize.box_vertices``, l >= w),
+        ``scores`` (R) f32, ``scan`` (R) and ``query`` (R) int64, ``cells`` (R) int32 — tensors where the predictions live.
+        Synchronises with the device (twice: the kept rows, then the non-empty ones)."""
+        from .rasterize import boxes_from_cells
+        if self.masks is None:
+            raise MaskBevHipError('boxes: these predictions were made without masks')
+        x_range, y_range, nx, ny = self._grid_ranges(x_range, y_range, voxel_size)
+        q = self.labels.shape[1]
+        rows = torch.nonzero(self.keep.reshape(-1)).flatten()
+        n, _, cell_boxes = ops.fit_boxes(self.masks, rows.to(self.masks.words.device))
+        full = torch.nonzero(n > 0).flatten()
+        rows, n, cell_boxes = rows[full.to(rows.device)], n[full], cell_boxes[full]
+        return dict(boxes=boxes_from_cells(cell_boxes, x_range, y_range, nx, ny), scores=self.scores.reshape(-1)[rows],
+                    scan=torch.div(rows, q, rounding_mode='floor'), query=rows % q, cells=n)
+
+    def kitti_predictions(self, x_range, y_range=None, voxel_size=None) -> List[dict]:
+        """Per scan what ``kitti_eval.eval_kitti`` takes: ``{'boxes': (k, 5) [x, y, l, w, yaw], 'score': (k), 'type': (k)
+        int64}`` of the scan's kept, non-empty queries; every box has the type Car (index 0 of ``rasterize.KITTI_TYPES``).
+        Arguments and synchronisation as :meth:`boxes`, plus one copy of the per-scan counts."""
+        out = self.boxes(x_range, y_range, voxel_size)
+        counts = torch.bincount(out['scan'], minlength=self.labels.shape[0]).tolist()
+        boxes, scores = torch.split(out['boxes'], counts), torch.split(out['scores'], counts)
+        return [dict(boxes=b, score=s, type=torch.zeros((b.shape[0],), dtype=torch.int64)) for b, s in zip(boxes, scores)]
+
 
 def extract_instances(cls: torch.Tensor, mask_logits: torch.Tensor, grid_hw, score_threshold: float = 0.0,
                       masks: bool = True, instance_map: bool = True) -> Predictions:

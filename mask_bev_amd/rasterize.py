@@ -197,6 +197,29 @@ def box_vertices(boxes, x_range, y_range, nx: int, ny: int) -> np.ndarray:
     return out
 
 
+def boxes_from_cells(boxes: torch.Tensor, x_range, y_range, nx: int, ny: int) -> torch.Tensor:
+    """The way back from ``box_vertices``' cell coordinates, taken at cell centres: K25's boxes (r, 5) [cx, cy, dx, dy, theta]
+    in cell units (cell index i along x covers [i, i + 1) of ``(x - x_lo) / (x_hi - x_lo) * nx``, so its centre is i + 0.5)
+    → (r, 5) float32 [x, y, l, w, yaw] in metres in the velodyne frame, yaw as ``box_vertices`` and
+    ``batch.kitti_labels_to_velodyne`` have it (the direction of the length, counter-clockwise, in [-pi, pi)), l >= w.
+    A box that K24 paints and K25 fits lands on itself up to the rasterisation.  On a grid whose cells are not square the
+    axis direction is scaled per axis and the extents by the length of the scaled unit vectors.  A box of zeros (an empty
+    mask) stays a box of zeros at the grid's origin cell.  Runs where ``boxes`` lives, in float64."""
+    b = boxes.to(torch.float64)
+    sx, sy = (float(x_range[1]) - float(x_range[0])) / nx, (float(y_range[1]) - float(y_range[0])) / ny
+    c, s = torch.cos(b[:, 4]), torch.sin(b[:, 4])
+    x = float(x_range[0]) + (b[:, 0] + 0.5) * sx
+    y = float(y_range[0]) + (b[:, 1] + 0.5) * sy
+    length = b[:, 2] * torch.hypot(c * sx, s * sy)
+    width = b[:, 3] * torch.hypot(s * sx, c * sy)
+    yaw = torch.atan2(s * sy, c * sx)
+    swap = width > length
+    yaw = torch.where(swap, yaw + np.pi / 2, yaw)
+    yaw = torch.atan2(torch.sin(yaw), torch.cos(yaw))
+    l, w = torch.where(swap, width, length), torch.where(swap, length, width)
+    return torch.stack([x, y, l, w, yaw], dim=1).to(torch.float32)
+
+
 class _BoxRasterizer:
     """What the two box rasterisers share: the reference's constructor keywords and grid sizes, the upload and the launch."""
 
@@ -314,5 +337,5 @@ class WaymoRasterizer(_BoxRasterizer):
         return {WAYMO_TYPE_VEHICLE: self.rasterize_batch([boxes], [types], [counts])[0].t()}
 
 
-__all__ = ['SemanticKittiRasterizer', 'scans_in_range', 'box_vertices', 'KittiRasterizer', 'WaymoRasterizer',
+__all__ = ['SemanticKittiRasterizer', 'scans_in_range', 'box_vertices', 'boxes_from_cells', 'KittiRasterizer', 'WaymoRasterizer',
            'KITTI_TYPES', 'KITTI_CAR', 'KITTI_CAR_LIKE', 'WAYMO_TYPE_VEHICLE']

@@ -208,6 +208,28 @@ class KittiObjectBatches:
         return self.collate(samples)
 
 
+def kitti_bev_evaluation(model, config, device, root, split='val', score_threshold=0.0):
+    """Car BEV AP (easy / moderate / hard at overlaps 0.7 and 0.5) of ``model`` on every frame of ``<root>/<split>.txt``:
+    ``model.predict`` per batch, an oriented box per kept mask (K25, ``Predictions.kitti_predictions``), then the KITTI protocol on
+    the device (K26, K27; ``mask_bev_amd.kitti_eval.eval_kitti``).  All labels of a frame take part, unfiltered: the protocol
+    itself decides what counts at which difficulty.  Returns the result (a string with ``.metrics``)."""
+    from mask_bev_amd import batch as B
+    from mask_bev_amd.kitti_eval import eval_kitti
+    frames = KittiObjectBatches(dict(config, shuffle_train=False, batch_size=1), device, 0, 1, root, split)
+    bsz = max(1, int(config.get('batch_size', 1)))
+    labels, predictions = [], []
+    for start in range(0, len(frames.frames), bsz):
+        scans = []
+        for frame in frames.frames[start:start + bsz]:
+            name = f'{frame:06d}'
+            scans.append(torch.from_numpy(B.read_velodyne_bin(frames.dirs['velodyne'] / f'{name}.bin')).to(device))
+            labels.append(B.kitti_labels_to_velodyne(B.read_kitti_label(frames.dirs['label_2'] / f'{name}.txt'),
+                                                     B.read_kitti_calib(frames.dirs['calib'] / f'{name}.txt')))
+        pred = model.predict(scans, score_threshold)
+        predictions += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'])
+    return eval_kitti(labels, predictions, device=device)
+
+
 def save_checkpoint(model, optimizer, path, epoch, metric_name, metric):
     torch.save({'state_dict': model.state_dict(), 'hyper_parameters': dict(getattr(model, 'hparams', {})),
                 'optimizer_states': [optimizer.state_dict()], 'epoch': epoch, metric_name: metric}, path)
@@ -399,6 +421,9 @@ def main(argv=None):
         v = validate(0)
         if rank == 0:
             print(f'val_loss {v}' if v is not None else 'no validation data configured')
+            if dataset_name == 'kitti' and val is not None:
+                # what the reference's mask_to_pred + eval_kitti are for: boxes from the predicted masks, KITTI BEV AP
+                print(kitti_bev_evaluation(model, config, device, args.data_root), end='', flush=True)
 
     if world > 1:
         dist.destroy_process_group()
