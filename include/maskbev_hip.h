@@ -1367,6 +1367,66 @@ int mbv_kitti_statistics(const float* overlaps, const int64_t* pair_offsets, con
                          const float* thresholds, int32_t num_thresholds, int32_t compute_fp, int64_t* stats,
                          float* tp_scores, int32_t* tp_flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K28 — KITTI object augmentations: per-object perturbation and ground-truth pasting (csrc/object_augment.hip).
+ * Replaces the per-point halves of BoxNoise and ObjectSample (mask_bev/augmentations/kitti_mask_augmentations.py:227-323):
+ * mmdet3d's points_in_rbbox and points_transform_ (every point against every box, numba on a DataLoader worker) and the
+ * numpy mask / concatenate that removes the scene points inside pasted boxes and appends the pasted points.  The decisions
+ * of a frame (which bank entries are pasted, the noise each box takes: object_augment.py) are made on the host.  Parity
+ * with mmdet3d itself is not pinned by any test: the rules below are the specification.
+ *
+ * points         (n_points, dim) f32, dim 3 or 4; the scans of a batch concatenated
+ * scan_offsets   (batch + 1) i32 on the device, ascending, scan_offsets[batch] = n_points; 1 <= batch <= 4096
+ * box_table      (n_boxes, 14) f64, 8-byte aligned, the rows of all scans concatenated; one row per box:
+ *                  0 cx, 1 cy, 2 cz (the BOTTOM face), 3 l / 2, 4 w / 2, 5 h     l along the yaw direction, w across it
+ *                  6 cos theta, 7 sin theta                                      centre and theta BEFORE the noise
+ *                  8 cos r, 9 sin r, 10 tx, 11 ty, 12 tz                          the box's noise: a turn about its centre, a shift
+ *                  13 flags (0 .. 3 as an f64): bit 0 = scene points inside are removed (a pasted box),
+ *                                               bit 1 = points inside are moved
+ *                The host supplies the cosines and sines; the kernels call no transcendental function.  Pasted boxes stand
+ *                last in a scan's rows, in paste order.
+ * box_offsets    (batch + 1) i32 on the device, ascending from 0, box_offsets[batch] = n_boxes.  Rows outside the table
+ *                are never read.
+ * max_boxes      the largest number of rows one scan owns, as the caller states it: no scan is given more than this many of
+ *                its rows.  More than 128: MBV_ERR_UNSUPPORTED.
+ * bank_points    (n_bank_points, 4) f32: the points of all bank samples (object_augment.ObjectBank), resident on the device
+ * paste_segments (n_segments, 2) i32: first bank row and number of rows of every pasted sample, grouped by scan
+ * paste_offsets  (batch + 1) i32: scan b owns the segments paste_offsets[b] .. paste_offsets[b + 1] - 1; n_segments <= 65535
+ * n_paste_points the sum of the segments' rows as the caller states it.  A segment is clipped to the bank, and the segments
+ *                together to n_paste_points: nothing is read outside the bank or written outside `out`.
+ * out            (n_points + n_paste_points, dim) f32, of which the first out_offsets[batch] rows are written;
+ *                n_points + n_paste_points < 2^28, else MBV_ERR_UNSUPPORTED
+ * out_offsets    (batch + 1) i32, out_counts (batch) i32: written on the device
+ * workspace      mbv_object_augment_workspace_bytes(n_points, batch, n_segments) bytes (0 = bad arguments), 256-byte aligned
+ *
+ * The rules.  f64 arithmetic, one rounding per operation, no contraction; (x, y, z) a point's f32 values taken to f64.
+ *   membership   dx = x - cx; dy = y - cy; lx = cos theta * dx + sin theta * dy; ly = cos theta * dy - sin theta * dx;
+ *                inside iff |lx| < l / 2 and |ly| < w / 2 and 0 < z - cz < h.  All strict: a point on a face is outside.
+ *   scene point  inside ANY of its scan's rows with bit 0: removed.  Otherwise the FIRST row in table order that holds it
+ *                and has bit 1 moves it:
+ *                  x' = (f32)(((cos r * dx - sin r * dy) + cx) + tx)
+ *                  y' = (f32)(((sin r * dx + cos r * dy) + cy) + ty)
+ *                  z' = (f32)(z + tz)
+ *                intensity untouched.  A box whose search found no free place has bit 1 and the identity noise: it still
+ *                claims its points from the rows behind it, as points_transform_ does.
+ *   pasted point never removed; moved by the same first-row rule, so a pasted object follows its own perturbed box.  A
+ *                dim = 3 batch takes the bank's first three columns.
+ *   output       per scan: the kept scene points in input order, then every segment's points in paste order.
+ * Count, scan, scatter; no atomics: the output is a pure function of the inputs and a scan comes out the same alone or
+ * beside others.
+ *
+ * mbv_points_in_boxes — index (n_points) i32: the first of the n_boxes rows of box_table (same layout; columns 8 .. 13 are
+ * not read) that holds the point by the membership rule, or -1.  ObjectBank.build cuts its samples with it.
+ */
+size_t mbv_object_augment_workspace_bytes(int64_t n_points, int32_t batch, int32_t n_segments);
+int mbv_object_augment(const float* points, int32_t dim, int64_t n_points, const int32_t* scan_offsets, int32_t batch,
+                       const double* box_table, const int32_t* box_offsets, int64_t n_boxes, int32_t max_boxes,
+                       const float* bank_points, int64_t n_bank_points, const int32_t* paste_segments,
+                       const int32_t* paste_offsets, int32_t n_segments, int64_t n_paste_points, float* out,
+                       int32_t* out_offsets, int32_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+int mbv_points_in_boxes(const float* points, int32_t dim, int64_t n_points, const double* box_table, int32_t n_boxes,
+                        int32_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_kitti_statistics_workspace_bytes': (c_size_t, [_L, _I]),
     'mbv_kitti_statistics': (ctypes.c_int, [_P, _P, _P, _P, _I, _L, _L, _L, _P, _P, _P, _D, _P, _I, _I, _P, _P, _P, _P,
                                             c_size_t, _P]),
+    'mbv_object_augment_workspace_bytes': (c_size_t, [_L, _I, _I]),
+    'mbv_object_augment': (ctypes.c_int, [_P, _I, _L, _P, _I, _P, _P, _L, _I, _P, _L, _P, _P, _I, _L, _P, _P, _P, _P,
+                                          c_size_t, _P]),
+    'mbv_points_in_boxes': (ctypes.c_int, [_P, _I, _L, _P, _I, _P, _P]),
 }
 
 _lib = None

@@ -14,7 +14,10 @@ Boxes [cx, cy, cz, l, w, h, theta] follow the points: a linear op acts on the ce
 ``rotation_y`` / ``heading`` — a rotation adds its angle, the KITTI y-flip negates it, the Waymo y-flip LEAVES the heading
 as it is (waymo_mask_augmentations.py:54-59 mirrors ``center_y`` only; restated, not repaired); ``global_noise`` scales
 centre and dimensions and shifts the centre.  ``object_sample`` (needs the dataset's ``samples.pkl``) and ``object_noise``
-(mmdet3d's numba collision search) are not provided and raise ``NotImplementedError``.
+(mmdet3d's numba collision search) are not provided by the three list factories here and raise ``NotImplementedError``;
+``object_augment.make_kitti_object_augmentation_list`` builds the KITTI list with both (K28): their object stage runs in
+``apply`` before the point program, which then returns an ``ObjectAugmentedBatch``: its ``boxes`` hold the pasted and
+perturbed boxes too.
 
 Differences from the reference: a rotated map turns about the origin's cell, not about OpenCV's
 (sx / 2, sy / 2) pixel; flips mirror about the origin also on an asymmetric range; a shuffle orders points by a 26-bit hash
@@ -336,6 +339,13 @@ class AugmentedBatch(NamedTuple):
     boxes: Optional[List[np.ndarray]] = None        # per sample (n, 7) f64, moved with the points
 
 
+class ObjectAugmentedBatch(AugmentedBatch):
+    """The ``AugmentedBatch`` of a list with object transforms (K28) — the same fields to unpacking and comparisons — that
+    also carries the object stage's decisions: one ``object_augment.ObjectFrame`` per sample.  ``boxes`` then holds the
+    labels and the pasted boxes, after the noise and the point ops."""
+    objects: Optional[List] = None
+
+
 class DeviceAugmentation:
     """Compose of the transforms above.  ``x_range``, ``y_range``, ``voxel_size`` are needed only to warp instance maps."""
 
@@ -362,7 +372,10 @@ class DeviceAugmentation:
     @torch.no_grad()
     def apply(self, scans: Sequence[torch.Tensor], instance_maps: Optional[torch.Tensor] = None,
               scene_transforms: Optional[Sequence] = None, draws: Optional[Sequence[SampleDraw]] = None,
-              boxes: Optional[Sequence] = None) -> AugmentedBatch:
+              boxes: Optional[Sequence] = None, object_frames: Optional[Sequence] = None,
+              object_bank=None) -> AugmentedBatch:
+        """``object_frames``: the object stage's decisions, made by the caller (one ``object_augment.ObjectFrame`` per scan)
+        instead of drawn here; ``object_bank``: the bank their pasted entries index, when the list holds no ``ObjectSample``."""
         scans = list(scans)
         if len(scans) == 0:
             raise ValueError('empty batch')
@@ -373,21 +386,30 @@ class DeviceAugmentation:
                 raise ValueError(f'scans must all be (n, 3) or all (n, 4), got {tuple(s.shape)}')
         if instance_maps is not None and not instance_maps.is_cuda:
             raise MaskBevHipError('DeviceAugmentation needs ROCm device tensors (no CPU fallback)')
+        if boxes is not None and len(boxes) != len(scans):
+            raise ValueError('one (n, 7) box table per scan expected')
+        objects = self._object_frames(len(scans), instance_maps, scene_transforms, boxes, object_frames)   # drawn first
         draws = self.draw(len(scans)) if draws is None else list(draws)
         if len(draws) != len(scans):
             raise ValueError(f'{len(draws)} draws for {len(scans)} scans')
-        if boxes is not None and len(boxes) != len(scans):
-            raise ValueError('one (n, 7) box table per scan expected')
         if (instance_maps is not None or scene_transforms is not None) and \
                 any(op.code == OP_GLOBAL_NOISE for d in draws for op in d.ops):
             raise ValueError('global_noise is not a linear map about the origin: it cannot be applied to instance maps or '
                              'scene transforms (use box tables)')
         dev = scans[0].device
-        counts = [int(s.shape[0]) for s in scans]
-        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         mode = batch_mode(draws)
         records = torch.from_numpy(pack_records(draws).view(np.uint8).reshape(-1)).to(dev, non_blocking=True)
-        points = torch.cat([s.to(torch.float32) for s in scans]) if len(scans) > 1 else scans[0].to(torch.float32)
+        if objects is not None:
+            # K28 first; "original index" below is the row in its output
+            from . import object_augment
+            points, offsets = object_augment.run_frames(
+                scans, objects, object_augment.stage_bank(self.transforms) if object_bank is None else object_bank)
+            offsets = np.asarray(offsets, dtype=np.int32)
+            boxes = [f.moved_boxes for f in objects]
+        else:
+            counts = [int(s.shape[0]) for s in scans]
+            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+            points = torch.cat([s.to(torch.float32) for s in scans]) if len(scans) > 1 else scans[0].to(torch.float32)
         out, out_offsets, out_counts = ops_augment.augment_points(
             points, torch.from_numpy(offsets).to(dev, non_blocking=True), records, mode)
         if mode:
@@ -416,13 +438,36 @@ class DeviceAugmentation:
                 a4[:2, :2] = m
                 tfs.append(a4 @ tf.reshape(-1, 4, 4))                        # the last row stays 0 0 0 1
         moved = None if boxes is None else [transform_boxes(b, d.ops) for b, d in zip(boxes, draws)]
-        return AugmentedBatch(views, maps, tfs, list(draws), out_offsets, bool(mode), moved)
+        if objects is None:
+            return AugmentedBatch(views, maps, tfs, list(draws), out_offsets, bool(mode), moved)
+        res = ObjectAugmentedBatch(views, maps, tfs, list(draws), out_offsets, True, moved)
+        res.objects = objects
+        return res
+
+    def _object_frames(self, batch_size, instance_maps, scene_transforms, boxes, object_frames):
+        """The object stage's host decisions (``object_augment``), or None when the list holds no object transform."""
+        stage = [t for t in self.transforms if getattr(t, 'is_object_transform', False)]
+        if not stage and object_frames is None:
+            return None
+        if instance_maps is not None or scene_transforms is not None:
+            raise ValueError('object transforms move and paste boxes: they cannot be applied to instance maps or scene '
+                             'transforms (use box tables)')
+        if object_frames is not None:
+            if len(object_frames) != batch_size:
+                raise ValueError(f'{len(object_frames)} object frames for {batch_size} scans')
+            return list(object_frames)
+        if boxes is None:
+            raise ValueError('object transforms need the box tables of the batch (boxes=)')
+        if any(getattr(t, 'is_object_transform', False) for t in self.transforms[len(stage):]):
+            raise ValueError('object transforms must come before every point transform of the list')
+        from . import object_augment
+        return object_augment.draw_frames(stage, self._rng, boxes)
 
     __call__ = apply
 
 
 __all__ = ['make_augmentation', 'make_semantic_kitti_augmentation_list', 'make_kitti_augmentation_list',
            'make_waymo_augmentation_list', 'KittiFlip', 'WaymoFlip', 'GlobalNoise', 'LinearOp', 'linear_op', 'transform_boxes', 'OP_GLOBAL_NOISE',
-           'DeviceAugmentation', 'AugmentedBatch', 'SampleDraw',
+           'DeviceAugmentation', 'AugmentedBatch', 'ObjectAugmentedBatch', 'SampleDraw',
            'Op', 'Flip', 'ShufflePoints', 'RandomRotate', 'DecimatePoints', 'JitterPoints', 'RandomDropPoints', 'RandAugment',
            'rotation_op', 'drop_threshold', 'pack_records', 'batch_mode', 'RECORD_DTYPE', 'MAX_OPS']

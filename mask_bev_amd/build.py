@@ -31,6 +31,8 @@ FILE_FLAGS = {
     'rasterize.hip': ['-ffp-contract=off'],
     # K23's f64 linear op, jitter sum and map warp: one rounding per operation, as the numpy restatement does them
     'augment.hip': ['-ffp-contract=off'],
+    # K28's f64 membership test and point move: one rounding per operation, as the numpy restatement does them
+    'object_augment.hip': ['-ffp-contract=off'],
     # K25's f64 projections x cos + y sin and the extents: one rounding per operation, as the numpy restatement does them
     'box_fit.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)

@@ -15,7 +15,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_loss       K8 point sampling, K9 Hungarian, K10 importance sampling, K13 loss rows / costs
     ops_instances  K21 query selection + BEV mask / instance-map extraction at inference
     ops_rasterize  K22 SemanticKITTI scene -> instance-id map (binning, close + open, paint)
-    ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp
+    ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp;
+                   K28 KITTI object augmentations: box-table membership, move, removal and pasting of points
     ops_eval       K25 oriented box of a packed mask, K26 rotated-box overlap over ragged frames, K27 KITTI tp / fp / fn
 """
 from .ops_core import *            # noqa: F401,F403

@@ -135,12 +135,19 @@ class SemanticKittiCacheBatches:
 
 
 def build_kitti_augmentation(config):
-    """The ``augmentations:`` list of a KITTI configuration (kitti_mask_augmentations.py's names).  ``object_sample`` and
-    ``object_noise`` need files and libraries this package does not have: training goes on without them after one line."""
+    """The ``augmentations:`` list of a KITTI configuration (kitti_mask_augmentations.py's names).  With
+    ``device_object_augmentation: true`` the whole list runs, ``object_sample`` and ``object_noise`` on the device (K28) with
+    the bank of ``object_bank:`` or ``<dataset_root>/samples.npz`` (``--build-object-bank`` writes it).  Without that key
+    training goes on without the two after one line."""
     spec = config.get('augmentations')
     if not spec:
         return None
     from mask_bev_amd.augment import DeviceAugmentation, make_kitti_augmentation_list
+    if config.get('device_object_augmentation', False):
+        from mask_bev_amd.object_augment import ObjectBank, make_kitti_object_augmentation_list
+        bank = ObjectBank.load(config['object_bank']) if config.get('object_bank') else None
+        return DeviceAugmentation(make_kitti_object_augmentation_list(spec, bank), int(config.get('seed', 420)),
+                                  config['x_range'], config['y_range'], config['voxel_size'])
     left_out = [a.get('name') for a in spec if a.get('name') in ('object_sample', 'object_noise')]
     if left_out:
         print(f'warning: training without {", ".join(left_out)} (not provided: samples.pkl / mmdet3d collision search)',
@@ -185,11 +192,12 @@ class KittiObjectBatches:
     def __len__(self):
         return len(self.frames) // self.bsz
 
-    def sample(self, frame):
+    def sample(self, frame, shuffle_points=True):
         B, np = self.B, self.np
         name = f'{frame:06d}'
         pc = torch.from_numpy(B.read_velodyne_bin(self.dirs['velodyne'] / f'{name}.bin'))
-        pc = pc[torch.randperm(pc.shape[0])]                         # ShufflePointCloud (kitti_transforms.py:35-38)
+        if shuffle_points:
+            pc = pc[torch.randperm(pc.shape[0])]                     # ShufflePointCloud (kitti_transforms.py:35-38)
         labels = B.kitti_labels_to_velodyne(B.read_kitti_label(self.dirs['label_2'] / f'{name}.txt'),
                                             B.read_kitti_calib(self.dirs['calib'] / f'{name}.txt'))
         keep = np.isin(labels['type'], self.car_like)
@@ -230,6 +238,29 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
     return eval_kitti(labels, predictions, device=device)
 
 
+def object_bank_path(config, root):
+    """``object_bank:``, else ``samples.npz`` under the ``dataset_root`` of the list's ``object_sample`` entry, else under ``root``."""
+    from mask_bev_amd.object_augment import ObjectBank
+    if config.get('object_bank'):
+        return pathlib.Path(config['object_bank']).expanduser()
+    for a in config.get('augmentations') or []:
+        if a.get('name') == 'object_sample' and a.get('dataset_root'):
+            return ObjectBank.default_path(a['dataset_root'])
+    return ObjectBank.default_path(root)
+
+
+def build_object_bank(config, device, root, split='train', min_points=5):
+    """The bank ``object_sample`` pastes from (scripts/generate_kitti_object_sampler.py): every labelled box of the split's
+    frames, as this launcher selects them, that holds at least ``min_points`` points; written to ``object_bank_path``."""
+    from mask_bev_amd.object_augment import ObjectBank
+    frames = KittiObjectBatches(dict(config, shuffle_train=False, batch_size=1), device, 0, 1, root, split)
+    bank = ObjectBank.build((frames.sample(f, shuffle_points=False) for f in frames.frames), min_points, device)
+    path = object_bank_path(config, root)
+    bank.save(path)
+    print(f'object bank: {len(bank)} samples, {len(bank.points)} points from {len(frames.frames)} frames -> {path}', flush=True)
+    return path
+
+
 def save_checkpoint(model, optimizer, path, epoch, metric_name, metric):
     torch.save({'state_dict': model.state_dict(), 'hyper_parameters': dict(getattr(model, 'hparams', {})),
                 'optimizer_states': [optimizer.state_dict()], 'epoch': epoch, metric_name: metric}, path)
@@ -249,6 +280,8 @@ def main(argv=None):
     parser.add_argument('--compute-dtype', default=None, choices=[None, 'fp32', 'bf16', 'fp16'])
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly (no HIP-graph replay)')
     parser.add_argument('--checkpoint-root', default='checkpoints')
+    parser.add_argument('--build-object-bank', action='store_true',
+                        help='dataset: kitti: write the object bank of object_sample from the training split and exit')
     args = parser.parse_args(argv)
 
     is_training, is_testing = args.train, args.test
@@ -285,6 +318,11 @@ def main(argv=None):
     dev_index = local_rank % max(1, torch.cuda.device_count())
     torch.cuda.set_device(dev_index)
     device = torch.device('cuda', dev_index)
+    if args.build_object_bank:
+        if config.get('dataset', 'semantic-kitti') != 'kitti':
+            raise ValueError('--build-object-bank needs dataset: kitti')
+        build_object_bank(config, device, args.data_root or 'data/KITTI')
+        return
     import torch.distributed as dist
     if world > 1:
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
