@@ -31,13 +31,12 @@ __global__ void __launch_bounds__(256) k_pfn_stats(float* __restrict__ Y, const 
   constexpr int UMAX = 64 * CPL;
   __shared__ double red[kWavesPerBlock][2 * UMAX];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float s[CPL], q[CPL];
-#pragma unroll
-  for (int k = 0; k < CPL; ++k) { s[k] = 0.f; q[k] = 0.f; }
+  // Σ y and Σ y² in f64 from the first add: the variance is E[y²] - mean², and rows that share a large common term (a
+  // layer's pillar term t when the batch is a pillar or two) leave a variance far below mean² — f32 partial sums of y²
+  // then cost the variance 1e-5 of its value (tests/test_k2_paths_gpu.py, V = 1)
   double ds[CPL], dq[CPL];
 #pragma unroll
   for (int k = 0; k < CPL; ++k) { ds[k] = 0.0; dq[k] = 0.0; }
-  int since_flush = 0;
   // Rows are read in chunks of kChunk with all their loads issued before the first use (and before the stores
   // that follow, which the compiler must otherwise order against later loads of Y): a pillar holds ≈ 5 rows, so
   // the walk costs about one memory round trip per pillar instead of one per row and channel half.  The header
@@ -75,8 +74,9 @@ __global__ void __launch_bounds__(256) k_pfn_stats(float* __restrict__ Y, const 
           if (j0 + j < n && c < U) {
             float yy = y[j][k];
             if (T) { yy += t[k]; Y[(rs + j0 + j) * U + c] = yy; }
-            s[k] += yy;
-            q[k] += yy * yy;
+            const double yd = (double)yy;
+            ds[k] += yd;
+            dq[k] += yd * yd;
           }
         }
     }
@@ -86,19 +86,15 @@ __global__ void __launch_bounds__(256) k_pfn_stats(float* __restrict__ Y, const 
       if (c >= U) continue;
       float ypp = yp[k];
       if (T) { ypp += t[k]; Ypad[(int64_t)v * U + c] = ypp; }
-      s[k] += mult * ypp;
-      q[k] += mult * ypp * ypp;
-    }
-    if (++since_flush == 64) {      // bound the f32 partial sums: fold into f64 every 64 pillars
-#pragma unroll
-      for (int k = 0; k < CPL; ++k) { ds[k] += s[k]; dq[k] += q[k]; s[k] = 0.f; q[k] = 0.f; }
-      since_flush = 0;
+      const double ypd = (double)ypp, md = (double)mult;
+      ds[k] += md * ypd;
+      dq[k] += md * ypd * ypd;
     }
   }
 #pragma unroll
   for (int k = 0; k < CPL; ++k) {
-    red[wave][lane + 64 * k] = ds[k] + s[k];
-    red[wave][UMAX + lane + 64 * k] = dq[k] + q[k];
+    red[wave][lane + 64 * k] = ds[k];
+    red[wave][UMAX + lane + 64 * k] = dq[k];
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 2 * UMAX; i += blockDim.x) {
