@@ -159,6 +159,8 @@ class GraphedTrainStep:
             feats = m._backbone(self._x_in, cut=cut)
             early = list(feats[:cut['stage']])
             leaves = [f.detach().requires_grad_() for f in early]
+            for leaf, f in zip(leaves, early):       # a detached tensor is a new object: its absmax record (the stage norm's
+                ops.amax_hint_set(leaf, ops.amax_hint_get(f))      # bound, read by the head's input projections) is handed on
             m._panoptic_head._panoptic_head.announce_targets(self.labels, self.masks)      # static buffers, filled before the replay
             cls, masks, heights = m._panoptic_head(leaves + list(feats[cut['stage']:]))
         loss = m.loss(m.compute_loss(cls, masks, self.labels, self.masks, heights, None))

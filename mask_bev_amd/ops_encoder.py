@@ -474,10 +474,9 @@ def scatter_layernorm(feats: torch.Tensor, weight: torch.Tensor, bias: torch.Ten
     ``patch`` = 4 returns :class:`PatchTokens` (the 16-bit type of the autocast region, or of ``out``) instead of the
     (B, C, ny, nx) f32 map; ``out`` is an optional destination buffer (no grad) of the result's shape and dtype."""
     patch_dtype = out.dtype if (out is not None and patch) else lo_dtype()
-    _LAST_HINT[1] = None             # (a forward that sets no hint must not hand `out` the record of an EARLIER tensor at its address)
     out = _ScatterLayerNorm.apply(feats.float(), weight.float(), bias.float(), p.cell_to_pillar,
                                   p.pillar_batch_start, batch, ny, nx, eps, patch, out, patch_dtype)
-    amax_hint_refresh(out)           # (mark_dirty bumped a caller-owned buffer's version behind the forward's hint)
+    amax_hint_restamp(out)           # (mark_dirty bumped a caller-owned buffer's version behind the forward's hint)
     return PatchTokens(out, int(weight.shape[0]), patch) if patch else out
 
 

@@ -955,8 +955,7 @@ class _Linear(torch.autograd.Function):
                     both = f32_absmax([x32, w])
                     ctx.amax = (both[0:1], both[1:2])
                 y2 = gemm32s_nt(x32, w, b, amax=ctx.amax, hint_out=hints)
-                y = y2.view(x.shape[:-1] + (w.shape[0],))
-                amax_hint_set(y, amax_hint_get(y2))
+                y = y2.view(x.shape[:-1] + (w.shape[0],))       # (reads y2's record through its _base)
             elif (x2k is not None and gemm16_policy() == 'all' and _gemm16_ok(x2k, w)
                     and (bias is None or bias.dtype == torch.float32)):
                 bf = None if bias is None else (bias if rows is None else bias[rows[0]:rows[1]])
@@ -997,7 +996,7 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if amax_g is not None:
                 gx = gemm32s_nn(g2, w, amax_g, ctx.amax[1], hint_out=bool(switches.get('amax_hints')))
-                gx = _hinted_view(gx, x.shape)
+                gx = gx.view(x.shape)        # (a view reads the record gemm32s_nn left on gx through its _base)
             elif gemm16_policy() == 'all' and g2.is_cuda and _gemm16_ok(g2, w):
                 gx = gemm16_nn(g2, w).view_as(x)
             elif ctx.gx_f32:         # an f32 input was cast for the GEMM: its gradient leaves the GEMM as f32 (no cast pass)
@@ -1047,10 +1046,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     without materialising slices or zero-padded slice gradients.  Parameters that live in a
     :class:`~mask_bev_amd.arena.ParameterArena` are read through their bf16 shadow and receive their gradient by
     direct f32 accumulation (the autograd gradient returned for them is ``None``)."""
-    _LAST_HINT[1] = None             # see amax_hint_refresh: only a hint THIS forward sets may be re-attached to y
-    y = _Linear.apply(x, weight, bias, rows, f32_out, skip_bias_grad)
-    amax_hint_refresh(y)
-    return y
+    return _Linear.apply(x, weight, bias, rows, f32_out, skip_bias_grad)
 
 
 class _FFN(torch.autograd.Function):
@@ -1138,9 +1134,7 @@ class _FFN32(torch.autograd.Function):
         ctx.params = (w1, b1, w2, b2)
         ctx.amax = (ax, aw1, aa, aw2)
         ctx.kind, ctx.defer_out_bias, ctx.xshape = kind, defer_out_bias, x.shape
-        y = out.view(x.shape[:-1] + (w2.shape[0],))
-        amax_hint_set(y, amax_hint_get(out))
-        return y
+        return out.view(x.shape[:-1] + (w2.shape[0],))           # (reads out's record through its _base)
 
     @staticmethod
     def backward(ctx, gout):
@@ -1180,7 +1174,7 @@ class _FFN32(torch.autograd.Function):
         gx = None
         if ctx.needs_input_grad[0]:
             gx2 = gemm32s_nn(dh, w1, adh, aw1, hint_out=bool(switches.get('amax_hints')))
-            gx = _hinted_view(gx2, ctx.xshape)
+            gx = gx2.view(ctx.xshape)
         return gx, None, None, None, None, None, None
 
 
@@ -1202,10 +1196,7 @@ def ffn32_ok(x: torch.Tensor, fc1_w, fc1_b, fc2_w, fc2_b) -> bool:
 
 
 def ffn32(x: torch.Tensor, fc1_w, fc1_b, fc2_w, fc2_b, kind: str, defer_out_bias: bool = False) -> torch.Tensor:
-    _LAST_HINT[1] = None
-    y = _FFN32.apply(x, fc1_w, fc1_b, fc2_w, fc2_b, kind, defer_out_bias)
-    amax_hint_refresh(y)
-    return y
+    return _FFN32.apply(x, fc1_w, fc1_b, fc2_w, fc2_b, kind, defer_out_bias)
 
 
 def ffn_fused_ok(x: torch.Tensor, fc1_w, fc1_b, fc2_w, fc2_b) -> bool:

@@ -195,10 +195,7 @@ def bias_act(z: torch.Tensor, bias: Optional[torch.Tensor], kind: str) -> torch.
         out = torch.nn.functional.gelu(z) if k == 1 else torch.relu(z)
         amax_hint_set(out, amax_hint_get(z))
         return out
-    _LAST_HINT[1] = None
-    out = _BiasAct.apply(z, bias, k)
-    amax_hint_refresh(out)
-    return out
+    return _BiasAct.apply(z, bias, k)
 
 
 class _AccumulateBiasGrad(torch.autograd.Function):

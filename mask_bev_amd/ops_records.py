@@ -1,13 +1,14 @@
-"""The absmax-record REGISTRIES of the fp32 compute mode (K20, csrc/gemm_f32s.hip) — one module that owns their invariants.
+"""The absmax RECORDS of the fp32 compute mode (K20, csrc/gemm_f32s.hip) — one module that owns their invariants.
 
 K20 forms f32 products from IEEE-half pairs and needs, per operand tensor, a power-of-two scale from max|x|.  That maximum
-travels as a RECORD (64 device words whose maximum is the bits of max|x| or of a bound of it).  Four registries hand records out:
+travels as a RECORD (64 device words whose maximum is the bits of max|x| or of a bound of it).  Records come from:
 
 * pools (`amax_record`): zeroed records in blocks of 256, one pool per (device, thread, stream); a block never spans the start
   of a stream capture, and capture GENERATIONS (`amax_new_capture`) keep a second captured step from taking the first's;
-* hints (`amax_hint_set / _get / _refresh`): the record a producer left for a tensor, found by the tensor's address, valid
-  while that very tensor object is alive, unmodified (version) and in the capture state / generation it was made in.  A missed
-  hint costs an absmax pass — never accuracy: callers clear `_LAST_HINT` before every `Function.apply` they refresh after;
+* hints (`amax_hint_set / _get / _restamp`): the record a producer left for a tensor, kept ON THE TENSOR OBJECT (one private attribute)
+  and valid while that object is unmodified (version) and in the capture state / generation it was made in; a view finds its
+  owner's through `_base`.  Nothing is looked up by address, so no other tensor can inherit a record.  What object identity does
+  not carry (`.detach()`, an output re-read from `ctx.saved_tensors`) is carried by hand; a missed hint costs an absmax pass;
 * static records (`static_amax_register`): ONE persistent record for a long-lived buffer that crosses the eager / captured
   line (the graph step's input map; K3 clears and rewrites it every step);
 * parameter records (`weight_amax`, `ln_bound`): keyed by the optimizer epoch (`note_parameters_changed`), refreshed in one
@@ -17,6 +18,8 @@ travels as a RECORD (64 device words whose maximum is the bits of max|x| or of a
 from __future__ import annotations
 
 import ctypes
+import threading
+import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -85,7 +88,6 @@ def amax_record(device, n: int = 1) -> torch.Tensor:
     """(n, 64) int32 zeroed absmax records on the current stream (see :class:`_AmaxPool`)."""
     # one pool per (device, thread, stream): a block is zero-filled on the stream that is current when it is made, and a
     # record handed to a launch on another stream could be read before that fill ran
-    import threading
     pool = _AMAX_POOLS.setdefault((device, threading.get_ident(), torch.cuda.current_stream(device).cuda_stream), _AmaxPool())
     return pool.take(device, n)
 
@@ -193,13 +195,17 @@ def operand_amax(tensors, activations=None):
 # Absmax HINTS: K20's epilogue can max-combine the values it stores into a record while they are in its registers, and the
 # wrappers carry that record — or a bound derived from it: |gelu(z)| <= |z|, a window-attention output is a convex combination
 # of v rows, |act'| <= 1.13 — to the next K20 product that reads the tensor (fc2's input behind fc1 + GELU, proj's input
-# behind qkv + attention, fc1's output gradient behind fc2's data gradient) — found by the tensor's address, valid only while the very tensor object is alive and unmodified
-# (weak reference + version).  A consumer without a valid hint runs the absmax pass: a missed hint costs time, never accuracy.
+# behind qkv + attention, fc1's output gradient behind fc2's data gradient).  The record is an attribute of the tensor OBJECT,
+# (version, record, capture tag): it belongs to that object while the object is unmodified, and dies with it.  A view made by
+# .view / .reshape / a slice has no attribute of its own and reads its owner's through `_base` (the whole tensor's record bounds
+# a slice; a view shares its owner's version counter).  Another tensor — a clone, a later tensor at a recycled address — can
+# not find it: a record that is too small is an IEEE-half overflow inside the product, a missed one only costs the absmax pass.
+# Two tensors that ARE the same values come without their owner: `.detach()`, and an output of a Function re-read from its
+# `ctx.saved_tensors`; there the record is handed on explicitly (ctx.amax, amax_hint_set on the detached leaf).
 # A record made OUTSIDE a stream capture must not be baked into a captured launch (the replay would read the address of that one
 # eager step's record for ever) and vice versa: a hint is valid only in the capture state it was made in.  What crosses that line
 # — the eager encoder's map that a captured graph reads — has a REGISTERED persistent record instead (static_amax_register).
-_AMAX_HINTS: dict = {}
-_LAST_HINT = [0, None]
+_HINT = '_mbv_amax_hint'
 _STATIC_RECS: dict = {}
 
 
@@ -207,7 +213,6 @@ def static_amax_register(buf: torch.Tensor) -> torch.Tensor:
     """Give a long-lived buffer (the static input of a captured graph, graph.py) ONE persistent (1, 64) absmax record: the
     producer that refills the buffer every step (K3) clears and rewrites it, every K20 product that reads the buffer — under
     whatever tensor object, inside or outside a capture — finds it by the buffer's address while ``buf`` itself is alive."""
-    import weakref
     for k in [k for k, (ref, _) in _STATIC_RECS.items() if ref() is None]:
         del _STATIC_RECS[k]
     rec = torch.zeros((1, AMAX_SLOTS), dtype=torch.int32, device=buf.device)
@@ -225,31 +230,33 @@ def static_amax_record(t: torch.Tensor) -> Optional[torch.Tensor]:
     return e[1]
 
 
-def amax_hint_set(t: torch.Tensor, rec: Optional[torch.Tensor]) -> None:
-    if rec is None or not torch.is_tensor(t) or not t.is_cuda:
-        return
-    import weakref
-    if len(_AMAX_HINTS) > 512:
-        for k in [k for k, e in _AMAX_HINTS.items() if e[0]() is None]:
-            del _AMAX_HINTS[k]
-        if len(_AMAX_HINTS) > 512:
-            _AMAX_HINTS.clear()
-    cap = _capture_tag()
+def _hint_owner(t: torch.Tensor) -> torch.Tensor:
+    """A reshaped view of the whole tensor: the hint lives with the tensor, not with the temporary view object."""
     base = t._base
-    if base is not None and base.data_ptr() == t.data_ptr() and base.numel() == t.numel() and base.dtype == t.dtype:
-        t = base          # a reshaped view of the whole tensor: the hint lives with the tensor, not with the temporary view object
-    _AMAX_HINTS[t.data_ptr()] = (weakref.ref(t), t._version, rec, cap)
-    _LAST_HINT[0], _LAST_HINT[1] = t.data_ptr(), rec
+    whole = base is not None and base.data_ptr() == t.data_ptr() and base.numel() == t.numel() and base.dtype == t.dtype
+    return base if whole else t
 
 
-def amax_hint_refresh(t) -> None:
-    """After ``Function.apply``: the tensor object the caller holds may be a new wrapper of the one the forward hinted (or the
-    same buffer with its version bumped by ``mark_dirty``).  Callers clear ``_LAST_HINT[1]`` BEFORE the apply: the match is
-    by address, and a forward that sets no hint (library path) would otherwise re-attach the record of an earlier, already
-    freed tensor whose address the caching allocator handed to this output (an f16 overflow, not "time")."""
-    if torch.is_tensor(t) and t.is_cuda and _LAST_HINT[0] == t.data_ptr() and _LAST_HINT[1] is not None \
-            and amax_hint_get(t) is None:
-        amax_hint_set(t, _LAST_HINT[1])
+def _hint_set(t: torch.Tensor, rec: Optional[torch.Tensor], tag: int) -> None:
+    """``rec`` describes ``t`` as it is now, in capture state ``tag`` (None: no record does — an older one is dropped)."""
+    t = _hint_owner(t)
+    if rec is not None:
+        setattr(t, _HINT, (t._version, rec, tag))
+    elif hasattr(t, _HINT):
+        delattr(t, _HINT)
+
+
+def _hint_get(t: torch.Tensor, tag: int) -> Optional[torch.Tensor]:
+    for src in (t, t._base):          # (a slice — column block, row range — of a hinted tensor: the whole tensor's record bounds it)
+        e = getattr(src, _HINT, None) if src is not None else None
+        if e is not None and e[0] == src._version and e[2] == tag and e[1].device == t.device and src.dtype == t.dtype:
+            return e[1]
+    return None
+
+
+def amax_hint_set(t: torch.Tensor, rec: Optional[torch.Tensor]) -> None:
+    if torch.is_tensor(t) and t.is_cuda:
+        _hint_set(t, rec, _capture_tag())
 
 
 def amax_hint_get(t: torch.Tensor) -> Optional[torch.Tensor]:
@@ -257,33 +264,16 @@ def amax_hint_get(t: torch.Tensor) -> Optional[torch.Tensor]:
         rec = static_amax_record(t)
         if rec is not None:
             return rec
-    capturing = _capture_tag() if t.is_cuda else 0
-    e = _AMAX_HINTS.get(t.data_ptr())
+    return _hint_get(t, _capture_tag() if t.is_cuda else 0)
+
+
+def amax_hint_restamp(t: torch.Tensor) -> None:
+    """After a ``Function.apply`` that returned the caller's buffer ``t`` through ``mark_dirty``, which bumped its version behind
+    the hint the forward set: the hint on this very object follows the version.  An object without one stays without."""
+    t = _hint_owner(t)
+    e = getattr(t, _HINT, None)
     if e is not None:
-        ref, version, rec, cap = e
-        src = ref()
-        if (src is not None and src.data_ptr() == t.data_ptr() and src.numel() == t.numel() and src._version == version
-                and rec.device == t.device and cap == capturing):
-            return rec
-    # a slice (column block, row range) of a hinted tensor: the whole tensor's record bounds it
-    base = t._base
-    if base is not None and base is not t and base.dtype == t.dtype:
-        e = _AMAX_HINTS.get(base.data_ptr())
-        if e is not None:
-            ref, version, rec, cap = e
-            src = ref()
-            if (src is not None and src.data_ptr() == base.data_ptr() and src.numel() == base.numel()
-                    and src._version == version and rec.device == t.device and cap == capturing):
-                return rec
-    return None
-
-
-def _hinted_view(t: torch.Tensor, shape) -> torch.Tensor:
-    """``t.view(shape)`` that keeps ``t``'s absmax hint (a view is another tensor object at the same address)."""
-    v = t.view(shape)
-    if v is not t:
-        amax_hint_set(v, amax_hint_get(t))
-    return v
+        setattr(t, _HINT, (t._version,) + e[1:])
 
 
 def amax_hint_wanted(rows: int) -> bool:
@@ -314,7 +304,6 @@ def _amax_tag(dev):
 def weight_amax(w: torch.Tensor) -> torch.Tensor:
     """The absmax record of a weight, good until the parameters change.  A miss refreshes the records of EVERY weight seen so
     far in one launch per 64 (they all went stale together, with the optimizer step): ~ 30 single launches per step otherwise."""
-    import weakref
     key = (w.data_ptr(), tuple(w.shape), w.stride(0))
     tag = _amax_tag(w.device)
     e = _WEIGHT_AMAX.get(key)
@@ -350,7 +339,6 @@ def weight_amax(w: torch.Tensor) -> torch.Tensor:
 def ln_bound(weight: torch.Tensor, bias: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """The absmax-BOUND record of a LayerNorm's output, sqrt(C) max|weight| + max|bias| (mbv_ln_bound_group), good until the
     parameters change; a miss refreshes every LayerNorm seen so far in one launch."""
-    import weakref
     if (not weight.is_cuda or weight.dtype != torch.float32 or not weight.is_contiguous()
             or (bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != weight.numel()))):
         return None
