@@ -1427,6 +1427,41 @@ int mbv_object_augment(const float* points, int32_t dim, int64_t n_points, const
 int mbv_points_in_boxes(const float* points, int32_t dim, int64_t n_points, const double* box_table, int32_t n_boxes,
                         int32_t* index, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K29 — COCO mask AP: the per-image part of the `map_metric` slot, torchmetrics MeanAveragePrecision(iou_type='segm')
+ * (mask_bev/mask_bev_module.py:85-94, fed at mask_bev/models/head/mask_bev_panoptic_head.py:87-96), which evaluates every
+ * image with pycocotools' COCOeval.evaluateImg at `compute`.  Parity with those packages is not pinned (neither is
+ * installed); the plain-loop statement of the protocol is oracle/metrics_oracle.py.
+ *
+ * K29a mbv_pairwise_mask_overlap — popcounts of N images' bit-packed masks (mbv_pack_binary_masks layout, tail bits zero):
+ *   pred_words (N * Q, words) u32, gt_words (N * G, words) u32, words = mbv_packed_mask_words of the grid
+ *   inter      (N, Q, G) i32   sum over the words of popc(pred & gt)
+ *   pred_area  (N, Q) i32, gt_area (N, G) i32   set bits of every row
+ *   Integer work, exact.  Q, G <= 1024 and words <= 2^26, else MBV_ERR_UNSUPPORTED.  N * Q * G == 0: MBV_OK whatever the
+ *   pointers are; `inter` is not touched, and an area table is written only where it has rows and was given with its words.
+ *   Nothing but the three outputs is written.
+ *
+ * K29b mbv_coco_match — COCOeval.evaluateImg for every image, class 0 .. num_labels-1, area range and IoU threshold at once:
+ *   inter, pred_area, gt_area as above; scores (N, Q) f32; pred_labels (N, Q) i32, gt_labels (N, G) i32 (a label outside
+ *   0 .. num_labels-1 takes no part); iou_thrs (T) f64; area_ranges (A, 2) f64 = [lo, hi] closed; T * A <= 64; max_det >= 1.
+ *   Per (image, class): the detections of that label in descending score, ties in index order, the first max_det of them;
+ *   a ground truth is ignored iff its area is outside the range; iou = (double)inter / (double)(pred_area + gt_area - inter),
+ *   0 for an empty union, compared in f64 with the thresholds as given; a detection tries the free, not ignored ground
+ *   truths of its class in index order and the ignored ones only if it found nothing, every comparison `iou >= best` with
+ *   best starting at min(threshold, 1 - 1e-10); matched to an ignored ground truth, or unmatched with its own area outside
+ *   the range: the detection is ignored.
+ *   rank    (N, Q) i32   position in the score order of the class; 2^30 past max_det or without a label in range
+ *   matched (N, Q) i64, ignored (N, Q) i64   bit a * T + t: area range a, threshold t
+ *   npig    (N, num_labels, A) i32   ground truths of the class that are not ignored
+ *   Q, G <= 1024, num_labels <= 65536, else MBV_ERR_UNSUPPORTED.  N == 0: MBV_OK.  Every index comes from the sizes: values
+ *   that disagree with them change results, never addresses. */
+int mbv_pairwise_mask_overlap(const uint32_t* pred_words, const uint32_t* gt_words, int32_t N, int32_t Q, int32_t G,
+                              int64_t words, int32_t* inter, int32_t* pred_area, int32_t* gt_area, void* stream);
+int mbv_coco_match(const int32_t* inter, const int32_t* pred_area, const int32_t* gt_area, const float* scores,
+                   const int32_t* pred_labels, const int32_t* gt_labels, int32_t N, int32_t Q, int32_t G, int32_t num_labels,
+                   const double* iou_thrs, int32_t T, const double* area_ranges, int32_t A, int32_t max_det, int32_t* rank,
+                   int64_t* matched, int64_t* ignored, int32_t* npig, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

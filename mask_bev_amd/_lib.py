@@ -204,6 +204,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_object_augment': (ctypes.c_int, [_P, _I, _L, _P, _I, _P, _P, _L, _I, _P, _L, _P, _P, _I, _L, _P, _P, _P, _P,
                                           c_size_t, _P]),
     'mbv_points_in_boxes': (ctypes.c_int, [_P, _I, _L, _P, _I, _P, _P]),
+    'mbv_pairwise_mask_overlap': (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _P, _P, _P, _P]),
+    'mbv_coco_match': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -307,17 +307,25 @@ class MaskBevModule(_Base):
         scans = batch[0] if isinstance(batch, tuple) and len(batch) in (2, 3) and not torch.is_tensor(batch[0]) else batch
         return self.predict(scans)
 
-    def enable_metrics(self, layers=(9,), train: bool = True, val: bool = True, mask_map: bool = False):
+    def enable_metrics(self, layers=(9,), train: bool = True, val: bool = True, mask_map=False):
         """Build extension: attach the GPU-native classification / mIoU metrics (mask_bev_amd/metrics.py) to the
         given decoder layers, in the reference's ``{layer: (cls_metric, map_metric, miou_metric)}`` layout
-        (mask_bev_module.py:85-98).  ``mask_map=True`` also fills the COCO mask-mAP slot (needs dense ground-truth
-        masks in the batch)."""
-        from .metrics import BinaryClassifScores, MaskMeanAveragePrecision, MeanIoU
+        (mask_bev_module.py:85-98).  ``mask_map=True`` also fills the COCO mask-mAP slot with
+        ``MaskMeanAveragePrecision`` (needs dense ground-truth masks in the batch); ``mask_map='device'`` fills it with
+        ``DeviceMaskMeanAveragePrecision`` (K29: no host synchronisation per step, dense or packed ground truth)."""
+        from .metrics import BinaryClassifScores, DeviceMaskMeanAveragePrecision, MaskMeanAveragePrecision, MeanIoU
+        if mask_map not in (False, True, 'device'):
+            raise ValueError(f"enable_metrics: mask_map must be False, True or 'device', got {mask_map!r}")
+
+        def map_metric():
+            if mask_map == 'device':
+                return DeviceMaskMeanAveragePrecision()
+            return MaskMeanAveragePrecision() if mask_map else None
+
         for flag, store in ((train, self._train_metric_per_layer), (val, self._val_metric_per_layer)):
             if flag:
                 for layer in layers:
-                    store[int(layer)] = (BinaryClassifScores(), MaskMeanAveragePrecision() if mask_map else None,
-                                         MeanIoU())
+                    store[int(layer)] = (BinaryClassifScores(), map_metric(), MeanIoU())
 
     def log_metrics(self, mode: str, per_layer):
         """mask_bev_module.py:209-224: log and reset the per-layer metrics at the end of an epoch."""

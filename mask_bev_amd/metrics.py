@@ -15,12 +15,16 @@ to ground-truth resolution, thresholds and hands dense tensors to torchmetrics. 
   dense masks to pycocotools at ``compute``) is :class:`MaskMeanAveragePrecision`: the (Q, G) IoU matrix of every image
   is formed on the GPU at ``update`` (bilinear upsampling, threshold, two {0,1} GEMMs) and only that matrix, the
   scores, labels and areas are kept; ``compute`` runs the COCO protocol on them.
+* :class:`DeviceMaskMeanAveragePrecision` fills the same slot without leaving the device: bit-packed predicted masks
+  from K21, pairwise popcounts and the per-image COCO matching from K29 (csrc/mask_map.hip), no host synchronisation in
+  ``update``; ``compute`` accumulates the whole dataset in vectorised torch and copies twelve numbers back.
 """
 from __future__ import annotations
 
 import ctypes
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -241,10 +245,159 @@ class MaskMeanAveragePrecision:
                     mar_medium=ar(2, 2), mar_large=ar(2, 3))
 
 
+class DeviceMaskMeanAveragePrecision:
+    """The metric of :class:`MaskMeanAveragePrecision` — same ``update`` / ``compute`` / ``reset``, same twelve keys — with
+    the per-image work on the device: ``update`` takes the predicted masks at ground-truth resolution bit-packed from K21
+    (``ops.extract_masks``), the pairwise popcounts from K29a and COCOeval.evaluateImg of every (image, class, area range,
+    IoU threshold) from K29b, and keeps per detection its score, label, rank in its class and two 64-bit flag words
+    (matched / ignored, bit ``area * T + threshold``) plus the counted ground truths per (class, area range): no dense
+    mask, no IoU matrix, no host synchronisation.  ``compute`` is plain torch on the device the state lives on (CPU
+    tensors work): one stable sort by score over the whole dataset, per class and detection limit f64 cumulative sums, the
+    monotone envelope and a ``searchsorted`` at the 101 recall thresholds, then ONE host copy of the twelve numbers.
+    Classes ``0 .. num_labels - 1`` are all evaluated; one without counted ground truths drops out of the means exactly as
+    a label that never occurs does in the other class.  With ``torch.distributed`` initialised, ``compute`` gathers the
+    states of all ranks first (``all_gather``: every rank must hold equally many images), so every rank returns the same
+    numbers.  The ground truth may be dense (B, G, ny, nx) or :class:`ops.PackedMasks`.
+    Checked against the plain-loop restatement in oracle/metrics_oracle.py; parity with torchmetrics / pycocotools
+    themselves stays unpinned: neither is installed."""
+
+    IOU_THRS = torch.from_numpy(np.linspace(0.5, 0.95, 10))          # the oracle's own f64 values: comparisons are bit-equal
+    REC_THRS = torch.from_numpy(np.linspace(0.0, 1.0, 101))
+    MAX_DETS = MaskMeanAveragePrecision.MAX_DETS
+    AREAS = MaskMeanAveragePrecision.AREAS
+    STATE = ('scores', 'labels', 'rank', 'matched', 'ignored', 'npig')
+
+    def __init__(self, num_labels: Optional[int] = None):
+        self.num_labels = num_labels            # update_metrics sets it from the class logits when None
+        self.state: List[tuple] = []
+        self._const = {}
+
+    def reset(self):
+        self.state = []
+
+    def append_state(self, scores: torch.Tensor, labels: torch.Tensor, rank: torch.Tensor, matched: torch.Tensor,
+                     ignored: torch.Tensor, npig: torch.Tensor):
+        """The state of some images as K29b leaves it: ``scores`` (.., Q) float, ``labels`` / ``rank`` (.., Q) integer,
+        ``matched`` / ``ignored`` (.., Q) int64 flag words, ``npig`` (.., num_labels, A) integer.  Tensors of any one device."""
+        a = len(self.AREAS)
+        if npig.dim() < 2 or npig.shape[-1] != a:
+            raise ValueError(f'append_state: npig must be (.., num_labels, {a}), got {tuple(npig.shape)}')
+        if not (scores.shape == labels.shape == rank.shape == matched.shape == ignored.shape):
+            raise ValueError('append_state: scores, labels, rank, matched and ignored must have one shape')
+        if self.num_labels is None:
+            self.num_labels = int(npig.shape[-2])
+        if int(npig.shape[-2]) != self.num_labels:
+            raise ValueError(f'append_state: npig of {npig.shape[-2]} classes, {self.num_labels} expected')
+        self.state.append((scores.detach().flatten(), labels.detach().flatten(), rank.detach().flatten(),
+                           matched.detach().flatten().to(torch.int64), ignored.detach().flatten().to(torch.int64),
+                           npig.detach().reshape(-1, self.num_labels, a)))
+
+    def _constants(self, dev):
+        if dev not in self._const:
+            areas = torch.tensor([[lo, hi] for _, lo, hi in self.AREAS], dtype=torch.float64)
+            self._const[dev] = (self.IOU_THRS.to(dev), areas.to(dev))
+        return self._const[dev]
+
+    @torch.no_grad()
+    def update(self, pred_logits: torch.Tensor, scores: torch.Tensor, pred_labels: torch.Tensor, gt_masks, gt_labels: torch.Tensor):
+        """One batch: ``pred_logits`` (B, Q, h, w) mask logits, ``scores`` / ``pred_labels`` (B, Q), ``gt_masks`` (B, G, ny, nx)
+        {0, 1} or the B * G maps as :class:`ops.PackedMasks`, ``gt_labels`` (B, G).  K21, K29a, K29b; nothing is copied back."""
+        if self.num_labels is None:
+            raise MaskBevHipError('DeviceMaskMeanAveragePrecision: num_labels is not set')
+        if not pred_logits.is_cuda:
+            raise MaskBevHipError('DeviceMaskMeanAveragePrecision.update needs ROCm device tensors (no CPU fallback)')
+        b, q = scores.shape
+        gt = gt_masks if isinstance(gt_masks, ops.PackedMasks) else ops.pack_binary_masks(gt_masks.float().flatten(0, 1))
+        dev = pred_logits.device
+        scores = scores.float().contiguous()
+        keep = torch.ones((b, q), dtype=torch.bool, device=dev)
+        pred = ops.extract_masks(pred_logits.float(), scores, keep, (gt.h, gt.w), masks=True, instance_map=False)['masks']
+        inter, pred_area, gt_area = ops.pairwise_mask_overlap(pred, gt, b)
+        thrs, areas = self._constants(dev)
+        labels = pred_labels.to(torch.int32)
+        rank, matched, ignored, npig = ops.coco_match(inter, pred_area, gt_area, scores, labels,
+                                                      gt_labels.to(torch.int32), self.num_labels, thrs, areas,
+                                                      self.MAX_DETS[-1])
+        self.append_state(scores, labels, rank, matched, ignored, npig)
+
+    def _gathered_state(self):
+        state = [torch.cat([s[i] for s in self.state]) for i in range(len(self.STATE))]
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            out = []
+            for x in state:
+                parts = [torch.empty_like(x) for _ in range(dist.get_world_size())]
+                dist.all_gather(parts, x.contiguous())
+                out.append(torch.cat(parts))
+            state = out
+        return state
+
+    @torch.no_grad()
+    def compute(self) -> dict:
+        keys = ('map', 'map_50', 'map_75', 'map_small', 'map_medium', 'map_large', 'mar_1', 'mar_10', 'mar_100',
+                'mar_small', 'mar_medium', 'mar_large')
+        if not self.state:
+            return {k: -1.0 for k in keys}
+        scores, labels, rank, matched, ignored, npig = self._gathered_state()
+        dev = scores.device
+        t_n, r_n, a_n, m_n, l_n = len(self.IOU_THRS), len(self.REC_THRS), len(self.AREAS), len(self.MAX_DETS), self.num_labels
+        n_det = scores.numel()
+        npig = npig.sum(0).double()                                                       # (L, A)
+        precision = -torch.ones((t_n, r_n, l_n, a_n, m_n), dtype=torch.float64, device=dev)
+        recall = -torch.ones((t_n, l_n, a_n, m_n), dtype=torch.float64, device=dev)
+        if n_det > 0:
+            # ONE stable sort by score for the whole dataset; a (class, detection limit) selection is a mask in that order: a
+            # masked-out detection adds nothing to the cumulative sums, so it repeats the values of the selected one before it
+            # (or the zeros in front of the first) and moves neither the envelope nor the first position that reaches a recall
+            order = torch.sort(-scores.double(), stable=True).indices
+            labels, rank = labels[order], rank[order]
+            shifts = torch.arange(a_n * t_n, device=dev, dtype=torch.int64)
+            dtm = ((matched[order].view(-1, 1) >> shifts) & 1).bool()                      # (D, A * T)
+            counted = ((ignored[order].view(-1, 1) >> shifts) & 1) == 0
+            tp_flag, fp_flag = dtm & counted, ~dtm & counted
+            eps = torch.finfo(torch.float64).eps
+            rec_thrs = self.REC_THRS.to(dev).view(1, r_n).expand(a_n * t_n, r_n).contiguous()
+            for c in range(l_n):
+                in_class = labels == c
+                denom = npig[c].repeat_interleave(t_n).view(-1, 1)                         # (A * T, 1)
+                valid = (denom > 0).view(a_n, t_n)
+                for m, max_det in enumerate(self.MAX_DETS):
+                    sel = (in_class & (rank < max_det)).view(-1, 1)
+                    tp = torch.cumsum((tp_flag & sel).double(), 0).t().contiguous()          # (A * T, D)
+                    fp = torch.cumsum((fp_flag & sel).double(), 0).t().contiguous()
+                    rc = tp / denom
+                    pr = tp / (fp + tp + eps)
+                    pr = torch.flip(torch.cummax(torch.flip(pr, (1,)), 1).values, (1,))     # monotone envelope
+                    idx = torch.searchsorted(rc, rec_thrs, right=False)
+                    q = torch.where(idx < n_det, pr.gather(1, idx.clamp(max=n_det - 1)), torch.zeros_like(rec_thrs))
+                    q = torch.where(valid.view(a_n, t_n, 1), q.view(a_n, t_n, r_n), -torch.ones_like(q).view(a_n, t_n, r_n))
+                    precision[:, :, c, :, m] = q.permute(1, 2, 0)
+                    recall[:, c, :, m] = torch.where(valid, rc[:, -1].view(a_n, t_n), -torch.ones_like(valid, dtype=torch.float64)).t()
+        else:
+            has = (npig > 0).view(1, l_n, a_n, 1)
+            precision = torch.where(has.view(1, 1, l_n, a_n, 1), torch.zeros_like(precision), precision)
+            recall = torch.where(has, torch.zeros_like(recall), recall)
+
+        def mean(s):
+            ok = s > -1
+            cnt = ok.sum()
+            return torch.where(cnt > 0, torch.where(ok, s, torch.zeros_like(s)).sum() / cnt.clamp(min=1), -torch.ones((), dtype=torch.float64, device=dev))
+
+        t50 = int(np.nonzero(np.isclose(self.IOU_THRS.numpy(), 0.5))[0][0])
+        t75 = int(np.nonzero(np.isclose(self.IOU_THRS.numpy(), 0.75))[0][0])
+        last = m_n - 1
+        out = torch.stack([mean(precision[:, :, :, 0, last]), mean(precision[t50, :, :, 0, last]),
+                           mean(precision[t75, :, :, 0, last]), mean(precision[:, :, :, 1, last]),
+                           mean(precision[:, :, :, 2, last]), mean(precision[:, :, :, 3, last]),
+                           mean(recall[:, :, 0, 0]), mean(recall[:, :, 0, 1]), mean(recall[:, :, 0, 2]),
+                           mean(recall[:, :, 1, last]), mean(recall[:, :, 2, last]), mean(recall[:, :, 3, last])]).cpu().tolist()
+        return dict(zip(keys, out))
+
+
 @torch.no_grad()
 def update_metrics(head, layer_index: int, pred_cls, pred_masks, labels_gt: torch.Tensor, masks_gt,
                    cls_metric: Optional[BinaryClassifScores], miou_metric: Optional[MeanIoU],
-                   map_metric: Optional[MaskMeanAveragePrecision] = None):
+                   map_metric=None):
     """``MaskBevPanopticHead.update_mAP_metrics`` for the classification and mIoU metrics, batched over the images and
     reusing the assignment of the loss that was just evaluated on the same predictions (``head`` is the
     ``Mask2FormerHead``; call after ``compute_loss``).  ``pred_cls`` / ``pred_masks``: the per-layer output lists."""
@@ -264,7 +417,13 @@ def update_metrics(head, layer_index: int, pred_cls, pred_masks, labels_gt: torc
                 masks_gt.float().flatten(0, 1))
         miou_metric.update(matched_mask_iou(pred_masks[layer_index], assigned, gt))
     if map_metric is not None:                            # mask_bev_panoptic_head.py:87-96
-        if isinstance(masks_gt, ops.PackedMasks):
-            raise MaskBevHipError('the mask-mAP metric needs the dense (B, G, ny, nx) ground-truth masks')
         sm = cls.float().softmax(-1)
-        map_metric.update(pred_masks[layer_index], sm[..., 0], cls.argmax(-1), masks_gt, labels_gt)
+        if isinstance(map_metric, DeviceMaskMeanAveragePrecision):
+            if map_metric.num_labels is None:
+                map_metric.num_labels = int(cls.shape[-1])
+            gt = head.last_gt_packed if getattr(head, 'last_gt_packed', None) is not None else masks_gt
+        elif isinstance(masks_gt, ops.PackedMasks):
+            raise MaskBevHipError('the mask-mAP metric needs the dense (B, G, ny, nx) ground-truth masks')
+        else:
+            gt = masks_gt
+        map_metric.update(pred_masks[layer_index], sm[..., 0], cls.argmax(-1), gt, labels_gt)

@@ -1,6 +1,8 @@
 """K25 — oriented box of a bit-packed mask (csrc/box_fit.hip); K26 — rotated-box overlap over ragged frames
 (csrc/rotate_iou.hip); K27 — KITTI tp / fp / fn of all frames and score thresholds (csrc/kitti_stats.hip).  The three
-kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``; the definitions are in include/maskbev_hip.h."""
+kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``.  K29 — pairwise overlap of bit-packed masks and
+the COCO per-image matching on its integer tables (csrc/mask_map.hip), behind ``metrics.DeviceMaskMeanAveragePrecision``.
+The definitions are in include/maskbev_hip.h."""
 from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple, Union
@@ -154,4 +156,75 @@ def kitti_statistics(overlaps: torch.Tensor, offsets: FrameOffsets, ignored_gt: 
     return (stats, tp_scores, tp_flags) if collect_scores else stats
 
 
-__all__ = ['fit_boxes', 'rotate_iou', 'kitti_statistics', 'FrameOffsets']
+def _packed_rows(masks: PackedMasks, n: int, what: str) -> int:
+    words = masks.words
+    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
+        raise MaskBevHipError(f'{what}: words must be a contiguous (rows, words) int32 tensor')
+    if n < 0 or (n == 0 and words.shape[0] != 0) or (n > 0 and words.shape[0] % n != 0):
+        raise MaskBevHipError(f'{what}: {words.shape[0]} maps do not divide into {n} images')
+    return words.shape[0] // n if n > 0 else 0
+
+
+@torch.no_grad()
+def pairwise_mask_overlap(pred: PackedMasks, gt: PackedMasks, n: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """pred: the n * Q predicted maps, gt: the n * G ground-truth maps of n images, bit-packed on one grid →
+    ``(inter (n, Q, G), pred_area (n, Q), gt_area (n, G))`` int32 popcounts (K29a): exact.  Q, G <= 1024.  No host
+    synchronisation."""
+    lib = _lib.load()
+    _need_gpu(pred.words, gt.words)
+    if (int(pred.h), int(pred.w)) != (int(gt.h), int(gt.w)) or pred.words.device != gt.words.device:
+        raise MaskBevHipError('pairwise_mask_overlap: the two sets of maps must share grid and device')
+    q, g = _packed_rows(pred, n, 'pairwise_mask_overlap: pred'), _packed_rows(gt, n, 'pairwise_mask_overlap: gt')
+    nwords = lib.mbv_packed_mask_words(int(pred.h), int(pred.w))
+    if pred.words.shape[1] != nwords or gt.words.shape[1] != nwords:
+        raise MaskBevHipError(f'pairwise_mask_overlap: {nwords} words per map expected for a {pred.h}x{pred.w} grid')
+    dev = pred.words.device
+    inter = torch.empty((n, q, g), dtype=torch.int32, device=dev)
+    pred_area = torch.empty((n, q), dtype=torch.int32, device=dev)
+    gt_area = torch.empty((n, g), dtype=torch.int32, device=dev)
+    check(lib.mbv_pairwise_mask_overlap(_ptr(pred.words), _ptr(gt.words), n, q, g, nwords, _ptr(inter), _ptr(pred_area),
+                                        _ptr(gt_area), _stream()), 'mbv_pairwise_mask_overlap')
+    return inter, pred_area, gt_area
+
+
+@torch.no_grad()
+def coco_match(inter: torch.Tensor, pred_area: torch.Tensor, gt_area: torch.Tensor, scores: torch.Tensor,
+               pred_labels: torch.Tensor, gt_labels: torch.Tensor, num_labels: int, iou_thrs: torch.Tensor,
+               area_ranges: torch.Tensor, max_det: int):
+    """K29b on K29a's tables: ``inter`` (n, Q, G), ``pred_area`` (n, Q), ``gt_area`` (n, G) int32, ``scores`` (n, Q) f32,
+    ``pred_labels`` (n, Q) / ``gt_labels`` (n, G) int32, ``iou_thrs`` (T) f64, ``area_ranges`` (A, 2) f64 with T * A <= 64 →
+    ``(rank (n, Q) int32, matched (n, Q) int64, ignored (n, Q) int64, npig (n, num_labels, A) int32)``: COCOeval.evaluateImg
+    of every (image, class, area range, threshold); bit a * T + t of the two masks.  Device tensors in and out, no host
+    synchronisation."""
+    lib = _lib.load()
+    _need_gpu(inter, pred_area, gt_area, scores, pred_labels, gt_labels, iou_thrs, area_ranges)
+    if inter.dim() != 3:
+        raise MaskBevHipError(f'coco_match: inter must be (n, Q, G), got {tuple(inter.shape)}')
+    n, q, g = inter.shape
+    dev = inter.device
+    for x, shape, dtype, what in ((inter, (n, q, g), torch.int32, 'inter'), (pred_area, (n, q), torch.int32, 'pred_area'),
+                                  (gt_area, (n, g), torch.int32, 'gt_area'), (scores, (n, q), torch.float32, 'scores'),
+                                  (pred_labels, (n, q), torch.int32, 'pred_labels'),
+                                  (gt_labels, (n, g), torch.int32, 'gt_labels')):
+        if tuple(x.shape) != shape or x.dtype != dtype or x.device != dev:
+            raise MaskBevHipError(f'coco_match: {what} must be {shape} {dtype} on {dev}, got {tuple(x.shape)} {x.dtype}')
+    if iou_thrs.dtype != torch.float64 or iou_thrs.dim() != 1 or area_ranges.dtype != torch.float64 \
+            or area_ranges.dim() != 2 or area_ranges.shape[1] != 2 or iou_thrs.device != dev or area_ranges.device != dev:
+        raise MaskBevHipError('coco_match: iou_thrs must be (T) f64 and area_ranges (A, 2) f64 on the tables\' device')
+    t, a = iou_thrs.numel(), area_ranges.shape[0]
+    if t < 1 or a < 1 or t * a > 64 or num_labels < 1 or max_det < 1:
+        raise MaskBevHipError(f'coco_match: T = {t}, A = {a} (T * A <= 64), num_labels = {num_labels}, max_det = {max_det}')
+    inter, pred_area, gt_area = inter.contiguous(), pred_area.contiguous(), gt_area.contiguous()
+    scores, pred_labels, gt_labels = scores.contiguous(), pred_labels.contiguous(), gt_labels.contiguous()
+    iou_thrs, area_ranges = iou_thrs.contiguous(), area_ranges.contiguous()
+    rank = torch.empty((n, q), dtype=torch.int32, device=dev)
+    matched = torch.empty((n, q), dtype=torch.int64, device=dev)
+    ignored = torch.empty((n, q), dtype=torch.int64, device=dev)
+    npig = torch.empty((n, int(num_labels), a), dtype=torch.int32, device=dev)
+    check(lib.mbv_coco_match(_ptr(inter), _ptr(pred_area), _ptr(gt_area), _ptr(scores), _ptr(pred_labels), _ptr(gt_labels),
+                             n, q, g, int(num_labels), _ptr(iou_thrs), t, _ptr(area_ranges), a, int(max_det), _ptr(rank),
+                             _ptr(matched), _ptr(ignored), _ptr(npig), _stream()), 'mbv_coco_match')
+    return rank, matched, ignored, npig
+
+
+__all__ = ['fit_boxes', 'rotate_iou', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match']

@@ -261,6 +261,14 @@ def build_object_bank(config, device, root, split='train', min_points=5):
     return path
 
 
+def format_layer_metrics(logged, layer):
+    """One line of ``--test`` per decoder layer from the module's logged values (mask_bev_module.py:209-224)."""
+    names = ('map', 'map_50', 'map_75', 'mar_100')
+    parts = [f'{n} {logged[f"val_mAP_{layer}_{n}"]:.4f}' for n in names]
+    parts += [f'mIoU {logged[f"val_mIoU_layer_{layer}"]:.4f}', f'cls_AP {logged[f"val_cls_mAP_layer_{layer}"]:.4f}']
+    return f'layer {layer}: ' + ' '.join(parts)
+
+
 def save_checkpoint(model, optimizer, path, epoch, metric_name, metric):
     torch.save({'state_dict': model.state_dict(), 'hyper_parameters': dict(getattr(model, 'hparams', {})),
                 'optimizer_states': [optimizer.state_dict()], 'epoch': epoch, metric_name: metric}, path)
@@ -456,9 +464,18 @@ def main(argv=None):
     if is_testing:
         # the reference runs trainer.validate then trainer.test (train_mask_bev.py:118-119); MaskBevModule defines no
         # test_step, so the test pass has nothing of its own to run: validation is the whole of it
+        layers = tuple(range(model.num_layers))    # the reference attaches its metrics to all ten decoder outputs (:85-98)
+        if val is not None:
+            # what trainer.validate logs there: COCO mask AP (K29), mIoU and class AP of every decoder layer
+            model.enable_metrics(layers=layers, train=False, val=True, mask_map='device')
         v = validate(0)
+        if val is not None:
+            model.on_validation_epoch_end()            # every rank: the mask AP gathers the states of all ranks
         if rank == 0:
             print(f'val_loss {v}' if v is not None else 'no validation data configured')
+            if val is not None:
+                for layer in layers:
+                    print(format_layer_metrics(model.logged, layer), flush=True)
             if dataset_name == 'kitti' and val is not None:
                 # what the reference's mask_to_pred + eval_kitti are for: boxes from the predicted masks, KITTI BEV AP
                 print(kitti_bev_evaluation(model, config, device, args.data_root), end='', flush=True)
