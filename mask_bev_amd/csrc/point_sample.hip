@@ -120,7 +120,8 @@ __global__ void __launch_bounds__(1024) k_point_sample_fwd_bands(const float* __
   const int y_end = (y0 + band_rows + 1) < H ? (y0 + band_rows + 1) : H;       // rows staged: [y0, y_end)
   const int lo = y0 * W, hw = (y_end - y0) * W;
   const float* s = src + (int64_t)src_index[g] * H * W + lo;
-  if ((lo & 3) == 0) {
+  // 16-byte loads need the MAP's base aligned too: map src_index[g] starts at a multiple of H * W floats
+  if ((lo & 3) == 0 && ((int64_t)H * W & 3) == 0) {
     stage_map(tile, s, hw);
   } else {
     for (int i = threadIdx.x; i < hw; i += blockDim.x) tile[i] = s[i];
