@@ -878,6 +878,7 @@ int mbv_upsample_bilinear_bwd(const void* grad_out, int32_t grad_dtype, int64_t 
  * align_corners=False)  between them.  x (batch, channels, h, w) in x_dtype (MBV_DT_*), h*w % 4 == 0, 16-byte aligned;
  *   y = GroupNorm(x; groups, gamma, beta, eps)  [+ up-sampled `add` (batch, channels, add_h, add_w), w % 4 == 0]  [ReLU]
  * stored in y_dtype; mean / rstd (batch * groups) f32 are saved for the backward; statistics in f64 (biased variance).
+ * `add` together with relu is MBV_ERR_UNSUPPORTED: the backward gates on GroupNorm(x) alone, not on the sum.
  * Backward: dx in dx_dtype, dgamma / dbeta (channels) stored or (accumulate != 0) added to; the ReLU gate is recomputed
  * from x with the forward's arithmetic; the gradient of `add` is the up-sampling's backward of dy (left to the caller).
  * plane_sums: batch * channels * 2 floats of scratch. */

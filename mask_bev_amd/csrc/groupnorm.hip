@@ -60,6 +60,12 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {      // 2
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+__device__ __forceinline__ void acc4(const float4 a, double& s1, double& s2) {
+  const double x0 = a.x, x1 = a.y, x2 = a.z, x3 = a.w;
+  s1 += (x0 + x1) + (x2 + x3);
+  s2 += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
+}
+
 // A group of an NCHW map is one contiguous run of n = (C / G) * H * W elements.  Block (bg, s) sums chunk s of it.
 __global__ void __launch_bounds__(256) k_gn_stats(const void* __restrict__ x, int kind, long n, int splits,
                                                   double* __restrict__ partial) {
@@ -68,19 +74,18 @@ __global__ void __launch_bounds__(256) k_gn_stats(const void* __restrict__ x, in
   const int s = blockIdx.x - (int)(bg * splits);
   const long nvec = n >> 2, per = (nvec + splits - 1) / splits;
   const long v0 = s * per, v1 = v0 + per < nvec ? v0 + per : nvec;
-  float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
+  // f64 from the first add: the variance is E[x²] − mean², and a map whose mean is far from zero (50 ± 1) loses the
+  // difference in f32 squares and f32 per-thread sums (as K3's and K2's statistics; the kernel stays HBM-bound)
+  double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
   long v = v0 + threadIdx.x;
   for (; v + 256 < v1; v += 512) {                   // two independent 16-byte loads in flight per thread
     const float4 a = ld4(x, kind, bg * n + 4 * v), b = ld4(x, kind, bg * n + 4 * (v + 256));
-    s1[0] += (a.x + a.y) + (a.z + a.w); s2[0] += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-    s1[1] += (b.x + b.y) + (b.z + b.w); s2[1] += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
+    acc4(a, s1[0], s2[0]);
+    acc4(b, s1[1], s2[1]);
   }
-  if (v < v1) {
-    const float4 a = ld4(x, kind, bg * n + 4 * v);
-    s1[0] += (a.x + a.y) + (a.z + a.w); s2[0] += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-  }
-  const double t1 = block_sum_d((double)s1[0] + (double)s1[1], red);
-  const double t2 = block_sum_d((double)s2[0] + (double)s2[1], red);
+  if (v < v1) acc4(ld4(x, kind, bg * n + 4 * v), s1[0], s2[0]);
+  const double t1 = block_sum_d(s1[0] + s1[1], red);
+  const double t2 = block_sum_d(s2[0] + s2[1], red);
   if (threadIdx.x == 0) {
     partial[((long)blockIdx.x) * 2] = t1;
     partial[((long)blockIdx.x) * 2 + 1] = t2;
@@ -362,6 +367,8 @@ extern "C" int mbv_groupnorm_fwd(const void* x, int32_t x_dtype, int64_t batch, 
   if (!x || !gamma || !beta || !y || !mean || !rstd || !kind_ok(x_dtype) || !kind_ok(y_dtype)) return MBV_ERR_BAD_ARG;
   if (add && (!kind_ok(add_dtype) || add_h <= 0 || add_w <= 0)) return MBV_ERR_BAD_ARG;
   if (add && (w & 3)) return MBV_ERR_UNSUPPORTED;
+  // the backward rebuilds the ReLU gate from x, γ, β and the statistics alone: it cannot know the sign of GN(x) + add
+  if (add && relu) return MBV_ERR_UNSUPPORTED;
   if ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(y)) & 15) return MBV_ERR_UNSUPPORTED;
   if (!workspace || workspace_bytes < mbv_groupnorm_workspace_bytes(batch, channels, groups, h, w)) return MBV_ERR_WORKSPACE;
   if (batch * channels > 0x7fffffffLL / 64) return MBV_ERR_UNSUPPORTED;

@@ -224,8 +224,10 @@ class ConvGN(nn.Module):
             y = ops.conv3x3_16(x, self.conv.weight)          # 16-bit compute: K17 products instead of MIOpen
         else:
             y = self.conv(x)
+        # (K18 refuses ReLU over the sum with an added map — its backward gates on GN(x) alone: the torch path below)
         if ops.group_norm_supported(y, self.gn.num_groups) and self.gn.weight is not None and \
-                (add_upsampled is None or (y.shape[-1] % 4 == 0 and add_upsampled.dtype in ops._ACT_DTYPES)):
+                (add_upsampled is None or (not self.relu and y.shape[-1] % 4 == 0
+                                           and add_upsampled.dtype in ops._ACT_DTYPES)):
             lo = (conv_input and torch.is_autocast_enabled('cuda')
                   and torch.get_autocast_dtype('cuda') in ops._LO_DTYPES)
             return ops.group_norm(y, self.gn.weight, self.gn.bias, self.gn.num_groups, self.gn.eps, self.relu,

@@ -414,6 +414,9 @@ class _GroupNorm(torch.autograd.Function):
         if (x.dtype not in _ACT_DTYPES or out_dtype not in _ACT_DTYPES or weight.dtype != torch.float32
                 or bias.dtype != torch.float32 or not lib.mbv_groupnorm_supported(c, groups, h, w)):
             raise MaskBevHipError('group_norm: (B, C, H, W) f32 / bf16 / fp16 map with H*W % 4 == 0, f32 parameters')
+        if relu and add is not None:
+            # the backward rebuilds the gate from x and the statistics alone — it cannot gate GN(x) + add (nor its d add)
+            raise MaskBevHipError('group_norm: relu together with add_upsampled is not supported')
         x2 = x.contiguous()
         add2 = None
         if add is not None:
@@ -485,7 +488,9 @@ def group_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, groups
                relu: bool = False, add_upsampled: Optional[torch.Tensor] = None,
                out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """``relu?(GroupNorm(x) + interpolate(add_upsampled, size=x.shape[-2:], mode='bilinear', align_corners=False))`` for
-    an NCHW map in two passes over ``x`` (K18); ``out_dtype`` (default f32) is the storage type of the result."""
+    an NCHW map in two passes over ``x`` (K18); ``out_dtype`` (default f32) is the storage type of the result.  ``relu``
+    together with ``add_upsampled`` raises: the backward rebuilds the gate from GroupNorm(x) alone (no layer of the model
+    asks for the pair; ``layers.ConvGN`` takes its torch path for it)."""
     return _GroupNorm.apply(x, weight, bias, int(groups), float(eps), bool(relu), add_upsampled,
                             out_dtype or torch.float32)
 
