@@ -319,20 +319,12 @@ class WeightCopies:
 # ---------------------------------------------------------------------------------------------------------------------
 # parameter-gradient helpers: arena parameters accumulate in place (deferred grouped launches), plain ones get tensors
 # ---------------------------------------------------------------------------------------------------------------------
-def _is_arena(p) -> bool:
-    return getattr(p, '_mbv_arena', False) and p.grad is not None and p.grad.dtype == torch.float32
-
-
 def _weight_grad(p, rows, g2: torch.Tensor, x2: torch.Tensor, want: bool):
     """d(p[rows]) = g2^T x2.  Arena: accumulated into p.grad (returns None).  Otherwise a full-size gradient tensor."""
     if not want:
         return None
-    if _is_arena(p):
-        acc = p.grad if rows is None else p.grad[rows[0]:rows[1]]
-        if g2.dtype != x2.dtype:
-            x2 = x2.to(g2.dtype)
-        ops._wgrad_into(acc, g2, x2, None, persistent=True)
-        ops._fire_grad_hooks(p)
+    if ops.arena_grad(p) is not None:
+        ops.accumulate_wgrad(p, g2, x2 if g2.dtype == x2.dtype else x2.to(g2.dtype), rows)
         return None
     gw = g2.float().t().mm(x2.float())
     if rows is None:
@@ -347,10 +339,9 @@ def _partial_grad(p, rows, partial: torch.Tensor, col0: int, n: int, want: bool)
     if not want:
         return None
     nblk, ld = partial.shape
-    if _is_arena(p):
-        dst = p.grad if rows is None else p.grad[rows[0]:rows[1]]
-        if not ops._defer_colsum(partial, dst, nblk, n, ld, offset=col0):
-            ops._colsum_now(partial, dst, nblk, n, ld, offset=col0)
+    dst = ops.arena_grad(p, rows)
+    if dst is not None:
+        ops.accumulate_colsum(partial, dst, nblk, n, ld, offset=col0)
         ops._fire_grad_hooks(p)
         return None
     g = partial[:, col0:col0 + n].sum(0)

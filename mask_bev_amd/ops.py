@@ -7,7 +7,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
 
     ops_core       pointers, stream, dtype flags, the HIP-event timer, workspaces
     ops_records    fp32 mode: absmax records — pools, hints, static / weight / LayerNorm-bound registries, amax_verify
-    ops_gemm       K17 / K20 GEMMs, Linear + FFN, the deferred / grouped parameter-gradient queues
+    ops_gemm_kernels, ops_pgrad, ops_gemm   K17 / K20 GEMM launches and who takes one; in-place arena parameter gradients
+                   and their deferred / grouped queues; the autograd nodes on both: patch projection, 3 x 3 conv, Linear, FFN
     ops_encoder    K1 voxelise, K2 PillarFeatureNet, K3 scatter + LayerNorm
     ops_attention  K4 window attention, K6 decoder attention (+ shared K / V), K7 mask logits
     ops_msda       K5 / K16 multi-scale deformable attention
@@ -22,6 +23,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403
+from .ops_gemm_kernels import *    # noqa: F401,F403
+from .ops_pgrad import *           # noqa: F401,F403
 from .ops_gemm import *            # noqa: F401,F403
 from .ops_encoder import *         # noqa: F401,F403
 from .ops_attention import *       # noqa: F401,F403

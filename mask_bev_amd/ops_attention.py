@@ -67,8 +67,7 @@ class _WindowAttention(torch.autograd.Function):
         g_qkv = torch.empty_like(qkv)
         is_bf16 = _dt_flag(qkv.dtype)
         pb, pt = ctx.params
-        direct = all(getattr(p, '_mbv_arena', False) and p.grad is not None and p.grad.dtype == torch.float32
-                     and p.grad.is_contiguous() for p in (pb, pt))
+        direct = all(arena_grad(p) is not None and p.grad.is_contiguous() for p in (pb, pt))
         if direct:          # the kernel's atomics add straight into the arena gradients: no fill, no add_ afterwards
             g_table, g_bias = pt.grad, pb.grad
         else:               # the two small f32 gradients share one allocation: the library clears them with one fill
@@ -96,8 +95,7 @@ class _WindowAttention(torch.autograd.Function):
                                          _ptr(g_bias), 1 if ctx.full_bias_grad else 0, 1 if direct else 0, _stream())
             check(rc, 'mbv_window_attn_bwd')
         if direct:
-            _fire_grad_hooks(pb)
-            _fire_grad_hooks(pt)
+            _fire_grad_hooks(pb, pt)
             return g_qkv, None, None, None, None, None, None
         return g_qkv, g_bias.to(bias_dtype), g_table.to(table_dtype), None, None, None, None
 
@@ -271,17 +269,13 @@ class _SharedKVProject(torch.autograd.Function):
         # gradient rows (strided column blocks of dk_cat / dv_cat; the 16-bit products and the column sums join the
         # grouped launches at the end of the pass) — per level that was 2 fills, 2 GEMMs + 2 part sums, 2 column sums
         # and a multi-tensor add: 9 launches of 5-20 us.
-        def _arena(p):
-            return getattr(p, '_mbv_arena', False) and p.grad is not None and p.grad.dtype == torch.float32
-        if all(_arena(ctx.params[i]) and ctx.needs_input_grad[3 + i] for i in range(2 * n)):
+        if all(arena_grad(ctx.params[i]) is not None and ctx.needs_input_grad[3 + i] for i in range(2 * n)):
             for j in range(n):
                 w, b_ = ctx.params[2 * j], ctx.params[2 * j + 1]
                 for g2, x2, r0 in ((dk2, key2, e), (dv2, val2, 2 * e)):
-                    _wgrad_into(w.grad[r0:r0 + e], g2[:, j * e:(j + 1) * e], x2, None, persistent=True)
-                    if not _defer_colsum(g2, b_.grad[r0:r0 + e], t, e, n * e, offset=j * e):
-                        _colsum_now(g2, b_.grad[r0:r0 + e], t, e, n * e, offset=j * e)
-                _fire_grad_hooks(w)
-                _fire_grad_hooks(b_)
+                    _wgrad_into(arena_grad(w, (r0, r0 + e)), g2[:, j * e:(j + 1) * e], x2, None, persistent=True)
+                    accumulate_colsum(g2, arena_grad(b_, (r0, r0 + e)), t, e, n * e, offset=j * e)
+                _fire_grad_hooks(w, b_)
             return tuple(grads)
         # ... otherwise: one f32-accumulating GEMM and one column-sum pass per operand ...
         gw = torch.zeros((2, n * e, e), dtype=torch.float32, device=dk.device)
@@ -298,7 +292,7 @@ class _SharedKVProject(torch.autograd.Function):
             for p, g, slot in ((w, gw, 3 + 2 * j), (b_, gb, 4 + 2 * j)):
                 if not ctx.needs_input_grad[slot]:
                     continue
-                if getattr(p, '_mbv_arena', False) and p.grad is not None and p.grad.dtype == torch.float32:
+                if arena_grad(p) is not None:
                     dst += [p.grad[e:2 * e], p.grad[2 * e:3 * e]]
                     src += [g[0][rows], g[1][rows]]
                 else:
@@ -308,9 +302,7 @@ class _SharedKVProject(torch.autograd.Function):
                     grads[slot] = full
         if dst:
             torch._foreach_add_(dst, src)
-            for j in range(n):
-                _fire_grad_hooks(ctx.params[2 * j])
-                _fire_grad_hooks(ctx.params[2 * j + 1])
+            _fire_grad_hooks(*ctx.params[:2 * n])
         return tuple(grads)
 
 
@@ -344,7 +336,7 @@ class _LevelInputs(torch.autograd.Function):
         g_w = None
         if ctx.needs_input_grad[1]:
             g2 = g.reshape(-1, c)
-            if getattr(w, '_mbv_arena', False) and w.grad is not None and w.grad.dtype == torch.float32 and g2.is_cuda:
+            if arena_grad(w) is not None and g2.is_cuda:
                 colsum_accum(g2, w.grad[i], persistent=True)
                 _fire_grad_hooks(w)
             else:
@@ -372,14 +364,12 @@ class _LevelPositions(torch.autograd.Function):
         c = g.shape[-1]
         g2 = g.reshape(-1, c) if g.shape[0] == 1 else g.sum(0)
         g2 = g2.contiguous()
-        direct = (getattr(w, '_mbv_arena', False) and w.grad is not None and w.grad.dtype == torch.float32
-                  and w.grad.is_contiguous() and g2.is_cuda and g2.dtype in _ACT_DTYPES)
+        direct = arena_grad(w) is not None and w.grad.is_contiguous() and g2.is_cuda and g2.dtype in _ACT_DTYPES
         gw = None if direct else torch.zeros_like(w)
         start = 0
         for i, n in enumerate(lengths):
             if direct:
-                if not _defer_colsum(g2, w.grad[i], n, c, c, offset=start * c):
-                    _colsum_now(g2, w.grad[i], n, c, c, offset=start * c)
+                accumulate_colsum(g2, w.grad[i], n, c, c, offset=start * c)
             else:
                 gw[i] = g2[start:start + n].sum(0).to(w.dtype)
             start += n

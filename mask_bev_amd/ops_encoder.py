@@ -323,7 +323,7 @@ def _pfn_mm(x: torch.Tensor, w: torch.Tensor, weight_is_nk: bool, stream=None) -
 def _param_grad_or_defer(p: torch.Tensor, g: torch.Tensor):
     """The gradient ``g`` of parameter ``p`` for autograd — or None when ``p`` lives in the arena and the add into its
     f32 gradient was queued with the pass's grouped accumulate launch (ops.flush_deferred_grads)."""
-    if (getattr(p, '_mbv_arena', False) and p.grad is not None and p.grad.dtype == torch.float32 and p.grad.is_contiguous()
+    if (arena_grad(p) is not None and p.grad.is_contiguous()
             and g.is_cuda and g.numel() == p.grad.numel() and g.numel() < (1 << 31)):
         gf = g.float().contiguous()
         if _defer_colsum(gf.view(1, -1), p.grad.view(-1), 1, gf.numel(), gf.numel()):
@@ -408,8 +408,7 @@ class _ScatterLayerNorm(torch.autograd.Function):
         dev = feats.device
         g_feats = torch.empty_like(feats)
         wp, bp = ctx.params
-        direct = all(getattr(t, '_mbv_arena', False) and t.grad is not None and t.grad.dtype == torch.float32
-                     and t.grad.is_contiguous() for t in (wp, bp))
+        direct = all(arena_grad(t) is not None and t.grad.is_contiguous() for t in (wp, bp))
         if direct:          # the two 134 MB affine gradients accumulate straight into the arena (no temporaries)
             g_w, g_b = wp.grad, bp.grad
         else:
@@ -428,8 +427,7 @@ class _ScatterLayerNorm(torch.autograd.Function):
                 fused['weight_decay'], fused['step'], fused['decoupled'], _ptr(ws), ws.numel(), _stream(),
                 *TIMER.events('k_ln_bwd_dense')[2:])
             check(rc, 'mbv_scatter_layernorm_bwd_adamw')
-            _fire_grad_hooks(wp)
-            _fire_grad_hooks(bp)
+            _fire_grad_hooks(wp, bp)
             return (g_feats,) + (None,) * 11
         rc = lib.mbv_scatter_layernorm_bwd(_ptr(grad_out), ctx.patch, _dt_flag(ctx.patch_dtype) if ctx.patch else 0,
                                            _ptr(feats), _ptr(pillar_batch_start),
@@ -439,8 +437,7 @@ class _ScatterLayerNorm(torch.autograd.Function):
                                            ws.numel(), _stream(), *TIMER.events('k_ln_bwd_dense')[2:])
         check(rc, 'mbv_scatter_layernorm_bwd')
         if direct:
-            _fire_grad_hooks(wp)
-            _fire_grad_hooks(bp)
+            _fire_grad_hooks(wp, bp)
             return (g_feats,) + (None,) * 11
         return (g_feats, g_w, g_b) + (None,) * 9
 

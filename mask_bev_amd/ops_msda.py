@@ -330,8 +330,7 @@ class _MSDAQuerySide(torch.autograd.Function):
         # column-sum launch (one entry per block, row stride `width`): no zero fill, no column-sum launch of its own, no
         # accumulate launch — 25 us per layer
         bias_tmp = None
-        arena_bias = [bool(ctx.needs_input_grad[4 + 2 * j] and getattr(bia, '_mbv_arena', False) and bia.grad is not None
-                           and bia.grad.dtype == torch.float32 and bia.grad.is_contiguous())
+        arena_bias = [bool(ctx.needs_input_grad[4 + 2 * j] and arena_grad(bia) is not None and bia.grad.is_contiguous())
                       for j, bia in enumerate((bv, bo, ba))]
         deferred = [False, False, False]
         for j, (c0, c1) in enumerate(((0, e), (e, e + lo), (e + lo, width))):
@@ -344,9 +343,8 @@ class _MSDAQuerySide(torch.autograd.Function):
         for j, ((c0, c1, inp), w, bia) in enumerate(zip(cols, (wv, wo, wa), (bv, bo, ba))):
             gj = g[:, c0:c1]                                              # column block: a GEMM operand with lda = width
             if ctx.needs_input_grad[3 + 2 * j]:
-                if getattr(w, '_mbv_arena', False) and w.grad is not None and w.grad.dtype == torch.float32:
-                    _wgrad_into(w.grad, gj, inp, persistent=True)
-                    _fire_grad_hooks(w)
+                if arena_grad(w) is not None:
+                    accumulate_wgrad(w, gj, inp)
                 else:
                     acc = torch.zeros(w.shape, dtype=torch.float32, device=dev)
                     _wgrad_into(acc, gj, inp)
@@ -354,7 +352,7 @@ class _MSDAQuerySide(torch.autograd.Function):
             if ctx.needs_input_grad[4 + 2 * j]:
                 if deferred[j]:
                     _fire_grad_hooks(bia)
-                elif getattr(bia, '_mbv_arena', False) and bia.grad is not None and bia.grad.dtype == torch.float32:
+                elif arena_grad(bia) is not None:
                     dst.append(bia.grad)
                     src.append(bias_tmp[c0:c1])
                 else:

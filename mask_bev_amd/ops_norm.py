@@ -106,12 +106,9 @@ class _AddLayerNorm(torch.autograd.Function):
         dx = torch.empty(s.shape, dtype=torch.float32, device=s.device)
         lo = da if da in _LO_DTYPES else (db if db in _LO_DTYPES else None)      # a and b share their 16-bit type
         dx_lo = torch.empty(s.shape, dtype=lo, device=s.device) if lo is not None else None
-        direct = (getattr(weight, '_mbv_arena', False) and getattr(bias, '_mbv_arena', False)
-                  and weight.grad is not None and bias.grad is not None
-                  and weight.grad.dtype == torch.float32 and bias.grad.dtype == torch.float32)
-        if direct:
-            dgamma, dbeta = weight.grad, bias.grad
-        else:
+        dgamma, dbeta = arena_grad(weight), arena_grad(bias)
+        direct = dgamma is not None and dbeta is not None
+        if not direct:
             dgamma = torch.empty(c, dtype=torch.float32, device=s.device)
             dbeta = torch.empty(c, dtype=torch.float32, device=s.device)
         nblk = lib.mbv_add_layernorm_bwd_blocks(rows, c)
@@ -135,13 +132,11 @@ class _AddLayerNorm(torch.autograd.Function):
         amax_hint_set(dx, rec)
         if defer:
             for j, dst in enumerate((dgamma, dbeta, None if bb is None else bb.grad)[:np_]):
-                if not _defer_colsum(ws, dst, nblk, c, np_ * c, offset=j * c):
-                    _colsum_now(ws, dst, nblk, c, np_ * c, offset=j * c)
+                accumulate_colsum(ws, dst, nblk, c, np_ * c, offset=j * c)
 
         # (the branch Linear's own backward, which runs after this one, announces its bias gradient to the hooks)
         if direct:
-            _fire_grad_hooks(weight)
-            _fire_grad_hooks(bias)
+            _fire_grad_hooks(weight, bias)
             dgamma = dbeta = None
         else:
             dgamma, dbeta = dgamma.to(weight.dtype), dbeta.to(bias.dtype)
@@ -224,8 +219,7 @@ def accumulate_bias_grad(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
 def bias_grad_deferrable(bias: Optional[torch.Tensor], channels: int) -> bool:
     """True when a Linear may leave its bias gradient to the K12 op that consumes its output as the residual branch:
     the bias lives in a parameter arena (so K12 can accumulate into its gradient) and K12 supports the width."""
-    return (bias is not None and getattr(bias, '_mbv_arena', False) and bias.grad is not None
-            and bias.grad.dtype == torch.float32 and bias.grad.is_contiguous() and bias.is_cuda
+    return (arena_grad(bias) is not None and bias.grad.is_contiguous() and bias.is_cuda
             and add_layernorm_supported(channels) and torch.is_grad_enabled())
 
 
@@ -278,8 +272,7 @@ class _PosTokens(torch.autograd.Function):
         ape = ctx.ape
         b, c, h, w = ctx.dims
         g = g.float().contiguous()
-        direct = (getattr(ape, '_mbv_arena', False) and ape.grad is not None and ape.grad.dtype == torch.float32
-                  and ape.grad.is_contiguous())
+        direct = arena_grad(ape) is not None and ape.grad.is_contiguous()
         acc = ape.grad if direct else torch.zeros((1, c, h * w), dtype=torch.float32, device=g.device)
         check(lib.mbv_transposed_batch_sum_accum(_ptr(g), b, h * w, c, _ptr(acc), _stream()),
               'mbv_transposed_batch_sum_accum')
@@ -450,12 +443,9 @@ class _GroupNorm(torch.autograd.Function):
         if gy.dtype not in _ACT_DTYPES:
             gy = gy.float()
         dx = torch.empty_like(x)
-        direct = (getattr(weight, '_mbv_arena', False) and getattr(bias, '_mbv_arena', False)
-                  and weight.grad is not None and bias.grad is not None
-                  and weight.grad.dtype == torch.float32 and bias.grad.dtype == torch.float32)
-        if direct:
-            dgamma, dbeta = weight.grad, bias.grad
-        else:
+        dgamma, dbeta = arena_grad(weight), arena_grad(bias)
+        direct = dgamma is not None and dbeta is not None
+        if not direct:
             dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
             dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
         sums = torch.empty(b * c * 2, dtype=torch.float32, device=x.device)
@@ -464,8 +454,7 @@ class _GroupNorm(torch.autograd.Function):
                                     _dt_flag(dx.dtype), _ptr(dgamma), _ptr(dbeta), 1 if direct else 0, _ptr(sums),
                                     _stream()), 'mbv_groupnorm_bwd')
         if direct:
-            _fire_grad_hooks(weight)
-            _fire_grad_hooks(bias)
+            _fire_grad_hooks(weight, bias)
             dgamma = dbeta = None
         else:
             dgamma, dbeta = dgamma.to(weight.dtype), dbeta.to(bias.dtype)
@@ -532,12 +521,9 @@ class _MergeLayerNorm(torch.autograd.Function):
         if gy.dtype not in _ACT_DTYPES:
             gy = gy.float()
         dx = torch.empty_like(x)
-        direct = (getattr(weight, '_mbv_arena', False) and getattr(bias, '_mbv_arena', False)
-                  and weight.grad is not None and bias.grad is not None
-                  and weight.grad.dtype == torch.float32 and bias.grad.dtype == torch.float32)
-        if direct:
-            dgamma, dbeta = weight.grad, bias.grad
-        else:
+        dgamma, dbeta = arena_grad(weight), arena_grad(bias)
+        direct = dgamma is not None and dbeta is not None
+        if not direct:
             dgamma = torch.empty(c4, dtype=torch.float32, device=x.device)
             dbeta = torch.empty(c4, dtype=torch.float32, device=x.device)
         nblk = lib.mbv_add_layernorm_bwd_blocks(rows, c4)
@@ -548,11 +534,9 @@ class _MergeLayerNorm(torch.autograd.Function):
                                           1 if defer else 0, _stream()), 'mbv_merge_layernorm_bwd')
         if defer:
             for j, dst in enumerate((dgamma, dbeta)):
-                if not _defer_colsum(ws, dst, nblk, c4, 2 * c4, offset=j * c4):
-                    _colsum_now(ws, dst, nblk, c4, 2 * c4, offset=j * c4)
+                accumulate_colsum(ws, dst, nblk, c4, 2 * c4, offset=j * c4)
         if direct:
-            _fire_grad_hooks(weight)
-            _fire_grad_hooks(bias)
+            _fire_grad_hooks(weight, bias)
             dgamma = dbeta = None
         else:
             dgamma, dbeta = dgamma.to(weight.dtype), dbeta.to(bias.dtype)

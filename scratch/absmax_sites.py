@@ -2,7 +2,7 @@
 import sys, os, collections, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from mask_bev_amd import ops, ops_records, ops_gemm
+from mask_bev_amd import ops, ops_records, ops_gemm_kernels, ops_pgrad, ops_gemm
 sites, byts = collections.Counter(), collections.Counter()
 orig = ops.f32_absmax
 def spy(tensors):
@@ -11,9 +11,9 @@ def spy(tensors):
     sites[key] += 1
     byts[key] += sum(t.numel() * 4 for t in tensors)
     return orig(tensors)
-# f32_absmax is resolved inside ops_records (operand_amax) and ops_gemm (the K20 wrappers): spy in both
-ops_records.f32_absmax = spy
-ops_gemm.f32_absmax = spy
+# f32_absmax is resolved inside ops_records (operand_amax), ops_gemm_kernels (the grouped K20 launch) and ops_gemm (the K20
+# autograd nodes): spy in all three
+ops_records.f32_absmax = ops_gemm_kernels.f32_absmax = ops_gemm.f32_absmax = spy
 orig_group = ops.gemm32s_tn_group
 seen = collections.Counter()
 def spy_group(items):
@@ -24,7 +24,8 @@ def spy_group(items):
                 t = it[j]
                 seen[('g' if j == 0 else 'x', tuple(t.shape), t.stride(0), t._base is not None)] += 1
     return orig_group(items)
-ops_gemm.gemm32s_tn_group = spy_group
+# called by ops_gemm (the convolution's nine taps) and ops_pgrad (the end-of-pass flush)
+ops_gemm.gemm32s_tn_group = ops_pgrad.gemm32s_tn_group = spy_group
 import bench
 sys.argv = ['bench.py', '--dtype', 'fp32', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-fp32', '--no-kernel-profile'] + (['--no-graph'] if os.environ.get('EAGER', '1') == '1' else [])
 bench.main()

@@ -408,3 +408,44 @@ def test_layernorm_affine_update_inside_k3_backward_is_bit_identical(device, dty
     assert float(arena.grad[lo:hi].abs().max()) > 0.0
     opt.step()
     opt.fuse_layernorm_affine(None)
+
+
+def test_accumulate_colsum_runs_at_once_outside_a_pass_and_at_its_end_inside_one(device):
+    """ops.accumulate_colsum on a strided column block ((5, 8) of a (5, 24) matrix of small integers, 8 elements in) into an
+    ``out`` that already holds values: outside a backward pass the sums are added at once and nothing is queued; called
+    from a node of a backward pass, ``out`` is untouched until the pass ends and then holds the same sums.  Every value is
+    an exact integer far below 2^24: the comparison is exact."""
+    from mask_bev_amd import ops
+    ops._PENDING.clear()
+    g2 = (torch.arange(5 * 24, device=device, dtype=torch.float32).view(5, 24) % 13) - 6
+    start = torch.arange(8, device=device, dtype=torch.float32) * 3 - 10
+    want = start + g2[:, 8:16].sum(0)
+    out = start.clone()
+    ops.accumulate_colsum(g2, out, 5, 8, 24, offset=8)
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    assert not ops._PENDING
+
+    out = start.clone()
+    seen = {}
+
+    class Node(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            ops.accumulate_colsum(g2, out, 5, 8, 24, offset=8)
+            torch.cuda.synchronize()
+            seen['queued'] = [len(lists.colsum) for lists in ops._PENDING.values()]
+            seen['out'] = out.clone()
+            return g
+
+    x = torch.zeros(3, device=device, requires_grad=True)
+    Node.apply(x).sum().backward()
+    torch.cuda.synchronize()
+    assert seen['queued'] == [1]
+    assert torch.equal(seen['out'], start)
+    assert torch.equal(out, want)
+    assert not ops._PENDING
