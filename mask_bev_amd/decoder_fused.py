@@ -363,16 +363,16 @@ def _sum_grads(a, b):
 class QueryPositions(torch.autograd.Function):
     """query_embed (Q, E) as used by the fused layers.  The layers' backward chains ACCUMULATE d(positions) row by row
     into ``acc`` (B*Q, E) (row-local read-modify-write, no atomics); this node, which autograd runs after all of its
-    consumers, folds the batch and hands the sum to the embedding."""
+    consumers, folds the batch and hands the sum to the embedding.  ``hp``: the pass's record (mask2former_head.HeadPass)."""
 
     @staticmethod
-    def forward(ctx, weight, acc_holder):
-        ctx.acc_holder = acc_holder
+    def forward(ctx, weight, hp):
+        ctx.hp = hp
         return weight.view_as(weight)
 
     @staticmethod
     def backward(ctx, g):
-        acc = ctx.acc_holder.pop('acc', None)
+        acc, ctx.hp.acc = ctx.hp.acc, None
         if acc is not None:
             q, e = g.shape
             g = g + acc.view(-1, q, e).sum(0)
@@ -385,10 +385,10 @@ class QueryPositions(torch.autograd.Function):
 class LayerCtx:
     """Per-call constants shared by the two Functions of a layer (plain Python object, not seen by autograd)."""
 
-    def __init__(self, batch, queries, embed, heads, ffn, eps, dt, tw: WeightCopies, dpos_holder, qpos):
+    def __init__(self, batch, queries, embed, heads, ffn, eps, dt, tw: WeightCopies, hp, qpos):
         self.b, self.q, self.e, self.h, self.f, self.eps, self.dt = batch, queries, embed, heads, ffn, eps, dt
         self.m = batch * queries
-        self.tw, self.dpos_holder, self.qpos = tw, dpos_holder, qpos
+        self.tw, self.hp, self.qpos = tw, hp, qpos
         self.wdt = torch.float32 if dt == torch.float32 else dt
 
     def w(self, p, rows=None):
@@ -400,9 +400,9 @@ class LayerCtx:
         return self.tw.get(p, rows, True)
 
     def dpos(self, like: torch.Tensor) -> torch.Tensor:
-        acc = self.dpos_holder.get('acc')
+        acc = self.hp.acc
         if acc is None:
-            acc = self.dpos_holder['acc'] = torch.zeros((self.m, self.e), dtype=torch.float32, device=like.device)
+            acc = self.hp.acc = torch.zeros((self.m, self.e), dtype=torch.float32, device=like.device)
         return acc
 
 
@@ -697,9 +697,9 @@ class _DecB(torch.autograd.Function):
                                       ctypes.c_void_p(holder.dv_cat.data_ptr() + off), ldk, bf, ops._stream()),
                   'mbv_attn_bwd_ld')
             holder.written.add(nxt.slot)
-        # the batched heads' share of d(x3), left in the layer context instead of on the autograd edge (mask2former_head.
+        # the batched heads' share of d(x3), left in the pass's record instead of on the autograd edge (mask2former_head.
         # _DeferredHeads.backward): added by the program below while it loads the gradient
-        g_heads = lc.dpos_holder.get('gq', {}).pop(ctx.head_index, None)
+        g_heads = lc.hp.gq.pop(ctx.head_index, None)
         if g_heads is not None:
             g_heads = g_heads.reshape(m, e).to(torch.float32).contiguous()
         if g_x3 is None:                  # (this layer's output fed nothing else that needed a gradient)

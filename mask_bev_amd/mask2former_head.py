@@ -250,6 +250,23 @@ class PointSource:
         return torch.rand(*shape, generator=self.gen).to(self.device)
 
 
+class HeadPass:
+    """What ONE ``Mask2FormerHead.forward`` leaves for its own loss and backward.  The head keeps one reference (``_pass``,
+    replaced by the next forward); the pass's autograd nodes (``_DeferredHeads``, ``decoder_fused.LayerCtx`` /
+    ``QueryPositions``) capture the record when they are built, so a backward never sees a later forward's state."""
+    __slots__ = ('autocast', 'lowp_heads', 'stack', 'sink', 'early', 'announced', 'acc', 'gq')
+
+    def __init__(self, autocast: Optional[torch.dtype]):
+        self.autocast = autocast        # the autocast dtype the pass ran under (None: no autocast, or not on the GPU)
+        self.lowp_heads = False         # the per-layer heads ran with 16-bit operands whatever the row count (row chain)
+        self.stack = None               # (D, B, Q, H, W) f32: the mask logits of all decoder outputs
+        self.sink = None                # ops.StackGradSink of that stack when the heads' backward is deferred
+        self.early = None               # event at the start of the pass: fork point of the loss's target preparation,
+        self.announced = None           # taken once by loss() and only for these announced target keys
+        self.acc = None                 # row-chain decoder, backward: (B*Q, E) f32 d(positions), see QueryPositions
+        self.gq = None                  # row-chain decoder: {output i: _DeferredHeads' share of its gradient, for _DecB}
+
+
 class _DeferredHeads(torch.autograd.Function):
     """The prediction heads of all D = layers + 1 decoder outputs, backward in ONE batched pass.
 
@@ -259,21 +276,22 @@ class _DeferredHeads(torch.autograd.Function):
     on B*Q = 400 rows each, ten times (two batched GEMMs against the mask features, nine accumulations of the 16 MB
     feature gradient, the three-layer MLP, the class head, the LayerNorm); here it is one cast + permute of the
     stacked logit gradient, two GEMMs with D*Q rows per sample, and one re-evaluation + backward of the small head
-    on D*B*Q rows (the re-evaluation uses the precision the per-layer forward used).  mask2former_head.py:428-472."""
+    on D*B*Q rows (the re-evaluation uses the precision the per-layer forward used).  mask2former_head.py:428-472.
+    Everything of the pass it needs — stack, sink, precision, the row chain's ``gq`` — is on the ``HeadPass`` it is handed
+    at forward time; ``head`` serves its modules only (post_norm, cls_embed, mask_embed)."""
 
     @staticmethod
-    def forward(ctx, head, cls_all, mask_feature, *query_feats):
-        ctx.head = head
+    def forward(ctx, head, hp: HeadPass, cls_all, mask_feature, *query_feats):
+        ctx.head, ctx.hp = head, hp
         ctx.nd = len(query_feats)
         ctx.save_for_backward(mask_feature, *query_feats)
         # the D mask predictions leave as the D slices of the stacked buffer the per-layer passes filled (views: the
         # loss re-assembles them without a copy, ops.stack_slices); the buffer itself is not an autograd input
-        stack = head._mask_stack
-        return (cls_all.view_as(cls_all),) + tuple(stack[i] for i in range(ctx.nd))
+        return (cls_all.view_as(cls_all),) + tuple(hp.stack[i] for i in range(ctx.nd))
 
     @staticmethod
     def backward(ctx, d_cls, *d_masks):
-        head, nd = ctx.head, ctx.nd
+        head, hp, nd = ctx.head, ctx.hp, ctx.nd
         mask_feature, *query_feats = ctx.saved_tensors
         b, q, c = query_feats[0].shape
         hh, ww = mask_feature.shape[-2:]
@@ -282,50 +300,34 @@ class _DeferredHeads(torch.autograd.Function):
         # K8's backward may have left the gradient sample-major in the operand type already (ops.StackGradSink): then what
         # arrives here are views of the sink's token; anything else means other gradients were added — ordinary path, plus
         # the sink's share
-        sink = getattr(head, '_stack_sink', None)
-        sunk = None
-        if sink is not None and sink.grad is not None:
+        sink, sunk = hp.sink, None
+        if sink.grad is not None:
             sunk, sink.grad = sink.grad, None
             if sunk.dtype != dt or tuple(sunk.shape) != (b, nd, q, hw):
                 raise ops.MaskBevHipError('deferred heads: the stacked gradient sink holds another layout')
         if sunk is not None and all(sink.is_token(g) for g in d_masks):
-            return _DeferredHeads._finish(ctx, d_cls, sunk.view(b, nd * q, hw))
-        # stacked logit gradient (D, B, Q, H, W): the slices handed back by ops.stack_slices are views of one buffer
-        g0 = d_masks[0]
-        full = None
-        if g0 is not None and all(g is not None and g.is_contiguous() and g.dtype == g0.dtype for g in d_masks):
-            step = g0.numel() * g0.element_size()
-            if all(g.data_ptr() == g0.data_ptr() + i * step for i, g in enumerate(d_masks)):
-                full = torch.as_strided(g0, (nd, b, q, hw), (b * q * hw, q * hw, hw, 1))
-        if full is None:
-            zero = None
-            parts = []
-            for g in d_masks:
-                if g is None:
-                    zero = zero if zero is not None else torch.zeros((b, q, hh, ww), dtype=torch.float32,
-                                                                     device=mask_feature.device)
-                    g = zero
-                parts.append(g.float())
-            full = torch.stack(parts, 0).view(nd, b, q, hw)
-        dl = torch.empty((b, nd, q, hw), dtype=dt, device=full.device)       # per sample: D*Q rows, one cast+permute
-        dl.copy_(full.permute(1, 0, 2, 3))
-        if sunk is not None:
-            dl += sunk
-        return _DeferredHeads._finish(ctx, d_cls, dl.view(b, nd * q, hw))
-
-    @staticmethod
-    def _finish(ctx, d_cls, dl):
-        """dl (B, D*Q, H*W): the stacked logit gradient, sample-major, in the mask features' dtype."""
-        head, nd = ctx.head, ctx.nd
-        mask_feature, *query_feats = ctx.saved_tensors
-        b, q, c = query_feats[0].shape
-        hh, ww = mask_feature.shape[-2:]
-        hw = hh * ww
-        dt = mask_feature.dtype
+            dl = sunk
+        else:
+            # stacked logit gradient (D, B, Q, H, W): the slices handed back by ops.stack_slices are views of one buffer
+            g0 = d_masks[0]
+            full = None
+            if g0 is not None and all(g is not None and g.is_contiguous() and g.dtype == g0.dtype for g in d_masks):
+                step = g0.numel() * g0.element_size()
+                if all(g.data_ptr() == g0.data_ptr() + i * step for i, g in enumerate(d_masks)):
+                    full = torch.as_strided(g0, (nd, b, q, hw), (b * q * hw, q * hw, hw, 1))
+            if full is None:
+                zero = (torch.zeros((b, q, hh, ww), dtype=torch.float32, device=mask_feature.device)
+                        if any(g is None for g in d_masks) else None)
+                full = torch.stack([(zero if g is None else g).float() for g in d_masks], 0).view(nd, b, q, hw)
+            dl = torch.empty((b, nd, q, hw), dtype=dt, device=full.device)       # per sample: D*Q rows, one cast+permute
+            dl.copy_(full.permute(1, 0, 2, 3))
+            if sunk is not None:
+                dl += sunk
+        dl = dl.view(b, nd * q, hw)       # the stacked logit gradient, sample-major, in the mask features' dtype
         # re-evaluate the small head on all D*B*Q rows with a graph, in the per-layer forward's precision
         # (the row-chain decoder evaluates its heads with 16-bit operands whatever the row count: so does this)
-        small = b * q * c <= ops._SMALL_F32_ROWS * c and not getattr(head, '_deferred_lowp_heads', False)
-        adt = head._deferred_autocast
+        small = b * q * c <= ops._SMALL_F32_ROWS * c and not hp.lowp_heads
+        adt = hp.autocast
         with torch.enable_grad(), torch.autocast('cuda', dtype=adt or torch.bfloat16,
                                                  enabled=(adt is not None) and not small, cache_enabled=False):
             q_all = torch.stack([t.detach() for t in query_feats], 0).requires_grad_()      # (D, B, Q, C)
@@ -346,15 +348,12 @@ class _DeferredHeads(torch.autograd.Function):
         torch.autograd.backward(roots, grads)                # parameter gradients accumulate where they always do
         gq = q_all.grad
         # Row-chain decoder: the gradient of decoder output i (i = 1 .. D - 2) also reaches its producer from the next layer;
-        # handed over through the layer context, the producer's backward program adds it while it loads that gradient — not
+        # handed over through the pass's record, the producer's backward program adds it while it loads that gradient — not
         # autograd with a launch per layer.  Output 0 is the query parameter, output D - 1 has no other consumer.
-        stash = getattr(head, '_gq_stash', None)
-        if stash is not None and nd > 2:
-            box = stash.setdefault('gq', {})
-            for i in range(1, nd - 1):
-                box[i] = gq[i]
-            return (None, None, d_f, gq[0]) + (None,) * (nd - 2) + (gq[nd - 1],)
-        return (None, None, d_f) + tuple(gq[i] for i in range(nd))
+        if hp.gq is not None and nd > 2:
+            hp.gq.update((i, gq[i]) for i in range(1, nd - 1))
+            return (None, None, None, d_f, gq[0]) + (None,) * (nd - 2) + (gq[nd - 1],)
+        return (None, None, None, d_f) + tuple(gq[i] for i in range(nd))
 
 
 class Mask2FormerHead(nn.Module):
@@ -416,6 +415,11 @@ class Mask2FormerHead(nn.Module):
         # set False to sample arbitrary-valued maps through the generic f32 path
         self.binary_gt_masks = True
         self.world_size_fn = None                      # set by the DDP wrapper: () -> (world, all_reduce_fn)
+        self._pass: Optional[HeadPass] = None          # the last forward's record: what loss() may take over
+        self._announced = None                         # announce_targets' keys, waiting for the next forward
+        self._dec_weights = None                       # decoder_fused.WeightCopies of the row-chain decoder (a cache)
+        # kept by loss() for the metrics path (mask_bev_amd/metrics.py), which the reference feeds by running the matcher again
+        self.last_assignment = self.last_gt_packed = None
 
     def init_weights(self):
         self.pixel_decoder.init_weights()
@@ -444,30 +448,30 @@ class Mask2FormerHead(nn.Module):
 
     def announce_targets(self, gt_labels, gt_masks) -> None:
         """The caller's promise that these device tensors — the ones it will hand to `loss()` — are complete in the
-        current stream's order NOW, before `forward()` starts.  Only then may the loss's target preparation fork from
-        the start of the head's forward (see loss()): targets that are stacked from a list inside `loss()`, moved to the
-        device after `forward()`, or produced by anything launched later would be read by the side stream before their
-        producers ran.  `MaskBevModule._step` and the HIP-graph step announce; a bare `forward()` +
+        current stream's order NOW, before `forward()` starts; that forward takes the keys into its `HeadPass`.  Only then
+        may the loss's target preparation fork from the start of the head's forward (see loss()): targets that are stacked
+        from a list inside `loss()`, moved to the device after `forward()`, or produced by anything launched later would be
+        read by the side stream before their producers ran.  `MaskBevModule._step` and the HIP-graph step announce; a bare `forward()` +
         `compute_loss()` pair does not, and then the preparation stays on the caller's stream."""
         keys = (self._target_key(gt_labels), self._target_key(gt_masks))
-        self._announced_targets = keys if None not in keys else None
+        self._announced = keys if None not in keys else None
 
     def forward(self, x: List[torch.Tensor], batch_data_samples=None):
         bs = x[0].shape[0]
+        hp = self._pass = HeadPass(torch.get_autocast_dtype('cuda')
+                                   if (torch.is_autocast_enabled('cuda') and x[0].is_cuda) else None)
         # fork point of the loss's target preparation (see loss()): everything it reads — the batch's labels and masks —
         # exists before the head starts, so it may run underneath the pixel decoder and the decoder layers
-        self._early_event = None
-        announced, self._announced_targets = getattr(self, '_announced_targets', None), None
+        announced, self._announced = self._announced, None
         if (announced is not None and x[0].is_cuda and self.training and torch.is_grad_enabled()
                 and switches.get('early_targets')):
-            self._early_event = (torch.cuda.Event(), announced)
-            self._early_event[0].record(torch.cuda.current_stream(x[0].device))
+            hp.early, hp.announced = torch.cuda.Event(), announced
+            hp.early.record(torch.cuda.current_stream(x[0].device))
         mask_features, memories = self.pixel_decoder(x)
         dec_in, dec_pos, dec_key = [], [], []
         # key = memory + pos, shared by the 3 layers of a level; under autocast one cast per level instead of one per
         # (layer, projection): the K / V GEMMs read these copies
-        adt = (torch.get_autocast_dtype('cuda') if (torch.is_autocast_enabled('cuda') and memories[0].is_cuda)
-               else memories[0].dtype)
+        adt = hp.autocast or memories[0].dtype
         for i in range(self.num_transformer_feat_level):
             m = memories[i]
             h, w = m.shape[-2:]
@@ -481,23 +485,18 @@ class Mask2FormerHead(nn.Module):
         cls_list, mask_list = [], []
         # the 10 mask predictions are written as f32 straight into one stacked buffer: the loss reads it as is
         nd = len(self.transformer_decoder.layers) + 1
-        stack = torch.empty((nd, bs, self.num_queries) + tuple(mask_features.shape[-2:]), dtype=torch.float32,
-                            device=mask_features.device) if mask_features.is_cuda else None
-        self._mask_stack = stack
-        self._stack_sink = None
-        self._gq_stash = None
+        stack = hp.stack = torch.empty((nd, bs, self.num_queries) + tuple(mask_features.shape[-2:]), dtype=torch.float32,
+                                       device=mask_features.device) if mask_features.is_cuda else None
         # training on the GPU: the heads run layer by layer WITHOUT a graph and get one batched backward (_DeferredHeads)
         deferred = (stack is not None and self.training and torch.is_grad_enabled()
                     and switches.get('deferred_heads'))
         if deferred:
             # K8's backward writes the stacked logit gradient where and how _DeferredHeads reads it (ops.StackGradSink)
-            self._stack_sink = ops.StackGradSink(nd, bs, self.num_queries, mask_features.dtype, mask_features.device)
+            hp.sink = ops.StackGradSink(nd, bs, self.num_queries, mask_features.dtype, mask_features.device)
         feats_q = [query_feat]
 
         def heads(qf, size, slot):
-            if not deferred:
-                return self._forward_head(qf, mask_features, size, slot)
-            with torch.no_grad():
+            with (torch.no_grad() if deferred else contextlib.nullcontext()):
                 return self._forward_head(qf, mask_features, size, slot)
 
         cls_pred, mask_pred, blocked = heads(query_feat, memories[0].shape[-2:], None if stack is None else stack[0])
@@ -517,9 +516,10 @@ class Mask2FormerHead(nn.Module):
                     [(layers[i].cross_attn.attn.in_proj_weight, layers[i].cross_attn.attn.in_proj_bias) for i in idx])
                 for slot, i in enumerate(idx):
                     shared[i] = (holder, token, slot)
-        if self._fused_decoder_ok(mask_features, shared, deferred):
-            return self._forward_decoder_fused(query_feat, query_embed, mask_features, memories, shared, stack, deferred,
-                                               cls_list, mask_list, blocked, feats_q)
+        if self._fused_decoder_ok(hp, mask_features, shared, deferred):
+            self._forward_decoder_fused(hp, query_feat, query_embed, mask_features, memories, shared, cls_list, mask_list,
+                                        blocked, feats_q)
+            return self._decoder_outputs(hp, deferred, cls_list, mask_list, mask_features, feats_q)
         query_branch = None
         for i, layer in enumerate(layers):
             lvl = i % nl
@@ -536,15 +536,17 @@ class Mask2FormerHead(nn.Module):
                                                  None if stack is None else stack[i + 1])
             cls_list.append(cls_pred)
             mask_list.append(mask_pred)
+        return self._decoder_outputs(hp, deferred, cls_list, mask_list, mask_features, feats_q)
+
+    def _decoder_outputs(self, hp, deferred, cls_list, mask_list, mask_features, feats_q):
+        """What either decoder loop returns: with deferred heads, through the node that owns their one batched backward."""
         if deferred:
-            self._deferred_lowp_heads = False
-            self._deferred_autocast = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else None
-            outs = _DeferredHeads.apply(self, torch.stack(cls_list, 0), mask_features, *feats_q)
+            outs = _DeferredHeads.apply(self, hp, torch.stack(cls_list, 0), mask_features, *feats_q)
             cls_list, mask_list = list(outs[0].unbind(0)), list(outs[1:])
         return cls_list, mask_list, [None for _ in cls_list]
 
     # ------------------------------------------------------------------ fused query side (K19)
-    def _fused_decoder_ok(self, mask_features, shared, deferred) -> bool:
+    def _fused_decoder_ok(self, hp, mask_features, shared, deferred) -> bool:
         """The row-chain form of the decoder layers (decoder_fused.py): GPU, shared key / value projections for every
         layer (<= 128 queries), embed / head widths the 256-column LDS slots hold, and either no autograd graph or the
         deferred (batched-backward) prediction heads — the chain's own heads carry no gradient."""
@@ -553,7 +555,7 @@ class Mask2FormerHead(nn.Module):
         layers = self.transformer_decoder.layers
         f = layers[0].ffn.layers[0][0].out_features
         oc = self.mask_embed[4].out_features
-        dt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
+        dt = hp.autocast or torch.float32
         # What a program can hold (mbv_rowchain_max_stages() = 64 stages, 256-column products): the class head is one
         # GEMM stage (<= 256 classes); the MLP is ONE stage in its fused form (16-bit weights, f % 256 == 0, at most 64
         # slices) and f / 256 chunks of 3 forward / 5 backward stages otherwise — beyond 2048 hidden units that form
@@ -568,20 +570,22 @@ class Mask2FormerHead(nn.Module):
                 and self.mask_embed[0].out_features % 32 == 0 and self.mask_embed[2].out_features % 32 == 0
                 and dt in ops._ACT_DTYPES and mask_features.dtype in ops._ACT_DTYPES)
 
-    def _forward_decoder_fused(self, query_feat, query_embed, mask_features, memories, shared, stack, deferred,
-                               cls_list, mask_list, blocked, feats_q):
+    def _forward_decoder_fused(self, hp, query_feat, query_embed, mask_features, memories, shared, cls_list, mask_list,
+                               blocked, feats_q):
         """The decoder loop of mask2former_head.py:535-560 with the query side of every layer as two row-chain launches
-        (+ the attention kernels): decoder_fused._DecA / _DecB."""
+        (+ the attention kernels): decoder_fused._DecA / _DecB.  Appends to ``cls_list`` / ``mask_list`` / ``feats_q``."""
         from . import decoder_fused as DF
         layers = self.transformer_decoder.layers
         nl = self.num_transformer_feat_level
         bs, q, e = query_feat.shape
         dev = mask_features.device
-        dt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
+        dt = hp.autocast or torch.float32
+        hp.lowp_heads = dt != torch.float32
+        stack, hp.gq = hp.stack, {}
         need_grad = torch.is_grad_enabled()
-        tw = getattr(self, '_dec_weights', None)
-        if tw is None:
-            tw = self._dec_weights = DF.WeightCopies()
+        if self._dec_weights is None:
+            self._dec_weights = DF.WeightCopies()
+        tw = self._dec_weights
         # the chains' GEMM operands (fragment-major 16-bit copies; with a graph also the transposed ones for the data
         # gradients): one grouped launch per step
         ents = [(self.cls_embed.weight, None, False)] + [(self.mask_embed[j].weight, None, False) for j in (0, 2, 4)]
@@ -601,11 +605,9 @@ class Mask2FormerHead(nn.Module):
                 if i > 0:
                     ents.append((ca.in_proj_weight, (0, e), True))
         tw.refresh(ents, dt)
-        holder = {}
-        self._gq_stash = holder if deferred else None
-        qpos = DF.QueryPositions.apply(self.query_embed.weight, holder)
+        qpos = DF.QueryPositions.apply(self.query_embed.weight, hp)
         f = layers[0].ffn.layers[0][0].out_features
-        lc = DF.LayerCtx(bs, q, e, self.num_heads, f, layers[0].norms[0].eps, dt, tw, holder, qpos)
+        lc = DF.LayerCtx(bs, q, e, self.num_heads, f, layers[0].norms[0].eps, dt, tw, hp, qpos)
         post = self.transformer_decoder.post_norm
         mlp = [(self.mask_embed[j].weight, self.mask_embed[j].bias) for j in (0, 2, 4)]
         with torch.autocast('cuda', enabled=False):
@@ -638,12 +640,6 @@ class Mask2FormerHead(nn.Module):
                 feats_q.append(x)
                 cls_list.append(cls_pred)
                 mask_list.append(mask_pred)
-        if deferred:
-            self._deferred_lowp_heads = dt != torch.float32
-            self._deferred_autocast = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else None
-            outs = _DeferredHeads.apply(self, torch.stack(cls_list, 0), mask_features, *feats_q)
-            cls_list, mask_list = list(outs[0].unbind(0)), list(outs[1:])
-        return cls_list, mask_list, [None for _ in cls_list]
 
     # ------------------------------------------------------------------ loss
     def _stream_for(self, name: str, device):
@@ -771,6 +767,25 @@ class Mask2FormerHead(nn.Module):
         terms, sums = ops.match_cost_terms(mp.reshape(d * b, nq, -1), ones_row=True)          # (DB, 3Q + 1, P), (DB, Q, 2)
         return ops.match_cost(cls, labels_gt, torch.matmul(terms, gpt), sums, self.num_points)
 
+    def _pred_rows(self, assigned, d, b, nq, m, dev):
+        """The matched rows of the (D*B*Q, H, W) logits in (d, b, q) order, without a host sync → (int32 rows, ``qsel``
+        (D, B, m): their query numbers).  ``assigned`` None: all are matched — every row in order, ``qsel`` None."""
+        if assigned is None:
+            return self._iota(d * b * nq, dev), None
+        qsel = torch.sort((~(assigned >= 0)).to(torch.uint8), dim=-1, stable=True).indices[..., :m]
+        db = self._iota(d * b, dev).long().view(d, b, 1)
+        return (db * nq + qsel).flatten().to(torch.int32), qsel
+
+    def _gt_rows(self, assigned, qsel, ng):
+        """The row of the (B*G, ny, nx) targets for each row of :meth:`_pred_rows`: b * G + the assigned column."""
+        (d, b, nq), dev = assigned.shape, assigned.device
+        if qsel is None:
+            # two launches on the int32 assignment instead of compare / clamp / cast / gather / multiply / add / cast
+            boff = self._iota(d * b * nq, dev, div=nq, mod=b, mul=ng).view(d, b, nq)
+            return (assigned.clamp(min=0) + boff).flatten()
+        bsel = self._iota(b, dev).long().view(1, b, 1)
+        return (bsel * ng + torch.gather(assigned.clamp(min=0).long(), 2, qsel)).flatten().to(torch.int32)
+
     def loss(self, all_cls_scores, all_mask_preds, gt_labels_list, gt_masks_list, img_metas=None, heights_pred=None,
              heights_gt=None) -> Dict[str, torch.Tensor]:
         """Mask2FormerHead.loss (mask2former_head.py:246-298 → _loss_by_feat_single :326-426) evaluated for all
@@ -792,23 +807,25 @@ class Mask2FormerHead(nn.Module):
         p = self.num_points
         eps = torch.finfo(torch.float32).eps
         cls = torch.stack([c.float() for c in all_cls_scores], 0)                                # (D, B, Q, K+1)
-        stacked = ops.stack_slices(getattr(self, '_mask_stack', None), list(all_mask_preds))
-        stack_is_buffer = stacked is not None
+        # the last forward's record is this loss's own only if the predictions ARE that pass's stack slices; anything else —
+        # an older pass's outputs, tensors made elsewhere — gets an ordinary stack, no gradient sink and no early fork
+        hp = self._pass
+        stacked = ops.stack_slices(hp.stack, list(all_mask_preds)) if hp is not None else None
         if stacked is None:
+            hp = None
             stacked = torch.stack([mk.float() for mk in all_mask_preds], 0)
         masks_flat = stacked.flatten(0, 2)                                                       # (D*B*Q, H, W)
         # Everything of the loss that depends on the BATCH only — the packed targets, the uniform points, the targets sampled
         # at the matcher's points, the count of real columns — is issued on a stream that forks where the head's forward began
         # (the event forward() recorded): in the captured step it is a parallel branch underneath the pixel decoder and the
         # decoder layers instead of ≈ 0.25 ms in front of the matcher.
-        early = getattr(self, '_early_event', None)
-        self._early_event = None
-        if early is not None:
-            # the fork is only taken for the very tensors announced before forward() (announce_targets): anything else —
-            # list targets stacked above, tensors that reached the device after the head started — is ordered by the
+        early = None
+        if hp is not None and hp.early is not None:
+            # the fork is only taken once, and for the very tensors announced before forward() (announce_targets): anything
+            # else — list targets stacked above, tensors that reached the device after the head started — is ordered by the
             # caller's stream, so its preparation stays there
-            early, announced = early
-            if announced != (self._target_key(labels_gt), self._target_key(packed_gt if packed_gt is not None else masks_gt)):
+            early, hp.early = hp.early, None
+            if hp.announced != (self._target_key(labels_gt), self._target_key(packed_gt if packed_gt is not None else masks_gt)):
                 early = None
         prep = self._stream_for('prep', dev) if (early is not None and cls.is_cuda) else None
         main = torch.cuda.current_stream() if cls.is_cuda else None
@@ -846,19 +863,8 @@ class Mask2FormerHead(nn.Module):
         else:
             cost = self._match_cost(cls, masks_flat.detach(), labels_gt, gp_match, match_c)
             assigned = ops.hungarian(cost, real_cols=real_k).view(d, b, nq)                       # (D, B, Q) i32
-            matched = assigned >= 0
-            safe = assigned.clamp(min=0).long()
-
-        # matched (decoder output, image, query) rows in (d, b, q) order, without a host sync
-        if m == nq:
-            qsel = self._iota(nq, dev).long().view(1, 1, nq).expand(d, b, nq)
-        else:
-            qsel = torch.sort((~matched).to(torch.uint8), dim=-1, stable=True).indices[..., :m]
-        if m == nq:
-            pred_index = self._iota(d * b * nq, dev)                                             # every row of masks_flat, in order
-        else:
-            db = self._iota(d * b, dev).long().view(d, b, 1)
-            pred_index = (db * nq + qsel).flatten().to(torch.int32)                              # rows of masks_flat
+        # (all matched: these rows do not depend on the assignment — nothing up to the join below may read `assigned`)
+        pred_index, qsel = self._pred_rows(None if m == nq else assigned, d, b, nq, m, dev)
         rows = self._iota(d * g, dev)
         with torch.no_grad():
             n_unc = int(self.importance_sample_ratio * p)
@@ -869,24 +875,15 @@ class Mask2FormerHead(nn.Module):
                                                      num_candidates=int(p * self.oversample_ratio))
             else:
                 coords = ops.sample_select_uncertain(masks_flat.detach(), pred_index, over_c, n_unc, rand_c)
-        # (the sink applies when the stack IS the heads' buffer and every map is sampled: all queries matched)
-        sink = getattr(self, '_stack_sink', None) if (stack_is_buffer and m == nq) else None
+        # (the sink applies when the stack IS the pass's buffer and every map is sampled: all queries matched)
+        sink = hp.sink if (hp is not None and m == nq) else None
         pred = ops.point_sample(masks_flat, pred_index, coords, rows, grad_sink=sink)            # (D*g, P), grads
         if overlap:                                     # join the matcher
             main.wait_stream(side)
-        # kept for the metrics path (mask_bev_amd/metrics.py), which the reference feeds by running the matcher again
         self.last_assignment = assigned.detach()
         self.last_gt_packed = gt_flat if isinstance(gt_flat, ops.PackedMasks) else None
         with torch.no_grad():
-            if m == nq:
-                # every query is matched and `qsel` is the identity: the ground-truth row of (d, b, q) is b * G + assigned —
-                # two launches on the int32 assignment instead of compare / clamp / cast / gather / multiply / add / cast
-                boff = self._iota(d * b * nq, dev, div=nq, mod=b, mul=ng).view(d, b, nq)
-                gt_index = (assigned.clamp(min=0) + boff).flatten()
-            else:
-                bsel = self._iota(b, dev).long().view(1, b, 1)
-                gt_index = (bsel * ng + torch.gather(safe, 2, qsel)).flatten().to(torch.int32)   # rows of gt_flat
-            tgt = self._sample_gt(gt_flat, gt_index, coords, rows)                               # (D*g, P)
+            tgt = self._sample_gt(gt_flat, self._gt_rows(assigned, qsel, ng), coords, rows)      # (D*g, P)
 
         # classification loss (class-weighted CE, avg_factor = sum of the class weights of the targets)
         class_weight = self._const(dev, self.class_weight)

@@ -401,7 +401,7 @@ def update_metrics(head, layer_index: int, pred_cls, pred_masks, labels_gt: torc
     """``MaskBevPanopticHead.update_mAP_metrics`` for the classification and mIoU metrics, batched over the images and
     reusing the assignment of the loss that was just evaluated on the same predictions (``head`` is the
     ``Mask2FormerHead``; call after ``compute_loss``).  ``pred_cls`` / ``pred_masks``: the per-layer output lists."""
-    if getattr(head, 'last_assignment', None) is None:
+    if head.last_assignment is None:
         raise MaskBevHipError('update_metrics: evaluate the loss first (it provides the assignment)')
     assigned = head.last_assignment[layer_index]                                 # (B, Q)
     cls = pred_cls[layer_index]
@@ -421,7 +421,7 @@ def update_metrics(head, layer_index: int, pred_cls, pred_masks, labels_gt: torc
         if isinstance(map_metric, DeviceMaskMeanAveragePrecision):
             if map_metric.num_labels is None:
                 map_metric.num_labels = int(cls.shape[-1])
-            gt = head.last_gt_packed if getattr(head, 'last_gt_packed', None) is not None else masks_gt
+            gt = head.last_gt_packed if head.last_gt_packed is not None else masks_gt
         elif isinstance(masks_gt, ops.PackedMasks):
             raise MaskBevHipError('the mask-mAP metric needs the dense (B, G, ny, nx) ground-truth masks')
         else:

@@ -22,7 +22,8 @@ class StackGradSink:
     prediction heads (mask2former_head._DeferredHeads), wants it sample-major in the GEMM operand type: a 262 MB permute +
     cast pass.  With a sink armed, K8's backward stores the gradient in THAT form here and hands autograd a zero-stride
     token of the required shape; the consumer checks that what reached it is the token (nothing else contributed a
-    gradient) and takes ``grad``; otherwise it finds ``grad`` unset or the token replaced and uses the ordinary tensors."""
+    gradient) and takes ``grad``; otherwise it finds ``grad`` unset or the token replaced and uses the ordinary tensors.
+    One sink per forward, on its record (mask2former_head.HeadPass): K8's node and the consumer both hold THAT pass's."""
 
     def __init__(self, outer: int, inner: int, rows: int, dtype: torch.dtype, device):
         self.dims = (int(outer), int(inner), int(rows))

@@ -382,11 +382,12 @@ def test_transpose_group():
             assert torch.equal(d, s.t())
 
 
-def _run_model(device, dtype, fused, monkeypatch, arena):
+def _tiny_model(device, dtype, arena):
+    """The tiny model with the oracle's weights (seed 7), 256 loss points drawn from seed 11, two scans and their targets
+    with every query matched (G == Q == 8) → (model, scans, batch)."""
     from mask_bev_amd.mask_bev_module import MaskBevModule
     from oracle import maskbev_oracle as O
     from tests.util_cfg import random_gt, random_scans, tiny_kwargs
-    switches.patch(monkeypatch, decoder_fused='1' if fused else '0')
     okw = tiny_kwargs()
     kw = dict(okw, compute_dtype=dtype)
     sd = O.make_state_dict(O.make_cfg(**okw), 7)
@@ -400,9 +401,15 @@ def _run_model(device, dtype, fused, monkeypatch, arena):
     head.point_seed = 11
     scans = [s.to(device) for s in random_scans(okw, [3000, 2000], seed=2)]
     labels, gt = random_gt(okw, 2, 3, seed=4)
+    return m, scans, (scans, (labels.to(device), gt.to(device)))
+
+
+def _run_model(device, dtype, fused, monkeypatch, arena):
+    switches.patch(monkeypatch, decoder_fused='1' if fused else '0')
+    m, scans, batch = _tiny_model(device, dtype, arena)
     with torch.no_grad():
         cls, masks, _ = m(scans)
-    loss = m.training_step((scans, (labels.to(device), gt.to(device))), 1)
+    loss = m.training_step(batch, 1)
     m.scale_loss(loss).backward()
     from mask_bev_amd import ops
     ops.flush_deferred_grads()
@@ -452,6 +459,74 @@ def test_no_grad_forward_between_training_forward_and_backward(device):
     torch.cuda.synchronize()
     g = m._panoptic_head._panoptic_head.transformer_decoder.layers[0].ffn.layers[1].weight.grad
     assert g is not None and torch.isfinite(g).all() and float(g.abs().max()) > 0
+
+
+def _step_grads(device, dtype, arena, interloper=None):
+    """One training step (training_step, backward, flush_deferred_grads) of a fresh :func:`_tiny_model`; ``interloper``
+    runs between training_step and backward → ({name: f32 gradient}, the names of the backward's C-ABI calls)."""
+    from mask_bev_amd import _lib, ops
+    m, scans, batch = _tiny_model(device, dtype, arena)
+    loss = m.training_step(batch, 1)
+    if interloper is not None:
+        interloper(m, scans)
+    lib, calls = _lib.load(), []
+    lib.hook = lambda name, fn, args: (calls.append(name), fn(*args))[1]
+    try:
+        m.scale_loss(loss).backward()
+        ops.flush_deferred_grads()
+    finally:
+        lib.hook = None
+    torch.cuda.synchronize()
+    return {k: p.grad.detach().float().clone() for k, p in m.named_parameters() if p.grad is not None}, calls
+
+
+def _worst_rel(got, ref):
+    """Largest difference of any parameter gradient, relative to that gradient's largest entry."""
+    assert got.keys() == ref.keys()
+    return max((float((got[k] - ref[k]).abs().max() / ref[k].abs().max().clamp(min=1e-30)), k) for k in ref)
+
+
+def _forward_no_grad(m, scans):
+    with torch.no_grad():
+        m(scans)
+
+
+def _forward_train_other_scans(m, scans):
+    from tests.util_cfg import random_scans, tiny_kwargs
+    m([s.to(scans[0].device) for s in random_scans(tiny_kwargs(), [2500, 3500], seed=5)])      # outputs discarded
+
+
+_INTERLOPERS = {'no_grad': _forward_no_grad, 'train': _forward_train_other_scans}
+_UNINTERRUPTED = {}      # (dtype, arena) -> (gradients of the uninterrupted step, bar): computed once, never changed
+
+
+@pytest.mark.parametrize('interloper', ['no_grad', 'train'])
+@pytest.mark.parametrize('dtype,arena', [('fp32', False), ('bf16', True)])
+def test_pending_backward_is_unaffected_by_a_forward_in_between(device, dtype, arena, interloper):
+    """A backward uses the state of ITS forward (mask2former_head.HeadPass), whatever ran through the head in between: a
+    forward of the same scans under no_grad, or a grad-enabled training-mode forward of other scans whose outputs are
+    dropped.  fp32 without an arena takes the per-op decoder, bf16 with an arena the row chain; every query is matched
+    (G == Q == 8), so the loss arms the stacked gradient sink — asserted through the backward's C-ABI calls.
+
+    Every parameter gradient of the interleaved step against the uninterrupted step on a fresh model with the same weights,
+    relative to that gradient's largest entry.  Bar: 4 x the largest such difference between two uninterrupted steps on
+    fresh models (the run-to-run spread of the step itself; factor 4 as in the float64 path tests), at least 1e-6 (a
+    deterministic path gives zero).  Losing the sink's gradient is an error of order one.  Measured: DESIGN.md §2."""
+    key = (dtype, arena)
+    if key not in _UNINTERRUPTED:
+        ref, _ = _step_grads(device, dtype, arena)
+        again, _ = _step_grads(device, dtype, arena)
+        spread = _worst_rel(again, ref)
+        print(f'uninterrupted twice {key}: worst relative gradient difference {spread[0]:.3e} ({spread[1]})')
+        _UNINTERRUPTED[key] = (ref, max(4 * spread[0], 1e-6))
+    ref, bar = _UNINTERRUPTED[key]
+    got, calls = _step_grads(device, dtype, arena, _INTERLOPERS[interloper])
+    worst = _worst_rel(got, ref)
+    print(f'{interloper} {key}: worst relative gradient difference {worst[0]:.3e} ({worst[1]}), bar {bar:.3e}')
+    assert calls.count('mbv_point_sample_bwd_stack') >= 1          # the sink was armed: the route this test is about
+    me = [k for k in got if k.endswith('mask_embed.4.weight')]
+    assert len(me) == 1 and float(got[me[0]].abs().max()) > 0
+    assert worst[0] < bar, worst
 
 
 def test_fragment_group_more_entries_than_one_launch_takes():
