@@ -1320,6 +1320,58 @@ int mbv_fit_boxes(const uint32_t* packed, int64_t num_maps, int32_t H, int32_t W
                   int32_t* n, int64_t* moments, float* boxes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K30a — the largest 8-connected component of a bit-packed mask (csrc/mask_components.hip).
+ * K30b — the minimum-area rectangle of the set cells of a bit-packed mask (csrc/min_area_rect.hip).
+ * Together what mask_to_pred (mask_bev/evaluation/kitti_eval.py:27-45) does with cv2.findContours + cv2.minAreaRect: the
+ * tightest rectangle around the largest blob of a mask.  K30b is over ALL set cells of the map it is given; the component
+ * logic lives in K30a alone and the two compose (K30a's output is K30b's input).
+ * Not reproduced: the reference picks the contour by cv2.contourArea (the polygon area through the border pixels'
+ * centres), which cannot be restated without OpenCV (not a dependency); K30a picks by the NUMBER OF CELLS.  OpenCV's own
+ * floating-point rectangle arithmetic is not restated either: K30b's choice of the rectangle is exact integer arithmetic.
+ *
+ * Common to both:
+ * packed        (num_maps, mbv_packed_mask_words(H, W)) u32, mbv_pack_binary_masks layout: pixel y * W + x is bit p % 32 of
+ *               word p / 32, maps are not row-aligned.  Bits at and beyond H * W are garbage and never cells.
+ * rows          (num_rows) i32, any order, repeats allowed; a row outside 0 .. num_maps - 1 counts as an empty map.
+ * 1 <= H, W <= 1024, anything else is MBV_ERR_BAD_ARG, as are a null pointer or num_maps < 1 with rows to do.
+ * num_rows == 0 returns MBV_OK without a launch.  One workgroup per listed row, one launch, no host readback, no device
+ * allocation, every loop bounded by construction: capturable into a HIP graph.  Integer work only up to the box's store,
+ * so the results are deterministic.
+ *
+ * K30a.  Connectivity is 8-neighbour (as findContours traces foreground).  The kept component is the one with the most
+ * cells; among components of equal size the one that contains the lowest raster index y * W + x wins.
+ * out_packed    (num_rows, words) u32: the kept component in the same layout; bits at and beyond H * W are 0.
+ * n             (num_rows) i32: cells of the kept component (0 for an empty map, with out_packed all 0).
+ * components    (num_rows) i32: number of components of the map.
+ * workspace     mbv_largest_component_workspace_bytes(H, W, num_rows) bytes (0 for small grids: two row-aligned planes of
+ *               the cells' bounding box live in LDS when they fit 16 KiB each, in the workspace otherwise);
+ *               MBV_ERR_WORKSPACE when it is smaller.  Nothing to pre-zero.
+ *
+ * K30b.  The points are the integer cell coordinates (x, y); everything that selects the rectangle is integer arithmetic.
+ * n             (num_rows) i32: set cells.
+ * hull          (num_rows) i32: vertices of the STRICTLY convex hull (collinear points dropped): 0 for an empty map, 1 for a
+ *               single cell, 2 for collinear cells.
+ * boxes         (num_rows, 5) f32: cx, cy, dx, dy, theta in cell units; all 0 for an empty map; [x, y, 1, 1, 0] for one cell.
+ *   For each hull edge direction e = (ex, ey) the rectangle through the points with a side along e has the area
+ *   (max - min of p . e) (max - min of p x e) / |e|^2, p x e = ex py - ey px: a ratio of integers; areas are compared
+ *   exactly by cross-multiplication.  The smallest area wins.  Among edges of exactly equal area: rotate e by multiples of
+ *   90 degrees to the canonical form ex > 0, -ex < ey <= ex and take the smallest |ey| / ex (cross-multiplied), then
+ *   ey >= 0.  Edges with the same canonical direction give the same rectangle.  Collinear cells: the direction of the
+ *   segment, canonicalised.
+ *   theta = atan2(ey, ex) of the canonical direction, in (-pi/4, pi/4].  With u = p . e / |e| and v = p x e / |e|:
+ *   dx = max u - min u + |cos theta| + |sin theta|, dy the same with v (K25's unit-cell support: an axis-aligned a x b
+ *   block of cells gives exactly (a, b) and rasterize.boxes_from_cells applies unchanged); the centre is
+ *   uc = (max u + min u) / 2, vc likewise, cx = uc cos theta - vc sin theta, cy = uc sin theta + vc cos theta.
+ *   f64 arithmetic, one rounding per operation, one rounding to f32 at the store.
+ */
+int64_t mbv_largest_component_workspace_bytes(int32_t H, int32_t W, int32_t num_rows);
+int mbv_largest_component(const uint32_t* packed, int64_t num_maps, int32_t H, int32_t W, const int32_t* rows,
+                          int32_t num_rows, uint32_t* out_packed, int32_t* n, int32_t* components, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int mbv_min_area_boxes(const uint32_t* packed, int64_t num_maps, int32_t H, int32_t W, const int32_t* rows, int32_t num_rows,
+                       int32_t* n, int32_t* hull, float* boxes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K26 — rotated-box overlap over ragged frames (csrc/rotate_iou.hip).
  * Stands where rotate_iou_gpu_eval (mask_bev/evaluation/rotate_iou.py) is called per part of the validation set.
  *

@@ -196,6 +196,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_warp_instance_maps': (ctypes.c_int, [_P, _P, _I, _I, _I, _D, _D, _P, _P]),
     'mbv_rasterize_boxes': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'mbv_fit_boxes': (ctypes.c_int, [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'mbv_largest_component_workspace_bytes': (_L, [_I, _I, _I]),
+    'mbv_largest_component': (ctypes.c_int, [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P, _L, _P]),
+    'mbv_min_area_boxes': (ctypes.c_int, [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P]),
     'mbv_rotate_iou': (ctypes.c_int, [_P, _L, _P, _L, _P, _P, _P, _I, _L, _I, _P, _P]),
     'mbv_kitti_statistics_workspace_bytes': (c_size_t, [_L, _I]),
     'mbv_kitti_statistics': (ctypes.c_int, [_P, _P, _P, _P, _I, _L, _L, _L, _P, _P, _P, _D, _P, _I, _I, _P, _P, _P, _P,

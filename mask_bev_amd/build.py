@@ -35,6 +35,8 @@ FILE_FLAGS = {
     'object_augment.hip': ['-ffp-contract=off'],
     # K25's f64 projections x cos + y sin and the extents: one rounding per operation, as the numpy restatement does them
     'box_fit.hip': ['-ffp-contract=off'],
+    # K30b's f64 box of the chosen direction: one rounding per operation, as the numpy restatement does them
+    'min_area_rect.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

@@ -14,8 +14,11 @@ Departures from the reference, all deliberate:
   ``batch.kitti_labels_to_velodyne`` (yaw turns counter-clockwise), not camera-frame (x, z) boxes with a clockwise angle:
   an overlap does not depend on the frame it is computed in.
 * ``mask_to_pred`` there takes ``cv2.minAreaRect`` of the largest contour (and, thresholding a sigmoid at 127, can never
-  produce a box).  Here ALL set cells of a mask are used and the box is the moment-axis box of K25; equality with
-  ``minAreaRect`` is not pinned by any test.
+  produce a box).  By default ALL set cells of a mask are used and the box is the moment-axis box of K25.
+  ``method='min_area_rect'`` (``Predictions.boxes``, ``mask_to_pred``; the launcher's ``kitti_box_method``) follows the
+  reference's recipe on the device: the largest 8-connected component (K30a), then its minimum-area rectangle (K30b), both
+  pinned against an exact oracle.  Still not pinned: the reference selects the contour by ``cv2.contourArea`` (K30a counts
+  cells), and OpenCV's own floating-point rectangle arithmetic (K30b chooses in exact integers).
 """
 from __future__ import annotations
 
@@ -246,9 +249,10 @@ def eval_kitti(labels: Sequence[dict], predictions: Sequence[dict], device=None)
     return get_official_eval_result(labels, predictions, [0], (0, 1, 2), device=device)
 
 
-def mask_to_pred(predictions, x_range, y_range=None, voxel_size=None) -> List[dict]:
-    """The reference's name for masks → boxes: ``Predictions.kitti_predictions`` (K25)."""
-    return predictions.kitti_predictions(x_range, y_range, voxel_size)
+def mask_to_pred(predictions, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> List[dict]:
+    """The reference's name for masks → boxes: ``Predictions.kitti_predictions`` (``method='moment'``: K25;
+    ``'min_area_rect'``: K30a + K30b, the reference's own recipe)."""
+    return predictions.kitti_predictions(x_range, y_range, voxel_size, method=method)
 
 
 __all__ = ['clean_data', 'get_thresholds', 'get_mAP', 'get_mAP_v2', 'bev_box_overlap', 'eval_class', 'eval_kitti',

@@ -19,7 +19,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp;
                    K28 KITTI object augmentations: box-table membership, move, removal and pasting of points
     ops_eval       K25 oriented box of a packed mask, K26 rotated-box overlap over ragged frames, K27 KITTI tp / fp / fn,
-                   K29 pairwise overlap of packed masks + COCO per-image matching (mask mAP)
+                   K29 pairwise overlap of packed masks + COCO per-image matching (mask mAP),
+                   K30 largest 8-connected component + minimum-area rectangle of a packed mask
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403

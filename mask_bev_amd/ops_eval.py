@@ -1,7 +1,8 @@
 """K25 — oriented box of a bit-packed mask (csrc/box_fit.hip); K26 — rotated-box overlap over ragged frames
 (csrc/rotate_iou.hip); K27 — KITTI tp / fp / fn of all frames and score thresholds (csrc/kitti_stats.hip).  The three
-kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``.  K29 — pairwise overlap of bit-packed masks and
-the COCO per-image matching on its integer tables (csrc/mask_map.hip), behind ``metrics.DeviceMaskMeanAveragePrecision``.
+kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``.  K30a — largest 8-connected component of a packed
+mask (csrc/mask_components.hip) and K30b — minimum-area rectangle of a packed mask (csrc/min_area_rect.hip), behind
+``Predictions.boxes(method='min_area_rect')``.  K29 — pairwise overlap of bit-packed masks and the COCO per-image matching on its integer tables (csrc/mask_map.hip), behind ``metrics.DeviceMaskMeanAveragePrecision``.
 The definitions are in include/maskbev_hip.h."""
 from __future__ import annotations
 
@@ -44,6 +45,60 @@ def fit_boxes(masks: PackedMasks, rows: torch.Tensor) -> Tuple[torch.Tensor, tor
         check(lib.mbv_fit_boxes(_ptr(words), words.shape[0], h, w, _ptr(rows), r, _ptr(n), _ptr(moments), _ptr(boxes),
                                 _stream()), 'mbv_fit_boxes')
     return n, moments, boxes
+
+
+def _packed_and_rows(masks: PackedMasks, rows: torch.Tensor, what: str):
+    """The argument checks K30a and K30b share: (lib, contiguous words, int32 rows, h, w)."""
+    words = masks.words
+    _need_gpu(words, rows)
+    lib = _lib.load()
+    h, w = int(masks.h), int(masks.w)
+    if not (1 <= h <= 1024 and 1 <= w <= 1024):
+        raise MaskBevHipError(f'{what}: grid {h}x{w} outside 1 <= H, W <= 1024')
+    if words.dim() != 2 or words.dtype != torch.int32 or words.shape[1] != lib.mbv_packed_mask_words(h, w):
+        raise MaskBevHipError(f'{what}: words must be (R, {lib.mbv_packed_mask_words(h, w)}) int32 for a {h}x{w} grid')
+    if rows.dim() != 1 or rows.dtype not in (torch.int32, torch.int64) or rows.device != words.device:
+        raise MaskBevHipError(f'{what}: rows must be a 1-d int32 / int64 tensor on the masks\' device')
+    if rows.numel() > 0 and words.shape[0] == 0:
+        raise MaskBevHipError(f'{what}: rows to do but no map')
+    return lib, words.contiguous(), rows.to(torch.int32).contiguous(), h, w
+
+
+@torch.no_grad()
+def largest_component(masks: PackedMasks, rows: torch.Tensor) -> Tuple[PackedMasks, torch.Tensor, torch.Tensor]:
+    """masks: the R maps at (H, W) of a :class:`PackedMasks`, H, W <= 1024; rows (r) integer device tensor (any order, repeats;
+    a row outside the table counts as an empty map) → ``(kept, n (r) int32, components (r) int32)``: ``kept`` the
+    :class:`PackedMasks` of the r listed maps reduced to their largest 8-connected component (K30a: most cells, ties to the
+    component holding the lowest raster index), ``n`` its cells, ``components`` how many the map had.  No host
+    synchronisation."""
+    lib, words, rows, h, w = _packed_and_rows(masks, rows, 'largest_component')
+    r, dev = rows.numel(), words.device
+    out = torch.empty((r, words.shape[1]), dtype=torch.int32, device=dev)
+    n = torch.empty((r,), dtype=torch.int32, device=dev)
+    components = torch.empty((r,), dtype=torch.int32, device=dev)
+    if r > 0:
+        ws = _workspace(lib.mbv_largest_component_workspace_bytes(h, w, r), dev)
+        check(lib.mbv_largest_component(_ptr(words), words.shape[0], h, w, _ptr(rows), r, _ptr(out), _ptr(n),
+                                        _ptr(components), _ptr(ws), ws.numel(), _stream()), 'mbv_largest_component')
+    return PackedMasks(out, h, w), n, components
+
+
+@torch.no_grad()
+def min_area_boxes(masks: PackedMasks, rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """masks, rows as :func:`largest_component` → ``(n (r) int32, hull (r) int32, boxes (r, 5) f32 = cx cy dx dy theta)`` in
+    cell units: the minimum-area rectangle of ALL set cells of each listed map (K30b), chosen in exact integer arithmetic
+    among the directions of the strictly convex hull's edges; ``hull`` is the hull's vertex count; theta in (-pi/4, pi/4];
+    the extents carry K25's unit-cell support, so ``rasterize.boxes_from_cells`` applies.  A row with ``n == 0`` gets a box
+    of zeros.  No host synchronisation."""
+    lib, words, rows, h, w = _packed_and_rows(masks, rows, 'min_area_boxes')
+    r, dev = rows.numel(), words.device
+    n = torch.empty((r,), dtype=torch.int32, device=dev)
+    hull = torch.empty((r,), dtype=torch.int32, device=dev)
+    boxes = torch.empty((r, 5), dtype=torch.float32, device=dev)
+    if r > 0:
+        check(lib.mbv_min_area_boxes(_ptr(words), words.shape[0], h, w, _ptr(rows), r, _ptr(n), _ptr(hull), _ptr(boxes),
+                                     _stream()), 'mbv_min_area_boxes')
+    return n, hull, boxes
 
 
 def _host_offsets(offsets: Offsets, total: int, what: str) -> np.ndarray:
@@ -227,4 +282,4 @@ def coco_match(inter: torch.Tensor, pred_area: torch.Tensor, gt_area: torch.Tens
     return rank, matched, ignored, npig
 
 
-__all__ = ['fit_boxes', 'rotate_iou', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match']
+__all__ = ['fit_boxes', 'largest_component', 'min_area_boxes', 'rotate_iou', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match']

@@ -20,6 +20,9 @@ from . import ops
 from ._lib import MaskBevHipError
 
 
+BOX_METHODS = ('moment', 'min_area_rect')     # Predictions.boxes: K25 | K30a + K30b
+
+
 def unpack_bits(words: torch.Tensor, h: int, w: int) -> torch.Tensor:
     """Bit-packed maps (N, words) int32 in the mbv_pack_binary_masks layout (pixel y*w + x at bit (y*w + x) % 32 of word
     (y*w + x) // 32) → (N, h, w) bool, on the words' device."""
@@ -94,30 +97,39 @@ class Predictions:
             raise ValueError(f'boxes: the ranges make a {ny}x{nx} (ny, nx) grid, the masks are {h}x{w}')
         return x_range, y_range, nx, ny
 
-    def boxes(self, x_range, y_range=None, voxel_size=None) -> dict:
-        """Oriented BEV boxes of the kept queries (K25, ``ops.fit_boxes``: the moment-axis box of all set cells of a mask),
-        in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a rasteriser (``KittiRasterizer``) in place of
-        ``x_range``.  A kept query whose mask is empty yields no box.  Returns, for the R remaining rows in (scan, query)
-        order, ``boxes`` (R, 5) f32 [x, y, l, w, yaw] (velodyne frame, the yaw of ``rasterize.box_vertices``, l >= w),
-        ``scores`` (R) f32, ``scan`` (R) and ``query`` (R) int64, ``cells`` (R) int32 — tensors where the predictions live.
-        Synchronises with the device (twice: the kept rows, then the non-empty ones)."""
+    def boxes(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> dict:
+        """Oriented BEV boxes of the kept queries, in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a
+        rasteriser (``KittiRasterizer``) in place of ``x_range``.  ``method='moment'``: K25, ``ops.fit_boxes``, the
+        moment-axis box of all set cells of a mask.  ``method='min_area_rect'``: K30a then K30b, ``ops.largest_component`` and
+        ``ops.min_area_boxes``, the minimum-area rectangle of the mask's largest 8-connected component (what the reference's
+        ``mask_to_pred`` asks of OpenCV; stray cells do not stretch the box).  A kept query whose mask is empty yields no box.
+        Returns, for the R remaining rows in (scan, query) order, ``boxes`` (R, 5) f32 [x, y, l, w, yaw] (velodyne frame, the
+        yaw of ``rasterize.box_vertices``, l >= w), ``scores`` (R) f32, ``scan`` (R) and ``query`` (R) int64, ``cells`` (R)
+        int32 (``min_area_rect``: the cells of the kept component) — tensors where the predictions live.
+        Synchronises with the device (twice, whatever the method: the kept rows, then the non-empty ones)."""
         from .rasterize import boxes_from_cells
+        if method not in BOX_METHODS:
+            raise ValueError(f'boxes: method must be one of {BOX_METHODS}, got {method!r}')
         if self.masks is None:
             raise MaskBevHipError('boxes: these predictions were made without masks')
         x_range, y_range, nx, ny = self._grid_ranges(x_range, y_range, voxel_size)
         q = self.labels.shape[1]
         rows = torch.nonzero(self.keep.reshape(-1)).flatten()
-        n, _, cell_boxes = ops.fit_boxes(self.masks, rows.to(self.masks.words.device))
+        if method == 'moment':
+            n, _, cell_boxes = ops.fit_boxes(self.masks, rows.to(self.masks.words.device))
+        else:
+            kept, _, _ = ops.largest_component(self.masks, rows.to(self.masks.words.device))
+            n, _, cell_boxes = ops.min_area_boxes(kept, torch.arange(rows.numel(), dtype=torch.int32, device=kept.words.device))
         full = torch.nonzero(n > 0).flatten()
         rows, n, cell_boxes = rows[full.to(rows.device)], n[full], cell_boxes[full]
         return dict(boxes=boxes_from_cells(cell_boxes, x_range, y_range, nx, ny), scores=self.scores.reshape(-1)[rows],
                     scan=torch.div(rows, q, rounding_mode='floor'), query=rows % q, cells=n)
 
-    def kitti_predictions(self, x_range, y_range=None, voxel_size=None) -> List[dict]:
+    def kitti_predictions(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> List[dict]:
         """Per scan what ``kitti_eval.eval_kitti`` takes: ``{'boxes': (k, 5) [x, y, l, w, yaw], 'score': (k), 'type': (k)
         int64}`` of the scan's kept, non-empty queries; every box has the type Car (index 0 of ``rasterize.KITTI_TYPES``).
         Arguments and synchronisation as :meth:`boxes`, plus one copy of the per-scan counts."""
-        out = self.boxes(x_range, y_range, voxel_size)
+        out = self.boxes(x_range, y_range, voxel_size, method=method)
         counts = torch.bincount(out['scan'], minlength=self.labels.shape[0]).tolist()
         boxes, scores = torch.split(out['boxes'], counts), torch.split(out['scores'], counts)
         return [dict(boxes=b, score=s, type=torch.zeros((b.shape[0],), dtype=torch.int64)) for b, s in zip(boxes, scores)]

@@ -216,11 +216,18 @@ class KittiObjectBatches:
         return self.collate(samples)
 
 
-def kitti_bev_evaluation(model, config, device, root, split='val', score_threshold=0.0):
+def kitti_bev_evaluation(model, config, device, root, split='val', score_threshold=0.0, box_method=None):
     """Car BEV AP (easy / moderate / hard at overlaps 0.7 and 0.5) of ``model`` on every frame of ``<root>/<split>.txt``:
-    ``model.predict`` per batch, an oriented box per kept mask (K25, ``Predictions.kitti_predictions``), then the KITTI protocol on
-    the device (K26, K27; ``mask_bev_amd.kitti_eval.eval_kitti``).  All labels of a frame take part, unfiltered: the protocol
-    itself decides what counts at which difficulty.  Returns the result (a string with ``.metrics``)."""
+    ``model.predict`` per batch, an oriented box per kept mask (``Predictions.kitti_predictions``), then the KITTI protocol on
+    the device (K26, K27; ``mask_bev_amd.kitti_eval.eval_kitti``).  ``box_method`` (default: the configuration's
+    ``kitti_box_method``, else ``moment``): ``moment`` — K25's moment-axis box of all set cells; ``min_area_rect`` — the
+    minimum-area rectangle of the mask's largest component (K30a + K30b), the reference's recipe.  All labels of a frame take
+    part, unfiltered: the protocol itself decides what counts at which difficulty.  Returns the result (a string with
+    ``.metrics``)."""
+    from mask_bev_amd.predict import BOX_METHODS
+    method = box_method if box_method is not None else config.get('kitti_box_method', 'moment')
+    if method not in BOX_METHODS:
+        raise ValueError(f'kitti_box_method must be one of {BOX_METHODS}, got {method!r}')
     from mask_bev_amd import batch as B
     from mask_bev_amd.kitti_eval import eval_kitti
     frames = KittiObjectBatches(dict(config, shuffle_train=False, batch_size=1), device, 0, 1, root, split)
@@ -234,7 +241,7 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
             labels.append(B.kitti_labels_to_velodyne(B.read_kitti_label(frames.dirs['label_2'] / f'{name}.txt'),
                                                      B.read_kitti_calib(frames.dirs['calib'] / f'{name}.txt')))
         pred = model.predict(scans, score_threshold)
-        predictions += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'])
+        predictions += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'], method=method)
     return eval_kitti(labels, predictions, device=device)
 
 
@@ -478,7 +485,8 @@ def main(argv=None):
                     print(format_layer_metrics(model.logged, layer), flush=True)
             if dataset_name == 'kitti' and val is not None:
                 # what the reference's mask_to_pred + eval_kitti are for: boxes from the predicted masks, KITTI BEV AP
-                print(kitti_bev_evaluation(model, config, device, args.data_root), end='', flush=True)
+                print(kitti_bev_evaluation(model, config, device, args.data_root,
+                                           box_method=config.get('kitti_box_method', 'moment')), end='', flush=True)
 
     if world > 1:
         dist.destroy_process_group()
