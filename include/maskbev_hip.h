@@ -1392,6 +1392,15 @@ int mbv_rotate_iou(const float* boxes, int64_t n_boxes, const float* qboxes, int
                    const int32_t* qbox_offsets, const int64_t* pair_offsets, int32_t frames, int64_t total_pairs,
                    int32_t criterion, float* overlaps, void* stream);
 
+/* K26b — the same for boxes with a height: (n, 7) f32 x, y, z, dx, dy, dz, angle with z the BOTTOM face (the `boxes` of
+ * batch.kitti_labels_to_velodyne, K28's membership rule); offsets, pair layout, criterion and error codes as K26.  The
+ * overlap is inter = inter_bev * max(0, min(z + dz) - max(z)), divided by  -1: vol_a + vol_b - inter;  0: vol_a;  1: vol_b;
+ * 2: 1  (vol = |dx dy dz|): the reference's d3_box_overlap_kernel with z_center = 1, moved to a z-up frame.  Exactly 0 where
+ * the BEV polygons do not meet or the z-intervals do not overlap (touching faces included). */
+int mbv_rotate_iou_3d(const float* boxes, int64_t n_boxes, const float* qboxes, int64_t n_qboxes, const int32_t* box_offsets,
+                      const int32_t* qbox_offsets, const int64_t* pair_offsets, int32_t frames, int64_t total_pairs,
+                      int32_t criterion, float* overlaps, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * K27 — KITTI statistics of all frames and score thresholds (csrc/kitti_stats.hip): the protocol's inner loop,
  * compute_statistics_jit / fused_compute_statistics of mask_bev/evaluation/kitti_eval.py:266-443 for metric == 1 (BEV).
@@ -1514,6 +1523,44 @@ int mbv_coco_match(const int32_t* inter, const int32_t* pred_area, const int32_t
                    const int32_t* pred_labels, const int32_t* gt_labels, int32_t N, int32_t Q, int32_t G, int32_t num_labels,
                    const double* iou_thrs, int32_t T, const double* area_ranges, int32_t A, int32_t max_det, int32_t* rank,
                    int64_t* matched, int64_t* ignored, int32_t* npig, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K31 — lift the predicted BEV instances to the points of the scans (csrc/point_lift.hip): per-point query labels, the
+ * points of every query and the z-extent of those points.  The reference has no counterpart: its mask_to_pred writes a
+ * height of 0.
+ *
+ * points        (total_points, point_dim) f32, point_dim 3 or 4, the scans concatenated as K1 takes them
+ * scan_offsets  (batch + 1) i32 on the device, ascending from 0 to total_points
+ * x_min .. gz, prefilter   the voxel geometry of K1 (see its entry above)
+ * instance_map  (batch, gy, gx) i32 from K21: row = y-cell, column = x-cell; -1 = none.  A value outside
+ *               [-1, num_queries) counts as -1 and is never used as an index.
+ * num_queries   <= 1024 (else MBV_ERR_UNSUPPORTED);  z_bins 1 .. 256;  0 <= q_lo <= q_hi <= 1
+ * point_query   (total_points) i32: the query that owns the point's BEV cell, or -1.  The cell is computed exactly as K1
+ *               computes it (f32 subtract, IEEE f32 divide, floorf, the rejection on all three axes, the strict pre-filter
+ *               under `prefilter`): a point K1 would drop gets -1.
+ * counts        (batch, num_queries) i32: lifted points per query
+ * z_extent      (batch, num_queries, 4) f32: z_min, z_max, z_lo, z_hi of a query's points; four zeros without a point.
+ *               With bw = (z_max - z_min) / (float)z_bins of the GEOMETRY, bin(z) = clamp((int)floorf((z - z_min) / bw), 0,
+ *               z_bins - 1), rank(q) = clamp((int64)floorf(q * (float)(n - 1)), 0, n - 1) and k(r) the first bin whose
+ *               cumulative count exceeds r:  z_lo = z_min + (float)k(rank(q_lo)) * bw,  z_hi = z_min + (float)(k(rank(q_hi))
+ *               + 1) * bw, each clamped into [z_min, z_max] of the query's own points.  f32 and integer operations only, one
+ *               rounding per operation.
+ * workspace     the byte count the _workspace_bytes entry returns (0 for sizes out of range): the encoded extremes and the
+ *               (batch, num_queries, z_bins) i32 histogram.
+ * Every element of the three outputs is written; nothing has to be pre-set.  Three launches (initialise; one thread per
+ * point, blocks of 256, grid.y = batch, per-block LDS aggregation flushed with integer atomics; finalise), integer atomics
+ * only: bit-deterministic.  No host synchronisation.
+ * batch * num_queries == 0: MBV_OK, a non-NULL point_query filled with -1.  total_points == 0: MBV_OK, non-NULL counts and
+ * z_extent filled with zeros.  MBV_ERR_BAD_ARG: a null pointer, point_dim other than 3 or 4, a grid size < 1, z_bins or the
+ * quantiles out of range;  MBV_ERR_UNSUPPORTED: num_queries > 1024, batch > 65535, total_points >= 2^31 - 1;
+ * MBV_ERR_WORKSPACE: a workspace that is too small.
+ */
+size_t mbv_lift_instances_workspace_bytes(int32_t batch, int32_t num_queries, int32_t z_bins);
+int mbv_lift_instances(const float* points, int32_t point_dim, int64_t total_points, const int32_t* scan_offsets,
+                       int32_t batch, float x_min, float y_min, float z_min, float x_max, float y_max, float z_max, float vx,
+                       float vy, float vz, int32_t gx, int32_t gy, int32_t gz, int32_t prefilter, const int32_t* instance_map,
+                       int32_t num_queries, int32_t z_bins, float q_lo, float q_hi, int32_t* point_query, int32_t* counts,
+                       float* z_extent, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

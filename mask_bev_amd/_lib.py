@@ -200,6 +200,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_largest_component': (ctypes.c_int, [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P, _L, _P]),
     'mbv_min_area_boxes': (ctypes.c_int, [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P]),
     'mbv_rotate_iou': (ctypes.c_int, [_P, _L, _P, _L, _P, _P, _P, _I, _L, _I, _P, _P]),
+    'mbv_rotate_iou_3d': (ctypes.c_int, [_P, _L, _P, _L, _P, _P, _P, _I, _L, _I, _P, _P]),
     'mbv_kitti_statistics_workspace_bytes': (c_size_t, [_L, _I]),
     'mbv_kitti_statistics': (ctypes.c_int, [_P, _P, _P, _P, _I, _L, _L, _L, _P, _P, _P, _D, _P, _I, _I, _P, _P, _P, _P,
                                             c_size_t, _P]),
@@ -209,6 +210,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_points_in_boxes': (ctypes.c_int, [_P, _I, _L, _P, _I, _P, _P]),
     'mbv_pairwise_mask_overlap': (ctypes.c_int, [_P, _P, _I, _I, _I, _L, _P, _P, _P, _P]),
     'mbv_coco_match': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'mbv_lift_instances_workspace_bytes': (c_size_t, [_I, _I, _I]),
+    'mbv_lift_instances': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _I, _I,
+                                          _F, _F, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

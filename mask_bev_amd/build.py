@@ -37,6 +37,8 @@ FILE_FLAGS = {
     'box_fit.hip': ['-ffp-contract=off'],
     # K30b's f64 box of the chosen direction: one rounding per operation, as the numpy restatement does them
     'min_area_rect.hip': ['-ffp-contract=off'],
+    # K31's cell rule is K1's `(p - min) / vs`, and its histogram edges `min + k * bw` are restated in numpy: one rounding each
+    'point_lift.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

@@ -12,6 +12,10 @@
 //
 // The polygon (at most 8 vertices) lives in two fixed arrays that are only ever indexed by unrolled loop counters; a vertex
 // is appended by a select over the slots, so nothing is addressed dynamically and the kernel needs no scratch.
+//
+// K26b — the same pairs for boxes with a height, (x, y, z, dx, dy, dz, angle) with z the bottom face: the BEV intersection of
+// the same device function times the length of the common z-interval, over the volumes (the reference's d3_box_overlap_kernel
+// with z_center = 1, in a z-up frame).  mbv_rotate_iou keeps its signature and its arithmetic.
 #include "common.hpp"
 
 namespace {
@@ -105,15 +109,12 @@ __device__ __forceinline__ float intersection_area(const float* __restrict__ a, 
   return 0.5f * fabsf(twice);
 }
 
-__global__ void __launch_bounds__(kThreads) k_rotate_iou(const float* __restrict__ boxes, const float* __restrict__ qboxes,
-                                                         const int32_t* __restrict__ box_offsets,
-                                                         const int32_t* __restrict__ qbox_offsets,
-                                                         const int64_t* __restrict__ pair_offsets, int frames,
-                                                         int64_t n_boxes, int64_t n_qboxes, int64_t total, int criterion,
-                                                         float* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (idx >= total) return;
-  // the last frame f with pair_offsets[f] <= idx (frames without pairs share their offset with the next one)
+// The pair a thread works on: frame f is the last one with pair_offsets[f] <= idx (frames without pairs share their offset
+// with the next one); false when the frame has no query box or the tables and offsets disagree (such a pair reads nothing).
+__device__ __forceinline__ bool locate_pair(int64_t idx, const int32_t* __restrict__ box_offsets,
+                                            const int32_t* __restrict__ qbox_offsets,
+                                            const int64_t* __restrict__ pair_offsets, int frames, int64_t n_boxes,
+                                            int64_t n_qboxes, int64_t& i, int64_t& j) {
   int lo = 0, hi = frames - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -122,19 +123,60 @@ __global__ void __launch_bounds__(kThreads) k_rotate_iou(const float* __restrict
   const int f = lo;
   const int64_t local = idx - pair_offsets[f];
   const int64_t k_f = (int64_t)qbox_offsets[f + 1] - qbox_offsets[f];
+  if (k_f <= 0 || local < 0) return false;
+  i = box_offsets[f] + local / k_f;
+  j = qbox_offsets[f] + local % k_f;
+  return i >= 0 && i < n_boxes && j >= 0 && j < n_qboxes;
+}
+
+__global__ void __launch_bounds__(kThreads) k_rotate_iou(const float* __restrict__ boxes, const float* __restrict__ qboxes,
+                                                         const int32_t* __restrict__ box_offsets,
+                                                         const int32_t* __restrict__ qbox_offsets,
+                                                         const int64_t* __restrict__ pair_offsets, int frames,
+                                                         int64_t n_boxes, int64_t n_qboxes, int64_t total, int criterion,
+                                                         float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= total) return;
   float r = 0.f;
-  if (k_f > 0 && local >= 0) {
-    const int64_t i = box_offsets[f] + local / k_f, j = qbox_offsets[f] + local % k_f;
-    if (i >= 0 && i < n_boxes && j >= 0 && j < n_qboxes) {             // tables and offsets that disagree read nothing
-      float a[5], b[5];
+  int64_t i, j;
+  if (locate_pair(idx, box_offsets, qbox_offsets, pair_offsets, frames, n_boxes, n_qboxes, i, j)) {
+    float a[5], b[5];
 #pragma unroll
-      for (int c = 0; c < 5; ++c) { a[c] = boxes[i * 5 + c]; b[c] = qboxes[j * 5 + c]; }
-      const float inter = intersection_area(a, b);
-      if (inter > 0.f) {
-        const float area_a = fabsf(a[2] * a[3]), area_b = fabsf(b[2] * b[3]);
-        const float den = criterion == -1 ? area_a + area_b - inter : criterion == 0 ? area_a : criterion == 1 ? area_b : 1.f;
-        r = inter / den;
-      }
+    for (int c = 0; c < 5; ++c) { a[c] = boxes[i * 5 + c]; b[c] = qboxes[j * 5 + c]; }
+    const float inter = intersection_area(a, b);
+    if (inter > 0.f) {
+      const float area_a = fabsf(a[2] * a[3]), area_b = fabsf(b[2] * b[3]);
+      const float den = criterion == -1 ? area_a + area_b - inter : criterion == 0 ? area_a : criterion == 1 ? area_b : 1.f;
+      r = inter / den;
+    }
+  }
+  out[idx] = r;
+}
+
+// K26b — the same pairs for boxes with a height: (x, y, z, dx, dy, dz, angle), z the BOTTOM face.  The overlap is K26's BEV
+// intersection times the length of the common z-interval; exactly 0 where either is empty.
+__global__ void __launch_bounds__(kThreads) k_rotate_iou_3d(const float* __restrict__ boxes, const float* __restrict__ qboxes,
+                                                            const int32_t* __restrict__ box_offsets,
+                                                            const int32_t* __restrict__ qbox_offsets,
+                                                            const int64_t* __restrict__ pair_offsets, int frames,
+                                                            int64_t n_boxes, int64_t n_qboxes, int64_t total, int criterion,
+                                                            float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= total) return;
+  float r = 0.f;
+  int64_t i, j;
+  if (locate_pair(idx, box_offsets, qbox_offsets, pair_offsets, frames, n_boxes, n_qboxes, i, j)) {
+    float p[7], q[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) { p[c] = boxes[i * 7 + c]; q[c] = qboxes[j * 7 + c]; }
+    const float a[5] = {p[0], p[1], p[3], p[4], p[6]}, b[5] = {q[0], q[1], q[3], q[4], q[6]};
+    const float inter_bev = intersection_area(a, b);
+    const float dz = fminf(p[2] + p[5], q[2] + q[5]) - fmaxf(p[2], q[2]);
+    if (inter_bev > 0.f && dz > 0.f) {
+      const float inter = inter_bev * dz;
+      const float vol_a = fabsf(p[3] * p[4] * p[5]), vol_b = fabsf(q[3] * q[4] * q[5]);
+      const float den = criterion == -1 ? vol_a + vol_b - inter : criterion == 0 ? vol_a : criterion == 1 ? vol_b : 1.f;
+      r = inter / den;
     }
   }
   out[idx] = r;
@@ -154,6 +196,22 @@ extern "C" int mbv_rotate_iou(const float* boxes, int64_t n_boxes, const float* 
   if (blocks > 0x7fffffff) return MBV_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_rotate_iou, dim3((unsigned)blocks), dim3(kThreads), 0, stream, boxes, qboxes, box_offsets, qbox_offsets,
                      pair_offsets, (int)frames, n_boxes, n_qboxes, total_pairs, (int)criterion, overlaps);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_rotate_iou_3d(const float* boxes, int64_t n_boxes, const float* qboxes, int64_t n_qboxes,
+                                 const int32_t* box_offsets, const int32_t* qbox_offsets, const int64_t* pair_offsets,
+                                 int32_t frames, int64_t total_pairs, int32_t criterion, float* overlaps, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (frames < 1 || n_boxes < 0 || n_qboxes < 0 || total_pairs < 0 || criterion < -1 || criterion > 2) return MBV_ERR_BAD_ARG;
+  if (!box_offsets || !qbox_offsets || !pair_offsets) return MBV_ERR_BAD_ARG;
+  if (total_pairs == 0) return MBV_OK;
+  if (!boxes || !qboxes || !overlaps) return MBV_ERR_BAD_ARG;
+  const int64_t blocks = (total_pairs + kThreads - 1) / kThreads;
+  if (blocks > 0x7fffffff) return MBV_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k_rotate_iou_3d, dim3((unsigned)blocks), dim3(kThreads), 0, stream, boxes, qboxes, box_offsets,
+                     qbox_offsets, pair_offsets, (int)frames, n_boxes, n_qboxes, total_pairs, (int)criterion, overlaps);
   MBV_CHECK_LAUNCH();
   return MBV_OK;
 }

@@ -1,4 +1,5 @@
-"""KITTI BEV evaluation on the device: "Car BEV AP, easy / moderate / hard" for boxes fitted to predicted instance masks.
+"""KITTI BEV and 3D evaluation on the device: "Car BEV AP, easy / moderate / hard" for boxes fitted to predicted instance
+masks and, when the predictions carry a height lifted from the points (``Predictions.boxes3d``, K31), "Car 3D AP".
 
 What the reference does in mask_bev/evaluation/kitti_eval.py (the official KITTI protocol in numba on the host) and
 mask_bev/evaluation/rotate_iou.py (a numba-CUDA rotated-box IoU, launched per part of the set), here on three kernels:
@@ -8,8 +9,14 @@ per box or per evaluation: the class / difficulty codes (``clean_data``), the 41
 and the 11-point AP (``get_mAP``).
 
 Departures from the reference, all deliberate:
-* BEV only.  The image-box and 3D lines of the result string are omitted (the model predicts neither an image box nor a
-  height), and with them DontCare regions and the orientation score (AOS), which only the image-box metric uses.
+* No image-box line (the model predicts no image box), and with it no DontCare regions and no orientation score (AOS),
+  which only the image-box metric uses.  The ``3d`` line is printed when every prediction carries ``boxes3d``: the model
+  predicts no height either, but the scan has a z for every point, and K31 lifts the z-extent of the returns inside a mask
+  (``Predictions.boxes3d``); K26b then multiplies K26's BEV intersection by the common z-interval — the reference's
+  ``d3_box_overlap`` with ``z_center = 1``, in a z-up frame — and K27 runs unchanged.  The reference's own ``mask_to_pred``
+  writes a height of 0, so its ``3d`` line is meaningless.  NOT pinned: that height is the extent of the returns — ground to
+  roof only if the ground is in range, stretched by overhanging structure unless a quantile extent is used — and no accuracy
+  number on real KITTI has been measured.
 * Boxes are (x, y, l, w, yaw) in the VELODYNE frame with the corner convention of ``rasterize.box_vertices`` and
   ``batch.kitti_labels_to_velodyne`` (yaw turns counter-clockwise), not camera-frame (x, z) boxes with a clockwise angle:
   an overlap does not depend on the frame it is computed in.
@@ -38,6 +45,9 @@ MAX_TRUNCATION = (0.15, 0.3, 0.5)
 N_SAMPLE_PTS = 41
 DIFFICULTIES = ('easy', 'moderate', 'hard')
 BEV_MIN_OVERLAPS = {0: (0.7, 0.5), 1: (0.5, 0.25), 2: (0.5, 0.25), 3: (0.7, 0.5), 4: (0.5, 0.25)}   # official, relaxed
+# the `3d` rows of the reference's get_official_eval_result (overlap_mod / overlap_easy): the same numbers as its `bev` rows
+D3_MIN_OVERLAPS = {0: (0.7, 0.5), 1: (0.5, 0.25), 2: (0.5, 0.25), 3: (0.7, 0.5), 4: (0.5, 0.25)}
+METRICS = ('bev', '3d')
 _DT_HEIGHT = 100.0                        # the reference's dummy image box [0, 0, 0, 100] of a prediction
 
 
@@ -114,6 +124,21 @@ def _gt_bev(label: dict) -> np.ndarray:
     return np.asarray(label['boxes'], dtype=np.float64).reshape(-1, 7)[:, [0, 1, 3, 4, 6]]
 
 
+def _gt_3d(label: dict) -> np.ndarray:
+    if 'boxes' not in label:
+        raise ValueError('eval_kitti: labels must be in the velodyne frame (batch.kitti_labels_to_velodyne adds `boxes`)')
+    return np.asarray(label['boxes'], dtype=np.float64).reshape(-1, 7)
+
+
+def d3_box_overlap(boxes, qboxes, criterion: int = -1, device=None) -> np.ndarray:
+    """(N, 7), (K, 7) arrays [x, y, z, dx, dy, dz, angle], z the bottom face → (N, K) float32 overlaps through K26b (one
+    frame, synchronises)."""
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    a, b = _as_device_f32(np.asarray(boxes).reshape(-1, 7), dev), _as_device_f32(np.asarray(qboxes).reshape(-1, 7), dev)
+    out, _ = ops_eval.rotate_iou_3d(a, b, criterion=criterion)
+    return out.view(a.shape[0], b.shape[0]).cpu().numpy()
+
+
 def bev_box_overlap(boxes, qboxes, criterion: int = -1, device=None) -> np.ndarray:
     """(N, 5), (K, 5) arrays [x, y, dx, dy, angle] → (N, K) float32 overlaps through K26 (one frame, synchronises)."""
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -124,8 +149,10 @@ def bev_box_overlap(boxes, qboxes, criterion: int = -1, device=None) -> np.ndarr
 
 @torch.no_grad()
 def eval_class(labels: Sequence[dict], predictions: Sequence[dict], current_classes=(0,), difficultys=(0, 1, 2),
-               min_overlaps=None, device=None) -> dict:
-    """The BEV metric (the reference's ``metric == 1``) for F frames.
+               min_overlaps=None, device=None, metric: str = 'bev') -> dict:
+    """The BEV metric (``metric='bev'``, the reference's ``metric == 1``) or the 3D metric (``metric='3d'``, its
+    ``metric == 2``: ``boxes3d`` (k, 7) [x, y, z_bottom, l, w, h, yaw] of the predictions against all seven columns of the
+    labels' ``boxes``, through K26b) for F frames.
 
     ``labels``: per frame a velodyne-frame label dictionary (``batch.kitti_labels_to_velodyne``: ``boxes`` (n, 7), ``type``,
     ``bbox``, ``occluded``, ``truncated``).  ``predictions``: per frame ``{'boxes': (k, 5) [x, y, l, w, yaw], 'score': (k),
@@ -138,13 +165,16 @@ def eval_class(labels: Sequence[dict], predictions: Sequence[dict], current_clas
     All per-pair and per-frame work runs on the device: one K26 launch, then per (class, difficulty, overlap) one K27 launch
     that collects the matched scores and one that counts tp / fp / fn at all thresholds.  Host synchronisations per call: TWO,
     whatever the number of frames — the copy of the matched scores of all combinations, and the copy of their (T, 3) sums."""
+    if metric not in METRICS:
+        raise ValueError(f'eval_class: metric must be one of {METRICS}, got {metric!r}')
     if len(labels) != len(predictions):
         raise ValueError('eval_class: one prediction entry per label frame expected')
     if len(labels) == 0:
         raise ValueError('eval_class: no frame')
     classes = [_class_index(c) for c in current_classes]
     if min_overlaps is None:
-        min_overlaps = np.array([[BEV_MIN_OVERLAPS[c][k] for c in classes] for k in range(2)], dtype=np.float64)
+        table = BEV_MIN_OVERLAPS if metric == 'bev' else D3_MIN_OVERLAPS
+        min_overlaps = np.array([[table[c][k] for c in classes] for k in range(2)], dtype=np.float64)
     min_overlaps = np.asarray(min_overlaps, dtype=np.float64).reshape(-1, len(classes))
     if device is None:
         devs = [p['boxes'].device for p in predictions if isinstance(p['boxes'], torch.Tensor) and p['boxes'].is_cuda]
@@ -152,19 +182,23 @@ def eval_class(labels: Sequence[dict], predictions: Sequence[dict], current_clas
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise MaskBevHipError(f'eval_class needs a ROCm device (no CPU fallback), got {dev}')
+    box_key, width = ('boxes', 5) if metric == 'bev' else ('boxes3d', 7)
+    if any(box_key not in p for p in predictions):
+        raise ValueError(f"eval_class: metric {metric!r} needs `{box_key}` in every prediction")
     for p in predictions:
-        for key in ('boxes', 'score'):
+        for key in (box_key, 'score'):
             if isinstance(p[key], torch.Tensor) and not p[key].is_cuda and p[key].numel() > 0:
                 raise MaskBevHipError('eval_class: prediction tensors must live on the ROCm device (or be numpy arrays)')
 
-    dt_counts = [int(p['boxes'].shape[0]) for p in predictions]
-    gt_boxes = [_gt_bev(lab) for lab in labels]
-    dt_tab = torch.cat([_as_device_f32(p['boxes'], dev).reshape(-1, 5) for p in predictions])
+    dt_counts = [int(p[box_key].shape[0]) for p in predictions]
+    gt_boxes = [_gt_bev(lab) if metric == 'bev' else _gt_3d(lab) for lab in labels]
+    dt_tab = torch.cat([_as_device_f32(p[box_key], dev).reshape(-1, width) for p in predictions])
     dt_scores = torch.cat([_as_device_f32(p['score'], dev).reshape(-1) for p in predictions])
     gt_tab = _as_device_f32(np.concatenate(gt_boxes), dev)
     dt_off = np.concatenate([[0], np.cumsum(dt_counts)])
     gt_off = np.concatenate([[0], np.cumsum([b.shape[0] for b in gt_boxes])])
-    overlaps, offs = ops_eval.rotate_iou(dt_tab, gt_tab, dt_off, gt_off, criterion=-1)      # detections first, as the protocol
+    overlap_fn = ops_eval.rotate_iou if metric == 'bev' else ops_eval.rotate_iou_3d
+    overlaps, offs = overlap_fn(dt_tab, gt_tab, dt_off, gt_off, criterion=-1)               # detections first, as the protocol
     dt_types = [np.asarray(p['type'].cpu() if isinstance(p['type'], torch.Tensor) else p['type']).reshape(-1)
                 for p in predictions]
     dt_host = [{'type': t, 'bbox': p.get('bbox')} for t, p in zip(dt_types, predictions)]
@@ -210,9 +244,11 @@ def eval_class(labels: Sequence[dict], predictions: Sequence[dict], current_clas
 
 
 class EvalResult(str):
-    """The result text of the reference's ``get_official_eval_result`` (BEV lines only); the numbers are in ``metrics``:
-    ``{'Car': {'bev_ap@0.70': {'easy': .., 'moderate': .., 'hard': ..}, 'bev_ap@0.50': {...}}}`` and in ``raw``
-    (what ``eval_class`` returned)."""
+    """The result text of the reference's ``get_official_eval_result`` (the ``bev`` lines, and the ``3d`` lines when the
+    predictions carry ``boxes3d``); the numbers are in ``metrics``:
+    ``{'Car': {'bev_ap@0.70': {'easy': .., 'moderate': .., 'hard': ..}, 'bev_ap@0.50': {...}}}`` (with ``boxes3d`` also
+    ``'3d_ap@0.70'``, ``'3d_ap@0.50'``) and in ``raw`` (what ``eval_class`` returned for the BEV metric; with ``boxes3d`` it
+    gains the entry ``'3d'``: what ``eval_class(metric='3d')`` returned)."""
     metrics: Dict[str, dict]
     raw: dict
 
@@ -220,12 +256,19 @@ class EvalResult(str):
 def get_official_eval_result(labels: Sequence[dict], predictions: Sequence[dict], current_classes=(0,),
                              difficultys=(0, 1, 2), device=None) -> EvalResult:
     """``eval_class`` formatted as the reference formats it: per class and overlap level a header line and the ``bev  AP:``
-    line with the APs of the difficulties.  The ``bbox``, ``3d`` and ``aos`` lines are omitted: nothing here predicts them."""
+    line with the APs of the difficulties; when EVERY prediction dictionary has ``boxes3d`` (``Predictions.kitti_predictions``
+    with ``scans``), a ``3d   AP:`` line follows each of them.  The ``bbox`` and ``aos`` lines are omitted: nothing here
+    predicts an image box.  The header shows the BEV overlap; the 3D table holds the same numbers."""
     if not isinstance(current_classes, (list, tuple)):
         current_classes = [current_classes]
     classes = [_class_index(c) for c in current_classes]
     raw = eval_class(labels, predictions, classes, difficultys, device=device)
     ap = get_mAP(raw['precision'])                                              # (C, D, K)
+    with_3d = len(predictions) > 0 and all('boxes3d' in p for p in predictions)
+    if with_3d:
+        raw = dict(raw)
+        raw['3d'] = eval_class(labels, predictions, classes, difficultys, device=device, metric='3d')
+        ap3d = get_mAP(raw['3d']['precision'])
     text, metrics = '', {}
     for m, cls in enumerate(classes):
         name = KITTI_TYPES[[t.lower() for t in KITTI_TYPES].index(CLASS_NAMES[cls])]
@@ -235,6 +278,10 @@ def get_official_eval_result(labels: Sequence[dict], predictions: Sequence[dict]
             text += f'{name} AP(Average Precision)@{mo:.2f}:\n'
             text += 'bev  AP:' + ', '.join(f'{v:.2f}' for v in ap[m, :, k]) + '\n'
             metrics[name][f'bev_ap@{mo:.2f}'] = {DIFFICULTIES[d]: float(ap[m, l, k]) for l, d in enumerate(difficultys)}
+            if with_3d:
+                mo3 = raw['3d']['min_overlaps'][k, m]
+                text += '3d   AP:' + ', '.join(f'{v:.2f}' for v in ap3d[m, :, k]) + '\n'
+                metrics[name][f'3d_ap@{mo3:.2f}'] = {DIFFICULTIES[d]: float(ap3d[m, l, k]) for l, d in enumerate(difficultys)}
     out = EvalResult(text)
     out.metrics, out.raw = metrics, raw
     return out
@@ -243,9 +290,9 @@ def get_official_eval_result(labels: Sequence[dict], predictions: Sequence[dict]
 def eval_kitti(labels: Sequence[dict], predictions: Sequence[dict], device=None) -> EvalResult:
     """Car BEV AP at overlaps 0.7 and 0.5, easy / moderate / hard, for F frames: ``labels`` the velodyne-frame label
     dictionaries (``batch.kitti_labels_to_velodyne(batch.read_kitti_label(..), calib)``), ``predictions`` what
-    ``Predictions.kitti_predictions`` returns per scan.  The returned string prints as the reference's block (BEV lines
-    only; the image-box and 3D lines are omitted) and carries the numbers in ``.metrics``.  Two host synchronisations per
-    call, independent of the number of frames (see ``eval_class``)."""
+    ``Predictions.kitti_predictions`` returns per scan.  The returned string prints as the reference's block (the image-box
+    lines are omitted; the ``3d   AP:`` lines appear when every prediction carries ``boxes3d``) and carries the numbers in
+    ``.metrics``.  Two host synchronisations per call and metric, independent of the number of frames (see ``eval_class``)."""
     return get_official_eval_result(labels, predictions, [0], (0, 1, 2), device=device)
 
 
@@ -255,5 +302,5 @@ def mask_to_pred(predictions, x_range, y_range=None, voxel_size=None, method: st
     return predictions.kitti_predictions(x_range, y_range, voxel_size, method=method)
 
 
-__all__ = ['clean_data', 'get_thresholds', 'get_mAP', 'get_mAP_v2', 'bev_box_overlap', 'eval_class', 'eval_kitti',
+__all__ = ['clean_data', 'get_thresholds', 'get_mAP', 'get_mAP_v2', 'bev_box_overlap', 'd3_box_overlap', 'eval_class', 'eval_kitti',
            'get_official_eval_result', 'mask_to_pred', 'EvalResult', 'CLASS_NAMES', 'N_SAMPLE_PTS']

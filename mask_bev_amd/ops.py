@@ -14,11 +14,12 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_msda       K5 / K16 multi-scale deformable attention
     ops_norm       K12 add + LayerNorm, bias + activation, K18 GroupNorm, patch merging
     ops_loss       K8 point sampling, K9 Hungarian, K10 importance sampling, K13 loss rows / costs
-    ops_instances  K21 query selection + BEV mask / instance-map extraction at inference
+    ops_instances  K21 query selection + BEV mask / instance-map extraction at inference; K31 lift of the instance map to
+                   the points (per-point labels, points and z-extent per query)
     ops_rasterize  K22 SemanticKITTI scene -> instance-id map (binning, close + open, paint)
     ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp;
                    K28 KITTI object augmentations: box-table membership, move, removal and pasting of points
-    ops_eval       K25 oriented box of a packed mask, K26 rotated-box overlap over ragged frames, K27 KITTI tp / fp / fn,
+    ops_eval       K25 oriented box of a packed mask, K26 / K26b rotated-box overlap (BEV / 3-D) over ragged frames, K27 KITTI tp / fp / fn,
                    K29 pairwise overlap of packed masks + COCO per-image matching (mask mAP),
                    K30 largest 8-connected component + minimum-area rectangle of a packed mask
 """

@@ -1,5 +1,5 @@
 """K25 — oriented box of a bit-packed mask (csrc/box_fit.hip); K26 — rotated-box overlap over ragged frames
-(csrc/rotate_iou.hip); K27 — KITTI tp / fp / fn of all frames and score thresholds (csrc/kitti_stats.hip).  The three
+(csrc/rotate_iou.hip), K26b — the same with heights (``rotate_iou_3d``); K27 — KITTI tp / fp / fn of all frames and score thresholds (csrc/kitti_stats.hip).  The three
 kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``.  K30a — largest 8-connected component of a packed
 mask (csrc/mask_components.hip) and K30b — minimum-area rectangle of a packed mask (csrc/min_area_rect.hip), behind
 ``Predictions.boxes(method='min_area_rect')``.  K29 — pairwise overlap of bit-packed masks and the COCO per-image matching on its integer tables (csrc/mask_map.hip), behind ``metrics.DeviceMaskMeanAveragePrecision``.
@@ -167,6 +167,39 @@ def rotate_iou(boxes: torch.Tensor, qboxes: torch.Tensor, box_offsets: Offsets =
 
 
 @torch.no_grad()
+def rotate_iou_3d(boxes: torch.Tensor, qboxes: torch.Tensor, box_offsets: Offsets = None, qbox_offsets: Offsets = None,
+                  criterion: int = -1, offsets: Optional[FrameOffsets] = None) -> Tuple[torch.Tensor, FrameOffsets]:
+    """:func:`rotate_iou` for boxes with a height (K26b): boxes (N, 7), qboxes (K, 7) f32 device tables
+    [x, y, z, dx, dy, dz, angle] with z the BOTTOM face (``batch.kitti_labels_to_velodyne``'s ``boxes``).  The overlap is the
+    BEV intersection times the common z-interval, by ``criterion`` over -1 the union of the volumes, 0 the first box's
+    volume, 1 the second's, 2 nothing; exactly 0 where the polygons do not meet or the z-intervals do not overlap.  Offsets,
+    output layout and synchronisation as :func:`rotate_iou`."""
+    lib = _lib.load()
+    _need_gpu(boxes, qboxes)
+    for t, what in ((boxes, 'boxes'), (qboxes, 'qboxes')):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 7:
+            raise MaskBevHipError(f'rotate_iou_3d: {what} must be (N, 7) f32 [x, y, z, dx, dy, dz, angle], got '
+                                  f'{tuple(t.shape)} {t.dtype}')
+    boxes, qboxes = boxes.contiguous(), qboxes.contiguous()
+    if boxes.device != qboxes.device:
+        raise MaskBevHipError('rotate_iou_3d: tables on different devices')
+    if criterion not in (-1, 0, 1, 2):
+        raise ValueError(f'rotate_iou_3d: criterion must be -1, 0, 1 or 2, got {criterion}')
+    n, k, dev = boxes.shape[0], qboxes.shape[0], boxes.device
+    if offsets is None:
+        offsets = FrameOffsets([0, n] if box_offsets is None else box_offsets, n,
+                               [0, k] if qbox_offsets is None else qbox_offsets, k, dev)
+    elif offsets.a[-1] != n or offsets.b[-1] != k:
+        raise ValueError('rotate_iou_3d: offsets of other tables')
+    out = torch.empty((offsets.total,), dtype=torch.float32, device=dev)
+    if offsets.total > 0:
+        check(lib.mbv_rotate_iou_3d(_ptr(boxes), n, _ptr(qboxes), k, _ptr(offsets.a_dev), _ptr(offsets.b_dev),
+                                    _ptr(offsets.pairs_dev), offsets.frames, offsets.total, int(criterion), _ptr(out),
+                                    _stream()), 'mbv_rotate_iou_3d')
+    return out, offsets
+
+
+@torch.no_grad()
 def kitti_statistics(overlaps: torch.Tensor, offsets: FrameOffsets, ignored_gt: torch.Tensor, ignored_dt: torch.Tensor,
                      dt_scores: torch.Tensor, min_overlap: float, thresholds: Optional[torch.Tensor] = None,
                      compute_fp: bool = True, collect_scores: bool = False):
@@ -282,4 +315,4 @@ def coco_match(inter: torch.Tensor, pred_area: torch.Tensor, gt_area: torch.Tens
     return rank, matched, ignored, npig
 
 
-__all__ = ['fit_boxes', 'largest_component', 'min_area_boxes', 'rotate_iou', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match']
+__all__ = ['fit_boxes', 'largest_component', 'min_area_boxes', 'rotate_iou', 'rotate_iou_3d', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match']

@@ -1,10 +1,12 @@
 """K21 — instance extraction at inference (csrc/instances.hip): query selection from the class logits and the BEV masks,
 areas, mask scores and instance map of one decoder output, straight from the (h, w) logits with no (B, Q, H, W)
-intermediate.  Class convention: index 0 = empty, > 0 = object; a pixel is set when its interpolated
+intermediate.  K31 — the lift of that instance map to the points of the scans (csrc/point_lift.hip): per-point query labels,
+points per query and their z-extent.  Class convention: index 0 = empty, > 0 = object; a pixel is set when its interpolated
 logit is > 0 (sigmoid > 0.5)."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -75,4 +77,72 @@ def extract_masks(logits: torch.Tensor, scores: torch.Tensor, keep: torch.Tensor
     return dict(masks=PackedMasks(words, H, W) if masks else None, areas=areas, mask_scores=mscores, instance_map=imap)
 
 
-__all__ = ['select_queries', 'extract_masks']
+@dataclass
+class PointInstances:
+    """K31's outputs for a batch of B scans and Q queries, on the device: ``point_query`` (total_points) int32 — per point of
+    the concatenated scans the query that owns its BEV cell, -1 for none (and for every point K1 drops); ``scan_offsets``
+    (B + 1) int32 on the device; ``counts`` (B, Q) int32 — lifted points per query; ``z_min``, ``z_max``, ``z_lo``, ``z_hi``
+    (B, Q) f32 — the extremes of a query's points and the histogram edges of the two quantiles (include/maskbev_hip.h, K31),
+    zeros for a query without a point.  ``lengths``: the scans' point counts, known on the host."""
+    point_query: torch.Tensor
+    scan_offsets: torch.Tensor
+    counts: torch.Tensor
+    z_min: torch.Tensor
+    z_max: torch.Tensor
+    z_lo: torch.Tensor
+    z_hi: torch.Tensor
+    lengths: Tuple[int, ...]
+
+    def per_scan(self) -> List[torch.Tensor]:
+        """The labels of every scan: a list of (N_i,) views of ``point_query``.  No host synchronisation."""
+        return list(torch.split(self.point_query, list(self.lengths)))
+
+
+@torch.no_grad()
+def lift_instances(scans: Sequence[torch.Tensor], instance_map: torch.Tensor, geom, num_queries: int, z_bins: int = 64,
+                   quantiles: Tuple[float, float] = (0., 1.), prefilter: bool = True) -> PointInstances:
+    """K31: ``scans`` — the list of (N_i, 3 | 4) f32 device tensors the module takes; ``instance_map`` (B, gy, gx) int32 of
+    :func:`extract_masks`; ``geom`` — the encoder's ``VoxelGeometry`` (``prefilter``: the encoder's strict range filter in
+    front of K1, on by default as there) → :class:`PointInstances`.  ``quantiles`` = (q_lo, q_hi) pick ``z_lo`` / ``z_hi``
+    among ``z_bins`` equal bins over the geometry's z range.  Device tensors only; no host synchronisation."""
+    lib = _lib.load()
+    if len(scans) == 0:
+        raise ValueError('lift_instances: empty batch')
+    _need_gpu(instance_map, *scans)
+    batch, dev = len(scans), instance_map.device
+    dim = int(scans[0].shape[1]) if scans[0].dim() == 2 else -1
+    if dim not in (3, 4) or any(p.dim() != 2 or p.shape[1] != dim or p.device != dev for p in scans):
+        raise MaskBevHipError('lift_instances: scans must be (N_i, 3) or (N_i, 4) tensors of one width on the map\'s device')
+    gx, gy, gz = (int(v) for v in geom.grid)
+    if instance_map.dtype != torch.int32 or tuple(instance_map.shape) != (batch, gy, gx):
+        raise MaskBevHipError(f'lift_instances: instance_map must be ({batch}, {gy}, {gx}) int32, got '
+                              f'{tuple(instance_map.shape)} {instance_map.dtype}')
+    q_lo, q_hi = float(quantiles[0]), float(quantiles[1])
+    if not 0 <= int(num_queries) <= 1024 or not 1 <= int(z_bins) <= 256 or not 0.0 <= q_lo <= q_hi <= 1.0:
+        raise MaskBevHipError(f'lift_instances: num_queries {num_queries} (<= 1024), z_bins {z_bins} (1 .. 256) or quantiles '
+                              f'{(q_lo, q_hi)} (0 <= q_lo <= q_hi <= 1) out of range')
+    num_queries, z_bins = int(num_queries), int(z_bins)
+    lens = [int(p.shape[0]) for p in scans]
+    n = sum(lens)
+    points = scans[0] if batch == 1 else torch.cat(list(scans), 0)
+    points = points.to(torch.float32).contiguous()
+    offs = [0]
+    for l in lens:
+        offs.append(offs[-1] + l)
+    scan_offsets = torch.tensor(offs, dtype=torch.int32).to(dev, non_blocking=True)
+    instance_map = instance_map.contiguous()
+    point_query = torch.empty((n,), dtype=torch.int32, device=dev)
+    counts = torch.empty((batch, num_queries), dtype=torch.int32, device=dev)
+    z_extent = torch.empty((batch, num_queries, 4), dtype=torch.float32, device=dev)
+    nbytes = lib.mbv_lift_instances_workspace_bytes(batch, num_queries, z_bins)
+    ws = _workspace(nbytes, dev) if nbytes > 0 else None
+    r, v = geom.pc_range, geom.voxel_size
+    check(lib.mbv_lift_instances(_ptr(points), dim, n, _ptr(scan_offsets), batch, r[0], r[1], r[2], r[3], r[4], r[5],
+                                 v[0], v[1], v[2], gx, gy, gz, 1 if prefilter else 0, _ptr(instance_map), num_queries, z_bins,
+                                 q_lo, q_hi, _ptr(point_query), _ptr(counts), _ptr(z_extent), _ptr(ws),
+                                 ws.numel() if ws is not None else 0, _stream()), 'mbv_lift_instances')
+    return PointInstances(point_query, scan_offsets, counts, z_extent[..., 0], z_extent[..., 1], z_extent[..., 2],
+                          z_extent[..., 3], tuple(lens))
+
+
+__all__ = ['select_queries', 'extract_masks', 'lift_instances', 'PointInstances']

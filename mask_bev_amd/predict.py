@@ -14,6 +14,7 @@ from __future__ import annotations
 from dataclasses import dataclass, fields
 from typing import List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -97,6 +98,17 @@ class Predictions:
             raise ValueError(f'boxes: the ranges make a {ny}x{nx} (ny, nx) grid, the masks are {h}x{w}')
         return x_range, y_range, nx, ny
 
+    def lift(self, scans, module_or_geometry, z_bins: int = 64, quantiles=(0., 1.)) -> 'ops.PointInstances':
+        """K31, ``ops.lift_instances``: the instance map lifted to the points of ``scans`` — the list of (N_i, 3 | 4) device
+        tensors these predictions were made from — with the encoder's voxel geometry (a module, or its ``VoxelGeometry``):
+        per point the query that owns its BEV cell (-1: none, and every point the voxeliser drops), and per query the points
+        and their z-extent.  No host synchronisation.  On the static outputs of a :class:`GraphedPredictStep` it must run
+        before the next replay overwrites ``instance_map``."""
+        if self.instance_map is None:
+            raise MaskBevHipError('lift: these predictions were made without an instance map')
+        return ops.lift_instances(scans, self.instance_map, voxel_geometry(module_or_geometry), self.labels.shape[1],
+                                  z_bins=z_bins, quantiles=quantiles)
+
     def boxes(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> dict:
         """Oriented BEV boxes of the kept queries, in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a
         rasteriser (``KittiRasterizer``) in place of ``x_range``.  ``method='moment'``: K25, ``ops.fit_boxes``, the
@@ -107,6 +119,11 @@ class Predictions:
         yaw of ``rasterize.box_vertices``, l >= w), ``scores`` (R) f32, ``scan`` (R) and ``query`` (R) int64, ``cells`` (R)
         int32 (``min_area_rect``: the cells of the kept component) — tensors where the predictions live.
         Synchronises with the device (twice, whatever the method: the kept rows, then the non-empty ones)."""
+        return self._boxes(x_range, y_range, voxel_size, method)[0]
+
+    def _boxes(self, x_range, y_range, voxel_size, method, also=None):
+        """:meth:`boxes`; ``also`` (B * Q) bool on the device: a second condition on the rows that remain, folded into the
+        second synchronisation.  Returns (the dictionary, the remaining rows b * Q + q)."""
         from .rasterize import boxes_from_cells
         if method not in BOX_METHODS:
             raise ValueError(f'boxes: method must be one of {BOX_METHODS}, got {method!r}')
@@ -120,19 +137,89 @@ class Predictions:
         else:
             kept, _, _ = ops.largest_component(self.masks, rows.to(self.masks.words.device))
             n, _, cell_boxes = ops.min_area_boxes(kept, torch.arange(rows.numel(), dtype=torch.int32, device=kept.words.device))
-        full = torch.nonzero(n > 0).flatten()
+        full = torch.nonzero(n > 0 if also is None else (n > 0) & also[rows].to(n.device)).flatten()
         rows, n, cell_boxes = rows[full.to(rows.device)], n[full], cell_boxes[full]
         return dict(boxes=boxes_from_cells(cell_boxes, x_range, y_range, nx, ny), scores=self.scores.reshape(-1)[rows],
-                    scan=torch.div(rows, q, rounding_mode='floor'), query=rows % q, cells=n)
+                    scan=torch.div(rows, q, rounding_mode='floor'), query=rows % q, cells=n), rows
 
-    def kitti_predictions(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> List[dict]:
+    def boxes3d(self, scans, module_or_geometry, x_range, y_range=None, voxel_size=None, method: str = 'moment',
+                extent='minmax', min_points: int = 1) -> dict:
+        """:meth:`boxes` with a height from the points (K31, :meth:`lift` of ``scans`` with the encoder's geometry): what
+        :meth:`boxes` returns plus ``boxes3d`` (R, 7) f32 [x, y, z_bottom, l, w, h, yaw] — the columns of
+        ``batch.kitti_labels_to_velodyne``'s ``boxes`` — and ``points`` (R) int32, the lifted points of the row's query.
+        ``extent='minmax'``: z_bottom and h from the lowest and the highest point whose BEV cell the query owns;
+        ``extent=(q_lo, q_hi)``: from the edges of the bins, among 64 over the geometry's z range, that hold the points
+        of those two quantiles (an outlier above a car no longer stretches it).  Rows with fewer than ``min_points`` (>= 1)
+        lifted points are dropped: a mask with no return has no height.  The height is the z-extent of the returns inside the
+        mask — ground to roof only if the ground is in range.  No synchronisation beyond the two of :meth:`boxes`."""
+        if int(min_points) < 1:
+            raise ValueError('boxes3d: min_points must be at least 1 (a mask with no return has no height)')
+        if isinstance(extent, str):
+            if extent != 'minmax':
+                raise ValueError(f"boxes3d: extent must be 'minmax' or (q_lo, q_hi), got {extent!r}")
+            quantiles = (0., 1.)
+        else:
+            quantiles = (float(extent[0]), float(extent[1]))
+        if self.masks is None:
+            raise MaskBevHipError('boxes: these predictions were made without masks')
+        lifted = self.lift(scans, module_or_geometry, quantiles=quantiles)
+        counts = lifted.counts.reshape(-1)
+        out, rows = self._boxes(x_range, y_range, voxel_size, method, also=counts >= int(min_points))
+        rows = rows.to(counts.device)
+        lo, hi = (lifted.z_min, lifted.z_max) if isinstance(extent, str) else (lifted.z_lo, lifted.z_hi)
+        z, top = lo.reshape(-1)[rows], hi.reshape(-1)[rows]
+        b = out['boxes']
+        z, top = z.to(b.device), top.to(b.device)
+        out['boxes3d'] = torch.stack([b[:, 0], b[:, 1], z, b[:, 2], b[:, 3], top - z, b[:, 4]], dim=1)
+        out['points'] = counts[rows]
+        return out
+
+    def kitti_predictions(self, x_range, y_range=None, voxel_size=None, method: str = 'moment', scans=None, module=None,
+                          extent='minmax', min_points: int = 1) -> List[dict]:
         """Per scan what ``kitti_eval.eval_kitti`` takes: ``{'boxes': (k, 5) [x, y, l, w, yaw], 'score': (k), 'type': (k)
         int64}`` of the scan's kept, non-empty queries; every box has the type Car (index 0 of ``rasterize.KITTI_TYPES``).
-        Arguments and synchronisation as :meth:`boxes`, plus one copy of the per-scan counts."""
-        out = self.boxes(x_range, y_range, voxel_size, method=method)
+        With ``scans`` (and ``module``, or its ``VoxelGeometry``) every dictionary also carries ``boxes3d`` (k, 7) of
+        :meth:`boxes3d` (``extent``, ``min_points`` as there) and ``boxes`` are its BEV columns: the 3D lines of the
+        evaluation.  Arguments and synchronisation as :meth:`boxes`, plus one copy of the per-scan counts."""
+        if scans is None:
+            out = self.boxes(x_range, y_range, voxel_size, method=method)
+        else:
+            if module is None:
+                raise ValueError('kitti_predictions: scans need the module (or its VoxelGeometry) they were voxelised with')
+            out = self.boxes3d(scans, module, x_range, y_range, voxel_size, method=method, extent=extent,
+                               min_points=min_points)
         counts = torch.bincount(out['scan'], minlength=self.labels.shape[0]).tolist()
         boxes, scores = torch.split(out['boxes'], counts), torch.split(out['scores'], counts)
-        return [dict(boxes=b, score=s, type=torch.zeros((b.shape[0],), dtype=torch.int64)) for b, s in zip(boxes, scores)]
+        dicts = [dict(boxes=b, score=s, type=torch.zeros((b.shape[0],), dtype=torch.int64)) for b, s in zip(boxes, scores)]
+        if scans is not None:
+            for d, b3 in zip(dicts, torch.split(out['boxes3d'], counts)):
+                d['boxes3d'] = b3
+        return dicts
+
+
+def voxel_geometry(module_or_geometry):
+    """The encoder's ``VoxelGeometry`` of a module (or of its encoder), or the geometry itself."""
+    g = module_or_geometry
+    for name in ('_encoder', '_voxel_layer', 'geometry'):
+        g = getattr(g, name, g)
+    if not (hasattr(g, 'pc_range') and hasattr(g, 'voxel_size') and hasattr(g, 'grid')):
+        raise MaskBevHipError('a MaskBevModule, its encoder or a VoxelGeometry is expected')
+    return g
+
+
+def write_semantic_kitti_labels(path, point_query, semantic_id: int = 10) -> None:
+    """A SemanticKITTI ``.label`` file of one scan from its per-point queries (``PointInstances.per_scan()``; a tensor
+    anywhere, or an array): ``uint32`` per point, the instance id ``query + 1`` in the upper 16 bits and ``semantic_id``
+    (default 10, car) in the lower 16; 0 for an unlabelled point (query -1).  ``batch.read_semantic_kitti_label`` reads it
+    back as (semantic, instance).  Copies a device tensor to the host."""
+    q = point_query.detach().cpu().numpy() if torch.is_tensor(point_query) else np.asarray(point_query)
+    q = q.astype(np.int64).reshape(-1)
+    if not 0 <= int(semantic_id) <= 0xffff:
+        raise ValueError(f'write_semantic_kitti_labels: semantic_id {semantic_id} outside 16 bits')
+    if q.size and (q.min() < -1 or q.max() > 0xfffe):
+        raise ValueError('write_semantic_kitti_labels: queries must lie in -1 .. 65534 (the instance id has 16 bits)')
+    out = np.where(q >= 0, ((q + 1) << 16) | int(semantic_id), 0).astype('<u4')
+    out.tofile(str(path))
 
 
 def extract_instances(cls: torch.Tensor, mask_logits: torch.Tensor, grid_hw, score_threshold: float = 0.0,
@@ -186,6 +273,8 @@ class GraphedPredictStep:
     The encoder runs eagerly in eval mode and writes into the graph's static input (the 16-bit patch rows of
     ``module._patch_handoff()``, or the f32 map with its registered absmax record in fp32 compute).  The returned
     :class:`Predictions` are the graph's static outputs: the NEXT replay overwrites them (``.clone()`` to keep them).
+    The lift to the points (``Predictions.lift``, ``boxes3d``) is not part of the graph: it runs eagerly on the step's
+    ``Predictions`` and the same ``scans``, and must run before the next replay overwrites ``instance_map``.
     The batch size is fixed at construction.  Weights are read at replay time, so in-place parameter updates (optimizer
     steps on the parameters or on a parameter arena and its 16-bit shadow) are followed; the decoder's weight copies are
     refreshed by a launch inside the graph.  May live beside a :class:`~mask_bev_amd.graph.GraphedTrainStep` (validation

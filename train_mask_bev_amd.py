@@ -25,6 +25,11 @@ instance-map cache ``<root>/sequences/SS/mask_cache/*.npy`` the reference's mask
 boxes on the GPU (rasterize.KittiRasterizer, K24) in front of K14.  ``dataset: waymo`` is not read here (``torch_waymo``
 frames); ``rasterize.WaymoRasterizer`` with ``batch.BoxCollate`` makes its batches from box tables.  The config's
 ``augmentations:`` list is applied to the training batches on the GPU (mask_bev_amd/augment.py, K23), never to validation.
+
+``--test`` extras: ``dataset: kitti`` prints the Car BEV AP block, with ``kitti_3d: true`` (optional ``kitti_3d_extent:
+[q_lo, q_hi]``) also the ``3d   AP:`` lines from heights lifted out of the scans (K31, K26b); ``dataset: semantic-kitti`` with
+``--write-labels DIR`` writes the per-point instance labels of every validated scan (K31) to
+``DIR/sequences/SS/predictions/NNNNNN.label``.
 """
 from __future__ import annotations
 
@@ -222,14 +227,18 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
     the device (K26, K27; ``mask_bev_amd.kitti_eval.eval_kitti``).  ``box_method`` (default: the configuration's
     ``kitti_box_method``, else ``moment``): ``moment`` — K25's moment-axis box of all set cells; ``min_area_rect`` — the
     minimum-area rectangle of the mask's largest component (K30a + K30b), the reference's recipe.  All labels of a frame take
-    part, unfiltered: the protocol itself decides what counts at which difficulty.  Returns the result (a string with
-    ``.metrics``)."""
+    part, unfiltered: the protocol itself decides what counts at which difficulty.  With the configuration's ``kitti_3d: true``
+    (default false) the scans go to ``kitti_predictions`` as well, every box gets the z-extent of the points inside
+    its mask (K31; ``kitti_3d_extent: [q_lo, q_hi]`` takes histogram quantiles instead of the extremes) and a ``3d   AP:``
+    line follows every ``bev  AP:`` line (K26b).  Returns the result (a string with ``.metrics``)."""
     from mask_bev_amd.predict import BOX_METHODS
     method = box_method if box_method is not None else config.get('kitti_box_method', 'moment')
     if method not in BOX_METHODS:
         raise ValueError(f'kitti_box_method must be one of {BOX_METHODS}, got {method!r}')
     from mask_bev_amd import batch as B
     from mask_bev_amd.kitti_eval import eval_kitti
+    with_3d = bool(config.get('kitti_3d', False))
+    extent = tuple(config['kitti_3d_extent']) if config.get('kitti_3d_extent') else 'minmax'
     frames = KittiObjectBatches(dict(config, shuffle_train=False, batch_size=1), device, 0, 1, root, split)
     bsz = max(1, int(config.get('batch_size', 1)))
     labels, predictions = [], []
@@ -241,8 +250,30 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
             labels.append(B.kitti_labels_to_velodyne(B.read_kitti_label(frames.dirs['label_2'] / f'{name}.txt'),
                                                      B.read_kitti_calib(frames.dirs['calib'] / f'{name}.txt')))
         pred = model.predict(scans, score_threshold)
-        predictions += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'], method=method)
+        lift = dict(scans=scans, module=model, extent=extent) if with_3d else {}
+        predictions += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'], method=method, **lift)
     return eval_kitti(labels, predictions, device=device)
+
+
+def write_point_labels(model, config, device, files, out_dir, score_threshold=0.0, semantic_id=10):
+    """Per-point instance labels of every scan of ``files`` — the (``.bin``, cache) pairs of a
+    :class:`SemanticKittiCacheBatches` — in SemanticKITTI's layout: ``model.predict`` per batch, the instance map lifted to
+    the points (K31, ``Predictions.lift``), one ``<out_dir>/sequences/SS/predictions/NNNNNN.label`` per scan (``uint32``:
+    query + 1 in the upper 16 bits, ``semantic_id`` in the lower, 0 for an unlabelled point).  Returns the paths written."""
+    from mask_bev_amd import batch as B
+    from mask_bev_amd.predict import write_semantic_kitti_labels
+    bsz = max(1, int(config.get('batch_size', 1)))
+    written = []
+    for start in range(0, len(files), bsz):
+        part = [f for f, _ in files[start:start + bsz]]
+        scans = [torch.from_numpy(B.read_velodyne_bin(f)).to(device) for f in part]
+        pred = model.predict(scans, score_threshold)
+        for f, labels in zip(part, pred.lift(scans, model).per_scan()):
+            d = pathlib.Path(out_dir) / 'sequences' / f.parent.parent.name / 'predictions'
+            d.mkdir(parents=True, exist_ok=True)
+            write_semantic_kitti_labels(d / (f.stem + '.label'), labels, semantic_id)
+            written.append(d / (f.stem + '.label'))
+    return written
 
 
 def object_bank_path(config, root):
@@ -297,6 +328,9 @@ def main(argv=None):
     parser.add_argument('--checkpoint-root', default='checkpoints')
     parser.add_argument('--build-object-bank', action='store_true',
                         help='dataset: kitti: write the object bank of object_sample from the training split and exit')
+    parser.add_argument('--write-labels', default=None, metavar='DIR',
+                        help='dataset: semantic-kitti with --test: write the per-point instance labels of every validated '
+                             'scan to DIR/sequences/SS/predictions/NNNNNN.label')
     args = parser.parse_args(argv)
 
     is_training, is_testing = args.train, args.test
@@ -485,8 +519,12 @@ def main(argv=None):
                     print(format_layer_metrics(model.logged, layer), flush=True)
             if dataset_name == 'kitti' and val is not None:
                 # what the reference's mask_to_pred + eval_kitti are for: boxes from the predicted masks, KITTI BEV AP
+                # (`kitti_3d: true`: with the heights lifted from the scans, and the 3D AP lines)
                 print(kitti_bev_evaluation(model, config, device, args.data_root,
                                            box_method=config.get('kitti_box_method', 'moment')), end='', flush=True)
+        if args.write_labels and dataset_name == 'semantic-kitti' and val is not None:
+            paths = write_point_labels(model, config, device, val.files, args.write_labels)     # every rank: its own scans
+            print(f'wrote {len(paths)} label files under {args.write_labels}', flush=True)
 
     if world > 1:
         dist.destroy_process_group()
