@@ -1562,6 +1562,61 @@ int mbv_lift_instances(const float* points, int32_t point_dim, int64_t total_poi
                        int32_t num_queries, int32_t z_bins, float q_lo, float q_hi, int32_t* point_query, int32_t* counts,
                        float* z_extent, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K32 — panoptic quality of point or BEV instances (csrc/panoptic.hip): per frame the tp / fp / fn, the IoU sums and the
+ * confusion of the SemanticKITTI panoptic protocol, PanopticEval.addBatchPanoptic of semantic-kitti-api's eval_np.py,
+ * restated, not repaired.  Parity with that package is not pinned (it is not installed); the numpy restatement in its own
+ * formulation is tests/panoptic_ref.py.
+ *
+ * Elements are the points (or BEV cells) of `frames` frames concatenated.
+ * pred_query    (total) i32: the query that owns the element (K31's point_query, K21's flattened instance_map), -1 for
+ *               none.  A value outside [0, P) counts as -1 and is never used as an index.
+ * gt_word       (total) u32 in the `.label` layout: semantic id in the low, instance id in the high 16 bits
+ * frame_offsets (frames + 1) i32 on the device; frame f owns the elements frame_offsets[f] .. frame_offsets[f + 1] - 1,
+ *               clamped into [0, total]
+ * query_class   (frames, P) i32: the class of every query; a value outside [1, C) turns the query's elements into class 0
+ *               with no instance
+ * class_lut     (lut_len) i32: semantic id -> class in [0, C), -1 = ignored.  A semantic id >= lut_len, or a table value
+ *               outside [-1, C), is ignored and never used as an index.
+ * C             classes: 0 = everything else, 1 .. C-1 the thing classes; C <= 16.  P <= 1024.  max_gt in 1 .. 1024: the
+ *               ground-truth segments a frame may hold.  min_points >= 0.
+ *
+ * An ignored element takes part in nothing: it does not count towards the area of the prediction it lies under.
+ *   ground-truth segment  the non-ignored elements of a frame that share a thing class and a 16-bit instance id (id 0 is a
+ *                         segment like any other); area = elements
+ *   prediction segment    the non-ignored elements of a frame that share a query of a thing class; at least one element
+ *   pair                  inter = elements in both, counted only where the two classes are equal;
+ *                         union = gt_area + pred_area - inter;  iou = (double)inter / (double)union
+ *   true positive         iff iou > 0.5 in f64 (inter = 2, union = 4 is none)
+ *   per thing class       tp = such pairs, iou_sum = the sum of their IoUs in ascending order of the ground truth's key;
+ *                         fn / fp = unmatched ground-truth / prediction segments of the class with area >= min_points
+ *
+ * frame_stats   (frames, C, 3) i32: tp, fp, fn; the row of class 0 is zeros (no stuff-style PQ)
+ * frame_iou     (frames, C) f64: iou_sum
+ * confusion     (frames, C, C) i64: [gt class][prediction class] over all non-ignored elements, class 0 included; the
+ *               prediction's class is its query's class, else 0
+ * n_gt          (frames) i32: the true number of ground-truth segments
+ * gt_key        (frames, max_gt) i32: class << 16 | instance, ascending, -1 past the end;  gt_area (frames, max_gt) i32
+ * pred_area     (frames, P) i32
+ * A frame with n_gt > max_gt gets zeros in frame_stats and frame_iou; its confusion and pred_area stay valid, n_gt reports
+ * it, and gt_key / gt_area hold its first max_gt segments.
+ * workspace     the byte count the _workspace_bytes entry returns (0 for sizes out of range): per frame a presence bitmap of
+ *               C * 65536 bits, its word-prefix counts, and the (max_gt, P) i32 pair table.
+ * Every element of the seven outputs is written by the call, nothing has to be pre-set and nothing else is written.  Five
+ * launches whatever the number of frames (initialise; mark, one thread per element; index, one workgroup per frame; count,
+ * one thread per element with LDS tables per block; match, one workgroup per frame).  Integer atomics only and a fixed
+ * order of the f64 sum: bit-deterministic.  No host synchronisation.
+ * frames == 0: MBV_OK whatever the pointers are.  Empty frames are fine.  MBV_ERR_UNSUPPORTED: P > 1024, max_gt > 1024,
+ * C > 16, frames > 65535, total >= 2^31 - 1;  MBV_ERR_BAD_ARG: a null pointer for a table that has elements, a negative
+ * size, C < 1, max_gt < 1, min_points < 0;  MBV_ERR_WORKSPACE: a workspace that is too small.
+ */
+size_t mbv_panoptic_frames_workspace_bytes(int32_t frames, int32_t P, int32_t max_gt, int32_t C);
+int mbv_panoptic_frames(const int32_t* pred_query, const uint32_t* gt_word, int64_t total, const int32_t* frame_offsets,
+                        int32_t frames, const int32_t* query_class, int32_t P, const int32_t* class_lut, int32_t lut_len,
+                        int32_t C, int32_t max_gt, int32_t min_points, int32_t* frame_stats, double* frame_iou,
+                        int64_t* confusion, int32_t* n_gt, int32_t* gt_key, int32_t* gt_area, int32_t* pred_area,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ to ground-truth resolution, thresholds and hands dense tensors to torchmetrics. 
 * :class:`DeviceMaskMeanAveragePrecision` fills the same slot without leaving the device: bit-packed predicted masks
   from K21, pairwise popcounts and the per-image COCO matching from K29 (csrc/mask_map.hip), no host synchronisation in
   ``update``; ``compute`` accumulates the whole dataset in vectorised torch and copies twelve numbers back.
+* :class:`DevicePanopticQuality` has no counterpart in the reference: PQ / SQ / RQ / IoU of the lifted point labels (K31)
+  or of the BEV instance map (K21) in the SemanticKITTI panoptic protocol, per-frame counts from K32 (csrc/panoptic.hip).
 """
 from __future__ import annotations
 
@@ -392,6 +394,131 @@ class DeviceMaskMeanAveragePrecision:
                            mean(recall[:, :, 0, 0]), mean(recall[:, :, 0, 1]), mean(recall[:, :, 0, 2]),
                            mean(recall[:, :, 1, last]), mean(recall[:, :, 2, last]), mean(recall[:, :, 3, last])]).cpu().tolist()
         return dict(zip(keys, out))
+
+
+def semantic_kitti_class_lut(things=((10,),), ignore=(0, 1, 252), length: int = 260) -> np.ndarray:
+    """The ``class_lut`` of :class:`DevicePanopticQuality` for raw SemanticKITTI semantic ids: an int32 table of ``length``
+    entries in which the ids of the k-th tuple of ``things`` map to class k + 1, the ids of ``ignore`` to -1 and every other
+    id to 0 ("everything else").  The default scores static cars: raw label 10 is class 1, as the reference trains on that
+    label alone (semantic_kitti_mask_data_module.py:56); unlabelled (0), outlier (1) and MOVING cars (252) are ignored, so
+    a moving car is neither rewarded nor penalised — its points take part in nothing, whatever was predicted on them."""
+    lut = np.zeros((int(length),), dtype=np.int32)
+    for k, ids in enumerate(things):
+        for i in ids:
+            if not 0 <= int(i) < length:
+                raise ValueError(f'semantic_kitti_class_lut: semantic id {i} outside the table of {length}')
+            lut[int(i)] = k + 1
+    for i in ignore:
+        if not 0 <= int(i) < length:
+            raise ValueError(f'semantic_kitti_class_lut: semantic id {i} outside the table of {length}')
+        lut[int(i)] = -1
+    return lut
+
+
+def panoptic_quality(tp, fp, fn, iou_sum, confusion) -> dict:
+    """The numbers of ``PanopticEval.getPQ`` / ``getSemIoU`` (semantic-kitti-api, eval_np.py) from the sums of a dataset:
+    ``tp``, ``fp``, ``fn``, ``iou_sum`` (C) per class (class 0 is not scored: zeros), ``confusion`` (C, C) [gt][prediction].
+    Per class ``pq = iou_sum / max(tp + 0.5 fp + 0.5 fn, 1e-15)``, ``sq = iou_sum / max(tp, 1e-15)``, ``rq = tp / max(tp +
+    0.5 fp + 0.5 fn, 1e-15)`` and ``iou = confusion[c][c] / max(row + column - confusion[c][c], 1e-15)`` →
+    ``{'pq', 'sq', 'rq', 'iou'}`` the means over the thing classes 1 .. C-1, ``'per_class'`` the lists of all C classes under
+    the same four names plus the raw ``tp``, ``fp``, ``fn``."""
+    tp, fp, fn = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (tp, fp, fn))
+    iou_sum, conf = np.asarray(iou_sum, dtype=np.float64).reshape(-1), np.asarray(confusion, dtype=np.float64)
+    c = tp.shape[0]
+    eps = 1e-15
+    denom = np.maximum(tp + 0.5 * fp + 0.5 * fn, eps)
+    pq, sq, rq = iou_sum / denom, iou_sum / np.maximum(tp, eps), tp / denom
+    inter = np.diag(conf)
+    iou = inter / np.maximum(conf.sum(1) + conf.sum(0) - inter, eps)
+    things = slice(1, c)
+
+    def mean(x):
+        return float(x[things].mean()) if c > 1 else 0.0
+
+    per_class = dict(pq=pq.tolist(), sq=sq.tolist(), rq=rq.tolist(), iou=iou.tolist(), tp=[int(v) for v in tp],
+                     fp=[int(v) for v in fp], fn=[int(v) for v in fn])
+    return dict(pq=mean(pq), sq=mean(sq), rq=mean(rq), iou=mean(iou), per_class=per_class)
+
+
+class DevicePanopticQuality:
+    """PQ / SQ / RQ and IoU of point or BEV instances in the SemanticKITTI panoptic protocol (``PanopticEval`` of
+    semantic-kitti-api's eval_np.py, restated; parity with that package is unpinned: it is not installed), with the per-frame
+    work on the device (K32, ``ops.panoptic_frames``).  ``class_lut``: semantic id → class, -1 = ignored
+    (:func:`semantic_kitti_class_lut`), a numpy array or a tensor; classes 1 .. ``num_classes`` - 1 are the thing classes.
+    ``update`` adds the frames' tp / fp / fn, IoU sums and confusion into running device tensors without a host copy;
+    ``compute`` sums the ranks (``all_reduce`` when ``torch.distributed`` is initialised), makes ONE host copy and returns
+    :func:`panoptic_quality` of the sums plus ``frames``.  It raises ``MaskBevHipError`` if any frame held more than ``max_gt``
+    ground-truth segments: such a frame has no numbers."""
+
+    def __init__(self, num_classes: int, class_lut, min_points: int = 50, max_gt: int = 256):
+        self.num_classes, self.min_points, self.max_gt = int(num_classes), int(min_points), int(max_gt)
+        if not 2 <= self.num_classes <= 16:
+            raise ValueError(f'DevicePanopticQuality: 2 <= num_classes <= 16, got {num_classes}')
+        lut = class_lut.detach().cpu().numpy() if torch.is_tensor(class_lut) else np.asarray(class_lut)
+        self._lut_host = np.ascontiguousarray(lut.reshape(-1).astype(np.int32))
+        self._lut = {}
+        self.state = None
+        self.frames = 0
+
+    def reset(self):
+        self.state = None
+        self.frames = 0
+
+    def class_lut(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device not in self._lut:
+            self._lut[device] = torch.from_numpy(self._lut_host).to(device)
+        return self._lut[device]
+
+    @torch.no_grad()
+    def update(self, pred_query: torch.Tensor, query_class: torch.Tensor, gt_words: torch.Tensor, lengths) -> 'ops.PanopticFrames':
+        """One batch of F frames: ``pred_query`` (N) int32, ``query_class`` (F, P) int32, ``gt_words`` (N) int32 / uint32,
+        ``lengths`` the frames' element counts (host) or (F + 1) int32 device offsets — the arguments of
+        ``ops.panoptic_frames``.  Returns the frames' record; nothing is copied back."""
+        out = ops.panoptic_frames(pred_query, gt_words, lengths, query_class, self.class_lut(pred_query.device),
+                                  self.num_classes, max_gt=self.max_gt, min_points=self.min_points)
+        self.append_state(out.frame_stats, out.frame_iou, out.confusion, out.n_gt)
+        return out
+
+    @torch.no_grad()
+    def append_state(self, frame_stats: torch.Tensor, frame_iou: torch.Tensor, confusion: torch.Tensor, n_gt: torch.Tensor):
+        """The records of some frames as K32 leaves them (tensors of any one device)."""
+        c = self.num_classes
+        if tuple(frame_stats.shape[1:]) != (c, 3) or tuple(frame_iou.shape[1:]) != (c,) or tuple(confusion.shape[1:]) != (c, c):
+            raise ValueError(f'append_state: records of {c} classes expected')
+        part = (frame_stats.to(torch.int64).sum(0), frame_iou.to(torch.float64).sum(0), confusion.to(torch.int64).sum(0),
+                (n_gt > self.max_gt).to(torch.int64).sum().view(1))
+        self.state = part if self.state is None else tuple(a + b for a, b in zip(self.state, part))
+        self.frames += int(frame_stats.shape[0])
+
+    @torch.no_grad()
+    def compute(self) -> dict:
+        c = self.num_classes
+        import torch.distributed as dist
+        gather = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if self.state is None and not gather:
+            return dict(panoptic_quality(np.zeros(c), np.zeros(c), np.zeros(c), np.zeros(c), np.zeros((c, c))), frames=0)
+        if self.state is None:
+            dev = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+            stats, iou, conf, over = (torch.zeros((c, 3), dtype=torch.int64, device=dev), torch.zeros((c,), dtype=torch.float64, device=dev),
+                                      torch.zeros((c, c), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int64, device=dev))
+        else:
+            stats, iou, conf, over = self.state
+        counts = torch.cat([stats.reshape(-1), conf.reshape(-1), over, torch.tensor([self.frames], dtype=torch.int64, device=over.device)])
+        if gather:                                         # sums over the ranks; the f64 sums in rank order, on every rank alike
+            dist.all_reduce(counts)
+            parts = [torch.empty_like(iou) for _ in range(dist.get_world_size())]
+            dist.all_gather(parts, iou.contiguous())
+            iou = torch.stack(parts).sum(0)
+        host = torch.cat([counts, iou.contiguous().view(torch.int64)]).cpu()          # the ONE host copy: f64 bits ride as int64
+        stats = host[:3 * c].view(c, 3).numpy()
+        conf = host[3 * c:3 * c + c * c].view(c, c).numpy()
+        over, frames = int(host[3 * c + c * c]), int(host[3 * c + c * c + 1])
+        iou_sum = host[3 * c + c * c + 2:].contiguous().view(torch.float64).numpy()
+        if over > 0:
+            raise MaskBevHipError(f'DevicePanopticQuality: {over} of {frames} frames hold more than max_gt = {self.max_gt} '
+                                  'ground-truth segments and have no numbers; raise max_gt (<= 1024)')
+        return dict(panoptic_quality(stats[:, 0], stats[:, 1], stats[:, 2], iou_sum, conf), frames=frames)
 
 
 @torch.no_grad()

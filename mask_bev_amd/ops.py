@@ -21,7 +21,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
                    K28 KITTI object augmentations: box-table membership, move, removal and pasting of points
     ops_eval       K25 oriented box of a packed mask, K26 / K26b rotated-box overlap (BEV / 3-D) over ragged frames, K27 KITTI tp / fp / fn,
                    K29 pairwise overlap of packed masks + COCO per-image matching (mask mAP),
-                   K30 largest 8-connected component + minimum-area rectangle of a packed mask
+                   K30 largest 8-connected component + minimum-area rectangle of a packed mask,
+                   K32 panoptic tp / fp / fn, IoU sums and confusion per frame from two id arrays (points or BEV cells)
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403

@@ -2,10 +2,12 @@
 (csrc/rotate_iou.hip), K26b — the same with heights (``rotate_iou_3d``); K27 — KITTI tp / fp / fn of all frames and score thresholds (csrc/kitti_stats.hip).  The three
 kernels behind ``kitti_eval`` (KITTI BEV AP) and ``Predictions.boxes``.  K30a — largest 8-connected component of a packed
 mask (csrc/mask_components.hip) and K30b — minimum-area rectangle of a packed mask (csrc/min_area_rect.hip), behind
-``Predictions.boxes(method='min_area_rect')``.  K29 — pairwise overlap of bit-packed masks and the COCO per-image matching on its integer tables (csrc/mask_map.hip), behind ``metrics.DeviceMaskMeanAveragePrecision``.
+``Predictions.boxes(method='min_area_rect')``.  K29 — pairwise overlap of bit-packed masks and the COCO per-image matching on its integer tables (csrc/mask_map.hip), behind ``metrics.DeviceMaskMeanAveragePrecision``.  K32 — per-frame panoptic tp / fp / fn, IoU sums and confusion of point or BEV
+instances (csrc/panoptic.hip), behind ``metrics.DevicePanopticQuality``.
 The definitions are in include/maskbev_hip.h."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -315,4 +317,86 @@ def coco_match(inter: torch.Tensor, pred_area: torch.Tensor, gt_area: torch.Tens
     return rank, matched, ignored, npig
 
 
-__all__ = ['fit_boxes', 'largest_component', 'min_area_boxes', 'rotate_iou', 'rotate_iou_3d', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match']
+@dataclass
+class PanopticFrames:
+    """K32's outputs for F frames, P queries and C classes, on the device (include/maskbev_hip.h, K32): ``frame_stats``
+    (F, C, 3) int32 = tp, fp, fn; ``frame_iou`` (F, C) f64 — the IoU sums of the true positives; ``confusion`` (F, C, C) int64
+    [gt class][prediction class]; ``n_gt`` (F) int32 — the true number of ground-truth segments (a frame with more than
+    ``max_gt`` has zeros in ``frame_stats`` and ``frame_iou``); ``gt_key`` (F, max_gt) int32 = class << 16 | instance,
+    ascending, -1 past the end; ``gt_area`` (F, max_gt) int32; ``pred_area`` (F, P) int32."""
+    frame_stats: torch.Tensor
+    frame_iou: torch.Tensor
+    confusion: torch.Tensor
+    n_gt: torch.Tensor
+    gt_key: torch.Tensor
+    gt_area: torch.Tensor
+    pred_area: torch.Tensor
+    max_gt: int
+
+
+@torch.no_grad()
+def panoptic_frames(pred_query: torch.Tensor, gt_words: torch.Tensor, lengths_or_offsets, query_class: torch.Tensor,
+                    class_lut: torch.Tensor, num_classes: int, max_gt: int = 256, min_points: int = 50) -> PanopticFrames:
+    """K32: ``pred_query`` (N) int32 — per element (point or BEV cell) of the F concatenated frames the query that owns it, -1
+    for none; ``gt_words`` (N) int32 / uint32 — the ground truth in the ``.label`` layout (semantic id low, instance id high
+    16 bits); ``lengths_or_offsets`` — the frames' element counts (a host sequence of F integers) or their (F + 1) int32
+    offsets on the device; ``query_class`` (F, P) int32 — the class of every query (outside 1 .. num_classes - 1: no thing);
+    ``class_lut`` (L) int32 device table semantic id → class, -1 = ignored → :class:`PanopticFrames`.  Device tensors only;
+    no host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(pred_query, gt_words, query_class, class_lut)
+    dev = pred_query.device
+    if pred_query.dim() != 1 or pred_query.dtype != torch.int32:
+        raise MaskBevHipError(f'panoptic_frames: pred_query must be (N) int32, got {tuple(pred_query.shape)} {pred_query.dtype}')
+    if gt_words.dtype == getattr(torch, 'uint32', None):
+        gt_words = gt_words.view(torch.int32)
+    if gt_words.dtype != torch.int32 or tuple(gt_words.shape) != tuple(pred_query.shape):
+        raise MaskBevHipError(f'panoptic_frames: gt_words must be ({pred_query.numel()}) int32 / uint32, got '
+                              f'{tuple(gt_words.shape)} {gt_words.dtype}')
+    if query_class.dim() != 2 or query_class.dtype != torch.int32:
+        raise MaskBevHipError(f'panoptic_frames: query_class must be (frames, P) int32, got {tuple(query_class.shape)} '
+                              f'{query_class.dtype}')
+    if class_lut.dim() != 1 or class_lut.dtype != torch.int32:
+        raise MaskBevHipError('panoptic_frames: class_lut must be a 1-d int32 table')
+    frames, p = int(query_class.shape[0]), int(query_class.shape[1])
+    n, c, max_gt, min_points = pred_query.numel(), int(num_classes), int(max_gt), int(min_points)
+    if not (1 <= c <= 16 and p <= 1024 and 1 <= max_gt <= 1024 and min_points >= 0 and frames <= 65535 and n < 2 ** 31 - 1):
+        raise MaskBevHipError(f'panoptic_frames: num_classes {c} (1 .. 16), P {p} (<= 1024), max_gt {max_gt} (1 .. 1024), '
+                              f'min_points {min_points} (>= 0), frames {frames} (<= 65535) or {n} elements out of range')
+    if torch.is_tensor(lengths_or_offsets):
+        offsets = lengths_or_offsets
+        if offsets.dtype != torch.int32 or tuple(offsets.shape) != (frames + 1,) or offsets.device != dev:
+            raise MaskBevHipError(f'panoptic_frames: offsets must be ({frames + 1}) int32 on the elements\' device')
+    else:
+        lens = [int(v) for v in lengths_or_offsets]
+        if len(lens) != frames or any(v < 0 for v in lens) or sum(lens) != n:
+            raise MaskBevHipError(f'panoptic_frames: {len(lens)} lengths summing to {sum(lens)} for {frames} frames of {n} elements')
+        offs = [0]
+        for v in lens:
+            offs.append(offs[-1] + v)
+        offsets = torch.tensor(offs, dtype=torch.int32).to(dev, non_blocking=True)
+    for x in (gt_words, query_class, class_lut):
+        if x.device != dev:
+            raise MaskBevHipError('panoptic_frames: tensors on different devices')
+    pred_query, gt_words, offsets = pred_query.contiguous(), gt_words.contiguous(), offsets.contiguous()
+    query_class, class_lut = query_class.contiguous(), class_lut.contiguous()
+    out = PanopticFrames(torch.empty((frames, c, 3), dtype=torch.int32, device=dev),
+                         torch.empty((frames, c), dtype=torch.float64, device=dev),
+                         torch.empty((frames, c, c), dtype=torch.int64, device=dev),
+                         torch.empty((frames,), dtype=torch.int32, device=dev),
+                         torch.empty((frames, max_gt), dtype=torch.int32, device=dev),
+                         torch.empty((frames, max_gt), dtype=torch.int32, device=dev),
+                         torch.empty((frames, p), dtype=torch.int32, device=dev), max_gt)
+    if frames == 0:
+        return out
+    nbytes = lib.mbv_panoptic_frames_workspace_bytes(frames, p, max_gt, c)
+    ws = _workspace(nbytes, dev)
+    check(lib.mbv_panoptic_frames(_ptr(pred_query), _ptr(gt_words), n, _ptr(offsets), frames, _ptr(query_class), p,
+                                  _ptr(class_lut), class_lut.numel(), c, max_gt, min_points, _ptr(out.frame_stats),
+                                  _ptr(out.frame_iou), _ptr(out.confusion), _ptr(out.n_gt), _ptr(out.gt_key),
+                                  _ptr(out.gt_area), _ptr(out.pred_area), _ptr(ws), ws.numel(), _stream()),
+          'mbv_panoptic_frames')
+    return out
+
+
+__all__ = ['fit_boxes', 'largest_component', 'min_area_boxes', 'rotate_iou', 'rotate_iou_3d', 'kitti_statistics', 'FrameOffsets', 'pairwise_mask_overlap', 'coco_match', 'panoptic_frames', 'PanopticFrames']

@@ -109,6 +109,48 @@ class Predictions:
         return ops.lift_instances(scans, self.instance_map, voxel_geometry(module_or_geometry), self.labels.shape[1],
                                   z_bins=z_bins, quantiles=quantiles)
 
+    def query_classes(self) -> torch.Tensor:
+        """(B, Q) int32, the panoptic class of every query: its label (1 .. K; index 0 of the class logits is "empty", so a
+        kept query's label is already a thing class) where ``keep``, else 0.  No host synchronisation."""
+        return torch.where(self.keep, self.labels.to(torch.int32), torch.zeros_like(self.labels, dtype=torch.int32))
+
+    def panoptic_points(self, lifted: 'ops.PointInstances', gt_words, metric) -> 'ops.PanopticFrames':
+        """Feeds a :class:`~mask_bev_amd.metrics.DevicePanopticQuality` with the lifted point labels of these predictions
+        (``lifted``: :meth:`lift` of the scans) against ``gt_words``, the list of the scans' ``.label`` words as (N_i) uint32 /
+        int32 device tensors (semantic id low, instance id high 16 bits) in the scans' point order.  K32; returns the
+        frames' record.  No host synchronisation."""
+        gt_words = list(gt_words)
+        if len(gt_words) != len(lifted.lengths) or any(w.dim() != 1 or int(w.shape[0]) != n
+                                                       for w, n in zip(gt_words, lifted.lengths)):
+            raise MaskBevHipError(f'panoptic_points: one (N_i) tensor of label words per scan expected, of {list(lifted.lengths)} '
+                                  f'points, got {[tuple(w.shape) for w in gt_words]}')
+        u32 = getattr(torch, 'uint32', None)
+        gt_words = [w.view(torch.int32) if w.dtype == u32 else w for w in gt_words]
+        words = gt_words[0] if len(gt_words) == 1 else torch.cat(gt_words)
+        return metric.update(lifted.point_query, self.query_classes(), words, lifted.scan_offsets)
+
+    def panoptic_bev(self, gt_instance_maps: torch.Tensor, metric, gt_class: int = 1) -> 'ops.PanopticFrames':
+        """Feeds a :class:`~mask_bev_amd.metrics.DevicePanopticQuality` with the BEV instance map of these predictions, one
+        cell an element: ``gt_instance_maps`` (B, ny, nx) integer device map in the cell layout of ``instance_map``, with the
+        ids as ``batch.instance_targets`` reads them — 0 = background, > 0 = an instance (a rasteriser's (B, nx, ny) map:
+        ``.permute(0, 2, 1)``); ids keep their low 16 bits.  The words are synthesised on the device: an instance cell
+        carries semantic id ``gt_class``, a background cell 0, so the metric's ``class_lut`` must map those two (e.g.
+        ``numpy.arange(num_classes)``).  K32; returns the frames' record.  No host synchronisation."""
+        if self.instance_map is None:
+            raise MaskBevHipError('panoptic_bev: these predictions were made without an instance map')
+        m = self.instance_map
+        if tuple(gt_instance_maps.shape) != tuple(m.shape) or gt_instance_maps.device != m.device \
+                or gt_instance_maps.dtype.is_floating_point:
+            raise MaskBevHipError(f'panoptic_bev: an integer ground-truth map {tuple(m.shape)} (B, ny, nx) on the predictions\' '
+                                  f'device expected, got {tuple(gt_instance_maps.shape)} {gt_instance_maps.dtype}')
+        if not 0 <= int(gt_class) <= 0xffff:
+            raise ValueError(f'panoptic_bev: gt_class {gt_class} outside 16 bits')
+        ids = gt_instance_maps.to(torch.int64).reshape(-1)
+        words = torch.where(ids > 0, ((ids & 0xffff) << 16) | int(gt_class), torch.zeros_like(ids))
+        words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)      # the u32 bits in an int32 tensor
+        b, cells = m.shape[0], m.shape[1] * m.shape[2]
+        return metric.update(m.reshape(-1).contiguous(), self.query_classes(), words, [cells] * b)
+
     def boxes(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> dict:
         """Oriented BEV boxes of the kept queries, in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a
         rasteriser (``KittiRasterizer``) in place of ``x_range``.  ``method='moment'``: K25, ``ops.fit_boxes``, the

@@ -29,7 +29,9 @@ frames); ``rasterize.WaymoRasterizer`` with ``batch.BoxCollate`` makes its batch
 ``--test`` extras: ``dataset: kitti`` prints the Car BEV AP block, with ``kitti_3d: true`` (optional ``kitti_3d_extent:
 [q_lo, q_hi]``) also the ``3d   AP:`` lines from heights lifted out of the scans (K31, K26b); ``dataset: semantic-kitti`` with
 ``--write-labels DIR`` writes the per-point instance labels of every validated scan (K31) to
-``DIR/sequences/SS/predictions/NNNNNN.label``.
+``DIR/sequences/SS/predictions/NNNNNN.label``; when ``sequences/SS/labels/NNNNNN.label`` lies next to every validated scan
+it also prints ``point PQ .. SQ .. RQ .. IoU .. (car; tp .. fp .. fn ..)``, the panoptic quality of those lifted labels (K32;
+``panoptic_min_points``, ``panoptic_things``, ``panoptic_ignore``).
 """
 from __future__ import annotations
 
@@ -274,6 +276,53 @@ def write_point_labels(model, config, device, files, out_dir, score_threshold=0.
             write_semantic_kitti_labels(d / (f.stem + '.label'), labels, semantic_id)
             written.append(d / (f.stem + '.label'))
     return written
+
+
+def semantic_kitti_label_path(scan_path):
+    """``sequences/SS/velodyne/NNNNNN.bin`` → ``sequences/SS/labels/NNNNNN.label``, the ground truth next to a scan."""
+    scan_path = pathlib.Path(scan_path)
+    return scan_path.parent.parent / 'labels' / (scan_path.stem + '.label')
+
+
+def panoptic_settings(config):
+    """The configuration's ``panoptic_min_points`` (default 50), ``panoptic_things`` (default [[10]]: raw label 10, car, is
+    thing class 1; one list of raw semantic ids per thing class) and ``panoptic_ignore`` (default [0, 1, 252])."""
+    things = config.get('panoptic_things', [[10]])
+    things = tuple(tuple(int(i) for i in (t if isinstance(t, (list, tuple)) else [t])) for t in things)
+    ignore = tuple(int(i) for i in config.get('panoptic_ignore', [0, 1, 252]))
+    return int(config.get('panoptic_min_points', 50)), things, ignore
+
+
+def point_panoptic_evaluation(model, config, device, files, score_threshold=0.0):
+    """Panoptic quality of the lifted point labels over ``files`` — the (``.bin``, cache) pairs of a
+    :class:`SemanticKittiCacheBatches` — against ``sequences/SS/labels/NNNNNN.label``: ``model.predict`` per batch, the lift
+    to the points (K31), the per-frame counts on the device (K32, ``metrics.DevicePanopticQuality``).  Returns the metric
+    after the last update (``compute()`` sums the ranks: call it on every rank), or ``None`` when a label file is missing.
+    ``panoptic_max_gt`` (default 256, at most 1024): the ground-truth segments a scan may hold."""
+    import numpy as np
+    from mask_bev_amd import batch as B
+    from mask_bev_amd.metrics import DevicePanopticQuality, semantic_kitti_class_lut
+    labels = [semantic_kitti_label_path(f) for f, _ in files]
+    if not labels or not all(p.exists() for p in labels):
+        return None
+    min_points, things, ignore = panoptic_settings(config)
+    metric = DevicePanopticQuality(len(things) + 1, semantic_kitti_class_lut(things, ignore), min_points=min_points,
+                                   max_gt=int(config.get('panoptic_max_gt', 256)))
+    bsz = max(1, int(config.get('batch_size', 1)))
+    for start in range(0, len(files), bsz):
+        scans = [torch.from_numpy(B.read_velodyne_bin(f)).to(device) for f, _ in files[start:start + bsz]]
+        words = [torch.from_numpy(np.fromfile(str(p), dtype='<u4').view(np.int32)).to(device) for p in labels[start:start + bsz]]
+        pred = model.predict(scans, score_threshold)
+        pred.panoptic_points(pred.lift(scans, model), words, metric)
+    return metric
+
+
+def format_point_panoptic(result, things=((10,),)):
+    """The ``point PQ`` line of ``--test`` from ``DevicePanopticQuality.compute()``."""
+    pc = result['per_class']
+    what = 'car' if tuple(tuple(t) for t in things) == ((10,),) else f'{len(things)} thing classes'
+    return (f'point PQ {result["pq"]:.4f} SQ {result["sq"]:.4f} RQ {result["rq"]:.4f} IoU {result["iou"]:.4f} '
+            f'({what}; tp {sum(pc["tp"][1:])} fp {sum(pc["fp"][1:])} fn {sum(pc["fn"][1:])})')
 
 
 def object_bank_path(config, root):
@@ -522,6 +571,18 @@ def main(argv=None):
                 # (`kitti_3d: true`: with the heights lifted from the scans, and the 3D AP lines)
                 print(kitti_bev_evaluation(model, config, device, args.data_root,
                                            box_method=config.get('kitti_box_method', 'moment')), end='', flush=True)
+        if dataset_name == 'semantic-kitti' and val is not None:
+            # point-level panoptic quality of the lifted labels, when the ground truth lies next to every validated scan
+            have = all(semantic_kitti_label_path(f).exists() for f, _ in val.files)
+            if world > 1:                              # every rank or none: compute() sums the ranks
+                flag = torch.tensor([int(have)], device=device)
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                have = bool(int(flag))
+            metric = point_panoptic_evaluation(model, config, device, val.files) if have else None
+            if metric is not None:
+                result = metric.compute()
+                if rank == 0:
+                    print(format_point_panoptic(result, panoptic_settings(config)[1]), flush=True)
         if args.write_labels and dataset_name == 'semantic-kitti' and val is not None:
             paths = write_point_labels(model, config, device, val.files, args.write_labels)     # every rank: its own scans
             print(f'wrote {len(paths)} label files under {args.write_labels}', flush=True)
