@@ -1617,6 +1617,91 @@ int mbv_panoptic_frames(const int32_t* pred_query, const uint32_t* gt_word, int6
                         int64_t* confusion, int32_t* n_gt, int32_t* gt_key, int32_t* gt_area, int32_t* pred_area,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K33a — the tracker step (csrc/track.hip): BEV instance maps of consecutive frames of ONE sequence are associated after
+ * ego-motion compensation, so that an object keeps one global id.  Built with -ffp-contract=off; the numpy restatement of
+ * the words below is tests/track_ref.py.  There is no motion model: a moving object is matched only while its footprints of
+ * consecutive frames overlap.
+ *
+ * Grid           H = ny rows, W = nx columns, the layout of Predictions.instance_map[b]; x_lo, y_lo, voxel f64.  Cell
+ *                (iy, ix) has the centre x = x_lo + (ix + 0.5) * voxel, y = y_lo + (iy + 0.5) * voxel.
+ * State          owned by the caller, on the device: state_map (H, W) i32, a local track index in [0, n_live) or -1;
+ *                live_id (P) i32, the global id; live_seen (P) i32, the frame counter at the last match; counters (4) i32 =
+ *                [n_live, next_id, frame, dropped].  A fresh tracker: the map filled with -1, the counters 0.  A stored
+ *                n_live outside [0, P] is clamped into it.
+ * One frame      instance_maps (F, H, W) i32: a query in [0, Q) or -1; any other value counts as -1 and is never used as
+ *                an index.  prev_from_cur (F, 2, 3) f64 row-major on the device: m00 m01 m02 / m10 m11 m12.
+ *                Q <= P <= 1024, H * W <= 1024 * 1024, min_iou f64, max_age >= 0, min_cells >= 1.
+ *
+ * 1. warp    for every current cell centre, in f64 with one rounding per operation:
+ *            xp = (m00 * x + m01 * y) + m02, yp = (m10 * x + m11 * y) + m12, jx = floor((xp - x_lo) / voxel), jy likewise;
+ *            warped[iy, ix] = state_map[jy, jx] when 0 <= jx < W and 0 <= jy < H, else -1 (NaN and inf fall under the
+ *            else); a stored index outside [0, n_live) counts as -1.
+ * 2. count   area_q[q] = cells of the instance map equal to q, area_t[t] = cells of warped equal to t, inter[q, t] = cells
+ *            where both hold.  A query is present iff area_q[q] >= min_cells; the cells of a query that is not present
+ *            count as empty from here on.
+ * 3. match   greedy and exact.  Candidates: (q, t) with q present, inter > 0 and (double)inter / (double)union >= min_iou,
+ *            union = area_q + area_t - inter (inter = 1, union = 2 at min_iou = 0.5 is one).  Order: IoU descending,
+ *            compared as inter_a * union_b against inter_b * union_a in i64; ties to the smaller q, then the smaller t.
+ *            Walk the order and take a pair when neither its q nor its t is taken.
+ * 4. update  the new live list: the present queries in ascending q — a matched one inherits live_id[t], an unmatched one
+ *            takes next_id and increments it; both get seen = frame.  Then the unmatched old tracks in ascending t: one
+ *            with frame - live_seen[t] <= max_age is appended with its id and seen unchanged while the list holds fewer
+ *            than P entries, otherwise dropped is incremented; older tracks vanish silently.  The new state_map of a cell:
+ *            the new index of its present query, else the new index of its warped track if that track was appended, else
+ *            -1 (a matched track's cells outside its query are released).  frame is incremented.  live_id and live_seen
+ *            past the new n_live are -1.
+ *
+ * query_track    (F, Q) i32: the global id, -1 when the query is not present
+ * track_map      (F, H, W) i32 or NULL: the global id on the cells of present queries, else -1
+ * workspace      the byte count the _workspace_bytes entry returns (0 for sizes out of range): the warped map, the two area
+ *                tables, the (Q, P) intersection table, a candidate list of Q * P pairs and two index tables.
+ * mbv_track_frames steps through the F frames in order: four launches per frame (clear; count, one thread per cell with the
+ * areas summed in LDS per block; match and update, ONE workgroup; paint, one thread per cell), enqueued on the stream, never
+ * synchronised.  Integer atomics only: bit-deterministic.  Every element of query_track, track_map and of the new state is
+ * written by the call; nothing has to be pre-set.
+ * F == 0: MBV_OK whatever the pointers are.  MBV_ERR_UNSUPPORTED: Q > P, P > 1024, H * W > 1024 * 1024;  MBV_ERR_BAD_ARG: a
+ * null pointer for a table that has elements, a negative size, min_cells < 1, max_age < 0;  MBV_ERR_WORKSPACE: a workspace
+ * that is too small.
+ */
+size_t mbv_track_frames_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P);
+int mbv_track_frames(const int32_t* instance_maps, const double* prev_from_cur, int32_t F, int32_t H, int32_t W, double x_lo,
+                     double y_lo, double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age, int32_t min_cells,
+                     int32_t* state_map, int32_t* live_id, int32_t* live_seen, int32_t* counters, int32_t* query_track,
+                     int32_t* track_map, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K33b — tube association (csrc/track.hip): the S_assoc term of LSTQ (Aygün et al., 4D Panoptic LiDAR Segmentation) over a
+ * whole sequence, from per-element track ids and `.label` words.  Parity with semantic-kitti-api's 4D evaluator is not
+ * pinned (it is not installed); the restatement is tests/track_ref.py.
+ *
+ * mbv_tube_accumulate adds `total` elements (points or cells) to tables that persist on the device; the caller zeroes them once.
+ * pred_track    (total) i32: the global track id, -1 (or any negative value) = none
+ * gt_word       (total) u32 in the `.label` layout; class_lut / lut_len / C exactly as in K32 (-1 = ignored, C <= 16)
+ * id_limit I    (1 .. 65536) and max_tracks T (1 .. 2^20), with (C - 1) * I * T < 2^31 - 1
+ * An ignored element takes part in nothing.  A ground-truth tube is a thing class c >= 1 with an instance id in [1, I); its
+ * row is r = (c - 1) * I + inst; instance id 0 is no tube.
+ * gt_size       ((C - 1) * I) i64 += 1 for every element of the tube
+ * pred_size     (T) i64 += 1 for every non-ignored element with 0 <= p < T, class-agnostic
+ * pair          ((C - 1) * I, T) i32 += 1 where both hold
+ * overflow      (2) i64: [0] += non-ignored thing elements with an instance id >= I; [1] += non-ignored elements with a
+ *               track id >= T
+ * The two size tables are summed in LDS per block where they have at most 4096 entries.  total == 0: MBV_OK.
+ *
+ * mbv_tube_scores, one workgroup per row: with g = gt_size[r] > 0,
+ *   assoc[r] = (sum over p ascending with pair > 0 of (double)tpa * ((double)tpa / (double)(g + pred_size[p] - tpa))) / (double)g
+ * summed in that fixed order, one rounding per operation; otherwise assoc[r] = 0.
+ * assoc         ((C - 1) * I) f64;  class_assoc (C) f64: the sum of the class's rows with g > 0 in ascending order (class 0:
+ *               0);  class_tubes (C) i32: those rows' number.
+ * Neither synchronises.  MBV_ERR_UNSUPPORTED beyond the limits, total >= 2^31 - 1;  MBV_ERR_BAD_ARG: a null table that has
+ * elements, a negative size, C < 1, I < 1, T < 1.
+ */
+int mbv_tube_accumulate(const int32_t* pred_track, const uint32_t* gt_word, int64_t total, const int32_t* class_lut,
+                        int32_t lut_len, int32_t C, int32_t id_limit, int32_t max_tracks, int64_t* gt_size, int64_t* pred_size,
+                        int32_t* pair, int64_t* overflow, void* stream);
+int mbv_tube_scores(const int64_t* gt_size, const int64_t* pred_size, const int32_t* pair, int32_t C, int32_t id_limit,
+                    int32_t max_tracks, double* assoc, double* class_assoc, int32_t* class_tubes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

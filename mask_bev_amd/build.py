@@ -39,6 +39,8 @@ FILE_FLAGS = {
     'min_area_rect.hip': ['-ffp-contract=off'],
     # K31's cell rule is K1's `(p - min) / vs`, and its histogram edges `min + k * bw` are restated in numpy: one rounding each
     'point_lift.hip': ['-ffp-contract=off'],
+    # K33a's f64 warp of a cell centre decides a cell index, K33b's f64 terms are summed one by one: one rounding per operation
+    'track.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

@@ -1,0 +1,511 @@
+// K33 — instance tracking over a sequence and tube association (the S_assoc term of LSTQ).  The rules are in
+// include/maskbev_hip.h (K33a, K33b); this file restates nothing, it implements them.
+//
+// K33a, four launches per frame, all on the caller's stream, no host synchronisation:
+//   1. clear     zeroes area_q, area_t and the (Q, P) intersection table of the workspace.
+//   2. count     one thread per cell (blocks of 256): the f64 warp of the cell centre into the previous frame's grid, one
+//                rounding per operation (-ffp-contract=off), the warped track index to the workspace; area_q and area_t in
+//                LDS tables (integer LDS atomics, one flush per block), the intersection table with global integer atomics.
+//   3. match     ONE workgroup of 1024: the candidate pairs are compacted into a list; then rounds in which every untaken
+//                row and column takes its best candidate under the exact order (IoU by i64 cross-multiplication, then q,
+//                then t) and a pair that is the best of both is taken.  Such a pair is the first of the remaining order
+//                among all pairs that share its query or its track, so the greedy walk takes it too; taking it removes
+//                what the walk would skip.  By induction the rounds end with the walk's result, and each round takes at
+//                least the first remaining pair.  Then the update of the live list with three block scans.
+//   4. paint     one thread per cell: the new state map and the optional map of global ids.
+// K33b: accumulate (grid-stride blocks with LDS tables for the two size tables where they fit), scores (one workgroup per
+// row; the terms of 256 tracks at a time in LDS, summed by one thread in ascending order) and the class sums.
+// Integer atomics only; every f64 sum in a fixed order: two runs are bit-equal.  Every index comes from the sizes: a query, a
+// stored track index, a counter or a label word that disagrees with them changes results, never addresses.
+#include "common.hpp"
+
+namespace {
+
+constexpr int kThreads = 256, kWide = 1024, kMaxTracks = 1024, kMaxClasses = 16, kLdsTable = 4096;
+constexpr int64_t kMaxCells = 1024 * 1024;
+
+struct TrackWorkspace {
+  int32_t* warped;   // (H, W): the old track index under every current cell, -1 for none
+  int32_t* area_q;   // (Q)
+  int32_t* area_t;   // (P)
+  int32_t* inter;    // (Q, P)
+  int32_t* cand;     // (Q * P): q * P + t of the candidate pairs, in no order
+  int32_t* q_new;    // (Q): the new local index of a present query, else -1
+  int32_t* t_new;    // (P): the new local index of an appended old track, else -1
+  size_t bytes;
+};
+
+TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P) {
+  MbvCarver c(ws);
+  TrackWorkspace w;
+  w.warped = c.take<int32_t>(cells);
+  w.area_q = c.take<int32_t>(Q);
+  w.area_t = c.take<int32_t>(P);
+  w.inter = c.take<int32_t>((int64_t)Q * P);
+  w.cand = c.take<int32_t>((int64_t)Q * P);
+  w.q_new = c.take<int32_t>(Q);
+  w.t_new = c.take<int32_t>(P);
+  w.bytes = c.off;
+  return w;
+}
+
+__device__ __forceinline__ int live_count(const int32_t* __restrict__ counters, int P) {
+  const int n = counters[0];
+  return n < 0 ? 0 : (n > P ? P : n);
+}
+
+__global__ void __launch_bounds__(kThreads) k_track_clear(int Q, int P, int32_t* __restrict__ area_q,
+                                                          int32_t* __restrict__ area_t, int32_t* __restrict__ inter) {
+  const int64_t stride = (int64_t)gridDim.x * kThreads, n = (int64_t)Q * P;
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  for (int64_t i = t; i < n; i += stride) inter[i] = 0;
+  for (int64_t i = t; i < Q; i += stride) area_q[i] = 0;
+  for (int64_t i = t; i < P; i += stride) area_t[i] = 0;
+}
+
+__global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restrict__ instance_map,
+                                                          const int32_t* __restrict__ state_map,
+                                                          const double* __restrict__ prev_from_cur, int H, int W, double x_lo,
+                                                          double y_lo, double voxel, int Q, int P,
+                                                          const int32_t* __restrict__ counters, int32_t* __restrict__ warped,
+                                                          int32_t* __restrict__ area_q, int32_t* __restrict__ area_t,
+                                                          int32_t* __restrict__ inter) {
+  __shared__ int32_t s_q[kMaxTracks];
+  __shared__ int32_t s_t[kMaxTracks];
+  const int n_live = live_count(counters, P);
+  for (int k = threadIdx.x; k < Q; k += kThreads) s_q[k] = 0;
+  for (int k = threadIdx.x; k < P; k += kThreads) s_t[k] = 0;
+  __syncthreads();
+  const int64_t cells = (int64_t)H * W;
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < cells) {
+    const int iy = (int)(i / W), ix = (int)(i - (int64_t)iy * W);
+    const double x = x_lo + ((double)ix + 0.5) * voxel;
+    const double y = y_lo + ((double)iy + 0.5) * voxel;
+    const double xp = (prev_from_cur[0] * x + prev_from_cur[1] * y) + prev_from_cur[2];
+    const double yp = (prev_from_cur[3] * x + prev_from_cur[4] * y) + prev_from_cur[5];
+    const double fx = floor((xp - x_lo) / voxel), fy = floor((yp - y_lo) / voxel);
+    int t = -1;
+    if (fx >= 0.0 && fx < (double)W && fy >= 0.0 && fy < (double)H) {       // NaN and inf fail a comparison
+      t = state_map[(int64_t)(int)fy * W + (int)fx];
+      if (t < 0 || t >= n_live) t = -1;
+    }
+    warped[i] = t;
+    int q = instance_map[i];
+    if (q < 0 || q >= Q) q = -1;
+    if (q >= 0) atomicAdd(&s_q[q], 1);
+    if (t >= 0) atomicAdd(&s_t[t], 1);
+    if (q >= 0 && t >= 0) atomicAdd(&inter[(int64_t)q * P + t], 1);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < Q; k += kThreads) {
+    const int32_t n = s_q[k];
+    if (n > 0) atomicAdd(&area_q[k], n);
+  }
+  for (int k = threadIdx.x; k < P; k += kThreads) {
+    const int32_t n = s_t[k];
+    if (n > 0) atomicAdd(&area_t[k], n);
+  }
+}
+
+// inclusive scan of one value per thread of a workgroup of kWide, through s_scan; every thread must call it
+__device__ __forceinline__ int32_t block_scan(int32_t mine, int32_t* s_scan) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  s_scan[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < kWide; o <<= 1) {
+    const int32_t v = t >= o ? s_scan[t - o] : 0;
+    __syncthreads();
+    s_scan[t] += v;
+    __syncthreads();
+  }
+  return s_scan[t];
+}
+
+struct MatchTables {
+  const int32_t* inter;
+  const int32_t* area_q;     // LDS
+  const int32_t* area_t;     // LDS
+  int P;
+};
+
+// whether candidate pair a (= q * P + t) comes before pair b in the matching order
+__device__ __forceinline__ bool pair_before(const MatchTables& m, int32_t a, int32_t b) {
+  const int qa = a / m.P, ta = a - qa * m.P, qb = b / m.P, tb = b - qb * m.P;
+  const int64_t ia = m.inter[a], ib = m.inter[b];
+  const int64_t ua = (int64_t)m.area_q[qa] + m.area_t[ta] - ia, ub = (int64_t)m.area_q[qb] + m.area_t[tb] - ib;
+  const int64_t lhs = ia * ub, rhs = ib * ua;                      // < 2^41: areas are at most 2^20 cells
+  if (lhs != rhs) return lhs > rhs;
+  return a < b;                                                    // q * P + t: the smaller q, then the smaller t
+}
+
+__device__ __forceinline__ void offer_best(const MatchTables& m, int32_t* slot, int32_t pair) {
+  int32_t cur = *slot;
+  while (cur < 0 || pair_before(m, pair, cur)) {
+    const int32_t seen = atomicCAS(slot, cur, pair);
+    if (seen == cur) break;
+    cur = seen;
+  }
+}
+
+__global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_iou, int max_age, int min_cells,
+                                                       const int32_t* __restrict__ g_area_q,
+                                                       const int32_t* __restrict__ g_area_t,
+                                                       const int32_t* __restrict__ inter, int32_t* __restrict__ cand,
+                                                       int32_t* __restrict__ live_id, int32_t* __restrict__ live_seen,
+                                                       int32_t* __restrict__ counters, int32_t* __restrict__ query_track,
+                                                       int32_t* __restrict__ q_new, int32_t* __restrict__ t_new) {
+  __shared__ int32_t s_area_q[kMaxTracks];
+  __shared__ int32_t s_area_t[kMaxTracks];
+  __shared__ int32_t s_best_q[kMaxTracks];                         // the round's best pair of a row
+  __shared__ int32_t s_best_t[kMaxTracks];                         // ... of a column
+  __shared__ int32_t s_q_match[kMaxTracks];                        // the track a query took, -1
+  __shared__ int32_t s_t_taken[kMaxTracks];
+  __shared__ int32_t s_id[kMaxTracks];
+  __shared__ int32_t s_seen[kMaxTracks];
+  __shared__ int32_t s_scan[kWide];
+  __shared__ int32_t s_n_cand, s_open;
+  const int t = threadIdx.x;
+  const int n_live = live_count(counters, P);
+  const int32_t next_id = counters[1], frame = counters[2], dropped = counters[3];
+  if (t < Q) {
+    s_area_q[t] = g_area_q[t];
+    s_q_match[t] = -1;
+  }
+  if (t < P) {
+    s_area_t[t] = g_area_t[t];
+    s_t_taken[t] = 0;
+    s_id[t] = t < n_live ? live_id[t] : -1;
+    s_seen[t] = t < n_live ? live_seen[t] : -1;
+  }
+  if (t == 0) s_n_cand = 0;
+  __syncthreads();
+
+  // the candidate list
+  const int64_t table = (int64_t)Q * n_live;
+  for (int64_t k = t; k < table; k += kWide) {
+    const int q = (int)(k / n_live), tr = (int)(k - (int64_t)q * n_live);
+    const int32_t pair = q * P + tr;
+    const int32_t n = inter[pair];
+    if (n > 0 && s_area_q[q] >= min_cells) {
+      const int64_t uni = (int64_t)s_area_q[q] + s_area_t[tr] - n;
+      if ((double)n / (double)uni >= min_iou) cand[atomicAdd(&s_n_cand, 1)] = pair;
+    }
+  }
+  __syncthreads();
+  const int n_cand = s_n_cand;
+  MatchTables m{inter, s_area_q, s_area_t, P};
+
+  for (int round = 0; round < kMaxTracks; ++round) {               // every round takes a pair or is the last
+    if (t < Q) s_best_q[t] = -1;
+    if (t < P) s_best_t[t] = -1;
+    if (t == 0) s_open = 0;
+    __syncthreads();
+    for (int k = t; k < n_cand; k += kWide) {
+      const int32_t pair = cand[k];
+      const int q = pair / P, tr = pair - q * P;
+      if (s_q_match[q] >= 0 || s_t_taken[tr]) continue;
+      s_open = 1;
+      offer_best(m, &s_best_q[q], pair);
+      offer_best(m, &s_best_t[tr], pair);
+    }
+    __syncthreads();
+    if (!s_open) break;                                            // uniform: read after the barrier
+    if (t < Q) {
+      const int32_t pair = s_best_q[t];
+      if (pair >= 0) {
+        const int tr = pair - t * P;
+        if (s_best_t[tr] == pair) {
+          s_q_match[t] = tr;
+          s_t_taken[tr] = 1;
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // the new live list: the present queries in ascending q, then the unmatched old tracks that are young enough
+  const bool present = t < Q && s_area_q[t] >= min_cells;
+  const int matched = present ? s_q_match[t] : -1;
+  const int32_t pos_q = block_scan(present ? 1 : 0, s_scan);
+  const int32_t n_present = s_scan[kWide - 1];
+  const int32_t born = block_scan(present && matched < 0 ? 1 : 0, s_scan);
+  const int32_t n_born = s_scan[kWide - 1];
+  const bool old = t < n_live && !s_t_taken[t] && (int64_t)frame - s_seen[t] <= (int64_t)max_age;
+  const int32_t pos_t = block_scan(old ? 1 : 0, s_scan);
+  const int32_t n_old = s_scan[kWide - 1];
+  const int32_t id_q = present ? (matched >= 0 ? s_id[matched] : next_id + born - 1) : -1;
+  const int room = P - n_present;                                  // >= 0: Q <= P
+  const int kept = n_old < room ? n_old : room;
+  const int n_new = n_present + kept;
+  // the old list lives in s_id / s_seen from here on, so every slot of the new one has exactly one writer
+  if (t >= n_new && t < P) {
+    live_id[t] = -1;
+    live_seen[t] = -1;
+  }
+  if (t < Q) {
+    query_track[t] = id_q;
+    q_new[t] = present ? pos_q - 1 : -1;
+    if (present) {
+      live_id[pos_q - 1] = id_q;
+      live_seen[pos_q - 1] = frame;
+    }
+  }
+  if (t < P) {
+    int32_t idx = -1;
+    if (old && pos_t - 1 < room) {
+      idx = n_present + pos_t - 1;
+      live_id[idx] = s_id[t];
+      live_seen[idx] = s_seen[t];
+    }
+    t_new[t] = idx;
+  }
+  if (t == 0) {
+    counters[0] = n_new;
+    counters[1] = next_id + n_born;
+    counters[2] = frame + 1;
+    counters[3] = dropped + (n_old - kept);
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) k_track_paint(const int32_t* __restrict__ instance_map, int64_t cells, int Q, int P,
+                                                          const int32_t* __restrict__ warped,
+                                                          const int32_t* __restrict__ q_new, const int32_t* __restrict__ t_new,
+                                                          const int32_t* __restrict__ query_track,
+                                                          int32_t* __restrict__ state_map, int32_t* __restrict__ track_map) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= cells) return;
+  const int q = instance_map[i];
+  int32_t idx = -1, id = -1;
+  if (q >= 0 && q < Q && q_new[q] >= 0) {
+    idx = q_new[q];
+    id = query_track[q];
+  } else {
+    const int w = warped[i];                                       // -1 or below the old n_live <= P
+    if (w >= 0 && w < P) idx = t_new[w];
+  }
+  state_map[i] = idx;
+  if (track_map) track_map[i] = id;
+}
+
+bool track_sizes_supported(int64_t H, int64_t W, int Q, int P) {
+  return H >= 0 && W >= 0 && H <= kMaxCells && W <= kMaxCells && H * W <= kMaxCells && Q >= 0 && Q <= P && P <= kMaxTracks;
+}
+
+// ---- K33b -------------------------------------------------------------------------------------------------------------
+
+// the class of a ground-truth word: -1 ignored, 0 everything else, 1 .. C-1 a thing (K32's rule)
+__device__ __forceinline__ int tube_class_of(uint32_t word, const int32_t* __restrict__ class_lut, int lut_len, int C) {
+  const int sem = (int)(word & 0xffffu);
+  if (sem >= lut_len) return -1;
+  const int c = class_lut[sem];
+  return (c < 0 || c >= C) ? -1 : c;
+}
+
+__device__ __forceinline__ void add64(int64_t* p, int64_t n) {
+  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)n);
+}
+
+__global__ void __launch_bounds__(kThreads) k_tube_accumulate(const int32_t* __restrict__ pred_track,
+                                                              const uint32_t* __restrict__ gt_word, int64_t total,
+                                                              const int32_t* __restrict__ class_lut, int lut_len, int C, int I,
+                                                              int T, int64_t* __restrict__ gt_size,
+                                                              int64_t* __restrict__ pred_size, int32_t* __restrict__ pair,
+                                                              int64_t* __restrict__ overflow) {
+  __shared__ int32_t s_gt[kLdsTable];
+  __shared__ int32_t s_pred[kLdsTable];
+  __shared__ int32_t s_over[2];
+  const int rows = (C - 1) * I;
+  const bool lds_gt = rows <= kLdsTable, lds_pred = T <= kLdsTable;   // a block adds fewer than 2^31 elements to a slot
+  if (lds_gt)
+    for (int k = threadIdx.x; k < rows; k += kThreads) s_gt[k] = 0;
+  if (lds_pred)
+    for (int k = threadIdx.x; k < T; k += kThreads) s_pred[k] = 0;
+  if (threadIdx.x < 2) s_over[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += stride) {
+    const uint32_t word = gt_word[i];
+    const int c = tube_class_of(word, class_lut, lut_len, C);
+    if (c < 0) continue;                                           // an ignored element takes part in nothing
+    int r = -1;
+    if (c >= 1) {
+      const int inst = (int)(word >> 16);
+      if (inst >= I) {
+        atomicAdd(&s_over[0], 1);
+      } else if (inst >= 1) {
+        r = (c - 1) * I + inst;
+        if (lds_gt) atomicAdd(&s_gt[r], 1);
+        else add64(&gt_size[r], 1);
+      }
+    }
+    const int p = pred_track[i];
+    if (p >= T) {
+      atomicAdd(&s_over[1], 1);
+    } else if (p >= 0) {
+      if (lds_pred) atomicAdd(&s_pred[p], 1);
+      else add64(&pred_size[p], 1);
+      if (r >= 0) atomicAdd(&pair[(int64_t)r * T + p], 1);
+    }
+  }
+  __syncthreads();
+  if (lds_gt)
+    for (int k = threadIdx.x; k < rows; k += kThreads)
+      if (s_gt[k] > 0) add64(&gt_size[k], s_gt[k]);
+  if (lds_pred)
+    for (int k = threadIdx.x; k < T; k += kThreads)
+      if (s_pred[k] > 0) add64(&pred_size[k], s_pred[k]);
+  if (threadIdx.x < 2 && s_over[threadIdx.x] > 0) add64(&overflow[threadIdx.x], s_over[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kThreads) k_tube_scores(const int64_t* __restrict__ gt_size,
+                                                          const int64_t* __restrict__ pred_size,
+                                                          const int32_t* __restrict__ pair, int T, double* __restrict__ assoc) {
+  __shared__ double s_term[kThreads];
+  __shared__ int32_t s_any;
+  const int64_t r = blockIdx.x;
+  const int64_t g = gt_size[r];
+  if (g <= 0) {                                                    // the whole block
+    if (threadIdx.x == 0) assoc[r] = 0.0;
+    return;
+  }
+  double sum = 0.0;                                                // thread 0's
+  for (int base = 0; base < T; base += kThreads) {
+    if (threadIdx.x == 0) s_any = 0;
+    __syncthreads();
+    const int p = base + threadIdx.x;
+    double term = 0.0;
+    if (p < T) {
+      const int32_t n = pair[r * T + p];
+      if (n > 0) {
+        const double tpa = (double)n;
+        const double iou = tpa / (double)(g + pred_size[p] - (int64_t)n);
+        term = tpa * iou;
+        s_any = 1;
+      }
+    }
+    s_term[threadIdx.x] = term;
+    __syncthreads();
+    if (threadIdx.x == 0 && s_any) {
+      const int lim = T - base < kThreads ? T - base : kThreads;
+      for (int k = 0; k < lim; ++k) {                              // ascending p; a term of a pair is > 0
+        const double v = s_term[k];
+        if (v > 0.0) sum = sum + v;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) assoc[r] = sum / (double)g;
+}
+
+__global__ void __launch_bounds__(MBV_WAVE) k_tube_classes(const int64_t* __restrict__ gt_size, const double* __restrict__ assoc,
+                                                           int C, int I, double* __restrict__ class_assoc,
+                                                           int32_t* __restrict__ class_tubes) {
+  const int c = threadIdx.x;
+  if (c >= C) return;
+  double sum = 0.0;
+  int32_t n = 0;
+  if (c >= 1) {
+    for (int64_t r = (int64_t)(c - 1) * I; r < (int64_t)c * I; ++r) {
+      if (gt_size[r] > 0) {
+        ++n;
+        sum = sum + assoc[r];
+      }
+    }
+  }
+  class_assoc[c] = sum;
+  class_tubes[c] = n;
+}
+
+bool tube_sizes_supported(int C, int I, int T) {
+  return C >= 1 && C <= kMaxClasses && I >= 1 && I <= 65536 && T >= 1 && T <= (1 << 20) &&
+         (int64_t)(C - 1) * I * T < 0x7FFFFFFFll;
+}
+
+}  // namespace
+
+extern "C" size_t mbv_track_frames_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
+  if (!track_sizes_supported(H, W, Q, P)) return 0;
+  return carve_track(nullptr, (int64_t)H * W, Q, P).bytes;
+}
+
+extern "C" int mbv_track_frames(const int32_t* instance_maps, const double* prev_from_cur, int32_t F, int32_t H, int32_t W,
+                                double x_lo, double y_lo, double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age,
+                                int32_t min_cells, int32_t* state_map, int32_t* live_id, int32_t* live_seen, int32_t* counters,
+                                int32_t* query_track, int32_t* track_map, void* workspace, size_t workspace_bytes,
+                                void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (F == 0) return MBV_OK;
+  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || min_cells < 1 || max_age < 0) return MBV_ERR_BAD_ARG;
+  if (!track_sizes_supported(H, W, Q, P)) return MBV_ERR_UNSUPPORTED;
+  const int64_t cells = (int64_t)H * W;
+  if (!prev_from_cur || !counters || (cells > 0 && (!instance_maps || !state_map)) || (P > 0 && (!live_id || !live_seen)) ||
+      (Q > 0 && !query_track))
+    return MBV_ERR_BAD_ARG;
+  TrackWorkspace w = carve_track(workspace, cells, Q, P);
+  if (!workspace || workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
+
+  int64_t clear_blocks = ((int64_t)Q * P + kThreads - 1) / kThreads;
+  clear_blocks = clear_blocks < 1 ? 1 : (clear_blocks > 1024 ? 1024 : clear_blocks);
+  const unsigned cell_blocks = (unsigned)((cells + kThreads - 1) / kThreads);
+  for (int f = 0; f < F; ++f) {
+    const int32_t* imap = instance_maps + (int64_t)f * cells;
+    hipLaunchKernelGGL(k_track_clear, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, (int)Q, (int)P, w.area_q,
+                       w.area_t, w.inter);
+    MBV_CHECK_LAUNCH();
+    if (cells > 0) {
+      hipLaunchKernelGGL(k_track_count, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, state_map,
+                         prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo, voxel, (int)Q, (int)P, counters, w.warped,
+                         w.area_q, w.area_t, w.inter);
+      MBV_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_track_match, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age, (int)min_cells,
+                       w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters, query_track + (int64_t)f * Q, w.q_new,
+                       w.t_new);
+    MBV_CHECK_LAUNCH();
+    if (cells > 0) {
+      hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
+                         w.q_new, w.t_new, query_track + (int64_t)f * Q, state_map,
+                         track_map ? track_map + (int64_t)f * cells : nullptr);
+      MBV_CHECK_LAUNCH();
+    }
+  }
+  return MBV_OK;
+}
+
+extern "C" int mbv_tube_accumulate(const int32_t* pred_track, const uint32_t* gt_word, int64_t total, const int32_t* class_lut,
+                                   int32_t lut_len, int32_t C, int32_t id_limit, int32_t max_tracks, int64_t* gt_size,
+                                   int64_t* pred_size, int32_t* pair, int64_t* overflow, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (total == 0) return MBV_OK;
+  if (total < 0 || lut_len < 0 || C < 1 || id_limit < 1 || max_tracks < 1) return MBV_ERR_BAD_ARG;
+  if (!tube_sizes_supported(C, id_limit, max_tracks) || total >= 0x7FFFFFFFll) return MBV_ERR_UNSUPPORTED;
+  if (!pred_track || !gt_word || (lut_len > 0 && !class_lut) || !pred_size || !overflow || (C > 1 && (!gt_size || !pair)))
+    return MBV_ERR_BAD_ARG;
+  int64_t blocks = (total + kThreads - 1) / kThreads;
+  blocks = blocks > 1024 ? 1024 : blocks;
+  hipLaunchKernelGGL(k_tube_accumulate, dim3((unsigned)blocks), dim3(kThreads), 0, stream, pred_track, gt_word, total,
+                     class_lut, (int)lut_len, (int)C, (int)id_limit, (int)max_tracks, gt_size, pred_size, pair, overflow);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_tube_scores(const int64_t* gt_size, const int64_t* pred_size, const int32_t* pair, int32_t C,
+                               int32_t id_limit, int32_t max_tracks, double* assoc, double* class_assoc, int32_t* class_tubes,
+                               void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (C < 1 || id_limit < 1 || max_tracks < 1) return MBV_ERR_BAD_ARG;
+  if (!tube_sizes_supported(C, id_limit, max_tracks)) return MBV_ERR_UNSUPPORTED;
+  if (!class_assoc || !class_tubes || !pred_size || (C > 1 && (!gt_size || !pair || !assoc))) return MBV_ERR_BAD_ARG;
+  const int rows = (C - 1) * id_limit;
+  if (rows > 0) {
+    hipLaunchKernelGGL(k_tube_scores, dim3((unsigned)rows), dim3(kThreads), 0, stream, gt_size, pred_size, pair,
+                       (int)max_tracks, assoc);
+    MBV_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_tube_classes, dim3(1), dim3(MBV_WAVE), 0, stream, gt_size, assoc, (int)C, (int)id_limit, class_assoc,
+                     class_tubes);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}

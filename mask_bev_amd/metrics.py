@@ -20,6 +20,8 @@ to ground-truth resolution, thresholds and hands dense tensors to torchmetrics. 
   ``update``; ``compute`` accumulates the whole dataset in vectorised torch and copies twelve numbers back.
 * :class:`DevicePanopticQuality` has no counterpart in the reference: PQ / SQ / RQ / IoU of the lifted point labels (K31)
   or of the BEV instance map (K21) in the SemanticKITTI panoptic protocol, per-frame counts from K32 (csrc/panoptic.hip).
+* :class:`DeviceTubeAssociation` and :func:`lstq`: the association term of LSTQ over a sequence from the tracked point ids
+  (K33, csrc/track.hip), for the thing classes the model predicts.
 """
 from __future__ import annotations
 
@@ -519,6 +521,84 @@ class DevicePanopticQuality:
             raise MaskBevHipError(f'DevicePanopticQuality: {over} of {frames} frames hold more than max_gt = {self.max_gt} '
                                   'ground-truth segments and have no numbers; raise max_gt (<= 1024)')
         return dict(panoptic_quality(stats[:, 0], stats[:, 1], stats[:, 2], iou_sum, conf), frames=frames)
+
+
+def lstq(s_assoc: float, s_cls: float) -> float:
+    """LSTQ = sqrt(S_assoc * S_cls) (Aygün et al., 4D Panoptic LiDAR Segmentation)."""
+    return float(np.sqrt(float(s_assoc) * float(s_cls)))
+
+
+class DeviceTubeAssociation:
+    """S_assoc, the association term of LSTQ, over a whole sequence, with the tables on the device (K33b,
+    ``ops.tube_accumulate`` / ``ops.tube_scores``).  A ground-truth tube is a (thing class, instance id) pair over all frames
+    fed since :meth:`reset`, a predicted tube a global track id (``Predictions.point_tracks``); a tube's score is ``(1 / |gt|)
+    * sum over the overlapping tracks of TPA * TPA / (|gt| + |track| - TPA)`` and S_assoc the mean over the tubes.
+    ``class_lut`` as in :class:`DevicePanopticQuality`; instance ids must stay below ``id_limit`` and track ids below
+    ``max_tracks`` — elements past either are counted and :meth:`compute` raises.  Feed ONE sequence, or give the tracks of
+    different sequences different ids: SemanticKITTI's instance ids are unique per sequence only.
+
+    This is LSTQ RESTRICTED TO THE THING CLASSES THE MODEL PREDICTS: with ``s_cls`` the ``iou`` of a
+    :class:`DevicePanopticQuality` over the same frames, :func:`lstq` gives ``sqrt(S_assoc * S_cls)`` of those classes, not
+    the benchmark's number over all 19.  Parity with semantic-kitti-api's 4D evaluator is not pinned (it is not installed).
+    ``update`` synchronises nothing; ``compute`` makes one host copy.  Ranks are not summed: a sequence is tracked on one rank.
+    Tables that live on the host (``tables=`` a record copied back) are scored by the same formula in numpy."""
+
+    def __init__(self, num_classes: int, class_lut, id_limit: int = 1024, max_tracks: int = 4096, tables=None):
+        self.num_classes, self.id_limit, self.max_tracks = int(num_classes), int(id_limit), int(max_tracks)
+        if not 2 <= self.num_classes <= 16:
+            raise ValueError(f'DeviceTubeAssociation: 2 <= num_classes <= 16, got {num_classes}')
+        lut = class_lut.detach().cpu().numpy() if torch.is_tensor(class_lut) else np.asarray(class_lut)
+        self._lut_host = np.ascontiguousarray(lut.reshape(-1).astype(np.int32))
+        self._lut = {}
+        self.tables = tables
+
+    def reset(self):
+        self.tables = None
+
+    def class_lut(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device not in self._lut:
+            self._lut[device] = torch.from_numpy(self._lut_host).to(device)
+        return self._lut[device]
+
+    @torch.no_grad()
+    def update(self, point_tracks: torch.Tensor, gt_words: torch.Tensor) -> None:
+        """``point_tracks`` (N) int32 global track ids (-1 = none) and ``gt_words`` (N) int32 / uint32 ``.label`` words of the
+        same elements, on the device.  Nothing is copied back."""
+        if self.tables is None:
+            self.tables = ops.TubeTables.zeros(self.num_classes, self.id_limit, self.max_tracks, point_tracks.device)
+        ops.tube_accumulate(point_tracks, gt_words, self.class_lut(point_tracks.device), self.tables)
+
+    @torch.no_grad()
+    def compute(self) -> dict:
+        """``{'s_assoc', 'tubes', 'per_class', 'overflow'}``: the mean over the ground-truth tubes of the thing classes, their
+        number, per class ``{'s_assoc', 'tubes'}`` lists of all C classes, and the two overflow counters (zeros).  Raises
+        ``MaskBevHipError`` when an overflow counter is not zero: the tables then miss elements."""
+        c = self.num_classes
+        if self.tables is None:
+            class_assoc, class_tubes, over = np.zeros(c), np.zeros(c, dtype=np.int64), np.zeros(2, dtype=np.int64)
+        elif self.tables.pair.is_cuda:
+            s = ops.tube_scores(self.tables)
+            host = torch.cat([s.class_assoc.view(torch.int64), s.class_tubes.to(torch.int64), self.tables.overflow]).cpu()
+            class_assoc = host[:c].contiguous().view(torch.float64).numpy()
+            class_tubes, over = host[c:2 * c].numpy(), host[2 * c:].numpy()
+        else:
+            gt, ps = self.tables.gt_size.numpy().astype(np.float64), self.tables.pred_size.numpy().astype(np.float64)
+            pair = self.tables.pair.numpy().astype(np.float64)
+            with np.errstate(all='ignore'):
+                terms = np.where(pair > 0, pair * (pair / (gt[:, None] + ps[None, :] - pair)), 0.0)
+                assoc = np.where(gt > 0, terms.sum(1) / np.maximum(gt, 1.0), 0.0).reshape(c - 1, self.id_limit)
+            class_assoc = np.concatenate([[0.0], assoc.sum(1)])
+            class_tubes = np.concatenate([[0], (gt > 0).reshape(c - 1, self.id_limit).sum(1)]).astype(np.int64)
+            over = self.tables.overflow.numpy()
+        if int(over[0]) or int(over[1]):
+            raise MaskBevHipError(f'DeviceTubeAssociation: {int(over[0])} elements carry an instance id >= id_limit = '
+                                  f'{self.id_limit} and {int(over[1])} a track id >= max_tracks = {self.max_tracks}; raise the limits')
+        tubes = int(class_tubes[1:].sum())
+        per_class = dict(s_assoc=[float(a) / max(int(n), 1) for a, n in zip(class_assoc, class_tubes)],
+                         tubes=[int(n) for n in class_tubes])
+        return dict(s_assoc=float(class_assoc[1:].sum()) / max(tubes, 1), tubes=tubes, per_class=per_class,
+                    overflow=[int(over[0]), int(over[1])])
 
 
 @torch.no_grad()

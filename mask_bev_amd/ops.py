@@ -23,6 +23,7 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
                    K29 pairwise overlap of packed masks + COCO per-image matching (mask mAP),
                    K30 largest 8-connected component + minimum-area rectangle of a packed mask,
                    K32 panoptic tp / fp / fn, IoU sums and confusion per frame from two id arrays (points or BEV cells)
+    ops_track      K33 the tracker step over consecutive BEV instance maps (global instance ids) and tube association (S_assoc of LSTQ)
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403
@@ -38,3 +39,4 @@ from .ops_instances import *       # noqa: F401,F403
 from .ops_rasterize import *       # noqa: F401,F403
 from .ops_augment import *         # noqa: F401,F403
 from .ops_eval import *            # noqa: F401,F403
+from .ops_track import *           # noqa: F401,F403

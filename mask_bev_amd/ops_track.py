@@ -1,0 +1,169 @@
+"""K33a — the tracker step over consecutive BEV instance maps of one sequence, and K33b — tube association, the S_assoc
+term of LSTQ (csrc/track.hip).  Behind ``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions
+are in include/maskbev_hip.h."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import _lib
+from ._lib import MaskBevHipError, check
+from .ops_core import _need_gpu, _ptr, _stream, _workspace
+
+
+@dataclass
+class TrackState:
+    """The tracker's persistent state on the device (include/maskbev_hip.h, K33a): ``state_map`` (H, W) int32 — a local
+    track index or -1; ``live_id`` / ``live_seen`` (P) int32 — the global id and the frame of the last match of every live
+    track; ``counters`` (4) int32 = n_live, next_id, frame, dropped."""
+    state_map: torch.Tensor
+    live_id: torch.Tensor
+    live_seen: torch.Tensor
+    counters: torch.Tensor
+
+    @staticmethod
+    def fresh(h: int, w: int, max_tracks: int, device) -> 'TrackState':
+        return TrackState(torch.full((int(h), int(w)), -1, dtype=torch.int32, device=device),
+                          torch.full((int(max_tracks),), -1, dtype=torch.int32, device=device),
+                          torch.full((int(max_tracks),), -1, dtype=torch.int32, device=device),
+                          torch.zeros((4,), dtype=torch.int32, device=device))
+
+
+@dataclass
+class TrackFrames:
+    """K33a's outputs for F frames: ``query_track`` (F, Q) int32 — the global id of every query, -1 when it is not present;
+    ``track_map`` (F, H, W) int32 — the global id on the cells of present queries, else -1 (None when not asked for)."""
+    query_track: torch.Tensor
+    track_map: Optional[torch.Tensor]
+
+
+@dataclass
+class TubeTables:
+    """K33b's running tables for C classes, ``id_limit`` I and ``max_tracks`` T, on the device: ``gt_size`` ((C - 1) * I)
+    int64, ``pred_size`` (T) int64, ``pair`` ((C - 1) * I, T) int32, ``overflow`` (2) int64 — elements of an instance id >= I,
+    of a track id >= T."""
+    gt_size: torch.Tensor
+    pred_size: torch.Tensor
+    pair: torch.Tensor
+    overflow: torch.Tensor
+    num_classes: int
+    id_limit: int
+    max_tracks: int
+
+    @staticmethod
+    def zeros(num_classes: int, id_limit: int, max_tracks: int, device) -> 'TubeTables':
+        c, i, t = int(num_classes), int(id_limit), int(max_tracks)
+        if not (1 <= c <= 16 and 1 <= i <= 65536 and 1 <= t <= 2 ** 20 and (c - 1) * i * t < 2 ** 31 - 1):
+            raise MaskBevHipError(f'TubeTables: num_classes {c} (1 .. 16), id_limit {i} (1 .. 65536), max_tracks {t} (1 .. 2^20) '
+                                  'or their product (< 2^31 - 1) out of range')
+        rows = (c - 1) * i
+        return TubeTables(torch.zeros((rows,), dtype=torch.int64, device=device), torch.zeros((t,), dtype=torch.int64, device=device),
+                          torch.zeros((rows, t), dtype=torch.int32, device=device), torch.zeros((2,), dtype=torch.int64, device=device),
+                          c, i, t)
+
+
+@dataclass
+class TubeScores:
+    """``assoc`` ((C - 1) * I) f64 — the association score of every ground-truth tube (0 for an empty row); ``class_assoc`` (C)
+    f64 — the sums over a class's tubes; ``class_tubes`` (C) int32 — their number."""
+    assoc: torch.Tensor
+    class_assoc: torch.Tensor
+    class_tubes: torch.Tensor
+
+
+@torch.no_grad()
+def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state: TrackState, x_lo: float, y_lo: float,
+                 voxel: float, num_queries: int, min_iou: float = 0.3, max_age: int = 2, min_cells: int = 4,
+                 track_map: bool = False) -> TrackFrames:
+    """K33a: ``instance_maps`` (F, H, W) int32 — F consecutive frames of ONE sequence, a query in [0, num_queries) or -1 per
+    cell; ``prev_from_cur`` (F, 2, 3) f64 — per frame the map of its BEV coordinates into the previous frame's; ``state`` is
+    stepped in place.  Device tensors only; no host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(instance_maps, prev_from_cur, state.state_map, state.live_id, state.live_seen, state.counters)
+    dev = instance_maps.device
+    if instance_maps.dim() != 3 or instance_maps.dtype != torch.int32:
+        raise MaskBevHipError(f'track_frames: instance_maps must be (F, H, W) int32, got {tuple(instance_maps.shape)} '
+                              f'{instance_maps.dtype}')
+    f, h, w = (int(v) for v in instance_maps.shape)
+    if tuple(prev_from_cur.shape) != (f, 2, 3) or prev_from_cur.dtype != torch.float64:
+        raise MaskBevHipError(f'track_frames: prev_from_cur must be ({f}, 2, 3) float64, got {tuple(prev_from_cur.shape)} '
+                              f'{prev_from_cur.dtype}')
+    q, p = int(num_queries), int(state.live_id.numel())
+    for name, x, shape in (('state_map', state.state_map, (h, w)), ('live_id', state.live_id, (p,)),
+                           ('live_seen', state.live_seen, (p,)), ('counters', state.counters, (4,))):
+        if tuple(x.shape) != shape or x.dtype != torch.int32 or x.device != dev or not x.is_contiguous():
+            raise MaskBevHipError(f'track_frames: state.{name} must be a contiguous {shape} int32 tensor on {dev}')
+    if prev_from_cur.device != dev:
+        raise MaskBevHipError('track_frames: tensors on different devices')
+    if not (0 <= q <= p <= 1024 and h * w <= 1024 * 1024 and int(min_cells) >= 1 and int(max_age) >= 0):
+        raise MaskBevHipError(f'track_frames: Q {q} <= P {p} <= 1024, H * W {h * w} <= 2^20, min_cells {min_cells} >= 1 or '
+                              f'max_age {max_age} >= 0 violated')
+    instance_maps, prev_from_cur = instance_maps.contiguous(), prev_from_cur.contiguous()
+    out = TrackFrames(torch.empty((f, q), dtype=torch.int32, device=dev),
+                      torch.empty((f, h, w), dtype=torch.int32, device=dev) if track_map else None)
+    if f == 0:
+        return out
+    ws = _workspace(lib.mbv_track_frames_workspace_bytes(h, w, q, p), dev)
+    check(lib.mbv_track_frames(_ptr(instance_maps), _ptr(prev_from_cur), f, h, w, float(x_lo), float(y_lo), float(voxel), q, p,
+                               float(min_iou), int(max_age), int(min_cells), _ptr(state.state_map), _ptr(state.live_id),
+                               _ptr(state.live_seen), _ptr(state.counters), _ptr(out.query_track), _ptr(out.track_map),
+                               _ptr(ws), ws.numel(), _stream()), 'mbv_track_frames')
+    return out
+
+
+@torch.no_grad()
+def tube_accumulate(pred_track: torch.Tensor, gt_words: torch.Tensor, class_lut: torch.Tensor, tables: TubeTables) -> TubeTables:
+    """K33b: adds the elements ``pred_track`` (N) int32 (the global track id, -1 = none) / ``gt_words`` (N) int32 / uint32
+    (``.label`` layout) to ``tables``; ``class_lut`` (L) int32 as in ``panoptic_frames``.  No host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(pred_track, gt_words, class_lut, tables.gt_size, tables.pred_size, tables.pair, tables.overflow)
+    dev = pred_track.device
+    if pred_track.dim() != 1 or pred_track.dtype != torch.int32:
+        raise MaskBevHipError(f'tube_accumulate: pred_track must be (N) int32, got {tuple(pred_track.shape)} {pred_track.dtype}')
+    if gt_words.dtype == getattr(torch, 'uint32', None):
+        gt_words = gt_words.view(torch.int32)
+    if gt_words.dtype != torch.int32 or tuple(gt_words.shape) != tuple(pred_track.shape):
+        raise MaskBevHipError(f'tube_accumulate: gt_words must be ({pred_track.numel()}) int32 / uint32, got '
+                              f'{tuple(gt_words.shape)} {gt_words.dtype}')
+    if class_lut.dim() != 1 or class_lut.dtype != torch.int32:
+        raise MaskBevHipError('tube_accumulate: class_lut must be a 1-d int32 table')
+    _check_tables('tube_accumulate', tables, dev)
+    if gt_words.device != dev or class_lut.device != dev:
+        raise MaskBevHipError('tube_accumulate: tensors on different devices')
+    n = pred_track.numel()
+    if n >= 2 ** 31 - 1:
+        raise MaskBevHipError(f'tube_accumulate: {n} elements out of range')
+    pred_track, gt_words, class_lut = pred_track.contiguous(), gt_words.contiguous(), class_lut.contiguous()
+    check(lib.mbv_tube_accumulate(_ptr(pred_track), _ptr(gt_words), n, _ptr(class_lut), class_lut.numel(), tables.num_classes,
+                                  tables.id_limit, tables.max_tracks, _ptr(tables.gt_size), _ptr(tables.pred_size),
+                                  _ptr(tables.pair), _ptr(tables.overflow), _stream()), 'mbv_tube_accumulate')
+    return tables
+
+
+def _check_tables(what: str, tables: TubeTables, dev) -> None:
+    rows, t = (tables.num_classes - 1) * tables.id_limit, tables.max_tracks
+    for name, x, shape, dt in (('gt_size', tables.gt_size, (rows,), torch.int64), ('pred_size', tables.pred_size, (t,), torch.int64),
+                               ('pair', tables.pair, (rows, t), torch.int32), ('overflow', tables.overflow, (2,), torch.int64)):
+        if tuple(x.shape) != shape or x.dtype != dt or x.device != dev or not x.is_contiguous():
+            raise MaskBevHipError(f'{what}: tables.{name} must be a contiguous {shape} {dt} tensor on {dev}')
+
+
+@torch.no_grad()
+def tube_scores(tables: TubeTables) -> TubeScores:
+    """K33b: the association score of every ground-truth tube of ``tables`` and the class sums.  No host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(tables.gt_size, tables.pred_size, tables.pair, tables.overflow)
+    dev = tables.pred_size.device
+    _check_tables('tube_scores', tables, dev)
+    c, rows = tables.num_classes, (tables.num_classes - 1) * tables.id_limit
+    out = TubeScores(torch.empty((rows,), dtype=torch.float64, device=dev), torch.empty((c,), dtype=torch.float64, device=dev),
+                     torch.empty((c,), dtype=torch.int32, device=dev))
+    check(lib.mbv_tube_scores(_ptr(tables.gt_size), _ptr(tables.pred_size), _ptr(tables.pair), c, tables.id_limit,
+                              tables.max_tracks, _ptr(out.assoc), _ptr(out.class_assoc), _ptr(out.class_tubes), _stream()),
+          'mbv_tube_scores')
+    return out
+
+
+__all__ = ['track_frames', 'tube_accumulate', 'tube_scores', 'TrackState', 'TrackFrames', 'TubeTables', 'TubeScores']

@@ -151,6 +151,30 @@ class Predictions:
         b, cells = m.shape[0], m.shape[1] * m.shape[2]
         return metric.update(m.reshape(-1).contiguous(), self.query_classes(), words, [cells] * b)
 
+    def track(self, tracker, poses=None, prev_from_cur=None) -> torch.Tensor:
+        """Steps a :class:`~mask_bev_amd.tracking.InstanceTracker` through the B frames of these predictions — CONSECUTIVE
+        scans of one sequence, in order — and returns ``query_track`` (B, Q) int32: the global track id of every query, -1
+        where the query owns too few cells.  ``poses`` (B, 4, 4) f64 sensor poses, or ``prev_from_cur`` (B, 2, 3) f64.  K33a;
+        no host synchronisation."""
+        if self.instance_map is None:
+            raise MaskBevHipError('track: these predictions were made without an instance map')
+        return tracker.update(self.instance_map, poses=poses, prev_from_cur=prev_from_cur)
+
+    def point_tracks(self, lifted: 'ops.PointInstances', query_track: torch.Tensor) -> torch.Tensor:
+        """The global track id of every point: ``query_track`` (B, Q) from :meth:`track`, gathered by K31's ``point_query``
+        (``lifted``: :meth:`lift` of the same scans); -1 stays -1.  (N) int32 in the scans' concatenated point order.  No host
+        synchronisation."""
+        b, q = query_track.shape
+        pq = lifted.point_query.long()
+        if b != len(lifted.lengths):
+            raise MaskBevHipError(f'point_tracks: query_track of {b} frames for {len(lifted.lengths)} lifted scans')
+        if q == 0 or pq.numel() == 0:
+            return torch.full_like(lifted.point_query, -1)
+        # the scan of a point: how many scans end at or before it
+        scan = torch.bucketize(torch.arange(pq.numel(), device=pq.device), lifted.scan_offsets[1:].long(), right=True)
+        ids = query_track.reshape(-1)[scan.clamp_(max=b - 1) * q + pq.clamp(0, q - 1)]
+        return torch.where((pq >= 0) & (pq < q), ids, torch.full_like(ids, -1)).to(torch.int32)
+
     def boxes(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> dict:
         """Oriented BEV boxes of the kept queries, in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a
         rasteriser (``KittiRasterizer``) in place of ``x_range``.  ``method='moment'``: K25, ``ops.fit_boxes``, the
@@ -249,15 +273,25 @@ def voxel_geometry(module_or_geometry):
     return g
 
 
-def write_semantic_kitti_labels(path, point_query, semantic_id: int = 10) -> None:
+def write_semantic_kitti_labels(path, point_query, semantic_id: int = 10, instance_ids=None) -> None:
     """A SemanticKITTI ``.label`` file of one scan from its per-point queries (``PointInstances.per_scan()``; a tensor
     anywhere, or an array): ``uint32`` per point, the instance id ``query + 1`` in the upper 16 bits and ``semantic_id``
-    (default 10, car) in the lower 16; 0 for an unlabelled point (query -1).  ``batch.read_semantic_kitti_label`` reads it
+    (default 10, car) in the lower 16; 0 for an unlabelled point (query -1).  With ``instance_ids`` — per point the global
+    track id of ``Predictions.point_tracks``, -1 = unlabelled — the instance id is ``id + 1`` instead, the same for an object
+    in every scan of a sequence; an id above 65534 raises ``ValueError``.  ``batch.read_semantic_kitti_label`` reads the file
     back as (semantic, instance).  Copies a device tensor to the host."""
     q = point_query.detach().cpu().numpy() if torch.is_tensor(point_query) else np.asarray(point_query)
     q = q.astype(np.int64).reshape(-1)
     if not 0 <= int(semantic_id) <= 0xffff:
         raise ValueError(f'write_semantic_kitti_labels: semantic_id {semantic_id} outside 16 bits')
+    if instance_ids is not None:
+        ids = instance_ids.detach().cpu().numpy() if torch.is_tensor(instance_ids) else np.asarray(instance_ids)
+        ids = ids.astype(np.int64).reshape(-1)
+        if ids.shape != q.shape:
+            raise ValueError(f'write_semantic_kitti_labels: {ids.size} instance ids for {q.size} points')
+        if ids.size and (ids.min() < -1 or ids.max() > 0xfffe):
+            raise ValueError('write_semantic_kitti_labels: instance ids must lie in -1 .. 65534 (the instance id has 16 bits)')
+        q = ids
     if q.size and (q.min() < -1 or q.max() > 0xfffe):
         raise ValueError('write_semantic_kitti_labels: queries must lie in -1 .. 65534 (the instance id has 16 bits)')
     out = np.where(q >= 0, ((q + 1) << 16) | int(semantic_id), 0).astype('<u4')

@@ -1,0 +1,113 @@
+"""Instance tracking over a sequence (K33a, csrc/track.hip): one stable global id per object from the per-frame BEV
+instance maps of ``MaskBevModule.predict``, after ego-motion compensation with the sequence's poses.
+
+There is no motion model and there are no appearance features: an object is matched to the track whose footprint, warped
+into the current frame by the ego motion, it overlaps best (greedy, exact IoU order).  A parked car keeps its id; a moving
+car keeps it only while its footprints of consecutive frames overlap.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import MaskBevHipError
+
+_IDENTITY = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]], dtype=np.float64)
+
+
+def prev_from_cur_2d(pose_prev, pose_cur) -> np.ndarray:
+    """The (2, 3) f64 map of the current frame's BEV coordinates into the previous frame's, from the two 4 x 4 f64 sensor
+    poses (sensor → world): rows 0 and 1, columns 0, 1 and 3 of ``inv(pose_prev) @ pose_cur``.  Roll, pitch and z are
+    dropped: the map is the planar part of the relative motion, exact for a vehicle that only yaws and moves in its plane."""
+    rel = np.linalg.inv(np.asarray(pose_prev, dtype=np.float64)) @ np.asarray(pose_cur, dtype=np.float64)
+    return np.ascontiguousarray(rel[:2][:, [0, 1, 3]])
+
+
+def velodyne_poses(poses, calib) -> np.ndarray:
+    """SemanticKITTI's ``poses.txt`` is in the left camera's frame: ``inv(Tr) @ pose @ Tr`` per scan gives the (N, 4, 4) f64
+    poses of the LiDAR.  ``poses`` from ``batch.read_poses``; ``calib`` from ``batch.read_calib`` (its ``velo_to_cam``) or the
+    4 x 4 ``Tr`` itself."""
+    tr = np.asarray(calib['velo_to_cam'] if isinstance(calib, dict) else calib, dtype=np.float64)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    inv = np.linalg.inv(tr)
+    return np.stack([inv @ p @ tr for p in poses]) if len(poses) else np.zeros((0, 4, 4))
+
+
+class InstanceTracker:
+    """The tracker of one sequence.  ``x_range``, ``y_range``, ``voxel_size`` describe the BEV grid of the instance maps
+    ((ny, nx) cells, cell (iy, ix) centred at ``x_range[0] + (ix + 0.5) * voxel_size``, ``y_range[0] + (iy + 0.5) *
+    voxel_size``); ``num_queries`` Q <= ``max_tracks`` P <= 1024.  A query with fewer than ``min_cells`` cells is left out; a
+    pair needs an IoU of at least ``min_iou``; a track unmatched for more than ``max_age`` frames is forgotten.  The state
+    lives on the device; :meth:`update` synchronises nothing and :meth:`counters` is the one host copy."""
+
+    def __init__(self, x_range, y_range, voxel_size: float, num_queries: int, max_tracks: int = 256, min_iou: float = 0.3,
+                 max_age: int = 2, min_cells: int = 4, device='cuda'):
+        self.x_lo, self.y_lo, self.voxel = float(x_range[0]), float(y_range[0]), float(voxel_size)
+        self.w = int((x_range[1] - x_range[0]) / voxel_size)
+        self.h = int((y_range[1] - y_range[0]) / voxel_size)
+        self.num_queries, self.max_tracks = int(num_queries), int(max_tracks)
+        self.min_iou, self.max_age, self.min_cells = float(min_iou), int(max_age), int(min_cells)
+        if not 0 <= self.num_queries <= self.max_tracks <= 1024:
+            raise ValueError(f'InstanceTracker: num_queries {num_queries} <= max_tracks {max_tracks} <= 1024 expected')
+        if self.min_cells < 1 or self.max_age < 0 or self.h * self.w > 1024 * 1024:
+            raise ValueError('InstanceTracker: min_cells >= 1, max_age >= 0 and at most 2^20 cells expected')
+        self.device = torch.device(device)
+        self.reset()
+
+    def reset(self) -> None:
+        """A fresh sequence: no live track, ids from 0, and the next frame takes the identity transform."""
+        self.state = ops.TrackState.fresh(self.h, self.w, self.max_tracks, self.device)
+        self._last_pose: Optional[np.ndarray] = None
+        self._started = False
+
+    def _transforms(self, b: int, poses, prev_from_cur) -> torch.Tensor:
+        if prev_from_cur is not None:
+            if torch.is_tensor(prev_from_cur):
+                m = prev_from_cur.to(self.device, torch.float64).reshape(b, 2, 3)
+            else:
+                m = torch.from_numpy(np.ascontiguousarray(np.asarray(prev_from_cur, dtype=np.float64).reshape(b, 2, 3))).to(self.device)
+            if not self._started:                          # the first frame after reset(): nothing to warp
+                m = m.clone()
+                m[0] = torch.from_numpy(_IDENTITY).to(self.device)
+            return m
+        out = np.empty((b, 2, 3), dtype=np.float64)
+        if poses is None:
+            out[:] = _IDENTITY                             # a standing sensor
+        else:
+            poses = np.asarray(poses, dtype=np.float64).reshape(b, 4, 4)
+            last = self._last_pose
+            for k in range(b):
+                out[k] = _IDENTITY if last is None else prev_from_cur_2d(last, poses[k])
+                last = poses[k]
+            self._last_pose = last
+        return torch.from_numpy(out).to(self.device, non_blocking=True)
+
+    @torch.no_grad()
+    def update(self, pred_or_instance_maps, poses=None, prev_from_cur=None, track_map: bool = False):
+        """``pred_or_instance_maps``: a ``Predictions`` or its (B, ny, nx) int32 ``instance_map`` — B CONSECUTIVE frames of
+        the sequence.  ``poses`` (B, 4, 4) f64 sensor poses on the host (the last pose is remembered between calls), or
+        ``prev_from_cur`` (B, 2, 3) f64 on the host or the device; with neither, the sensor stands still.  Returns
+        ``query_track`` (B, Q) int32 on the device — the global id of every query, -1 where it is not present — or, with
+        ``track_map=True``, the ``ops.TrackFrames`` record that also holds the (B, ny, nx) map of global ids."""
+        maps = getattr(pred_or_instance_maps, 'instance_map', pred_or_instance_maps)
+        if maps is None:
+            raise MaskBevHipError('InstanceTracker.update: these predictions were made without an instance map')
+        if maps.dim() != 3 or tuple(maps.shape[1:]) != (self.h, self.w):
+            raise MaskBevHipError(f'InstanceTracker.update: (B, {self.h}, {self.w}) instance maps expected, got {tuple(maps.shape)}')
+        m = self._transforms(int(maps.shape[0]), poses, prev_from_cur)
+        out = ops.track_frames(maps, m, self.state, self.x_lo, self.y_lo, self.voxel, self.num_queries, self.min_iou,
+                               self.max_age, self.min_cells, track_map=track_map)
+        self._started = self._started or maps.shape[0] > 0
+        return out if track_map else out.query_track
+
+    def counters(self) -> dict:
+        """The one host copy: ``{'live', 'tracks', 'frames', 'dropped'}`` — the live tracks, the ids given out so far, the
+        frames seen since :meth:`reset` and the tracks dropped because ``max_tracks`` were live."""
+        n_live, next_id, frame, dropped = (int(v) for v in self.state.counters.cpu())
+        return dict(live=n_live, tracks=next_id, frames=frame, dropped=dropped)
+
+
+__all__ = ['InstanceTracker', 'prev_from_cur_2d', 'velodyne_poses']

@@ -31,7 +31,11 @@ frames); ``rasterize.WaymoRasterizer`` with ``batch.BoxCollate`` makes its batch
 ``--write-labels DIR`` writes the per-point instance labels of every validated scan (K31) to
 ``DIR/sequences/SS/predictions/NNNNNN.label``; when ``sequences/SS/labels/NNNNNN.label`` lies next to every validated scan
 it also prints ``point PQ .. SQ .. RQ .. IoU .. (car; tp .. fp .. fn ..)``, the panoptic quality of those lifted labels (K32;
-``panoptic_min_points``, ``panoptic_things``, ``panoptic_ignore``).
+``panoptic_min_points``, ``panoptic_things``, ``panoptic_ignore``).  ``track_instances: true`` adds a pass on rank 0 over the
+validation sequences in scan order (K33; needs ``sequences/SS/poses.txt`` and ``calib.txt``, says so in one line and skips
+without them): one global instance id per object, written by ``--write-labels`` in place of the query index, and with label
+files ``point LSTQ .. S_assoc .. S_cls .. (tubes .., tracks .., dropped ..)`` (``track_min_iou``, ``track_max_age``,
+``track_min_cells``, ``track_max_tracks``).
 """
 from __future__ import annotations
 
@@ -325,6 +329,95 @@ def format_point_panoptic(result, things=((10,),)):
             f'({what}; tp {sum(pc["tp"][1:])} fp {sum(pc["fp"][1:])} fn {sum(pc["fn"][1:])})')
 
 
+def tracking_settings(config):
+    """``track_min_iou`` (0.3), ``track_max_age`` (2), ``track_min_cells`` (4), ``track_max_tracks`` (256): the arguments of
+    :class:`mask_bev_amd.tracking.InstanceTracker`."""
+    return dict(min_iou=float(config.get('track_min_iou', 0.3)), max_age=int(config.get('track_max_age', 2)),
+                min_cells=int(config.get('track_min_cells', 4)), max_tracks=int(config.get('track_max_tracks', 256)))
+
+
+def sequence_tracking(model, config, device, root, sequences, out_dir=None, score_threshold=0.0, semantic_id=10):
+    """``track_instances: true``: one pass over the scans of ``sequences`` in scan order, on ONE rank — predict, the tracker
+    step on the BEV instance maps (K33a; the tracker is reset at every sequence change, the ego motion comes from
+    ``poses.txt`` and ``calib.txt`` of the sequence), the lift to the points (K31) and the per-point track ids.  With
+    ``labels/NNNNNN.label`` next to every scan the tube association (K33b) per sequence and the panoptic IoU (K32) over the
+    same frames; with ``out_dir`` the ``.label`` files carry the track id + 1 as the instance id.  Returns ``None`` — after
+    one line that says why — when a sequence lacks ``poses.txt`` or ``calib.txt``, else ``{'tracks', 'dropped', 'frames',
+    'written'}`` plus, with labels, ``{'lstq', 's_assoc', 's_cls', 'tubes'}``.  Not pinned: parity with semantic-kitti-api's
+    4D evaluator (not installed), and any LSTQ on real SemanticKITTI (none has been measured)."""
+    import numpy as np
+    from mask_bev_amd import batch as B
+    from mask_bev_amd.metrics import (DevicePanopticQuality, DeviceTubeAssociation, lstq, panoptic_quality,
+                                      semantic_kitti_class_lut)
+    from mask_bev_amd.predict import write_semantic_kitti_labels
+    from mask_bev_amd.tracking import InstanceTracker, velodyne_poses
+    files = SemanticKittiCacheBatches(dict(config, shuffle_train=False, batch_size=1), device, 0, 1, root, sequences).files
+    by_seq = {}
+    for f, _ in files:
+        by_seq.setdefault(f.parent.parent, []).append(f)
+    missing = [d for d in by_seq if not ((d / 'poses.txt').exists() and (d / 'calib.txt').exists())]
+    if missing:
+        print(f'track_instances: skipped, poses.txt or calib.txt is missing under {missing[0]}', flush=True)
+        return None
+    have_labels = all(semantic_kitti_label_path(f).exists() for f, _ in files)
+    min_points, things, ignore = panoptic_settings(config)
+    lut = semantic_kitti_class_lut(things, ignore)
+    settings = tracking_settings(config)
+    tracker = InstanceTracker(config['x_range'], config['y_range'], config['voxel_size'], int(config['num_queries']),
+                              device=device, **settings)
+    tubes = DeviceTubeAssociation(len(things) + 1, lut, id_limit=int(config.get('track_id_limit', 1024)),
+                                  max_tracks=int(config.get('track_tube_tracks', 4096)))
+    quality = DevicePanopticQuality(len(things) + 1, lut, min_points=min_points, max_gt=int(config.get('panoptic_max_gt', 256)))
+    bsz = max(1, int(config.get('batch_size', 1)))
+    out = dict(tracks=0, dropped=0, frames=0, written=[])
+    assoc_sum, n_tubes = 0.0, 0
+    for seq_dir, scans_of in by_seq.items():
+        poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
+        tracker.reset()
+        tubes.reset()
+        for start in range(0, len(scans_of), bsz):
+            part = scans_of[start:start + bsz]
+            scans = [torch.from_numpy(B.read_velodyne_bin(f)).to(device) for f in part]
+            pred = model.predict(scans, score_threshold)
+            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]])
+            lifted = pred.lift(scans, model)
+            ids = pred.point_tracks(lifted, query_track)
+            if have_labels:
+                words = [torch.from_numpy(np.fromfile(str(semantic_kitti_label_path(f)), dtype='<u4').view(np.int32)).to(device)
+                         for f in part]
+                tubes.update(ids, words[0] if len(words) == 1 else torch.cat(words))
+                pred.panoptic_points(lifted, words, quality)
+            if out_dir is not None:
+                for f, labels, tracks in zip(part, lifted.per_scan(), torch.split(ids, list(lifted.lengths))):
+                    d = pathlib.Path(out_dir) / 'sequences' / seq_dir.name / 'predictions'
+                    d.mkdir(parents=True, exist_ok=True)
+                    write_semantic_kitti_labels(d / (f.stem + '.label'), labels, semantic_id, instance_ids=tracks)
+                    out['written'].append(d / (f.stem + '.label'))
+        counts = tracker.counters()
+        out['tracks'] += counts['tracks']
+        out['dropped'] += counts['dropped']
+        out['frames'] += counts['frames']
+        if have_labels:
+            res = tubes.compute()                  # per sequence: SemanticKITTI's instance ids are unique inside one only
+            assoc_sum += res['s_assoc'] * res['tubes']
+            n_tubes += res['tubes']
+    if have_labels:
+        s_assoc, s_cls = assoc_sum / max(n_tubes, 1), 0.0
+        if quality.state is not None:              # this rank's sums alone: compute() would wait for the other ranks
+            stats, iou_sum, conf, over = (x.cpu().numpy() for x in quality.state)
+            if int(over[0]) > 0:
+                raise RuntimeError(f'track_instances: {int(over[0])} scans hold more than panoptic_max_gt ground-truth segments')
+            s_cls = panoptic_quality(stats[:, 0], stats[:, 1], stats[:, 2], iou_sum, conf)['iou']
+        out.update(lstq=lstq(s_assoc, s_cls), s_assoc=s_assoc, s_cls=s_cls, tubes=n_tubes)
+    return out
+
+
+def format_point_lstq(result):
+    """The ``point LSTQ`` line of ``--test`` from :func:`sequence_tracking`."""
+    return (f'point LSTQ {result["lstq"]:.4f} S_assoc {result["s_assoc"]:.4f} S_cls {result["s_cls"]:.4f} '
+            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]})')
+
+
 def object_bank_path(config, root):
     """``object_bank:``, else ``samples.npz`` under the ``dataset_root`` of the list's ``object_sample`` entry, else under ``root``."""
     from mask_bev_amd.object_augment import ObjectBank
@@ -583,7 +676,22 @@ def main(argv=None):
                 result = metric.compute()
                 if rank == 0:
                     print(format_point_panoptic(result, panoptic_settings(config)[1]), flush=True)
-        if args.write_labels and dataset_name == 'semantic-kitti' and val is not None:
+        tracked = None
+        track = dataset_name == 'semantic-kitti' and val is not None and bool(config.get('track_instances', False))
+        if track and rank == 0:
+            # global instance ids over the validation sequences (K33), LSTQ of the predicted thing classes when labels exist
+            tracked = sequence_tracking(model, config, device, args.data_root, config.get('val_sequences', [8]),
+                                        out_dir=args.write_labels)
+            if tracked is not None and 'lstq' in tracked:
+                print(format_point_lstq(tracked), flush=True)
+            if tracked is not None and args.write_labels:
+                print(f'wrote {len(tracked["written"])} label files with track ids under {args.write_labels}', flush=True)
+        if track and world > 1 and args.write_labels:
+            flag = torch.tensor([int(tracked is not None)], device=device)
+            dist.broadcast(flag, 0)                    # rank 0 wrote every scan with its track id, or nobody did
+            if int(flag) and tracked is None:
+                tracked = {}
+        if args.write_labels and dataset_name == 'semantic-kitti' and val is not None and tracked is None:
             paths = write_point_labels(model, config, device, val.files, args.write_labels)     # every rank: its own scans
             print(f'wrote {len(paths)} label files under {args.write_labels}', flush=True)
 
