@@ -1,0 +1,185 @@
+"""What ``--test`` runs after the validation loss, one pass over the scans per feature: KITTI BEV / 3D AP (K25-K27, K30, K31),
+per-point labels (K31), their panoptic quality (K32), tracking with LSTQ (K33); the settings and printed lines of each."""
+import pathlib
+
+import numpy as np
+import torch
+
+from . import batch as B
+from .datasets import KittiFrames, semantic_kitti_files
+from .kitti_eval import eval_kitti
+from .metrics import DevicePanopticQuality, DeviceTubeAssociation, lstq, semantic_kitti_class_lut
+from .predict import BOX_METHODS, write_semantic_kitti_labels
+from .tracking import InstanceTracker, velodyne_poses
+
+
+def predictions(model, scan_paths, bsz, device, score_threshold=0.0):
+    """``(paths, scans, pred)`` per batch of ``bsz`` of ``scan_paths``: the scans on the device and ``model.predict`` of them."""
+    bsz = max(1, int(bsz))
+    for start in range(0, len(scan_paths), bsz):
+        part = scan_paths[start:start + bsz]
+        scans = [torch.from_numpy(B.read_velodyne_bin(f)).to(device) for f in part]
+        yield part, scans, model.predict(scans, score_threshold)
+
+
+def semantic_kitti_label_path(scan_path):
+    """``sequences/SS/velodyne/NNNNNN.bin`` → ``sequences/SS/labels/NNNNNN.label``, the ground truth next to a scan."""
+    scan_path = pathlib.Path(scan_path)
+    return scan_path.parent.parent / 'labels' / (scan_path.stem + '.label')
+
+
+def read_label_words(path, device):
+    """The ``uint32`` words of a ``.label`` file as an int32 tensor on the device, as K32 and K33 take them."""
+    return torch.from_numpy(np.fromfile(str(path), dtype='<u4').view(np.int32)).to(device)
+
+
+def prediction_label_path(out_dir, scan_path):
+    """``sequences/SS/velodyne/NNNNNN.bin`` → ``<out_dir>/sequences/SS/predictions/NNNNNN.label``; creates the folder."""
+    scan_path = pathlib.Path(scan_path)
+    d = pathlib.Path(out_dir) / 'sequences' / scan_path.parent.parent.name / 'predictions'
+    d.mkdir(parents=True, exist_ok=True)
+    return d / (scan_path.stem + '.label')
+
+
+def kitti_bev_evaluation(model, config, device, root, split='val', score_threshold=0.0, box_method=None):
+    """Car BEV AP (easy / moderate / hard at overlaps 0.7 and 0.5) of ``model`` on every frame of ``<root>/<split>.txt``:
+    ``model.predict`` per batch, an oriented box per kept mask (``Predictions.kitti_predictions``), then the KITTI protocol on
+    the device (K26, K27; ``kitti_eval.eval_kitti``).  ``box_method`` (default: the configuration's ``kitti_box_method``, else
+    ``moment``): ``moment`` — K25's moment-axis box of all set cells; ``min_area_rect`` — the minimum-area rectangle of the
+    mask's largest component (K30), the reference's recipe.  All labels of a frame take part, unfiltered: the protocol decides
+    what counts at which difficulty.  With ``kitti_3d: true`` every box gets the z-extent of the points inside its mask (K31;
+    ``kitti_3d_extent: [q_lo, q_hi]``: histogram quantiles instead of the extremes) and a ``3d   AP:`` line follows every
+    ``bev  AP:`` line (K26b).  Returns the result (a string with ``.metrics``)."""
+    method = box_method if box_method is not None else config.get('kitti_box_method', 'moment')
+    if method not in BOX_METHODS:
+        raise ValueError(f'kitti_box_method must be one of {BOX_METHODS}, got {method!r}')
+    with_3d = bool(config.get('kitti_3d', False))
+    extent = tuple(config['kitti_3d_extent']) if config.get('kitti_3d_extent') else 'minmax'
+    tree = KittiFrames(root, split)
+    labels, scan_paths, boxes = [tree.labels(f) for f in tree.frames], [tree.scan(f) for f in tree.frames], []
+    for _, scans, pred in predictions(model, scan_paths, config.get('batch_size', 1), device, score_threshold):
+        lift = dict(scans=scans, module=model, extent=extent) if with_3d else {}
+        boxes += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'], method=method, **lift)
+    return eval_kitti(labels, boxes, device=device)
+
+
+def write_point_labels(model, config, device, files, out_dir, score_threshold=0.0, semantic_id=10):
+    """Per-point instance labels of every scan of ``files`` — the (``.bin``, cache) pairs of a ``SemanticKittiCacheBatches``:
+    ``model.predict`` per batch, the instance map lifted to the points (K31), one :func:`prediction_label_path` file per scan
+    (``uint32``: query + 1 in the upper 16 bits, ``semantic_id`` in the lower, 0 = unlabelled).  Returns the paths written."""
+    written = []
+    for part, scans, pred in predictions(model, [f for f, _ in files], config.get('batch_size', 1), device, score_threshold):
+        for f, labels in zip(part, pred.lift(scans, model).per_scan()):
+            written.append(prediction_label_path(out_dir, f))
+            write_semantic_kitti_labels(written[-1], labels, semantic_id)
+    return written
+
+
+def panoptic_settings(config):
+    """The configuration's ``panoptic_min_points`` (default 50), ``panoptic_things`` (default [[10]]: raw label 10, car, is
+    thing class 1; one list of raw semantic ids per thing class) and ``panoptic_ignore`` (default [0, 1, 252])."""
+    things = config.get('panoptic_things', [[10]])
+    things = tuple(tuple(int(i) for i in (t if isinstance(t, (list, tuple)) else [t])) for t in things)
+    ignore = tuple(int(i) for i in config.get('panoptic_ignore', [0, 1, 252]))
+    return int(config.get('panoptic_min_points', 50)), things, ignore
+
+
+def panoptic_metric(config):
+    """The K32 metric of :func:`panoptic_settings` and ``panoptic_max_gt`` (default 256: the segments a scan may hold)."""
+    min_points, things, ignore = panoptic_settings(config)
+    return DevicePanopticQuality(len(things) + 1, semantic_kitti_class_lut(things, ignore), min_points=min_points,
+                                 max_gt=int(config.get('panoptic_max_gt', 256)))
+
+
+def point_panoptic_evaluation(model, config, device, files, score_threshold=0.0):
+    """Panoptic quality of the lifted point labels over ``files`` (as in :func:`write_point_labels`) against the ground truth
+    next to the scans: ``model.predict`` per batch, the lift to the points (K31), the per-frame counts on the device (K32).  Returns
+    the metric (``compute()`` sums the ranks: call it on every rank), or ``None`` when a label file is missing."""
+    scans_of = [f for f, _ in files]
+    if not scans_of or not all(semantic_kitti_label_path(f).exists() for f in scans_of):
+        return None
+    metric = panoptic_metric(config)
+    for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
+        words = [read_label_words(semantic_kitti_label_path(f), device) for f in part]
+        pred.panoptic_points(pred.lift(scans, model), words, metric)
+    return metric
+
+
+def format_point_panoptic(result, things=((10,),)):
+    """The ``point PQ`` line of ``--test`` from ``DevicePanopticQuality.compute()``."""
+    pc = result['per_class']
+    what = 'car' if tuple(tuple(t) for t in things) == ((10,),) else f'{len(things)} thing classes'
+    return (f'point PQ {result["pq"]:.4f} SQ {result["sq"]:.4f} RQ {result["rq"]:.4f} IoU {result["iou"]:.4f} '
+            f'({what}; tp {sum(pc["tp"][1:])} fp {sum(pc["fp"][1:])} fn {sum(pc["fn"][1:])})')
+
+
+def tracking_settings(config):
+    """``track_min_iou`` (0.3), ``track_max_age`` (2), ``track_min_cells`` (4), ``track_max_tracks`` (256): ``InstanceTracker``'s."""
+    return dict(min_iou=float(config.get('track_min_iou', 0.3)), max_age=int(config.get('track_max_age', 2)),
+                min_cells=int(config.get('track_min_cells', 4)), max_tracks=int(config.get('track_max_tracks', 256)))
+
+
+def sequence_tracking(model, config, device, root, sequences, out_dir=None, score_threshold=0.0, semantic_id=10):
+    """``track_instances: true``: one pass over the scans of ``sequences`` in scan order, on ONE rank — predict, the tracker step
+    on the BEV instance maps (K33a; reset at every sequence change, the ego motion from the sequence's ``poses.txt`` and
+    ``calib.txt``), the lift to the points (K31) and the per-point track ids.  With ``labels/NNNNNN.label`` next to every scan the
+    tube association (K33b) per sequence and the panoptic IoU (K32) of this rank alone over the same frames; with ``out_dir`` the
+    ``.label`` files carry the track id + 1 as the instance id.  Returns ``None`` — after one line that says why — when a
+    sequence lacks ``poses.txt`` or ``calib.txt``, else ``{'tracks', 'dropped', 'frames', 'written'}`` plus, with labels,
+    ``{'lstq', 's_assoc', 's_cls', 'tubes'}``.  Not pinned: parity with semantic-kitti-api's 4D evaluator, LSTQ on real data."""
+    by_seq = {}
+    for f, _ in semantic_kitti_files(root, sequences):
+        by_seq.setdefault(f.parent.parent, []).append(f)
+    missing = [d for d in by_seq if not ((d / 'poses.txt').exists() and (d / 'calib.txt').exists())]
+    if missing:
+        print(f'track_instances: skipped, poses.txt or calib.txt is missing under {missing[0]}', flush=True)
+        return None
+    have_labels = all(semantic_kitti_label_path(f).exists() for scans_of in by_seq.values() for f in scans_of)
+    tracker = InstanceTracker(config['x_range'], config['y_range'], config['voxel_size'], int(config['num_queries']),
+                              device=device, **tracking_settings(config))
+    quality = panoptic_metric(config)
+    tubes = DeviceTubeAssociation(quality.num_classes, quality.class_lut('cpu'), id_limit=int(config.get('track_id_limit', 1024)),
+                                  max_tracks=int(config.get('track_tube_tracks', 4096)))      # the same classes as `quality`
+    out = dict(tracks=0, dropped=0, frames=0, written=[])
+    assoc_sum, n_tubes = 0.0, 0
+    for seq_dir, scans_of in by_seq.items():
+        poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
+        tracker.reset()
+        tubes.reset()
+        for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
+            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]])
+            lifted = pred.lift(scans, model)
+            ids = pred.point_tracks(lifted, query_track)
+            if have_labels:
+                words = [read_label_words(semantic_kitti_label_path(f), device) for f in part]
+                tubes.update(ids, words[0] if len(words) == 1 else torch.cat(words))
+                pred.panoptic_points(lifted, words, quality)
+            if out_dir is not None:
+                for f, labels, tracks in zip(part, lifted.per_scan(), torch.split(ids, list(lifted.lengths))):
+                    out['written'].append(prediction_label_path(out_dir, f))
+                    write_semantic_kitti_labels(out['written'][-1], labels, semantic_id, instance_ids=tracks)
+        counts = tracker.counters()
+        for key in ('tracks', 'dropped', 'frames'):
+            out[key] += counts[key]
+        if have_labels:
+            res = tubes.compute()                  # per sequence: SemanticKITTI's instance ids are unique inside one only
+            assoc_sum += res['s_assoc'] * res['tubes']
+            n_tubes += res['tubes']
+    if have_labels:
+        s_assoc = assoc_sum / max(n_tubes, 1)
+        s_cls = quality.compute(reduce=False)['iou'] if quality.frames else 0.0     # compute() would wait for the other ranks
+        out.update(lstq=lstq(s_assoc, s_cls), s_assoc=s_assoc, s_cls=s_cls, tubes=n_tubes)
+    return out
+
+
+def format_point_lstq(result):
+    """The ``point LSTQ`` line of ``--test`` from :func:`sequence_tracking`."""
+    return (f'point LSTQ {result["lstq"]:.4f} S_assoc {result["s_assoc"]:.4f} S_cls {result["s_cls"]:.4f} '
+            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]})')
+
+
+def format_layer_metrics(logged, layer):
+    """One line of ``--test`` per decoder layer from the module's logged values (mask_bev_module.py:209-224)."""
+    parts = [f'{n} {logged[f"val_mAP_{layer}_{n}"]:.4f}' for n in ('map', 'map_50', 'map_75', 'mar_100')]
+    parts += [f'mIoU {logged[f"val_mIoU_layer_{layer}"]:.4f}', f'cls_AP {logged[f"val_cls_mAP_layer_{layer}"]:.4f}']
+    return f'layer {layer}: ' + ' '.join(parts)

@@ -442,7 +442,26 @@ def panoptic_quality(tp, fp, fn, iou_sum, confusion) -> dict:
     return dict(pq=mean(pq), sq=mean(sq), rq=mean(rq), iou=mean(iou), per_class=per_class)
 
 
-class DevicePanopticQuality:
+class _ClassTable:
+    """What the point metrics share: ``num_classes`` (2 .. 16) and ``class_lut``, the int32 table semantic id → class, given
+    as a numpy array or a tensor, kept on the host and handed out per device."""
+
+    def __init__(self, num_classes: int, class_lut):
+        self.num_classes = int(num_classes)
+        if not 2 <= self.num_classes <= 16:
+            raise ValueError(f'{type(self).__name__}: 2 <= num_classes <= 16, got {num_classes}')
+        lut = class_lut.detach().cpu().numpy() if torch.is_tensor(class_lut) else np.asarray(class_lut)
+        self._lut_host = np.ascontiguousarray(lut.reshape(-1).astype(np.int32))
+        self._lut = {}
+
+    def class_lut(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device not in self._lut:
+            self._lut[device] = torch.from_numpy(self._lut_host).to(device)
+        return self._lut[device]
+
+
+class DevicePanopticQuality(_ClassTable):
     """PQ / SQ / RQ and IoU of point or BEV instances in the SemanticKITTI panoptic protocol (``PanopticEval`` of
     semantic-kitti-api's eval_np.py, restated; parity with that package is unpinned: it is not installed), with the per-frame
     work on the device (K32, ``ops.panoptic_frames``).  ``class_lut``: semantic id → class, -1 = ignored
@@ -453,24 +472,13 @@ class DevicePanopticQuality:
     ground-truth segments: such a frame has no numbers."""
 
     def __init__(self, num_classes: int, class_lut, min_points: int = 50, max_gt: int = 256):
-        self.num_classes, self.min_points, self.max_gt = int(num_classes), int(min_points), int(max_gt)
-        if not 2 <= self.num_classes <= 16:
-            raise ValueError(f'DevicePanopticQuality: 2 <= num_classes <= 16, got {num_classes}')
-        lut = class_lut.detach().cpu().numpy() if torch.is_tensor(class_lut) else np.asarray(class_lut)
-        self._lut_host = np.ascontiguousarray(lut.reshape(-1).astype(np.int32))
-        self._lut = {}
-        self.state = None
-        self.frames = 0
+        super().__init__(num_classes, class_lut)
+        self.min_points, self.max_gt = int(min_points), int(max_gt)
+        self.reset()
 
     def reset(self):
         self.state = None
         self.frames = 0
-
-    def class_lut(self, device) -> torch.Tensor:
-        device = torch.device(device)
-        if device not in self._lut:
-            self._lut[device] = torch.from_numpy(self._lut_host).to(device)
-        return self._lut[device]
 
     @torch.no_grad()
     def update(self, pred_query: torch.Tensor, query_class: torch.Tensor, gt_words: torch.Tensor, lengths) -> 'ops.PanopticFrames':
@@ -494,10 +502,11 @@ class DevicePanopticQuality:
         self.frames += int(frame_stats.shape[0])
 
     @torch.no_grad()
-    def compute(self) -> dict:
+    def compute(self, reduce: bool = True) -> dict:
+        """``reduce=False``: the numbers of this rank alone, without a collective (the other ranks need not call)."""
         c = self.num_classes
         import torch.distributed as dist
-        gather = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        gather = reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if self.state is None and not gather:
             return dict(panoptic_quality(np.zeros(c), np.zeros(c), np.zeros(c), np.zeros(c), np.zeros((c, c))), frames=0)
         if self.state is None:
@@ -528,7 +537,7 @@ def lstq(s_assoc: float, s_cls: float) -> float:
     return float(np.sqrt(float(s_assoc) * float(s_cls)))
 
 
-class DeviceTubeAssociation:
+class DeviceTubeAssociation(_ClassTable):
     """S_assoc, the association term of LSTQ, over a whole sequence, with the tables on the device (K33b,
     ``ops.tube_accumulate`` / ``ops.tube_scores``).  A ground-truth tube is a (thing class, instance id) pair over all frames
     fed since :meth:`reset`, a predicted tube a global track id (``Predictions.point_tracks``); a tube's score is ``(1 / |gt|)
@@ -544,22 +553,11 @@ class DeviceTubeAssociation:
     Tables that live on the host (``tables=`` a record copied back) are scored by the same formula in numpy."""
 
     def __init__(self, num_classes: int, class_lut, id_limit: int = 1024, max_tracks: int = 4096, tables=None):
-        self.num_classes, self.id_limit, self.max_tracks = int(num_classes), int(id_limit), int(max_tracks)
-        if not 2 <= self.num_classes <= 16:
-            raise ValueError(f'DeviceTubeAssociation: 2 <= num_classes <= 16, got {num_classes}')
-        lut = class_lut.detach().cpu().numpy() if torch.is_tensor(class_lut) else np.asarray(class_lut)
-        self._lut_host = np.ascontiguousarray(lut.reshape(-1).astype(np.int32))
-        self._lut = {}
-        self.tables = tables
+        super().__init__(num_classes, class_lut)
+        self.id_limit, self.max_tracks, self.tables = int(id_limit), int(max_tracks), tables
 
     def reset(self):
         self.tables = None
-
-    def class_lut(self, device) -> torch.Tensor:
-        device = torch.device(device)
-        if device not in self._lut:
-            self._lut[device] = torch.from_numpy(self._lut_host).to(device)
-        return self._lut[device]
 
     @torch.no_grad()
     def update(self, point_tracks: torch.Tensor, gt_words: torch.Tensor) -> None:

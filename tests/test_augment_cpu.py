@@ -216,9 +216,9 @@ def test_cpu_tensors_and_bad_dims_are_refused():
 
 
 def test_launcher_builds_the_augmentation_from_the_config():
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.datasets import build_augmentation
     from mask_bev_amd import augment as A
     cfg = {'x_range': [-40, 40], 'y_range': [-40, 40], 'voxel_size': 0.16, 'seed': 3}
-    assert launcher.build_augmentation(cfg) is None and launcher.build_augmentation(dict(cfg, augmentations=[])) is None
-    aug = launcher.build_augmentation(dict(cfg, augmentations=GENTLE))
+    assert build_augmentation(cfg) is None and build_augmentation(dict(cfg, augmentations=[])) is None
+    aug = build_augmentation(dict(cfg, augmentations=GENTLE))
     assert isinstance(aug, A.DeviceAugmentation) and len(aug.transforms) == 5 and aug.voxel_size == 0.16

@@ -394,7 +394,7 @@ def test_collates_with_an_augmentation_match_their_own_maps(device):
 # the launcher
 # ---------------------------------------------------------------------------------------------------------------
 def test_launcher_augments_training_batches_only(device, tmp_path):
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.datasets import SemanticKittiCacheBatches
     pts, inst = _scene(2)
     r = _rasterizer()
     base = r.rasterize(torch.from_numpy(pts).to(device), torch.from_numpy(inst).to(device), np.eye(4)[None]).cpu().numpy()
@@ -421,8 +421,8 @@ augmentations:
     prob_drop: 1
     per_point_drop_prob: 0.25
 """)
-    train = launcher.SemanticKittiCacheBatches(config, device, 0, 1, tmp_path, [0], augment=True)
-    val = launcher.SemanticKittiCacheBatches(config, device, 0, 1, tmp_path, [0])
+    train = SemanticKittiCacheBatches(config, device, 0, 1, tmp_path, [0], augment=True)
+    val = SemanticKittiCacheBatches(config, device, 0, 1, tmp_path, [0])
     assert train.augmentation is not None and len(train.augmentation.transforms) == 2 and val.augmentation is None
     torch.manual_seed(0)
     vs, (vl, vm) = val.batch(0, 0)

@@ -272,7 +272,7 @@ def test_launcher_kitti_batches(device, tmp_path, capsys):
     keys of the reference's configs/training/kitti files; ``object_sample`` / ``object_noise`` are left out with one line."""
     import shutil
     import yaml
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.datasets import KittiObjectBatches
     from mask_bev_amd import batch as B, rasterize
     from tests.test_boxes_cpu import SAMPLE
     import os
@@ -310,9 +310,9 @@ augmentations:
   - name: 'global_noise'
     prob_aug: 0.5
 """)
-    train = launcher.KittiObjectBatches(config, device, 0, 1, tmp_path, 'train', augment=True)
+    train = KittiObjectBatches(config, device, 0, 1, tmp_path, 'train', augment=True)
     assert 'training without object_sample, object_noise' in capsys.readouterr().out
-    val = launcher.KittiObjectBatches(dict(config, batch_size=1), device, 0, 1, tmp_path, 'val')
+    val = KittiObjectBatches(dict(config, batch_size=1), device, 0, 1, tmp_path, 'val')
     assert len(train) == 1 and len(val) == 1 and val.augmentation is None and len(train.augmentation.transforms) == 2
     pcs, (labels, masks) = val.batch(0, 0)
     assert pcs[0].shape == (301, 4) and masks.shape == (1, 45, 800, 800) and labels.shape == (1, 45)

@@ -341,10 +341,10 @@ def test_predictions_boxes_and_kitti_predictions(device):
 
 # ------------------------------------------------------------------------------------------------ the launcher's hook
 def test_launcher_kitti_bev_evaluation(device, tmp_path):
-    """``train_mask_bev_amd.kitti_bev_evaluation`` over a KITTI object tree holding the sample frame twice, with an untrained
+    """``evaluate.kitti_bev_evaluation`` over a KITTI object tree holding the sample frame twice, with an untrained
     tiny model: predict → boxes → protocol end to end; the block has the reference's lines for Car at 0.7 and 0.5."""
     import shutil
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.evaluate import kitti_bev_evaluation
     from mask_bev_amd.mask_bev_module import MaskBevModule
     rng = np.random.default_rng(2)
     for k in ('velodyne', 'label_2', 'calib'):
@@ -362,7 +362,7 @@ def test_launcher_kitti_bev_evaluation(device, tmp_path):
     model = MaskBevModule(**kw).to(device)
     model.log_scalars = False
     config = dict(kw, dataset='kitti', batch_size=2)
-    out = launcher.kitti_bev_evaluation(model, config, device, tmp_path)
+    out = kitti_bev_evaluation(model, config, device, tmp_path)
     lines = out.splitlines()
     assert len(lines) == 4 and lines[0] == 'Car AP(Average Precision)@0.70:' and lines[2] == 'Car AP(Average Precision)@0.50:'
     assert all(l.startswith('bev  AP:') and len(l.split(',')) == 3 for l in (lines[1], lines[3]))

@@ -368,7 +368,7 @@ def test_launcher_with_device_object_augmentation(device, tmp_path, capsys):
     bank is built from the training split, the list holds both object transforms, nothing is left out."""
     import shutil
     import yaml
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.datasets import KittiObjectBatches, build_object_bank
     from mask_bev_amd import batch as B
     from tests.test_boxes_cpu import SAMPLE
     OA = _OA()
@@ -412,12 +412,12 @@ augmentations:
 """)
     config['object_bank'] = str(tmp_path / 'bank' / 'samples.npz')
     with pytest.raises(FileNotFoundError, match='build-object-bank'):
-        launcher.KittiObjectBatches(config, device, 0, 1, tmp_path, 'train', augment=True)
-    path = launcher.build_object_bank(config, device, tmp_path)
+        KittiObjectBatches(config, device, 0, 1, tmp_path, 'train', augment=True)
+    path = build_object_bank(config, device, tmp_path)
     assert str(path) == config['object_bank'] and 'object bank:' in capsys.readouterr().out
     bank = OA.ObjectBank.load(path)
     assert 2 <= len(bank) <= 6 and (np.diff(bank.offsets) >= 5).all()
-    train = launcher.KittiObjectBatches(config, device, 0, 1, tmp_path, 'train', augment=True)
+    train = KittiObjectBatches(config, device, 0, 1, tmp_path, 'train', augment=True)
     assert 'training without' not in capsys.readouterr().out
     kinds = [type(t) for t in train.augmentation.transforms]
     assert kinds[:2] == [OA.ObjectSample, OA.ObjectNoise] and len(kinds) == 4

@@ -233,11 +233,11 @@ def test_capture_and_replay(device, capsys):
 
 
 def test_launcher_kitti_box_method(device, tmp_path):
-    """``train_mask_bev_amd.kitti_bev_evaluation`` over a small KITTI object tree with an untrained tiny model: the
+    """``evaluate.kitti_bev_evaluation`` over a small KITTI object tree with an untrained tiny model: the
     configuration's ``kitti_box_method`` selects the boxes, the default is ``moment``, and the block keeps its four lines."""
     import os
     import shutil
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.evaluate import kitti_bev_evaluation
     from mask_bev_amd.mask_bev_module import MaskBevModule
     sample = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'kitti_object_sample')
     rng = np.random.default_rng(2)
@@ -255,14 +255,14 @@ def test_launcher_kitti_box_method(device, tmp_path):
     model = MaskBevModule(**kw).to(device)
     model.log_scalars = False
     config = dict(kw, dataset='kitti', batch_size=2)
-    default = launcher.kitti_bev_evaluation(model, config, device, tmp_path)
-    moment = launcher.kitti_bev_evaluation(model, dict(config, kitti_box_method='moment'), device, tmp_path)
+    default = kitti_bev_evaluation(model, config, device, tmp_path)
+    moment = kitti_bev_evaluation(model, dict(config, kitti_box_method='moment'), device, tmp_path)
     assert str(default) == str(moment) and np.array_equal(default.raw['stats'], moment.raw['stats'])
-    by_key = launcher.kitti_bev_evaluation(model, dict(config, kitti_box_method='min_area_rect'), device, tmp_path)
-    by_arg = launcher.kitti_bev_evaluation(model, config, device, tmp_path, box_method='min_area_rect')
+    by_key = kitti_bev_evaluation(model, dict(config, kitti_box_method='min_area_rect'), device, tmp_path)
+    by_arg = kitti_bev_evaluation(model, config, device, tmp_path, box_method='min_area_rect')
     assert str(by_key) == str(by_arg) and np.array_equal(by_key.raw['stats'], by_arg.raw['stats'])
     lines = by_key.splitlines()
     assert len(lines) == 4 and lines[0] == 'Car AP(Average Precision)@0.70:' and lines[2] == 'Car AP(Average Precision)@0.50:'
     assert all(l.startswith('bev  AP:') and len(l.split(',')) == 3 for l in (lines[1], lines[3]))
     with pytest.raises(ValueError):
-        launcher.kitti_bev_evaluation(model, dict(config, kitti_box_method='nope'), device, tmp_path)
+        kitti_bev_evaluation(model, dict(config, kitti_box_method='nope'), device, tmp_path)

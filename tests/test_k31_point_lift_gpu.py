@@ -418,7 +418,7 @@ def test_end_to_end_boxes3d_and_3d_ap(device):
 def test_launcher_writes_point_labels(device, tmp_path):
     """``write_point_labels`` (behind ``--write-labels``): one ``.label`` per scan under sequences/SS/predictions, holding the
     lifted queries of that scan as SemanticKITTI packs them."""
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.evaluate import write_point_labels
     from mask_bev_amd import batch as B
     from mask_bev_amd.mask_bev_module import MaskBevModule
     from tests.util_cfg import random_scans
@@ -434,7 +434,7 @@ def test_launcher_writes_point_labels(device, tmp_path):
         s.numpy().tofile(d / f'{i:06d}.bin')
         files.append((d / f'{i:06d}.bin', None))
     out = tmp_path / 'out'
-    paths = launcher.write_point_labels(model, dict(kw, batch_size=2), device, files, out)
+    paths = write_point_labels(model, dict(kw, batch_size=2), device, files, out)
     assert [p.relative_to(out).as_posix() for p in paths] == [f'sequences/08/predictions/{i:06d}.label' for i in range(3)]
     labelled, wants = 0, []
     for start in (0, 2):                                                # the batches the launcher made

@@ -226,6 +226,7 @@ def test_launcher_prints_point_pq(device, tmp_path, capsys):
     """``--test`` on ``dataset: semantic-kitti``: with ``labels/NNNNNN.label`` next to every validated scan one ``point PQ``
     line whose tp, fp and fn are the restatement's on the same predictions; without the files no such line."""
     import train_mask_bev_amd as launcher
+    from mask_bev_amd.evaluate import semantic_kitti_label_path
     from mask_bev_amd.mask_bev_module import MaskBevModule
     from mask_bev_amd.metrics import semantic_kitti_class_lut
     kw, model = _tiny_model(device)
@@ -254,7 +255,7 @@ def test_launcher_prints_point_pq(device, tmp_path, capsys):
     loaded.log_scalars = False
     loaded.flatten_parameters()
     files = [(seq / 'velodyne' / f'{i:06d}.bin', None) for i in range(4)]
-    assert launcher.semantic_kitti_label_path(files[2][0]) == seq / 'labels' / '000002.label'
+    assert semantic_kitti_label_path(files[2][0]) == seq / 'labels' / '000002.label'
     (seq / 'labels').mkdir()
     per, classes = [], []
     for start in (0, 2):

@@ -366,6 +366,8 @@ def test_launcher_tracks_sequences(device, tmp_path, capsys):
     assert len(got) == 1 and got[0], lines
     pq_at = [i for i, l in enumerate(lines) if l.startswith('point PQ')]
     assert len(pq_at) == 1 and lines[pq_at[0] + 1].startswith('point LSTQ')
+    # one sequence, one rank: both passes see the same batches, so this rank's IoU alone is the IoU summed over the ranks
+    assert got[0].group(3) == re.search(r' IoU (\S+) ', lines[pq_at[0]]).group(1)
     assert any(l.startswith('wrote 4 label files with track ids') for l in lines)
     # the restatement on the predictions of the model as the launcher loads it
     loaded = MaskBevModule.from_config(dict(cfg, checkpoint=str(path))).to(device)

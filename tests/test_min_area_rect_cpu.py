@@ -145,8 +145,8 @@ def test_unknown_box_method_is_a_value_error():
 
 
 def test_launcher_refuses_an_unknown_kitti_box_method(tmp_path):
-    import train_mask_bev_amd as launcher
+    from mask_bev_amd.evaluate import kitti_bev_evaluation
     with pytest.raises(ValueError):
-        launcher.kitti_bev_evaluation(None, dict(kitti_box_method='nope'), 'cpu', tmp_path)
+        kitti_bev_evaluation(None, dict(kitti_box_method='nope'), 'cpu', tmp_path)
     with pytest.raises(ValueError):
-        launcher.kitti_bev_evaluation(None, {}, 'cpu', tmp_path, box_method='nope')
+        kitti_bev_evaluation(None, {}, 'cpu', tmp_path, box_method='nope')

@@ -130,17 +130,59 @@ def test_device_metric_state_on_cpu_tensors():
         DevicePanopticQuality(17, lut)
 
 
+def _three_frames(n_gt=(1, 2, 0)):
+    """Hand-made K32 records of 3 frames and 2 classes as CPU tensors: (F, C, 3) tp / fp / fn, (F, C) IoU sums, (F, C, C)
+    confusion, (F) ground-truth segments."""
+    import torch
+    stats = torch.tensor([[[0, 0, 0], [2, 1, 0]], [[0, 0, 0], [1, 0, 2]], [[0, 0, 0], [0, 1, 0]]], dtype=torch.int32)
+    iou = torch.tensor([[0.0, 1.5], [0.0, 0.625], [0.0, 0.0]], dtype=torch.float64)
+    conf = torch.tensor([[[40, 3], [2, 30]], [[10, 0], [7, 12]], [[5, 4], [0, 0]]], dtype=torch.int32)
+    return stats, iou, conf, torch.tensor(n_gt, dtype=torch.int32)
+
+
+def test_compute_without_reduce_equals_compute():
+    """No process group: ``compute(reduce=False)`` is ``compute()`` key for key, on fed and on fresh metrics, and both raise
+    on a frame above ``max_gt``."""
+    from mask_bev_amd._lib import MaskBevHipError
+    from mask_bev_amd.metrics import DevicePanopticQuality
+    m = DevicePanopticQuality(2, LUT, min_points=1, max_gt=4)
+    fresh = m.compute(reduce=False)
+    assert fresh == m.compute() and fresh['frames'] == 0
+    assert fresh['per_class']['tp'] == fresh['per_class']['fp'] == fresh['per_class']['fn'] == [0, 0]
+    m.append_state(*_three_frames())
+    alone, summed = m.compute(reduce=False), m.compute()
+    assert set(alone) == set(summed) == {'pq', 'sq', 'rq', 'iou', 'per_class', 'frames'}
+    for key in summed:
+        assert alone[key] == summed[key], key
+    assert alone['frames'] == 3 and alone['per_class']['tp'] == [0, 3] and alone['per_class']['fp'] == [0, 2]
+    assert alone['sq'] == pytest.approx(2.125 / 3) and alone['iou'] == pytest.approx(42 / (42 + 9 + 7))
+    over = DevicePanopticQuality(2, LUT, min_points=1, max_gt=4)
+    over.append_state(*_three_frames(n_gt=(1, 5, 0)))
+    for kw in ({}, dict(reduce=False)):
+        with pytest.raises(MaskBevHipError, match='1 of 3 frames'):
+            over.compute(**kw)
+
+
+def test_prediction_label_path(tmp_path):
+    import pathlib
+    from mask_bev_amd.evaluate import prediction_label_path
+    p = prediction_label_path(tmp_path / 'out', '/d/sequences/08/velodyne/000123.bin')
+    assert p == tmp_path / 'out' / 'sequences' / '08' / 'predictions' / '000123.label'
+    assert p.parent.is_dir() and not p.exists()
+    assert prediction_label_path(tmp_path / 'out', pathlib.Path('/d/sequences/08/velodyne/000124.bin')).parent == p.parent
+
+
 def test_launcher_label_path_and_config_keys():
     import pathlib
-    import train_mask_bev_amd as launcher
-    p = launcher.semantic_kitti_label_path('/data/sequences/08/velodyne/000123.bin')
+    from mask_bev_amd.evaluate import format_point_panoptic, panoptic_settings, point_panoptic_evaluation, semantic_kitti_label_path
+    p = semantic_kitti_label_path('/data/sequences/08/velodyne/000123.bin')
     assert p == pathlib.Path('/data/sequences/08/labels/000123.label')
-    assert launcher.panoptic_settings({}) == (50, ((10,),), (0, 1, 252))
-    got = launcher.panoptic_settings(dict(panoptic_min_points=30, panoptic_things=[[10, 252], 18], panoptic_ignore=[0]))
+    assert panoptic_settings({}) == (50, ((10,),), (0, 1, 252))
+    got = panoptic_settings(dict(panoptic_min_points=30, panoptic_things=[[10, 252], 18], panoptic_ignore=[0]))
     assert got == (30, ((10, 252), (18,)), (0,))
-    assert launcher.point_panoptic_evaluation(None, {}, None, [(pathlib.Path('/nowhere/sequences/08/velodyne/000000.bin'), None)]) is None
+    assert point_panoptic_evaluation(None, {}, None, [(pathlib.Path('/nowhere/sequences/08/velodyne/000000.bin'), None)]) is None
     res = dict(pq=0.5, sq=0.75, rq=2 / 3, iou=0.25, per_class=dict(tp=[0, 4], fp=[0, 1], fn=[0, 3]))
-    assert launcher.format_point_panoptic(res) == 'point PQ 0.5000 SQ 0.7500 RQ 0.6667 IoU 0.2500 (car; tp 4 fp 1 fn 3)'
+    assert format_point_panoptic(res) == 'point PQ 0.5000 SQ 0.7500 RQ 0.6667 IoU 0.2500 (car; tp 4 fp 1 fn 3)'
 
 
 def test_binding_declares_k32():
