@@ -1193,6 +1193,39 @@ int mbv_rasterize_paint(const uint32_t* occupancy, const int32_t* bbox, const in
                         int32_t n_slots_max, int32_t nx, int32_t ny, int32_t morph_kernel, int32_t* instance_map,
                         void* stream);
 
+/* K34 — mbv_rasterize for a whole batch on a scene bank that stays on the device (scene_bank.SceneBank): the labelled
+ * points of a sequence, every scan in its own frame.  A sample's scene is a list of SEGMENTS of the bank, each with the
+ * transform that takes its scan into the sample's frame; the bank is read in place, nothing is copied or reordered, and
+ * the number of launches depends neither on the number of segments nor on `batch`.
+ *
+ * points, inst    the bank: (n_bank, 3) f32 and (n_bank) i32, both 16-byte aligned
+ * seg_start       (n_seg) i64 first bank point, seg_count (n_seg) i32 points of each segment; the segments of sample 0
+ *                 first, then sample 1's, ... in the order in which mbv_rasterize would get the scans.  The caller checks
+ *                 0 <= seg_start and seg_start + seg_count <= n_bank; the kernels also never read beyond n_bank.
+ * transforms      (n_seg, 4, 4) f64 row-major, as in mbv_rasterize
+ * chunks          (n_chunks, 4) i32, 16-byte aligned, made on the host: segment, first point inside the segment, sample, 0.
+ *                 One workgroup bins the points [first, first + chunk_points) of the segment (fewer at its end), so every
+ *                 point of a workgroup has one transform; chunk_points is a multiple of 4.  Every point of every segment
+ *                 must lie in exactly one chunk, whose sample is the one the segment belongs to.
+ * centre_start    (batch) i64, centre_count (batch) i32: sample b's centre_inst is inst[centre_start[b] : centre_start[b] +
+ *                 centre_count[b]]; centre_count[b] < 0 = remove_unseen off for that sample (n_centre < 0 there)
+ * instance_maps   (batch, nx, ny) i32; status (batch) i32, the bits of mbv_rasterize per sample.
+ * Map b and status[b] are bit-equal to what mbv_rasterize gives for the concatenation of sample b's segments in table
+ * order with sample b's transforms and that centre_inst: every rule above holds, the same device functions run.  A sample
+ * without segments, or without a kept point, gets an all-zero map.  batch = 0 returns MBV_OK before anything is checked.
+ * geometry, morph_kernel, min_points, max_instances, phases: as in mbv_rasterize.
+ * workspace       mbv_rasterize_bank_workspace_bytes(batch, nx, ny, max_instances) bytes, 256-byte aligned; 0 = bad
+ *                 geometry or batch outside 1 ... 65535.
+ */
+size_t mbv_rasterize_bank_workspace_bytes(int32_t batch, int32_t nx, int32_t ny, int32_t max_instances);
+int mbv_rasterize_bank(const float* points, const int32_t* inst, int64_t n_bank, const int64_t* seg_start,
+                       const int32_t* seg_count, int32_t n_seg, const double* transforms, const int32_t* chunks,
+                       int32_t n_chunks, int32_t chunk_points, const int64_t* centre_start, const int32_t* centre_count,
+                       int32_t batch, double x_lo, double x_hi, double y_lo, double y_hi, double z_lo, double z_hi,
+                       double voxel_size, int32_t nx, int32_t ny, int32_t morph_kernel, int32_t min_points,
+                       int32_t max_instances, int32_t phases, int32_t* instance_maps, int32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * K23 — training augmentations of scans and instance maps (csrc/augment.hip).
  * Replaces: Flip, ShufflePoints, RandomRotate, DecimatePoints, JitterPoints, RandomDropPoints of

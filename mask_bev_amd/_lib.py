@@ -191,6 +191,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_rasterize': (ctypes.c_int, [_P, _I, _I, _P, _L, _P, _I, _P, _P, _L, _D, _D, _D, _D, _D, _D, _D, _I, _I, _I, _I, _I, _I,
                                      _P, _P, _P, c_size_t, _P]),
     'mbv_rasterize_paint': (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    'mbv_rasterize_bank_workspace_bytes': (c_size_t, [_I, _I, _I, _I]),
+    'mbv_rasterize_bank': (ctypes.c_int, [_P, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _D, _D, _D, _D, _D, _D, _D,
+                                          _I, _I, _I, _I, _I, _I, _P, _P, _P, c_size_t, _P]),
     'mbv_augment_workspace_bytes': (c_size_t, [_L, _I, _I]),
     'mbv_augment_points': (ctypes.c_int, [_P, _I, _L, _P, _I, _P, _I, _P, _P, _P, _P, c_size_t, _P]),
     'mbv_warp_instance_maps': (ctypes.c_int, [_P, _P, _I, _I, _I, _D, _D, _P, _P]),

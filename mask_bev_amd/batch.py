@@ -286,6 +286,43 @@ class SceneCollate:
         return pcs, (labels, masks)
 
 
+class BankSceneCollate:
+    """:class:`SceneCollate` on scene banks that stay on the device (``scene_bank.SceneBank``, K34): samples are
+    ``(point_cloud (N, pc_dim) f32 array/tensor, (sequence key, scan_indices, transforms (S, 4, 4) f64, centre scan or
+    None)[, metadata])`` and ``banks`` maps a sequence key to its bank.  Nothing of a scene crosses PCIe but its indices and
+    matrices: the augmentation runs on the scans and folds its flips and rotations into the scene transforms as there, then
+    every sequence present in the batch (a batch may mix them) takes one ``rasterize_bank`` call, and the maps go to K14."""
+
+    def __init__(self, rasterizer, banks, num_queries: int, device, min_num_inst_pixels: int = 0, packed: bool = False,
+                 augmentation=None):
+        self.rasterizer, self.banks, self.num_queries, self.device = rasterizer, banks, num_queries, torch.device(device)
+        self.min_num_inst_pixels, self.packed = min_num_inst_pixels, packed
+        self.augmentation = augmentation
+
+    def __call__(self, batch: Sequence):
+        pcs = [torch.as_tensor(s[0], dtype=torch.float32).to(self.device, non_blocking=True) for s in batch]
+        scene_tfs = [s[1][2] for s in batch]
+        if self.augmentation is not None:
+            aug = self.augmentation.apply(pcs, scene_transforms=scene_tfs)
+            pcs, scene_tfs = aug.scans, aug.scene_transforms
+        groups = {}
+        for b, s in enumerate(batch):
+            groups.setdefault(s[1][0], []).append(b)
+        maps = None
+        for key, members in groups.items():
+            scenes = [(batch[b][1][1], scene_tfs[b], batch[b][1][3]) for b in members]
+            if len(groups) == 1:
+                maps = self.rasterizer.rasterize_bank(self.banks[key], scenes)
+                break
+            if maps is None:
+                maps = torch.empty((len(batch), self.rasterizer.nx, self.rasterizer.ny), dtype=torch.int32, device=self.device)
+            maps[torch.as_tensor(members, device=self.device)] = self.rasterizer.rasterize_bank(self.banks[key], scenes)
+        labels, masks = instance_targets(maps, self.num_queries, self.min_num_inst_pixels, self.packed)
+        if len(batch[0]) > 2:
+            return pcs, (labels, masks), [s[2] for s in batch]
+        return pcs, (labels, masks)
+
+
 class BoxCollate:
     """Collate of ``(point_cloud (N, pc_dim) f32 array/tensor, boxes (n, 7) f64 [cx, cy, cz, l, w, h, theta][, metadata])``
     samples into the batch ``MaskBevModule.training_step`` takes — the reference's ``FrameMaskListCollate``

@@ -14,6 +14,12 @@
 //   k_clear_occ      zeroes the bit images of the slots in use
 //   k_stream<.., 1>  kept point -> atomicOr of its cell bit into its slot's image; the cell bounding box is widened by
 //                    atomicMin / Max only when the cell lies outside the box read first (rare after the first points)
+// K34, binning for a whole batch on a scene bank that stays on the device (mbv_rasterize_bank): the same stages on
+// sample-major tables, launches independent of the batch size and of the number of scans.
+//   k_bank_centre_count / k_bank_stream<0>   as above per sample; one workgroup per host-made chunk of one scan's points
+//   k_scan_table, k_clear_occ                sample = blockIdx.y
+//   k_bank_stream<1>                         occupancy bits only, the bit read before the atomic
+//   k_occ_bbox                               cell bounding boxes read off the finished images
 // K22b, morphology + paint.
 //   k_morph_paint    one workgroup per slot.  The window (bounding box grown by 2 * (k / 2) cells, clipped to the grid)
 //                    is loaded into LDS as bits, rows = ix, 32 cells of iy per word.  close = dilate, erode and
@@ -52,19 +58,9 @@ __device__ __forceinline__ void load_xyz(const T* __restrict__ pts, int stride, 
   }
 }
 
-// the cell of point i, false when the point is not kept (:53-68)
-template <typename T, bool F4>
-__device__ __forceinline__ bool point_cell(const T* __restrict__ pts, int stride, int64_t i,
-                                           const int32_t* __restrict__ offs, int n_scans,
-                                           const double* __restrict__ tf, const Geom& g, int& ix, int& iy) {
-  int lo = 0, hi = n_scans - 1;      // the scan that owns point i: the last s with offs[s] <= i
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((int64_t)offs[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  const double* m = tf + (int64_t)lo * 16;
-  double px, py, pz;
-  load_xyz<T, F4>(pts, stride, i, px, py, pz);
+// the cell of the point (px, py, pz) of a scan with the transform m, false when the point is not kept (:53-68)
+__device__ __forceinline__ bool cell_of(const double* __restrict__ m, double px, double py, double pz, const Geom& g,
+                                        int& ix, int& iy) {
   const double x = m[0] * px + m[1] * py + m[2] * pz + m[3];
   const double y = m[4] * px + m[5] * py + m[6] * pz + m[7];
   const double z = m[8] * px + m[9] * py + m[10] * pz + m[11];
@@ -74,6 +70,21 @@ __device__ __forceinline__ bool point_cell(const T* __restrict__ pts, int stride
   ix = (int)fx;
   iy = (int)fy;
   return true;
+}
+
+// the cell of point i, false when the point is not kept
+template <typename T, bool F4>
+__device__ __forceinline__ bool point_cell(const T* __restrict__ pts, int stride, int64_t i,
+                                           const int32_t* __restrict__ offs, int n_scans,
+                                           const double* __restrict__ tf, const Geom& g, int& ix, int& iy) {
+  int lo = 0, hi = n_scans - 1;      // the scan that owns point i: the last s with offs[s] <= i
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int64_t)offs[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  double px, py, pz;
+  load_xyz<T, F4>(pts, stride, i, px, py, pz);
+  return cell_of(tf + (int64_t)lo * 16, px, py, pz, g, ix, iy);
 }
 
 // MODE 0: table[id] = 1 for every id with a kept point.  MODE 1: table = id -> slot; occupancy bits + bounding boxes.
@@ -127,18 +138,156 @@ __global__ void __launch_bounds__(256) k_centre_count(const int32_t* __restrict_
   }
 }
 
-// table[id] (a flag or a count) >= threshold -> slot (ascending id order), everything else -> -1
-__global__ void __launch_bounds__(1024) k_scan_table(int32_t* __restrict__ table, int threshold, int max_instances,
+// K34: the scene bank read in place.  One workgroup per chunk = (segment, first point inside it, sample): every point of
+// a workgroup has one transform, read through uniform loads.  Points are taken four at a time at bank indices that are
+// multiples of 4, so the labels come as one int4 and the coordinates as three float4 whatever the segment's first point
+// is; the points of a quad outside [begin, end) are masked.  Both tables come from the host, so every index is checked.
+struct BankTables {
+  const float* pts;                  // (n_bank, 3)
+  const int32_t* inst;               // (n_bank)
+  int64_t n_bank;
+  const int64_t* seg_start;
+  const int32_t* seg_count;
+  int n_seg;
+  const double* tf;                  // (n_seg, 4, 4)
+  const int4* chunks;                // (n_chunks): segment, first point inside the segment, sample, unused
+  int chunk_points;
+  const int64_t* centre_start;
+  const int32_t* centre_count;
+  int batch, max_instances;
+};
+
+// MODE as in k_stream, on sample-major tables; MODE 0 skips the samples whose centre scan names the instances.  MODE 1 sets
+// occupancy bits only: with every point of a bank labelled, widening four box words per instance by atomics from millions
+// of points is what the pass would wait for, so k_occ_bbox reads the boxes off the finished images instead.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_bank_stream(BankTables t, Geom g, int32_t* __restrict__ tables,
+                                                     uint32_t* __restrict__ occ, int32_t* __restrict__ status) {
+  const int4 c = t.chunks[blockIdx.x];
+  const int seg = c.x, sample = c.z;
+  if ((uint32_t)seg >= (uint32_t)t.n_seg || (uint32_t)sample >= (uint32_t)t.batch || c.y < 0) return;
+  if (MODE == 0 && t.centre_count[sample] >= 0) return;
+  const int64_t s0 = t.seg_start[seg];
+  const int32_t cnt = t.seg_count[seg];
+  if (s0 < 0 || s0 > t.n_bank || cnt <= c.y) return;
+  const int64_t begin = s0 + c.y;
+  const int64_t len = cnt - c.y < t.chunk_points ? cnt - c.y : t.chunk_points;
+  const int64_t end = begin + len < t.n_bank ? begin + len : t.n_bank;
+  double m[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) m[j] = t.tf[(int64_t)seg * 16 + j];
+  const int64_t words_per_slot = (int64_t)g.nx * g.wpr;
+  int32_t* table = tables + (int64_t)sample * kIds;
+  uint32_t* socc = occ + (int64_t)sample * t.max_instances * words_per_slot;
+  for (int64_t q = (begin >> 2) + threadIdx.x; q * 4 < end; q += 256) {
+    const int64_t base = q * 4;
+    int32_t id[4] = {0, 0, 0, 0};
+    float xyz[12];
+    if (base + 4 <= t.n_bank) {
+      const int4 v = reinterpret_cast<const int4*>(t.inst)[q];
+      id[0] = v.x; id[1] = v.y; id[2] = v.z; id[3] = v.w;
+      const float4* p = reinterpret_cast<const float4*>(t.pts) + q * 3;
+      const float4 a = p[0], b = p[1], d = p[2];
+      xyz[0] = a.x; xyz[1] = a.y; xyz[2] = a.z; xyz[3] = a.w; xyz[4] = b.x; xyz[5] = b.y; xyz[6] = b.z; xyz[7] = b.w;
+      xyz[8] = d.x; xyz[9] = d.y; xyz[10] = d.z; xyz[11] = d.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool in = base + j < t.n_bank;
+        id[j] = in ? t.inst[base + j] : 0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) xyz[j * 3 + e] = in ? t.pts[(base + j) * 3 + e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (base + j < begin || base + j >= end || id[j] == 0) continue;
+      if ((uint32_t)id[j] >= (uint32_t)kIds) { atomicOr(status + sample, 2); continue; }
+      // A bank holds labelled points only, hundreds on every cell of an instance: what is already known is read first (a
+      // flag or bit only ever gets set during a pass, so a stale 0 costs one redundant store or atomic and nothing else).
+      const int known = __atomic_load_n(table + id[j], __ATOMIC_RELAXED);    // MODE 0: the flag, MODE 1: the slot
+      if (MODE == 0 ? known != 0 : known < 0) continue;
+      int ix, iy;
+      if (!cell_of(m, (double)xyz[j * 3], (double)xyz[j * 3 + 1], (double)xyz[j * 3 + 2], g, ix, iy)) continue;
+      if (MODE == 0) {
+        table[id[j]] = 1;
+      } else {
+        const uint32_t* word = socc + known * words_per_slot + (int64_t)ix * g.wpr + (iy >> 5);
+        if (__atomic_load_n(word, __ATOMIC_RELAXED) & (1u << (iy & 31))) continue;
+        atomicOr(socc + known * words_per_slot + (int64_t)ix * g.wpr + (iy >> 5), 1u << (iy & 31));
+      }
+    }
+  }
+}
+
+// the inclusive cell bounds of the set bits of slot blockIdx.x of sample blockIdx.y (gridDim.x slots a sample): exactly what
+// k_stream's atomicMin / Max leave, (INT_MAX, INT_MAX, -1, -1) for an empty image
+__global__ void __launch_bounds__(256) k_occ_bbox(const uint32_t* __restrict__ occ, const int32_t* __restrict__ n_slots,
+                                                  int nx, int wpr, int32_t* __restrict__ bbox) {
+  __shared__ int bb[4];
+  const int slot = blockIdx.x, sample = blockIdx.y;
+  if (slot >= n_slots[sample]) return;
+  const int64_t first = (int64_t)sample * gridDim.x + slot;
+  const uint32_t* img = occ + first * nx * wpr;
+  if (threadIdx.x == 0) { bb[0] = INT_MAX; bb[1] = INT_MAX; bb[2] = -1; bb[3] = -1; }
+  __syncthreads();
+  int x0 = INT_MAX, y0 = INT_MAX, x1 = -1, y1 = -1;
+  for (int i = threadIdx.x; i < nx * wpr; i += 256) {
+    const uint32_t v = img[i];
+    if (!v) continue;
+    const int r = i / wpr, w = i - r * wpr;
+    x0 = min(x0, r); x1 = max(x1, r);
+    y0 = min(y0, w * 32 + __ffs((int)v) - 1); y1 = max(y1, w * 32 + 31 - __clz((int)v));
+  }
+  if (x1 >= 0) { atomicMin(&bb[0], x0); atomicMin(&bb[1], y0); atomicMax(&bb[2], x1); atomicMax(&bb[3], y1); }
+  __syncthreads();
+  if (threadIdx.x < 4) bbox[first * 4 + threadIdx.x] = bb[threadIdx.x];
+}
+
+// remove_unseen: the labels of sample blockIdx.y's centre scan counted per id, in the sample's table
+__global__ void __launch_bounds__(256) k_bank_centre_count(BankTables t, int32_t* __restrict__ tables,
+                                                           int32_t* __restrict__ status) {
+  const int sample = blockIdx.y;
+  const int64_t n = t.centre_count[sample], s0 = t.centre_start[sample];
+  if (n <= 0 || s0 < 0 || s0 > t.n_bank) return;
+  const int64_t end = s0 + n < t.n_bank ? s0 + n : t.n_bank;
+  int32_t* table = tables + (int64_t)sample * kIds;
+  for (int64_t i = s0 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)gridDim.x * 256) {
+    const int32_t id = t.inst[i];
+    if (id == 0) continue;
+    if ((uint32_t)id >= (uint32_t)kIds) { atomicOr(status + sample, 2); continue; }
+    atomicAdd(table + id, 1);
+  }
+}
+
+// table[id] (a flag or a count) >= threshold -> slot (ascending id order), everything else -> -1.  Sample blockIdx.y of
+// sample-major tables; `centre_count` (null: `threshold` for every sample) < 0 for a sample makes its threshold 1.
+__global__ void __launch_bounds__(1024) k_scan_table(int32_t* __restrict__ table, int threshold,
+                                                     const int32_t* __restrict__ centre_count, int max_instances,
                                                      int32_t* __restrict__ slot_ids, int32_t* __restrict__ bbox,
                                                      int32_t* __restrict__ n_slots, int32_t* __restrict__ status) {
   __shared__ int wave_total[16];
   constexpr int kPer = kIds / 1024;
+  const int sample = blockIdx.y;
+  if (centre_count && centre_count[sample] < 0) threshold = 1;
+  table += (int64_t)sample * kIds;
+  slot_ids += (int64_t)sample * max_instances;
+  bbox += (int64_t)sample * max_instances * 4;
+  n_slots += sample;
+  status += sample;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int mine = 0;
-  for (int j = 0; j < kPer; ++j) {
-    const int id = t * kPer + j;
-    mine += (id != 0 && table[id] >= threshold) ? 1 : 0;
+  // the thread's kPer = 64 entries are 16 int4 (the table is 256-byte aligned): all in flight at once, kept as one bit each
+  static_assert(kPer == 64, "one presence bit per entry in a 64-bit word");
+  int4* mine4 = reinterpret_cast<int4*>(table + t * kPer);
+  uint64_t present = 0;
+#pragma unroll
+  for (int q = 0; q < kPer / 4; ++q) {
+    const int4 v = mine4[q];
+    present |= (uint64_t)(v.x >= threshold) << (q * 4) | (uint64_t)(v.y >= threshold) << (q * 4 + 1) |
+               (uint64_t)(v.z >= threshold) << (q * 4 + 2) | (uint64_t)(v.w >= threshold) << (q * 4 + 3);
   }
+  if (t == 0) present &= ~(uint64_t)1;               // id 0 is no instance
+  const int mine = __popcll(present);
   int incl = mine;                                   // inclusive scan inside the wave
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
@@ -153,19 +302,24 @@ __global__ void __launch_bounds__(1024) k_scan_table(int32_t* __restrict__ table
     total += wave_total[w];
   }
   int slot = before + incl - mine;
-  for (int j = 0; j < kPer; ++j) {
-    const int id = t * kPer + j;
-    const bool present = id != 0 && table[id] >= threshold;
-    int s = -1;
-    if (present) {
-      if (slot < max_instances) {
-        s = slot;
-        slot_ids[s] = id;
-        bbox[s * 4 + 0] = INT_MAX; bbox[s * 4 + 1] = INT_MAX; bbox[s * 4 + 2] = -1; bbox[s * 4 + 3] = -1;
+#pragma unroll
+  for (int q = 0; q < kPer / 4; ++q) {
+    int s4[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = q * 4 + e, id = t * kPer + j;
+      int s = -1;
+      if ((present >> j) & 1) {
+        if (slot < max_instances) {
+          s = slot;
+          slot_ids[s] = id;
+          bbox[s * 4 + 0] = INT_MAX; bbox[s * 4 + 1] = INT_MAX; bbox[s * 4 + 2] = -1; bbox[s * 4 + 3] = -1;
+        }
+        ++slot;
       }
-      ++slot;
+      s4[e] = s;
     }
-    table[id] = s;
+    mine4[q] = make_int4(s4[0], s4[1], s4[2], s4[3]);
   }
   if (t == 0) {
     n_slots[0] = total < max_instances ? total : max_instances;
@@ -173,9 +327,11 @@ __global__ void __launch_bounds__(1024) k_scan_table(int32_t* __restrict__ table
   }
 }
 
+// sample blockIdx.y: its images start `sample_words` after the previous sample's
 __global__ void __launch_bounds__(256) k_clear_occ(uint32_t* __restrict__ occ, const int32_t* __restrict__ n_slots,
-                                                   int64_t words_per_slot) {
-  const int64_t total = (int64_t)n_slots[0] * words_per_slot;
+                                                   int64_t words_per_slot, int64_t sample_words) {
+  const int64_t total = (int64_t)n_slots[blockIdx.y] * words_per_slot;
+  occ += blockIdx.y * sample_words;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) occ[i] = 0u;
 }
 
@@ -225,6 +381,14 @@ __global__ void __launch_bounds__(kMorphThreads) k_morph_paint(const uint32_t* _
                                                                int32_t* __restrict__ map) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_img[];      // two images of kImgWords
   const int slot = blockIdx.x;
+  {                                  // sample blockIdx.y of sample-major tables of gridDim.x slots each
+    const int64_t first = (int64_t)blockIdx.y * gridDim.x;
+    n_slots += blockIdx.y;
+    bbox += first * 4;
+    slot_ids += first;
+    occ += first * nx * ((ny + 31) >> 5);
+    map += (int64_t)blockIdx.y * nx * ny;
+  }
   if (slot >= n_slots[0]) return;
   const int xmin = bbox[slot * 4 + 0], ymin = bbox[slot * 4 + 1], xmax = bbox[slot * 4 + 2], ymax = bbox[slot * 4 + 3];
   if (xmax < 0 || ymax < 0 || xmin > xmax || ymin > ymax || xmin < 0 || ymin < 0 || xmax >= nx || ymax >= ny) return;
@@ -279,14 +443,15 @@ struct Workspace {
   size_t bytes;
 };
 
-Workspace carve(void* base, int nx, int ny, int max_instances) {
+// `batch` samples: every table sample-major
+Workspace carve(void* base, int nx, int ny, int max_instances, int batch = 1) {
   MbvCarver c(base);
   Workspace w;
-  w.table = c.take<int32_t>(kIds);
-  w.n_slots = c.take<int32_t>(1);
-  w.slot_ids = c.take<int32_t>((size_t)max_instances);
-  w.bbox = c.take<int32_t>((size_t)max_instances * 4);
-  w.occ = c.take<uint32_t>((size_t)max_instances * nx * ((ny + 31) / 32));
+  w.table = c.take<int32_t>((size_t)batch * kIds);
+  w.n_slots = c.take<int32_t>((size_t)batch);
+  w.slot_ids = c.take<int32_t>((size_t)batch * max_instances);
+  w.bbox = c.take<int32_t>((size_t)batch * max_instances * 4);
+  w.occ = c.take<uint32_t>((size_t)batch * max_instances * nx * ((ny + 31) / 32));
   w.bytes = c.off;
   return w;
 }
@@ -297,9 +462,9 @@ bool kernel_ok(int k) { return k >= 1 && k <= 31 && (k & 1); }
 bool band_ok(int ny, int k) { return kImgWords / ((ny + 31) / 32) - 8 * (k / 2) >= 1; }
 
 int launch_paint(const uint32_t* occ, const int32_t* bbox, const int32_t* slot_ids, const int32_t* n_slots,
-                 int n_slots_max, int nx, int ny, int k, int32_t* map, hipStream_t stream) {
-  MBV_CHECK_HIP(mbv_fill_async(map, 0, sizeof(int32_t) * (size_t)nx * ny, stream));
-  hipLaunchKernelGGL(k_morph_paint, dim3(n_slots_max), dim3(kMorphThreads), 2 * kImgWords * sizeof(uint32_t), stream,
+                 int n_slots_max, int nx, int ny, int k, int32_t* map, hipStream_t stream, int batch = 1) {
+  MBV_CHECK_HIP(mbv_fill_async(map, 0, sizeof(int32_t) * (size_t)nx * ny * batch, stream));
+  hipLaunchKernelGGL(k_morph_paint, dim3(n_slots_max, batch), dim3(kMorphThreads), 2 * kImgWords * sizeof(uint32_t), stream,
                      occ, bbox, slot_ids, n_slots, nx, ny, k, map);
   MBV_CHECK_LAUNCH();
   return MBV_OK;
@@ -371,10 +536,10 @@ extern "C" int mbv_rasterize(const void* points, int32_t points_f64, int32_t str
                                         w, status, stream);
       if (rc != MBV_OK) return rc;
     }
-    hipLaunchKernelGGL(k_scan_table, dim3(1), dim3(1024), 0, stream, w.table, threshold, max_instances, w.slot_ids, w.bbox,
-                       w.n_slots, status);
+    hipLaunchKernelGGL(k_scan_table, dim3(1), dim3(1024), 0, stream, w.table, threshold, (const int32_t*)nullptr,
+                       max_instances, w.slot_ids, w.bbox, w.n_slots, status);
     MBV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_clear_occ, dim3(1024), dim3(256), 0, stream, w.occ, w.n_slots, (int64_t)nx * g.wpr);
+    hipLaunchKernelGGL(k_clear_occ, dim3(1024), dim3(256), 0, stream, w.occ, w.n_slots, (int64_t)nx * g.wpr, (int64_t)0);
     MBV_CHECK_LAUNCH();
     if (n_points > 0) {
       const int rc = dispatch_stream<1>(points, points_f64, stride, inst, n_points, scan_offsets, n_scans, transforms, g,
@@ -395,4 +560,70 @@ extern "C" int mbv_rasterize_paint(const uint32_t* occupancy, const int32_t* bbo
   if (!band_ok(ny, morph_kernel)) return MBV_ERR_UNSUPPORTED;
   if (!occupancy || !bbox || !slot_ids || !n_slots || !instance_map) return MBV_ERR_BAD_ARG;
   return launch_paint(occupancy, bbox, slot_ids, n_slots, n_slots_max, nx, ny, morph_kernel, instance_map, stream);
+}
+
+extern "C" size_t mbv_rasterize_bank_workspace_bytes(int32_t batch, int32_t nx, int32_t ny, int32_t max_instances) {
+  if (batch < 1 || batch > 65535 || !geometry_ok(nx, ny) || max_instances < 1 || max_instances >= kIds) return 0;
+  return carve(nullptr, nx, ny, max_instances, batch).bytes;
+}
+
+extern "C" int mbv_rasterize_bank(const float* points, const int32_t* inst, int64_t n_bank, const int64_t* seg_start,
+                                  const int32_t* seg_count, int32_t n_seg, const double* transforms,
+                                  const int32_t* chunks, int32_t n_chunks, int32_t chunk_points,
+                                  const int64_t* centre_start, const int32_t* centre_count, int32_t batch, double x_lo,
+                                  double x_hi, double y_lo, double y_hi, double z_lo, double z_hi, double voxel_size,
+                                  int32_t nx, int32_t ny, int32_t morph_kernel, int32_t min_points,
+                                  int32_t max_instances, int32_t phases, int32_t* instance_maps, int32_t* status,
+                                  void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (batch == 0) return MBV_OK;
+  if (batch < 0 || batch > 65535 || !geometry_ok(nx, ny) || !kernel_ok(morph_kernel) || max_instances < 1 ||
+      max_instances >= kIds || n_bank < 0 || n_seg < 0 || n_chunks < 0 || chunk_points < 4 || (chunk_points & 3) ||
+      !(voxel_size > 0.0) || (phases & ~3) || phases == 0)
+    return MBV_ERR_BAD_ARG;
+  if (!band_ok(ny, morph_kernel)) return MBV_ERR_UNSUPPORTED;
+  if (!workspace || !status || !centre_start || !centre_count || ((phases & 2) && !instance_maps))
+    return MBV_ERR_BAD_ARG;
+  if (n_chunks > 0 && (!points || !inst || !seg_start || !seg_count || !transforms || !chunks || n_seg < 1 || n_bank < 1))
+    return MBV_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(inst) & 15) ||
+      (reinterpret_cast<uintptr_t>(points) & 15) || (reinterpret_cast<uintptr_t>(chunks) & 15))
+    return MBV_ERR_BAD_ARG;
+  const Workspace w = carve(workspace, nx, ny, max_instances, batch);
+  if (workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
+  if (phases & 1) {
+    Geom g;
+    g.x0 = x_lo; g.x1 = x_hi; g.y0 = y_lo; g.y1 = y_hi; g.z0 = z_lo; g.z1 = z_hi; g.vs = voxel_size;
+    g.nx = nx; g.ny = ny; g.wpr = (ny + 31) / 32;
+    BankTables t;
+    t.pts = points; t.inst = inst; t.n_bank = n_bank; t.seg_start = seg_start; t.seg_count = seg_count; t.n_seg = n_seg;
+    t.tf = transforms; t.chunks = reinterpret_cast<const int4*>(chunks); t.chunk_points = chunk_points;
+    t.centre_start = centre_start; t.centre_count = centre_count; t.batch = batch; t.max_instances = max_instances;
+    MBV_CHECK_HIP(mbv_fill_async(status, 0, sizeof(int32_t) * (size_t)batch, stream));
+    MBV_CHECK_HIP(mbv_fill_async(w.table, 0, sizeof(int32_t) * (size_t)batch * kIds, stream));
+    if (inst && n_bank > 0) {                                    // remove_unseen samples; the others leave at once
+      hipLaunchKernelGGL(k_bank_centre_count, dim3(16, batch), dim3(256), 0, stream, t, w.table, status);
+      MBV_CHECK_LAUNCH();
+    }
+    if (n_chunks > 0) {
+      hipLaunchKernelGGL(k_bank_stream<0>, dim3(n_chunks), dim3(256), 0, stream, t, g, w.table, w.occ, status);
+      MBV_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_scan_table, dim3(1, batch), dim3(1024), 0, stream, w.table, min_points > 1 ? min_points : 1,
+                       centre_count, max_instances, w.slot_ids, w.bbox, w.n_slots, status);
+    MBV_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_clear_occ, dim3(256, batch), dim3(256), 0, stream, w.occ, w.n_slots, (int64_t)nx * g.wpr,
+                       (int64_t)max_instances * nx * g.wpr);
+    MBV_CHECK_LAUNCH();
+    if (n_chunks > 0) {
+      hipLaunchKernelGGL(k_bank_stream<1>, dim3(n_chunks), dim3(256), 0, stream, t, g, w.table, w.occ, status);
+      MBV_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_occ_bbox, dim3(max_instances, batch), dim3(256), 0, stream, w.occ, w.n_slots, nx, g.wpr, w.bbox);
+      MBV_CHECK_LAUNCH();
+    }
+  }
+  if (phases & 2)
+    return launch_paint(w.occ, w.bbox, w.slot_ids, w.n_slots, max_instances, nx, ny, morph_kernel, instance_maps, stream,
+                        batch);
+  return MBV_OK;
 }

@@ -1,5 +1,5 @@
 """The launcher's data readers (the reference's DataModules are outside the hot path): synthetic scans, SemanticKITTI scans with
-the instance-map cache, KITTI object frames, as batches in the reference's batch contract with the targets built on the device."""
+the instance-map cache or with scene banks, KITTI object frames, as batches in the reference's batch contract with the targets built on the device."""
 import pathlib
 
 import numpy as np
@@ -9,7 +9,8 @@ from . import batch as B
 from . import synthetic as syn
 from .augment import DeviceAugmentation, make_kitti_augmentation_list, make_semantic_kitti_augmentation_list
 from .object_augment import ObjectBank, make_kitti_object_augmentation_list
-from .rasterize import KITTI_CAR_LIKE, KittiRasterizer
+from .rasterize import KITTI_CAR_LIKE, KittiRasterizer, SemanticKittiRasterizer
+from .scene_bank import SceneBank
 
 
 def shard(items, rank, world, bsz):
@@ -104,6 +105,105 @@ class SemanticKittiCacheBatches(ShardedBatches):
 
     def sample(self, pair):
         return torch.from_numpy(B.read_velodyne_bin(pair[0])), B.read_mask_cache(pair[1])
+
+
+def scene_sequences(root, sequences):
+    """Those of ``sequences`` under ``root`` that lie there as downloaded — ``velodyne/``, ``labels/``, ``poses.txt``,
+    ``calib.txt`` — as (sequence number, folder) pairs."""
+    found = []
+    for seq in sequences:
+        d = pathlib.Path(root).expanduser() / 'sequences' / f'{int(seq):02d}'
+        if (d / 'velodyne').is_dir() and (d / 'labels').is_dir() and (d / 'poses.txt').exists() and (d / 'calib.txt').exists():
+            found.append((int(seq), d))
+    if not found:
+        raise ValueError(f'no sequence with velodyne/, labels/, poses.txt and calib.txt among {list(sequences)} under {root}')
+    return found
+
+
+def scene_rasterizer(config):
+    """The rasteriser of a SemanticKITTI configuration, as the reference's data module builds its own."""
+    return SemanticKittiRasterizer(config['x_range'], config['y_range'], config['z_range'], config['voxel_size'],
+                                   bool(config.get('remove_unseen', False)), int(config.get('min_num_points', 1)))
+
+
+class SceneSequence:
+    """One sequence as the scene readers use it: ``scans`` (the ``.bin`` paths in scan order), ``poses`` (S, 4, 4) f64 in the
+    velodyne frame, and ``bank``, loaded from ``SceneBank.default_path`` when the file is there, else built from the label
+    files (and saved when ``save``)."""
+
+    def __init__(self, root, seq, folder, device, save=False, build_only=False):
+        self.seq, self.folder = seq, folder
+        self.scans = sorted((folder / 'velodyne').glob('*.bin'))
+        poses, v2c = B.read_poses(folder / 'poses.txt'), B.read_calib(folder / 'calib.txt')['velo_to_cam']
+        if len(poses) != len(self.scans):
+            raise ValueError(f'{folder}: {len(poses)} poses for {len(self.scans)} scans')
+        self.poses = np.linalg.inv(v2c) @ poses @ v2c
+        path = SceneBank.default_path(root, seq)
+        if path.exists() and not build_only:
+            self.bank = SceneBank.load(path, device, num_scans=len(self.scans))
+        else:
+            bank = SceneBank.build(self.scans, [folder / 'labels' / (f.stem + '.label') for f in self.scans])
+            if save:
+                bank.save(path)
+                print(f'scene bank: {len(bank)} scans, {bank.points.shape[0]} points -> {path}', flush=True)
+            self.bank = bank if build_only else bank.to(device)
+            if not build_only:
+                print(f'scene bank of sequence {seq:02d} built: {len(bank)} scans, {bank.points.shape[0]} points, '
+                      f'{bank.nbytes} bytes on {self.bank.device}', flush=True)
+
+    def scene(self, centre, config):
+        """(scan_indices, transforms) of the scene around scan ``centre``."""
+        return SceneBank.scene(centre, self.poses, None, config['x_range'], config['y_range'])
+
+
+class SemanticKittiSceneBatches(ShardedBatches):
+    """SemanticKITTI as downloaded, without a mask cache (``semantic_kitti_targets: scenes``): ``.bin`` scans, and targets
+    rasterised per batch from the sequences' scene banks on the GPU (K34) and expanded by K14.  ``files``: this rank's
+    ``(scan path, None)`` pairs.  ``augment``: apply the config's ``augmentations:`` (training batches only); its flips and
+    rotations go into the scene transforms, so no map is warped."""
+
+    def __init__(self, config, device, rank, world, root, sequences, augment=False):
+        save = bool(config.get('save_scene_bank', False)) and rank == 0
+        self.sequences = {seq: SceneSequence(root, seq, d, device, save) for seq, d in scene_sequences(root, sequences)}
+        items = [(seq, k, f) for seq, s in self.sequences.items() for k, f in enumerate(s.scans)]
+        super().__init__(config, rank, world, items, build_augmentation(config) if augment else None)
+        self.config, self.device, self.files = config, device, [(f, None) for _, _, f in self.items]
+        self.rasterizer = scene_rasterizer(config)
+        self.collate = B.BankSceneCollate(self.rasterizer, {seq: s.bank for seq, s in self.sequences.items()},
+                                          int(config['num_queries']), device, int(config.get('min_num_inst_pixels', 0)),
+                                          augmentation=self.augmentation)
+
+    def sample(self, item):
+        seq, k, path = item
+        index, transforms = self.sequences[seq].scene(k, self.config)
+        return torch.from_numpy(B.read_velodyne_bin(path)), (seq, index, transforms, k)
+
+
+def build_scene_banks(config, root, sequences):
+    """``--build-scene-bank``: the banks of ``sequences`` written next to their scans."""
+    for seq, d in scene_sequences(root, sequences):
+        SceneSequence(root, seq, d, None, save=True, build_only=True)
+    return [SceneBank.default_path(root, seq) for seq, _ in scene_sequences(root, sequences)]
+
+
+def build_mask_cache(config, device, root, sequences, overwrite=False, batch_size=8):
+    """``--build-mask-cache``: every scan of ``sequences`` rasterised through its sequence's bank (K34) and written as the
+    reference's mask cache, ``sequences/SS/mask_cache/NNNNNN.npy`` = ``np.save`` of the (nx, ny) int64 map.  Files that exist
+    are left alone unless ``overwrite``.  Returns the paths written."""
+    rasterizer, written = scene_rasterizer(config), []
+    for seq, d in scene_sequences(root, sequences):
+        s = SceneSequence(root, seq, d, device)
+        (d / 'mask_cache').mkdir(exist_ok=True)
+        todo = [(k, d / 'mask_cache' / (f.stem + '.npy')) for k, f in enumerate(s.scans)]
+        todo = [(k, p) for k, p in todo if overwrite or not p.exists()]
+        for i in range(0, len(todo), batch_size):
+            part = todo[i:i + batch_size]
+            maps = rasterizer.rasterize_bank(s.bank, [(*s.scene(k, config), k) for k, _ in part]).cpu().numpy()
+            for (_, p), m in zip(part, maps):
+                np.save(p, m.astype(np.int64))
+                written.append(p)
+        print(f'mask cache: sequence {seq:02d}, {len(todo)} of {len(s.scans)} scans written', flush=True)
+    return written
 
 
 def build_kitti_augmentation(config):

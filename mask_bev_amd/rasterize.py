@@ -4,6 +4,9 @@ and one OpenCV call pair per instance, and therefore caches on disk.  The map is
 (K14), so a training step needs neither the reference's cache nor OpenCV, and a scene can be rasterised after a
 point-level augmentation: ``augment.DeviceAugmentation`` (K23) folds its flips and rotations into ``transforms``.
 
+``rasterize_bank`` (K34) does the same for a whole batch in one native call on a ``scene_bank.SceneBank`` — the labelled points
+of a sequence, kept on the device — without copying a scan: what the launcher uses for ``semantic_kitti_targets: scenes``.
+
 Where two closed-and-opened instances claim one cell the HIGHEST ID wins (the reference paints in the hash order of a
 Python set); everywhere else the map equals the reference's.  Not covered: the approximate scene branch.
 
@@ -143,6 +146,64 @@ class SemanticKittiRasterizer:
         for b, scene in enumerate(scenes):
             self.rasterize(scene[0], scene[1], scene[2], scene[3] if len(scene) > 3 else None,
                            check_overflow=check_overflow, out=maps[b])
+        return maps
+
+    def bank_tables(self, bank, scenes: Sequence):
+        """``rasterize_bank``'s scenes as the host tables of ``ops_rasterize.rasterize_bank``: (seg_start, seg_count,
+        sample_seg_offsets, transforms, centre_start, centre_count)."""
+        offsets, n_scans = bank.scan_offsets, len(bank)
+        index, tfs, c_start, c_count = [], [], [], []
+        for scans, transforms, *rest in scenes:
+            scans = np.asarray(scans, dtype=np.int64).reshape(-1)
+            tf = np.asarray(transforms.detach().cpu().numpy() if isinstance(transforms, torch.Tensor) else transforms,
+                            dtype=np.float64).reshape(-1, 4, 4)
+            if tf.shape[0] != scans.size:
+                raise ValueError(f'{tf.shape[0]} transforms for {scans.size} scans')
+            if scans.size and (scans.min() < 0 or scans.max() >= n_scans):
+                raise IndexError(f'a scene names a scan outside 0 … {n_scans - 1}')
+            centre = rest[0] if rest else None
+            if self.remove_unseen:
+                if centre is None:
+                    raise ValueError('remove_unseen=True needs the centre scan of every scene')
+                if not 0 <= int(centre) < n_scans:
+                    raise IndexError(f'centre scan {centre} outside 0 … {n_scans - 1}')
+                c_start.append(offsets[int(centre)])
+                c_count.append(offsets[int(centre) + 1] - offsets[int(centre)])
+            else:
+                c_start.append(0)
+                c_count.append(-1)
+            index.append(scans)
+            tfs.append(tf)
+        tf = np.concatenate(tfs)
+        if not np.allclose(tf[:, 3, :], [0., 0., 0., 1.], rtol=0, atol=1e-12):
+            raise ValueError('the last row of every transform must be 0 0 0 1')
+        scans = np.concatenate(index)
+        return (offsets[scans], offsets[scans + 1] - offsets[scans], np.concatenate([[0], np.cumsum([len(i) for i in index])]),
+                tf, np.asarray(c_start, dtype=np.int64), np.asarray(c_count, dtype=np.int64))
+
+    @torch.no_grad()
+    def rasterize_bank(self, bank, scenes: Sequence, out: Optional[torch.Tensor] = None,
+                       check_overflow: bool = False) -> torch.Tensor:
+        """The scenes of a whole batch from a ``scene_bank.SceneBank`` that lives on the device, in one native call (K34):
+        ``scenes`` is a list of ``(scan_indices (k), transforms (k, 4, 4) f64, centre_scan or None)`` — the scans of the bank
+        that make up the sample's scene, the matrices that take them into its frame (``SceneBank.scene``) and, for
+        ``remove_unseen``, the scan whose labels name the instances.  The bank is read in place: no scan is copied or
+        concatenated.  Map b equals ``rasterize`` on the listed scans, bit for bit.  → (B, nx, ny) int32 on the device.
+        ``check_overflow`` reads the B status words in one host copy and raises as ``rasterize`` does."""
+        if len(scenes) == 0:
+            raise ValueError('empty batch')
+        if not bank.points.is_cuda:
+            raise MaskBevHipError('SemanticKittiRasterizer needs ROCm device tensors (no CPU fallback)')
+        maps, status, _ = ops_rasterize.rasterize_bank(
+            bank.points, bank.inst, *self.bank_tables(bank, scenes), self.x_range, self.y_range, self.z_range,
+            self.voxel_size, self.nx, self.ny, self.morph_kernel_size, self.min_points, self.max_instances, out=out)
+        if check_overflow:
+            st = status.cpu().numpy()
+            if (st & 1).any():
+                raise IndexError(f'scene {int(np.flatnonzero(st & 1)[0])} holds more than max_instances = '
+                                 f'{self.max_instances} instances')
+            if (st & 2).any():
+                raise MaskBevHipError('an instance id outside 0 … 65535 (SemanticKITTI ids are 16 bits)')
         return maps
 
     def get_mask_around(self, scan, scene, device=None) -> torch.Tensor:

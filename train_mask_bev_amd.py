@@ -26,6 +26,13 @@ boxes on the GPU (rasterize.KittiRasterizer, K24) in front of K14.  ``dataset: w
 frames); ``rasterize.WaymoRasterizer`` with ``batch.BoxCollate`` makes its batches from box tables.  The config's
 ``augmentations:`` list is applied to the training batches on the GPU (mask_bev_amd/augment.py, K23), never to validation.
 
+``semantic_kitti_targets: scenes`` (default ``cache``) needs no mask cache: the dataset as downloaded is enough
+(``sequences/SS/velodyne/``, ``labels/``, ``poses.txt``, ``calib.txt``).  The instance-labelled points of every sequence stay on
+the GPU as a scene bank (mask_bev_amd/scene_bank.py; ``sequences/SS/instance_points.npz`` when there, else built from the label
+files, and saved with ``save_scene_bank: true``), and each batch's instance maps are rasterised from it in one native call (K34).
+``--build-scene-bank`` writes the banks of the train and validation sequences and exits; ``--build-mask-cache`` [``--overwrite``]
+writes the reference's ``mask_cache/NNNNNN.npy`` files from them and exits.
+
 ``--test`` extras: ``dataset: kitti`` prints the Car BEV AP block, with ``kitti_3d: true`` (optional ``kitti_3d_extent:
 [q_lo, q_hi]``) also the ``3d   AP:`` lines from heights lifted out of the scans (K31, K26b); ``dataset: semantic-kitti`` with
 ``--write-labels DIR`` writes the per-point instance labels of every validated scan (K31) to
@@ -228,6 +235,13 @@ def main(argv=None):
     parser.add_argument('--checkpoint-root', default='checkpoints')
     parser.add_argument('--build-object-bank', action='store_true',
                         help='dataset: kitti: write the object bank of object_sample from the training split and exit')
+    parser.add_argument('--build-scene-bank', action='store_true',
+                        help='dataset: semantic-kitti: write sequences/SS/instance_points.npz of the train and validation '
+                             'sequences and exit')
+    parser.add_argument('--build-mask-cache', action='store_true',
+                        help='dataset: semantic-kitti: write sequences/SS/mask_cache/NNNNNN.npy of the train and validation '
+                             'sequences through the scene banks and exit')
+    parser.add_argument('--overwrite', action='store_true', help='--build-mask-cache: rewrite the files that exist')
     parser.add_argument('--write-labels', default=None, metavar='DIR',
                         help='dataset: semantic-kitti with --test: write the per-point instance labels of every validated '
                              'scan to DIR/sequences/SS/predictions/NNNNNN.label')
@@ -272,6 +286,17 @@ def main(argv=None):
             raise ValueError('--build-object-bank needs dataset: kitti')
         datasets.build_object_bank(config, device, args.data_root or 'data/KITTI')
         return
+    if args.build_scene_bank or args.build_mask_cache:
+        if config.get('dataset', 'semantic-kitti') != 'semantic-kitti':
+            raise ValueError('--build-scene-bank and --build-mask-cache need dataset: semantic-kitti')
+        root = args.data_root or 'data/SemanticKITTI'
+        sequences = list(dict.fromkeys(list(config.get('train_sequences', [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]))
+                                      + list(config.get('val_sequences', [8]))))         # each sequence once
+        if args.build_scene_bank:
+            datasets.build_scene_banks(config, root, sequences)
+        if args.build_mask_cache:
+            datasets.build_mask_cache(config, device, root, sequences, args.overwrite)
+        return
     if world > 1:
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         backend = os.environ.get('MBV_DIST_BACKEND', 'nccl')       # 'nccl' is RCCL on ROCm
@@ -294,10 +319,14 @@ def main(argv=None):
         val = None
     elif dataset_name == 'semantic-kitti':
         args.data_root = args.data_root or 'data/SemanticKITTI'
-        data = datasets.SemanticKittiCacheBatches(config, device, rank, world, args.data_root,
-                                                  config.get('train_sequences', [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]), augment=True)
-        val = datasets.SemanticKittiCacheBatches(dict(config, shuffle_train=False), device, rank, world, args.data_root,
-                                                 config.get('val_sequences', [8])) if limit_val_batches > 0 else None
+        targets = config.get('semantic_kitti_targets', 'cache')
+        if targets not in ('cache', 'scenes'):
+            raise ValueError(f'semantic_kitti_targets must be cache or scenes, got {targets}')
+        reader = datasets.SemanticKittiSceneBatches if targets == 'scenes' else datasets.SemanticKittiCacheBatches
+        data = reader(config, device, rank, world, args.data_root,
+                      config.get('train_sequences', [0, 1, 2, 3, 4, 5, 6, 7, 9, 10]), augment=True)
+        val = reader(dict(config, shuffle_train=False), device, rank, world, args.data_root,
+                     config.get('val_sequences', [8])) if limit_val_batches > 0 else None
     elif dataset_name == 'kitti':
         args.data_root = args.data_root or 'data/KITTI'
         data = datasets.KittiObjectBatches(config, device, rank, world, args.data_root, 'train', augment=True)
