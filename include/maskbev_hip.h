@@ -1596,6 +1596,66 @@ int mbv_lift_instances(const float* points, int32_t point_dim, int64_t total_poi
                        float* z_extent, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K35 — a ground height for every BEV cell from the scan itself, and K31's lift restricted to the returns above it
+ * (csrc/point_lift.hip, built with -ffp-contract=off; the numpy restatement of the words below is tests/ground_ref.py).
+ * A BEV mask is a footprint: K31 labels the road returns inside it too.  K35a estimates the ground under every cell as the
+ * lowest return nearby, K35b keeps a point's query only when the point stands clear of that height.
+ *
+ * K35a — mbv_ground_map.  points, point_dim, total_points, scan_offsets, batch, x_min .. gz, prefilter: as in K31.
+ * radius        cells, 0 .. 32;  z_floor f32, may be -inf
+ * A point TAKES PART iff K1's cell rule accepts it — the arithmetic of K31's point_query, the same device function: separate
+ * IEEE f32 subtract and divide, floorf, the rejection on all three axes, the strict pre-filter first under `prefilter`; NaN
+ * fails every compare — and, in addition, z >= z_floor (a NaN z_floor lets no point take part).
+ * cell_min      (batch, gy, gx) f32, row = y-cell, column = x-cell (the layout of instance_map): the minimum z of the points
+ *               that take part in the cell, +inf for a cell without one.  The minimum is taken on the order-preserving u32
+ *               encoding of K31 (negative numbers: all bits flipped; others: the sign bit set) with integer atomicMin, so
+ *               -0.0 < +0.0 and the result does not depend on the order of the points.
+ * ground        (batch, gy, gx) f32: the minimum — on the same encoding — of cell_min over cy' in [max(0, cy - radius),
+ *               min(gy - 1, cy + radius)] and cx' likewise; +inf when the whole window is empty.  radius = 0: ground ==
+ *               cell_min.
+ * workspace     the byte count the _workspace_bytes entry returns (0 for sizes out of range): two (batch, gy, gx) u32 planes,
+ *               the encoded cell minima and their row-window minima.
+ * Every element of both outputs and of the workspace is written by a kernel; nothing has to be pre-set.  Four launches
+ * whatever the batch (initialise; one thread per point, integer atomicMin; the window minimum along x; along y), three
+ * when total_points == 0 (both maps are +inf then).  The two window passes work on tiles of 64 x 16 and 64 x 64 cells staged
+ * in LDS with a halo of `radius` cells: no cell is read from memory more than once per tile that needs it.  16-byte accesses
+ * when gx is a multiple of 4 and the outputs and the workspace are 16-byte aligned, dword accesses otherwise (one condition
+ * for every path).  Bit-deterministic.  No host synchronisation, no allocation.
+ * batch == 0: MBV_OK, nothing is written.  MBV_ERR_UNSUPPORTED: radius > 32, batch > 65535, total_points >= 2^31 - 1, gx or
+ * gy > 65536;  MBV_ERR_BAD_ARG: a negative size, radius < 0, point_dim other than 3 or 4, a grid size < 1, a null output,
+ * null points or scan_offsets with total_points > 0;  MBV_ERR_WORKSPACE: a workspace that is too small.
+ *
+ * K35b — mbv_lift_instances_ground: K31 with a ground map.  All arguments of mbv_lift_instances, and
+ * ground        (batch, gy, gx) f32, K35a's (or any map of that layout)
+ * clearance, max_height   f32; max_height may be +inf
+ * q is found exactly as in K31.  With g = ground[b][cy][cx] the point KEEPS q iff  z > g + clearance  and
+ * z <= g + max_height, each sum one rounded f32 addition; otherwise it gets -1.  There are no special cases: g = +inf (an
+ * empty window) fails the first compare, a NaN anywhere fails both.
+ * counts, z_extent        K31's, over the kept points only
+ * z_ground      (batch, num_queries) f32: the minimum of g over the kept points of the query, on the integer encoding; 0
+ *               for a query without a kept point.
+ * The device code is K31's: one kernel body, instantiated with and without the ground.  Launches, determinism, the cases
+ * batch * num_queries == 0 and total_points == 0 (z_ground: zeros) and the error codes are K31's; ground and z_ground must
+ * not be null when there is work.
+ *
+ * Not pinned: the defaults of the host API (a window of 1.6 m, a clearance of 0.3 m) rest on geometry — half a car's width
+ * plus slack; above road noise and the 8 cm a window minimum loses on a 5 % slope, below a sill — not on measurement.  One
+ * return below the road (a multipath reflection) pulls the ground down over its whole window; z_floor is the only defence.
+ */
+size_t mbv_ground_map_workspace_bytes(int32_t batch, int32_t gx, int32_t gy);
+int mbv_ground_map(const float* points, int32_t point_dim, int64_t total_points, const int32_t* scan_offsets, int32_t batch,
+                   float x_min, float y_min, float z_min, float x_max, float y_max, float z_max, float vx, float vy, float vz,
+                   int32_t gx, int32_t gy, int32_t gz, int32_t prefilter, int32_t radius, float z_floor, float* cell_min,
+                   float* ground, void* workspace, size_t workspace_bytes, void* stream);
+size_t mbv_lift_instances_ground_workspace_bytes(int32_t batch, int32_t num_queries, int32_t z_bins);
+int mbv_lift_instances_ground(const float* points, int32_t point_dim, int64_t total_points, const int32_t* scan_offsets,
+                              int32_t batch, float x_min, float y_min, float z_min, float x_max, float y_max, float z_max,
+                              float vx, float vy, float vz, int32_t gx, int32_t gy, int32_t gz, int32_t prefilter,
+                              const int32_t* instance_map, int32_t num_queries, int32_t z_bins, float q_lo, float q_hi,
+                              const float* ground, float clearance, float max_height, int32_t* point_query, int32_t* counts,
+                              float* z_extent, float* z_ground, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K32 — panoptic quality of point or BEV instances (csrc/panoptic.hip): per frame the tp / fp / fn, the IoU sums and the
  * confusion of the SemanticKITTI panoptic protocol, PanopticEval.addBatchPanoptic of semantic-kitti-api's eval_np.py,
  * restated, not repaired.  Parity with that package is not pinned (it is not installed); the numpy restatement in its own

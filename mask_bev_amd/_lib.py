@@ -216,6 +216,12 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_lift_instances_workspace_bytes': (c_size_t, [_I, _I, _I]),
     'mbv_lift_instances': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _I, _I,
                                           _F, _F, _P, _P, _P, _P, c_size_t, _P]),
+    'mbv_ground_map_workspace_bytes': (c_size_t, [_I, _I, _I]),
+    'mbv_ground_map': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _F, _P, _P,
+                                      _P, c_size_t, _P]),
+    'mbv_lift_instances_ground_workspace_bytes': (c_size_t, [_I, _I, _I]),
+    'mbv_lift_instances_ground': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _I,
+                                                 _I, _F, _F, _P, _F, _F, _P, _P, _P, _P, _P, c_size_t, _P]),
     'mbv_panoptic_frames_workspace_bytes': (c_size_t, [_I, _I, _I, _I]),
     'mbv_panoptic_frames': (ctypes.c_int, [_P, _P, _L, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                                            c_size_t, _P]),

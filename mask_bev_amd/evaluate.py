@@ -1,5 +1,6 @@
 """What ``--test`` runs after the validation loss, one pass over the scans per feature: KITTI BEV / 3D AP (K25-K27, K30, K31),
-per-point labels (K31), their panoptic quality (K32), tracking with LSTQ (K33); the settings and printed lines of each."""
+per-point labels (K31), their panoptic quality (K32), tracking with LSTQ (K33); the settings and printed lines of each.  With
+``lift_ground: true`` every lift labels only the returns above a ground estimate made from the scan itself (K35)."""
 import pathlib
 
 import numpy as np
@@ -9,7 +10,7 @@ from . import batch as B
 from .datasets import KittiFrames, semantic_kitti_files
 from .kitti_eval import eval_kitti
 from .metrics import DevicePanopticQuality, DeviceTubeAssociation, lstq, semantic_kitti_class_lut
-from .predict import BOX_METHODS, write_semantic_kitti_labels
+from .predict import BOX_METHODS, GroundSettings, write_semantic_kitti_labels
 from .tracking import InstanceTracker, velodyne_poses
 
 
@@ -41,6 +42,36 @@ def prediction_label_path(out_dir, scan_path):
     return d / (scan_path.stem + '.label')
 
 
+def lift_settings(config):
+    """The ground-aware lift of the configuration (K35), ``None`` when off: ``lift_ground`` (default false) switches it on;
+    ``lift_ground_radius`` (metres, default 1.6), ``lift_ground_clearance`` (default 0.3), ``lift_max_height`` and ``lift_z_floor``
+    (default none) fill a :class:`~mask_bev_amd.predict.GroundSettings`.  With a ``voxel_size`` in the configuration the radius
+    is checked here: more than 32 cells raises ``ValueError``.  The defaults rest on geometry, not on measurement."""
+    if not bool(config.get('lift_ground', False)):
+        return None
+    opt = lambda key: None if config.get(key) is None else float(config[key])
+    settings = GroundSettings(radius_m=float(config.get('lift_ground_radius', 1.6)),
+                              clearance=float(config.get('lift_ground_clearance', 0.3)), max_height=opt('lift_max_height'),
+                              z_floor=opt('lift_z_floor'))
+    if config.get('voxel_size') is not None:
+        settings.radius_cells(config['voxel_size'])
+    return settings
+
+
+def format_lift_settings(settings, voxel_size):
+    """The line ``--test`` prints in front of the results a ground-aware lift changes."""
+    extra = ''.join(f', {name} {value:g} m' for name, value in (('max height', settings.max_height), ('z floor', settings.z_floor))
+                    if value is not None)
+    return (f'ground-aware lift: radius {settings.radius_m:g} m ({settings.radius_cells(voxel_size)} cells), clearance '
+            f'{settings.clearance:g} m{extra}')
+
+
+def _ground(config):
+    """``pred.lift``'s keyword for the configuration: nothing when the ground-aware lift is off."""
+    settings = lift_settings(config)
+    return {} if settings is None else dict(ground=settings)
+
+
 def kitti_bev_evaluation(model, config, device, root, split='val', score_threshold=0.0, box_method=None):
     """Car BEV AP (easy / moderate / hard at overlaps 0.7 and 0.5) of ``model`` on every frame of ``<root>/<split>.txt``:
     ``model.predict`` per batch, an oriented box per kept mask (``Predictions.kitti_predictions``), then the KITTI protocol on
@@ -49,16 +80,20 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
     mask's largest component (K30), the reference's recipe.  All labels of a frame take part, unfiltered: the protocol decides
     what counts at which difficulty.  With ``kitti_3d: true`` every box gets the z-extent of the points inside its mask (K31;
     ``kitti_3d_extent: [q_lo, q_hi]``: histogram quantiles instead of the extremes) and a ``3d   AP:`` line follows every
-    ``bev  AP:`` line (K26b).  Returns the result (a string with ``.metrics``)."""
+    ``bev  AP:`` line (K26b); with ``lift_ground: true`` as well only the returns above the estimated ground count and the
+    boxes stand on it (K35, ``bottom='ground'``).  Returns the result (a string with ``.metrics``)."""
     method = box_method if box_method is not None else config.get('kitti_box_method', 'moment')
     if method not in BOX_METHODS:
         raise ValueError(f'kitti_box_method must be one of {BOX_METHODS}, got {method!r}')
     with_3d = bool(config.get('kitti_3d', False))
     extent = tuple(config['kitti_3d_extent']) if config.get('kitti_3d_extent') else 'minmax'
+    ground = _ground(config)
     tree = KittiFrames(root, split)
     labels, scan_paths, boxes = [tree.labels(f) for f in tree.frames], [tree.scan(f) for f in tree.frames], []
     for _, scans, pred in predictions(model, scan_paths, config.get('batch_size', 1), device, score_threshold):
         lift = dict(scans=scans, module=model, extent=extent) if with_3d else {}
+        if with_3d and ground:
+            lift.update(ground=ground['ground'], bottom='ground')
         boxes += pred.kitti_predictions(config['x_range'], config['y_range'], config['voxel_size'], method=method, **lift)
     return eval_kitti(labels, boxes, device=device)
 
@@ -66,10 +101,12 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
 def write_point_labels(model, config, device, files, out_dir, score_threshold=0.0, semantic_id=10):
     """Per-point instance labels of every scan of ``files`` — the (``.bin``, cache) pairs of a ``SemanticKittiCacheBatches``:
     ``model.predict`` per batch, the instance map lifted to the points (K31), one :func:`prediction_label_path` file per scan
-    (``uint32``: query + 1 in the upper 16 bits, ``semantic_id`` in the lower, 0 = unlabelled).  Returns the paths written."""
+    (``uint32``: query + 1 in the upper 16 bits, ``semantic_id`` in the lower, 0 = unlabelled).  ``lift_ground: true``: only the
+    returns above the estimated ground are labelled (:func:`lift_settings`).  Returns the paths written."""
     written = []
+    ground = _ground(config)
     for part, scans, pred in predictions(model, [f for f, _ in files], config.get('batch_size', 1), device, score_threshold):
-        for f, labels in zip(part, pred.lift(scans, model).per_scan()):
+        for f, labels in zip(part, pred.lift(scans, model, **ground).per_scan()):
             written.append(prediction_label_path(out_dir, f))
             write_semantic_kitti_labels(written[-1], labels, semantic_id)
     return written
@@ -99,9 +136,10 @@ def point_panoptic_evaluation(model, config, device, files, score_threshold=0.0)
     if not scans_of or not all(semantic_kitti_label_path(f).exists() for f in scans_of):
         return None
     metric = panoptic_metric(config)
+    ground = _ground(config)
     for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
         words = [read_label_words(semantic_kitti_label_path(f), device) for f in part]
-        pred.panoptic_points(pred.lift(scans, model), words, metric)
+        pred.panoptic_points(pred.lift(scans, model, **ground), words, metric)
     return metric
 
 
@@ -141,6 +179,7 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
     tubes = DeviceTubeAssociation(quality.num_classes, quality.class_lut('cpu'), id_limit=int(config.get('track_id_limit', 1024)),
                                   max_tracks=int(config.get('track_tube_tracks', 4096)))      # the same classes as `quality`
     out = dict(tracks=0, dropped=0, frames=0, written=[])
+    ground = _ground(config)
     assoc_sum, n_tubes = 0.0, 0
     for seq_dir, scans_of in by_seq.items():
         poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
@@ -148,7 +187,7 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
         tubes.reset()
         for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
             query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]])
-            lifted = pred.lift(scans, model)
+            lifted = pred.lift(scans, model, **ground)
             ids = pred.point_tracks(lifted, query_track)
             if have_labels:
                 words = [read_label_words(semantic_kitti_label_path(f), device) for f in part]

@@ -1,7 +1,8 @@
 """K21 — instance extraction at inference (csrc/instances.hip): query selection from the class logits and the BEV masks,
 areas, mask scores and instance map of one decoder output, straight from the (h, w) logits with no (B, Q, H, W)
 intermediate.  K31 — the lift of that instance map to the points of the scans (csrc/point_lift.hip): per-point query labels,
-points per query and their z-extent.  Class convention: index 0 = empty, > 0 = object; a pixel is set when its interpolated
+points per query and their z-extent.  K35 — a ground height per BEV cell from the scans themselves and the lift restricted to the
+returns above it (same file).  Class convention: index 0 = empty, > 0 = object; a pixel is set when its interpolated
 logit is > 0 (sigmoid > 0.5)."""
 from __future__ import annotations
 
@@ -83,7 +84,8 @@ class PointInstances:
     the concatenated scans the query that owns its BEV cell, -1 for none (and for every point K1 drops); ``scan_offsets``
     (B + 1) int32 on the device; ``counts`` (B, Q) int32 — lifted points per query; ``z_min``, ``z_max``, ``z_lo``, ``z_hi``
     (B, Q) f32 — the extremes of a query's points and the histogram edges of the two quantiles (include/maskbev_hip.h, K31),
-    zeros for a query without a point.  ``lengths``: the scans' point counts, known on the host."""
+    zeros for a query without a point.  ``lengths``: the scans' point counts, known on the host.  ``z_ground`` (B, Q) f32, only
+    from a lift with a ground map (K35b): the lowest ground height under the query's kept points, 0 without one."""
     point_query: torch.Tensor
     scan_offsets: torch.Tensor
     counts: torch.Tensor
@@ -92,27 +94,88 @@ class PointInstances:
     z_lo: torch.Tensor
     z_hi: torch.Tensor
     lengths: Tuple[int, ...]
+    z_ground: Optional[torch.Tensor] = None
 
     def per_scan(self) -> List[torch.Tensor]:
         """The labels of every scan: a list of (N_i,) views of ``point_query``.  No host synchronisation."""
         return list(torch.split(self.point_query, list(self.lengths)))
 
 
+@dataclass
+class GroundMap:
+    """K35a's outputs for a batch of B scans, on the device: ``ground`` (B, gy, gx) f32 — per BEV cell (row = y-cell, column =
+    x-cell, the layout of ``instance_map``) the lowest return within ``radius`` cells, +inf where that window holds none;
+    ``cell_min`` (B, gy, gx) f32 — the lowest return of the cell itself, +inf for an empty cell."""
+    ground: torch.Tensor
+    cell_min: torch.Tensor
+    radius: int
+
+
+MAX_GROUND_RADIUS = 32        # cells: the halo K35a's window passes stage in LDS
+
+
+def _concat_scans(what: str, scans: Sequence[torch.Tensor], dev):
+    """The scans as K1 takes them: (points (sum N_i, dim) f32 contiguous, dim, lengths, scan_offsets (B + 1) i32 on ``dev``)."""
+    dim = int(scans[0].shape[1]) if scans[0].dim() == 2 else -1
+    if dim not in (3, 4) or any(p.dim() != 2 or p.shape[1] != dim or p.device != dev for p in scans):
+        raise MaskBevHipError(f'{what}: scans must be (N_i, 3) or (N_i, 4) tensors of one width on the map\'s device')
+    lens = [int(p.shape[0]) for p in scans]
+    points = scans[0] if len(scans) == 1 else torch.cat(list(scans), 0)
+    points = points.to(torch.float32).contiguous()
+    offs = [0]
+    for l in lens:
+        offs.append(offs[-1] + l)
+    return points, dim, lens, torch.tensor(offs, dtype=torch.int32).to(dev, non_blocking=True)
+
+
+@torch.no_grad()
+def ground_map(scans: Sequence[torch.Tensor], geom, radius: int, z_floor: Optional[float] = None,
+               prefilter: bool = True) -> GroundMap:
+    """K35a: a ground height for every BEV cell of every scan — the lowest z among the points K1's cell rule accepts (``geom``,
+    ``prefilter`` as in :func:`lift_instances`) and that are not below ``z_floor`` (None: no floor), per cell and then over
+    the window of ``radius`` cells (0 .. 32) around it.  One return below the road pulls the ground down over its whole
+    window; ``z_floor`` is the only defence.  Device tensors only; no host synchronisation."""
+    lib = _lib.load()
+    if len(scans) == 0:
+        raise ValueError('ground_map: empty batch')
+    _need_gpu(*scans)
+    radius = int(radius)
+    if not 0 <= radius <= MAX_GROUND_RADIUS:
+        raise ValueError(f'ground_map: radius {radius} outside 0 .. {MAX_GROUND_RADIUS} cells')
+    batch, dev = len(scans), scans[0].device
+    points, dim, lens, scan_offsets = _concat_scans('ground_map', scans, dev)
+    gx, gy, gz = (int(v) for v in geom.grid)
+    cell_min = torch.empty((batch, gy, gx), dtype=torch.float32, device=dev)
+    ground = torch.empty((batch, gy, gx), dtype=torch.float32, device=dev)
+    nbytes = lib.mbv_ground_map_workspace_bytes(batch, gx, gy)
+    if nbytes == 0:
+        raise MaskBevHipError(f'ground_map: a batch of {batch} on a {gy}x{gx} grid is not supported')
+    ws = _workspace(nbytes, dev)
+    r, v = geom.pc_range, geom.voxel_size
+    check(lib.mbv_ground_map(_ptr(points), dim, sum(lens), _ptr(scan_offsets), batch, r[0], r[1], r[2], r[3], r[4], r[5],
+                             v[0], v[1], v[2], gx, gy, gz, 1 if prefilter else 0, radius,
+                             float('-inf') if z_floor is None else float(z_floor), _ptr(cell_min), _ptr(ground), _ptr(ws),
+                             ws.numel(), _stream()), 'mbv_ground_map')
+    return GroundMap(ground, cell_min, radius)
+
+
 @torch.no_grad()
 def lift_instances(scans: Sequence[torch.Tensor], instance_map: torch.Tensor, geom, num_queries: int, z_bins: int = 64,
-                   quantiles: Tuple[float, float] = (0., 1.), prefilter: bool = True) -> PointInstances:
+                   quantiles: Tuple[float, float] = (0., 1.), prefilter: bool = True, ground=None, clearance: float = 0.3,
+                   max_height: Optional[float] = None) -> PointInstances:
     """K31: ``scans`` — the list of (N_i, 3 | 4) f32 device tensors the module takes; ``instance_map`` (B, gy, gx) int32 of
     :func:`extract_masks`; ``geom`` — the encoder's ``VoxelGeometry`` (``prefilter``: the encoder's strict range filter in
     front of K1, on by default as there) → :class:`PointInstances`.  ``quantiles`` = (q_lo, q_hi) pick ``z_lo`` / ``z_hi``
-    among ``z_bins`` equal bins over the geometry's z range.  Device tensors only; no host synchronisation."""
+    among ``z_bins`` equal bins over the geometry's z range.  With ``ground`` — a :class:`GroundMap` or a (B, gy, gx) f32
+    tensor — K35b: a point keeps its query only when ``z > g + clearance`` and ``z <= g + max_height`` (None: no limit) with
+    ``g`` the ground height of its cell; counts and z columns are then those of the kept points and ``z_ground`` is set.
+    Device tensors only; no host synchronisation."""
     lib = _lib.load()
     if len(scans) == 0:
         raise ValueError('lift_instances: empty batch')
     _need_gpu(instance_map, *scans)
     batch, dev = len(scans), instance_map.device
-    dim = int(scans[0].shape[1]) if scans[0].dim() == 2 else -1
-    if dim not in (3, 4) or any(p.dim() != 2 or p.shape[1] != dim or p.device != dev for p in scans):
-        raise MaskBevHipError('lift_instances: scans must be (N_i, 3) or (N_i, 4) tensors of one width on the map\'s device')
+    points, dim, lens, scan_offsets = _concat_scans('lift_instances', scans, dev)
     gx, gy, gz = (int(v) for v in geom.grid)
     if instance_map.dtype != torch.int32 or tuple(instance_map.shape) != (batch, gy, gx):
         raise MaskBevHipError(f'lift_instances: instance_map must be ({batch}, {gy}, {gx}) int32, got '
@@ -122,27 +185,39 @@ def lift_instances(scans: Sequence[torch.Tensor], instance_map: torch.Tensor, ge
         raise MaskBevHipError(f'lift_instances: num_queries {num_queries} (<= 1024), z_bins {z_bins} (1 .. 256) or quantiles '
                               f'{(q_lo, q_hi)} (0 <= q_lo <= q_hi <= 1) out of range')
     num_queries, z_bins = int(num_queries), int(z_bins)
-    lens = [int(p.shape[0]) for p in scans]
     n = sum(lens)
-    points = scans[0] if batch == 1 else torch.cat(list(scans), 0)
-    points = points.to(torch.float32).contiguous()
-    offs = [0]
-    for l in lens:
-        offs.append(offs[-1] + l)
-    scan_offsets = torch.tensor(offs, dtype=torch.int32).to(dev, non_blocking=True)
     instance_map = instance_map.contiguous()
     point_query = torch.empty((n,), dtype=torch.int32, device=dev)
     counts = torch.empty((batch, num_queries), dtype=torch.int32, device=dev)
     z_extent = torch.empty((batch, num_queries, 4), dtype=torch.float32, device=dev)
-    nbytes = lib.mbv_lift_instances_workspace_bytes(batch, num_queries, z_bins)
-    ws = _workspace(nbytes, dev) if nbytes > 0 else None
     r, v = geom.pc_range, geom.voxel_size
-    check(lib.mbv_lift_instances(_ptr(points), dim, n, _ptr(scan_offsets), batch, r[0], r[1], r[2], r[3], r[4], r[5],
-                                 v[0], v[1], v[2], gx, gy, gz, 1 if prefilter else 0, _ptr(instance_map), num_queries, z_bins,
-                                 q_lo, q_hi, _ptr(point_query), _ptr(counts), _ptr(z_extent), _ptr(ws),
-                                 ws.numel() if ws is not None else 0, _stream()), 'mbv_lift_instances')
+    z_ground = None
+    if ground is None:
+        nbytes = lib.mbv_lift_instances_workspace_bytes(batch, num_queries, z_bins)
+        ws = _workspace(nbytes, dev) if nbytes > 0 else None
+        check(lib.mbv_lift_instances(_ptr(points), dim, n, _ptr(scan_offsets), batch, r[0], r[1], r[2], r[3], r[4], r[5],
+                                     v[0], v[1], v[2], gx, gy, gz, 1 if prefilter else 0, _ptr(instance_map), num_queries,
+                                     z_bins, q_lo, q_hi, _ptr(point_query), _ptr(counts), _ptr(z_extent), _ptr(ws),
+                                     ws.numel() if ws is not None else 0, _stream()), 'mbv_lift_instances')
+    else:
+        gmap = ground.ground if isinstance(ground, GroundMap) else ground
+        if (not torch.is_tensor(gmap) or gmap.dtype != torch.float32 or tuple(gmap.shape) != (batch, gy, gx)
+                or gmap.device != dev):
+            raise MaskBevHipError(f'lift_instances: ground must be a GroundMap or a ({batch}, {gy}, {gx}) f32 tensor on the '
+                                  f'map\'s device')
+        gmap = gmap.contiguous()
+        z_ground = torch.empty((batch, num_queries), dtype=torch.float32, device=dev)
+        nbytes = lib.mbv_lift_instances_ground_workspace_bytes(batch, num_queries, z_bins)
+        ws = _workspace(nbytes, dev) if nbytes > 0 else None
+        check(lib.mbv_lift_instances_ground(_ptr(points), dim, n, _ptr(scan_offsets), batch, r[0], r[1], r[2], r[3], r[4],
+                                            r[5], v[0], v[1], v[2], gx, gy, gz, 1 if prefilter else 0, _ptr(instance_map),
+                                            num_queries, z_bins, q_lo, q_hi, _ptr(gmap), float(clearance),
+                                            float('inf') if max_height is None else float(max_height), _ptr(point_query),
+                                            _ptr(counts), _ptr(z_extent), _ptr(z_ground), _ptr(ws),
+                                            ws.numel() if ws is not None else 0, _stream()), 'mbv_lift_instances_ground')
     return PointInstances(point_query, scan_offsets, counts, z_extent[..., 0], z_extent[..., 1], z_extent[..., 2],
-                          z_extent[..., 3], tuple(lens))
+                          z_extent[..., 3], tuple(lens), z_ground)
 
 
-__all__ = ['select_queries', 'extract_masks', 'lift_instances', 'PointInstances']
+__all__ = ['select_queries', 'extract_masks', 'lift_instances', 'PointInstances', 'ground_map', 'GroundMap',
+           'MAX_GROUND_RADIUS']

@@ -14,6 +14,8 @@ from __future__ import annotations
 from dataclasses import dataclass, fields
 from typing import List, Optional, Tuple
 
+import math
+
 import numpy as np
 import torch
 
@@ -22,6 +24,28 @@ from ._lib import MaskBevHipError
 
 
 BOX_METHODS = ('moment', 'min_area_rect')     # Predictions.boxes: K25 | K30a + K30b
+
+
+@dataclass
+class GroundSettings:
+    """What :meth:`Predictions.lift` needs to estimate the ground itself (K35): ``radius_m`` — the half-width of the window a
+    cell's ground height is the lowest return of, in metres; ``clearance`` — a point is labelled only above ground +
+    clearance; ``max_height`` — and at most that far above it (None: no limit); ``z_floor`` — returns below it are not ground
+    candidates (None: no floor).  The defaults rest on geometry, not on measurement: 1.6 m is half a car's width plus slack, so
+    the window of a cell under a car reaches the visible road beside it; 0.3 m is above road noise and the 8 cm a window
+    minimum loses on a 5 % slope, below a sill."""
+    radius_m: float = 1.6
+    clearance: float = 0.3
+    max_height: Optional[float] = None
+    z_floor: Optional[float] = None
+
+    def radius_cells(self, voxel_size_x: float) -> int:
+        """``ceil(radius_m / voxel_size_x)``; ``ValueError`` above ``ops.MAX_GROUND_RADIUS`` cells."""
+        cells = int(math.ceil(float(self.radius_m) / float(voxel_size_x)))
+        if not 0 <= cells <= ops.MAX_GROUND_RADIUS:
+            raise ValueError(f'ground radius {self.radius_m} m is {cells} cells of {voxel_size_x} m; the limit is '
+                             f'{ops.MAX_GROUND_RADIUS} cells')
+        return cells
 
 
 def unpack_bits(words: torch.Tensor, h: int, w: int) -> torch.Tensor:
@@ -98,16 +122,26 @@ class Predictions:
             raise ValueError(f'boxes: the ranges make a {ny}x{nx} (ny, nx) grid, the masks are {h}x{w}')
         return x_range, y_range, nx, ny
 
-    def lift(self, scans, module_or_geometry, z_bins: int = 64, quantiles=(0., 1.)) -> 'ops.PointInstances':
+    def lift(self, scans, module_or_geometry, z_bins: int = 64, quantiles=(0., 1.), ground=None) -> 'ops.PointInstances':
         """K31, ``ops.lift_instances``: the instance map lifted to the points of ``scans`` — the list of (N_i, 3 | 4) device
         tensors these predictions were made from — with the encoder's voxel geometry (a module, or its ``VoxelGeometry``):
         per point the query that owns its BEV cell (-1: none, and every point the voxeliser drops), and per query the points
         and their z-extent.  No host synchronisation.  On the static outputs of a :class:`GraphedPredictStep` it must run
-        before the next replay overwrites ``instance_map``."""
+        before the next replay overwrites ``instance_map``.  ``ground`` (K35): None — every return in an owned cell is labelled,
+        road under the car too; an ``ops.GroundMap`` of the same scans — only the returns more than 0.3 m above it are; a
+        :class:`GroundSettings` — the map is computed from ``scans`` first (``ops.ground_map``), clearance and height
+        limit are the record's.  ``z_ground`` of the result is then set."""
         if self.instance_map is None:
             raise MaskBevHipError('lift: these predictions were made without an instance map')
-        return ops.lift_instances(scans, self.instance_map, voxel_geometry(module_or_geometry), self.labels.shape[1],
-                                  z_bins=z_bins, quantiles=quantiles)
+        geom = voxel_geometry(module_or_geometry)
+        extra = {}
+        if isinstance(ground, GroundSettings):
+            extra = dict(ground=ops.ground_map(scans, geom, ground.radius_cells(geom.voxel_size[0]), z_floor=ground.z_floor),
+                         clearance=ground.clearance, max_height=ground.max_height)
+        elif ground is not None:
+            extra = dict(ground=ground)
+        return ops.lift_instances(scans, self.instance_map, geom, self.labels.shape[1], z_bins=z_bins, quantiles=quantiles,
+                                  **extra)
 
     def query_classes(self) -> torch.Tensor:
         """(B, Q) int32, the panoptic class of every query: its label (1 .. K; index 0 of the class logits is "empty", so a
@@ -209,7 +243,7 @@ class Predictions:
                     scan=torch.div(rows, q, rounding_mode='floor'), query=rows % q, cells=n), rows
 
     def boxes3d(self, scans, module_or_geometry, x_range, y_range=None, voxel_size=None, method: str = 'moment',
-                extent='minmax', min_points: int = 1) -> dict:
+                extent='minmax', min_points: int = 1, ground=None, bottom: str = 'points') -> dict:
         """:meth:`boxes` with a height from the points (K31, :meth:`lift` of ``scans`` with the encoder's geometry): what
         :meth:`boxes` returns plus ``boxes3d`` (R, 7) f32 [x, y, z_bottom, l, w, h, yaw] — the columns of
         ``batch.kitti_labels_to_velodyne``'s ``boxes`` — and ``points`` (R) int32, the lifted points of the row's query.
@@ -217,7 +251,14 @@ class Predictions:
         ``extent=(q_lo, q_hi)``: from the edges of the bins, among 64 over the geometry's z range, that hold the points
         of those two quantiles (an outlier above a car no longer stretches it).  Rows with fewer than ``min_points`` (>= 1)
         lifted points are dropped: a mask with no return has no height.  The height is the z-extent of the returns inside the
-        mask — ground to roof only if the ground is in range.  No synchronisation beyond the two of :meth:`boxes`."""
+        mask — ground to roof only if the ground is in range.  ``ground`` (K35, as in :meth:`lift`): only the returns above the
+        estimated ground count, so z_bottom is the lowest kept return; with ``bottom='ground'`` (needs ``ground``) z_bottom is
+        ``z_ground``, the estimated ground under the object, and h reaches from there to the top: the box stands on the
+        ground as a KITTI label does.  No synchronisation beyond the two of :meth:`boxes`."""
+        if bottom not in ('points', 'ground'):
+            raise ValueError(f"boxes3d: bottom must be 'points' or 'ground', got {bottom!r}")
+        if bottom == 'ground' and ground is None:
+            raise ValueError("boxes3d: bottom='ground' needs ground= (a GroundMap or GroundSettings)")
         if int(min_points) < 1:
             raise ValueError('boxes3d: min_points must be at least 1 (a mask with no return has no height)')
         if isinstance(extent, str):
@@ -228,11 +269,13 @@ class Predictions:
             quantiles = (float(extent[0]), float(extent[1]))
         if self.masks is None:
             raise MaskBevHipError('boxes: these predictions were made without masks')
-        lifted = self.lift(scans, module_or_geometry, quantiles=quantiles)
+        lifted = self.lift(scans, module_or_geometry, quantiles=quantiles, **({} if ground is None else dict(ground=ground)))
         counts = lifted.counts.reshape(-1)
         out, rows = self._boxes(x_range, y_range, voxel_size, method, also=counts >= int(min_points))
         rows = rows.to(counts.device)
         lo, hi = (lifted.z_min, lifted.z_max) if isinstance(extent, str) else (lifted.z_lo, lifted.z_hi)
+        if bottom == 'ground':
+            lo = lifted.z_ground
         z, top = lo.reshape(-1)[rows], hi.reshape(-1)[rows]
         b = out['boxes']
         z, top = z.to(b.device), top.to(b.device)
@@ -241,19 +284,21 @@ class Predictions:
         return out
 
     def kitti_predictions(self, x_range, y_range=None, voxel_size=None, method: str = 'moment', scans=None, module=None,
-                          extent='minmax', min_points: int = 1) -> List[dict]:
+                          extent='minmax', min_points: int = 1, ground=None, bottom: str = 'points') -> List[dict]:
         """Per scan what ``kitti_eval.eval_kitti`` takes: ``{'boxes': (k, 5) [x, y, l, w, yaw], 'score': (k), 'type': (k)
         int64}`` of the scan's kept, non-empty queries; every box has the type Car (index 0 of ``rasterize.KITTI_TYPES``).
         With ``scans`` (and ``module``, or its ``VoxelGeometry``) every dictionary also carries ``boxes3d`` (k, 7) of
-        :meth:`boxes3d` (``extent``, ``min_points`` as there) and ``boxes`` are its BEV columns: the 3D lines of the
+        :meth:`boxes3d` (``extent``, ``min_points``, ``ground``, ``bottom`` as there) and ``boxes`` are its BEV columns: the 3D lines of the
         evaluation.  Arguments and synchronisation as :meth:`boxes`, plus one copy of the per-scan counts."""
         if scans is None:
+            if ground is not None or bottom != 'points':
+                raise ValueError('kitti_predictions: ground and bottom apply to the 3D boxes, which need scans')
             out = self.boxes(x_range, y_range, voxel_size, method=method)
         else:
             if module is None:
                 raise ValueError('kitti_predictions: scans need the module (or its VoxelGeometry) they were voxelised with')
             out = self.boxes3d(scans, module, x_range, y_range, voxel_size, method=method, extent=extent,
-                               min_points=min_points)
+                               min_points=min_points, ground=ground, bottom=bottom)
         counts = torch.bincount(out['scan'], minlength=self.labels.shape[0]).tolist()
         boxes, scores = torch.split(out['boxes'], counts), torch.split(out['scores'], counts)
         dicts = [dict(boxes=b, score=s, type=torch.zeros((b.shape[0],), dtype=torch.int64)) for b, s in zip(boxes, scores)]

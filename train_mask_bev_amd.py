@@ -42,7 +42,9 @@ it also prints ``point PQ .. SQ .. RQ .. IoU .. (car; tp .. fp .. fn ..)``, the 
 validation sequences in scan order (K33; needs ``sequences/SS/poses.txt`` and ``calib.txt``, says so in one line and skips
 without them): one global instance id per object, written by ``--write-labels`` in place of the query index, and with label
 files ``point LSTQ .. S_assoc .. S_cls .. (tubes .., tracks .., dropped ..)`` (``track_min_iou``, ``track_max_age``,
-``track_min_cells``, ``track_max_tracks``).
+``track_min_cells``, ``track_max_tracks``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
+``lift_max_height``, ``lift_z_floor``) makes every one of these lifts label only the returns above a ground estimate made from
+the scan, lets the 3D boxes stand on it, and prints one ``ground-aware lift: ..`` line in front of the results it changes.
 """
 import argparse
 import os
@@ -170,6 +172,7 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
 def test(args, config, model, val, dataset_name, device, rank, world):
     """The reference runs trainer.validate then trainer.test (train_mask_bev.py:118-119); MaskBevModule defines no test_step
     (SURVEY Appendix B), so the test pass has nothing of its own to run: validation, then the extras of mask_bev_amd/evaluate.py."""
+    lifting = evaluate.lift_settings(config)   # None unless `lift_ground: true` (K35)
     layers = tuple(range(model.num_layers))    # the reference attaches its metrics to all ten decoder outputs (:85-98)
     if val is not None:
         # what trainer.validate logs there: COCO mask AP (K29), mIoU and class AP of every decoder layer
@@ -185,9 +188,13 @@ def test(args, config, model, val, dataset_name, device, rank, world):
         if dataset_name == 'kitti' and val is not None:
             # what the reference's mask_to_pred + eval_kitti are for: boxes from the predicted masks, KITTI BEV AP
             # (`kitti_3d: true`: with the heights lifted from the scans, and the 3D AP lines)
+            if lifting is not None and config.get('kitti_3d', False):
+                print(evaluate.format_lift_settings(lifting, config['voxel_size']), flush=True)
             print(evaluate.kitti_bev_evaluation(model, config, device, args.data_root), end='', flush=True)
     if dataset_name != 'semantic-kitti' or val is None:
         return
+    if lifting is not None and rank == 0:
+        print(evaluate.format_lift_settings(lifting, config['voxel_size']), flush=True)
     # point-level panoptic quality of the lifted labels, when the ground truth lies next to every validated scan
     have = all(evaluate.semantic_kitti_label_path(f).exists() for f, _ in val.files)
     if world > 1:                              # every rank or none: compute() sums the ranks
