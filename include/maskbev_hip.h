@@ -1656,6 +1656,66 @@ int mbv_lift_instances_ground(const float* points, int32_t point_dim, int64_t to
                               float* z_extent, float* z_ground, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K36 — BEV frames of scans, predicted instances, tracks and boxes, composed on the device (csrc/render.hip, built with
+ * -ffp-contract=off for K36a's cell rule; the plain-loop restatement of the words below is tests/render_ref.py).
+ *
+ * K36a — mbv_cell_counts.  points, point_dim, total_points, scan_offsets, batch, x_min .. gz, prefilter: as in K31.
+ * counts        (batch, gy, gx) i32, row = y-cell, column = x-cell (the layout of instance_map): the points of the scan that
+ *               K1's cell rule accepts in the cell — the device function K31 and K35 decide with (csrc/point_cell.hpp).
+ * Two launches (zero the table; one thread per point, an integer atomic add), one when total_points == 0.  The result does
+ * not depend on the order of the points.  No workspace, no host synchronisation.
+ * batch == 0: MBV_OK, nothing is written.  MBV_ERR_UNSUPPORTED: batch > 65535, total_points >= 2^31 - 1, gx or gy > 65536;
+ * MBV_ERR_BAD_ARG: a negative size, point_dim other than 3 or 4, a grid size < 1, null counts, null points or scan_offsets
+ * with total_points > 0.
+ *
+ * K36b — mbv_render_bev.  image (batch, H, W, 3) u8 with H = gy * scale, W = gx * scale, scale in 1 .. 8, H and W at most
+ * 4096; 4-byte aligned.  Every table below may be null (its layer is then skipped) except image.  Colours passed by value
+ * are packed r | g << 8 | b << 16.  For pixel (py, px) of scan b the cell is (cy, cx) = (py / scale, px / scale); the layers
+ * apply in this order, in integer arithmetic only:
+ *   1. density    c = counts[b][cy][cx] (0 without counts);  level = min(bit_length(max(c, 0)), 15);
+ *                 rgb = density_lut[level], density_lut (16, 3) u8.  Without density_lut: rgb = (0, 0, 0), and counts must
+ *                 be null.
+ *   2. instances  q = instance_map[b][cy][cx], (batch, gy, gx) i32; drawn only for 0 <= q < num_queries.
+ *                 id = id_table[b][q] with id_table (batch, num_queries) i32, else q.
+ *                 col = palette[id % palette_size] for id >= 0 (palette (palette_size, 3) u8), untracked_rgb for id < 0.
+ *                 per channel rgb = (rgb * (256 - alpha) + col * alpha + 128) >> 8, alpha in 0 .. 256.
+ *   3. contour    v = gt_map[b][cy][cx], (batch, gy, gx) i32.  The pixel takes gt_rgb iff v != gt_background and at least
+ *                 one of the pixels (py, px - 1), (py, px + 1), (py - 1, px), (py + 1, px) lies in a cell whose value is not
+ *                 v; a neighbour outside the image counts as gt_background.  A one-pixel inner outline at any scale.
+ *   4. boxes      rows box_offsets[b] .. box_offsets[b + 1] - 1 (clamped into [0, num_boxes]; box_offsets (batch + 1) i32) of
+ *                 box_corners (num_boxes, 4, 2) i32, (x, y) per corner in HALF-PIXEL units — round(2 * scale * c) of a cell
+ *                 coordinate c, made on the host — in order, later rows win.  line in 1 .. 32, half-pixel units.  With the
+ *                 pixel centre P = (2 px + 1, 2 py + 1) the pixel takes box_rgb[r] ((num_boxes, 3) u8) iff P is within
+ *                 line / 2 of one of the four segments corner k -> corner (k + 1) % 4, decided exactly in 64-bit integers:
+ *                 u = B - A, v = P - A, d = u.v, L = u.u;  d <= 0: 4 |v|^2 <= line^2;  d >= L: 4 |P - B|^2 <= line^2;
+ *                 otherwise 4 cross(u, v)^2 <= line^2 L (the left side as an unsigned 64-bit number: it can pass 2^63).
+ *                 A box with a corner coordinate outside [-16384, 16384] is not drawn and counts in skipped[b] — the bound
+ *                 keeps cross^2 below 2^62.  A box whose four corners are equal is a dot of diameter `line`.
+ * flip_rows != 0: pixel row py is written to image row H - 1 - py (y up); the layers do not change.
+ * skipped       (batch) i32 or null: the boxes of the scan outside the coordinate bound; written for every scan, 0 without
+ *               boxes.
+ * One launch.  A lane composes four consecutive pixels of the flat (batch * H * W) pixel run and stores them as three dwords,
+ * so a row length that is no multiple of 4 bytes needs no scalar head or tail; a workgroup owns 128 x 8 pixels of one scan,
+ * stages the scan's boxes in LDS in chunks of mbv_render_box_chunk() rows and rejects each by its bounding box, grown by
+ * `line`, against the tile.  No dense (batch, queries, gy, gx) tensor, no workspace, no host synchronisation.
+ * batch == 0: MBV_OK, nothing is written.  MBV_ERR_UNSUPPORTED: H or W > 4096, batch > 65535, num_boxes >= 2^31 - 1;
+ * MBV_ERR_BAD_ARG: a grid size < 1, scale outside 1 .. 8, a negative size, a null or unaligned image, counts without
+ * density_lut, an instance_map without palette (or palette_size < 1, num_queries < 0, alpha outside 0 .. 256), box_corners
+ * (with num_boxes > 0) without box_rgb or box_offsets or with line outside 1 .. 32.
+ *
+ * Not pinned: any speed; profiles/k36 holds what was measured.
+ */
+int32_t mbv_render_box_chunk(void);
+int mbv_cell_counts(const float* points, int32_t point_dim, int64_t total_points, const int32_t* scan_offsets, int32_t batch,
+                    float x_min, float y_min, float z_min, float x_max, float y_max, float z_max, float vx, float vy, float vz,
+                    int32_t gx, int32_t gy, int32_t gz, int32_t prefilter, int32_t* counts, void* stream);
+int mbv_render_bev(int32_t batch, int32_t gx, int32_t gy, int32_t scale, int32_t flip_rows, const int32_t* counts,
+                   const uint8_t* density_lut, const int32_t* instance_map, int32_t num_queries, const int32_t* id_table,
+                   const uint8_t* palette, int32_t palette_size, int32_t alpha, uint32_t untracked_rgb, const int32_t* gt_map,
+                   int32_t gt_background, uint32_t gt_rgb, const int32_t* box_corners, const uint8_t* box_rgb,
+                   const int32_t* box_offsets, int64_t num_boxes, int32_t line, uint8_t* image, int32_t* skipped, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K32 — panoptic quality of point or BEV instances (csrc/panoptic.hip): per frame the tp / fp / fn, the IoU sums and the
  * confusion of the SemanticKITTI panoptic protocol, PanopticEval.addBatchPanoptic of semantic-kitti-api's eval_np.py,
  * restated, not repaired.  Parity with that package is not pinned (it is not installed); the numpy restatement in its own

@@ -230,6 +230,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
                                         c_size_t, _P]),
     'mbv_tube_accumulate': (ctypes.c_int, [_P, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'mbv_tube_scores': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'mbv_render_box_chunk': (_I, []),
+    'mbv_cell_counts': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P]),
+    'mbv_render_bev': (ctypes.c_int, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, ctypes.c_uint32, _P, _I,
+                                      ctypes.c_uint32, _P, _P, _P, _L, _I, _P, _P, _P]),
 }
 
 _lib = None

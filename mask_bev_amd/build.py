@@ -41,6 +41,8 @@ FILE_FLAGS = {
     'point_lift.hip': ['-ffp-contract=off'],
     # K33a's f64 warp of a cell centre decides a cell index, K33b's f64 terms are summed one by one: one rounding per operation
     'track.hip': ['-ffp-contract=off'],
+    # K36a counts with K1's cell rule `(p - min) / vs`, the copy of point_lift.hip: one rounding per operation
+    'render.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

@@ -36,18 +36,13 @@
 //         z > g + clearance and z <= g + max_height (one rounded add each: this file is compiled without contraction); a
 //         fourth table takes the minimum of g per query.  K31 is k_lift_points<false> of the same body.
 #include "common.hpp"
+#include "point_cell.hpp"   // LiftGeom, point_cell: K1's cell rule, the one copy
 
 namespace {
 
 constexpr int kThreads = 256, kMaxQueries = 1024, kMaxBins = 256;
 constexpr int kTile = 64, kRowTileRows = 16, kMaxRadius = 32;   // K35a: tiles of the window passes, the largest halo
 constexpr uint32_t kEncInf = 0xff800000u;                       // encode_ordered(+inf)
-
-struct LiftGeom {          // VoxelGeom of voxelize.hip
-  float x_min, y_min, z_min, x_max, y_max, z_max;
-  float vx, vy, vz;
-  int gx, gy, gz;
-};
 
 // f32 → u32 with the order of the floats (negative numbers: all bits flipped; others: the sign bit set) and back
 __device__ __forceinline__ uint32_t encode_ordered(float z) {
@@ -56,26 +51,6 @@ __device__ __forceinline__ uint32_t encode_ordered(float z) {
 }
 __device__ __forceinline__ float decode_ordered(uint32_t e) {
   return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
-
-// K1's cell rule for the point at p: true iff the voxeliser keeps the point, then (cx, cy) is its BEV cell.  The one copy:
-// K31, K35a and K35b all decide with it.
-__device__ __forceinline__ bool point_cell(const float* __restrict__ p, const LiftGeom& g, int prefilter, int64_t& cx,
-                                           int64_t& cy, float& z_out) {
-  const float x = p[0], y = p[1], z = p[2];
-  bool ok = true;
-  if (prefilter) {
-    ok = (g.x_min < x) && (x < g.x_max) && (g.y_min < y) && (y < g.y_max) && (g.z_min < z) && (z < g.z_max);
-  }
-  const float qx = floorf((x - g.x_min) / g.vx);
-  const float qy = floorf((y - g.y_min) / g.vy);
-  const float qz = floorf((z - g.z_min) / g.vz);
-  ok = ok && (qx >= 0.f) && (qx < (float)g.gx) && (qy >= 0.f) && (qy < (float)g.gy) && (qz >= 0.f) &&
-       (qz < (float)g.gz);  // NaN fails every compare
-  cx = ok ? (int64_t)qx : 0;
-  cy = ok ? (int64_t)qy : 0;
-  z_out = z;
-  return ok;
 }
 
 __global__ void __launch_bounds__(kThreads) k_lift_init(int64_t total_points, int64_t bq, int64_t hist_elems,

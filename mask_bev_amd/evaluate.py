@@ -1,5 +1,5 @@
 """What ``--test`` runs after the validation loss, one pass over the scans per feature: KITTI BEV / 3D AP (K25-K27, K30, K31),
-per-point labels (K31), their panoptic quality (K32), tracking with LSTQ (K33); the settings and printed lines of each.  With
+per-point labels (K31), their panoptic quality (K32), tracking with LSTQ (K33), BEV frames as PNG files (K36); the settings and printed lines of each.  With
 ``lift_ground: true`` every lift labels only the returns above a ground estimate made from the scan itself (K35)."""
 import pathlib
 
@@ -222,3 +222,80 @@ def format_layer_metrics(logged, layer):
     parts = [f'{n} {logged[f"val_mAP_{layer}_{n}"]:.4f}' for n in ('map', 'map_50', 'map_75', 'mar_100')]
     parts += [f'mIoU {logged[f"val_mIoU_layer_{layer}"]:.4f}', f'cls_AP {logged[f"val_cls_mAP_layer_{layer}"]:.4f}']
     return f'layer {layer}: ' + ' '.join(parts)
+
+
+def render_settings(config):
+    """The :class:`~mask_bev_amd.render.RenderSettings` of a configuration: ``render_scale`` (pixels per cell, default 2) and
+    ``render_alpha`` (0 .. 256, default 128); everything else keeps its default."""
+    from .render import RenderSettings
+    return RenderSettings(scale=int(config.get('render_scale', 2)), alpha=int(config.get('render_alpha', 128)))
+
+
+def render_frame_path(out_dir, scan_path, dataset):
+    """``dataset: semantic-kitti``: ``sequences/SS/velodyne/NNNNNN.bin`` → ``<out_dir>/sequences/SS/bev/NNNNNN.png``; ``kitti``:
+    ``<out_dir>/NNNNNN.png``.  Creates the folder."""
+    scan_path, d = pathlib.Path(scan_path), pathlib.Path(out_dir)
+    if dataset == 'semantic-kitti':
+        d = d / 'sequences' / scan_path.parent.parent.name / 'bev'
+    d.mkdir(parents=True, exist_ok=True)
+    return d / (scan_path.stem + '.png')
+
+
+def _cached_maps(part, shape, device):
+    """The mask-cache maps next to the scans ``part`` as one (B, ny, nx) int32 device map (a scan without a file: background),
+    ``None`` when no scan has one."""
+    paths = [pathlib.Path(f).parent.parent / 'mask_cache' / (pathlib.Path(f).stem + '.npy') for f in part]
+    if not any(p.exists() for p in paths):
+        return None
+    ny, nx = shape
+    maps = [np.asarray(B.read_mask_cache(p)).astype(np.int32) if p.exists() else np.zeros((nx, ny), np.int32) for p in paths]
+    if any(m.shape != (nx, ny) for m in maps):
+        raise ValueError(f'render_frames: a mask cache next to {part[0]} is not the (nx, ny) = {(nx, ny)} map of the configuration')
+    return torch.from_numpy(np.stack(maps)).to(device).permute(0, 2, 1).contiguous()       # the cache is (nx, ny)
+
+
+def render_frames(model, config, device, scan_paths, out_dir, dataset='semantic-kitti', label_boxes=None, score_threshold=0.0):
+    """``--render DIR``: one PNG per scan of ``scan_paths`` (:func:`render_frame_path`), composed on the device (K36,
+    ``Predictions.render``) from ``model.predict`` per batch: the returns per cell underneath, every predicted instance in its
+    colour (:func:`render_settings`).  ``dataset='semantic-kitti'`` — ``scan_paths`` in scan order: the contour of the mask
+    cache's instances where ``mask_cache/NNNNNN.npy`` lies next to a scan; with ``track_instances: true`` the colours are the
+    track ids of an ``InstanceTracker`` of this pass's own, reset at every sequence change (K33a; ``poses.txt`` and
+    ``calib.txt`` of the sequence, without them one line says so and the colours are the query indices).  ``dataset='kitti'``:
+    with ``render_boxes`` (default true) the predicted boxes and ``label_boxes`` — per scan an (n, 7) array in the velodyne
+    frame — in a second colour.  Returns the paths written."""
+    from .render import write_png
+    settings, written = render_settings(config), []
+    if dataset == 'kitti':
+        with_boxes = bool(config.get('render_boxes', True))
+        ranges = (config['x_range'], config['y_range'], config['voxel_size'])
+        start = 0
+        for part, scans, pred in predictions(model, list(scan_paths), config.get('batch_size', 1), device, score_threshold):
+            gt = None if (label_boxes is None or not with_boxes) else list(label_boxes[start:start + len(part)])
+            start += len(part)
+            frames = pred.render(settings, scans=scans, module=model, boxes='pred' if with_boxes else None, gt_boxes=gt,
+                                 ranges=ranges if with_boxes else None).cpu().numpy()
+            for f, frame in zip(part, frames):
+                written.append(render_frame_path(out_dir, f, dataset))
+                write_png(written[-1], frame)
+        return written
+    by_seq = {}
+    for f in scan_paths:
+        by_seq.setdefault(pathlib.Path(f).parent.parent, []).append(pathlib.Path(f))
+    track = bool(config.get('track_instances', False))
+    if track and any(not ((d / 'poses.txt').exists() and (d / 'calib.txt').exists()) for d in by_seq):
+        print('render: poses.txt or calib.txt is missing, colours are query indices', flush=True)
+        track = False
+    tracker = InstanceTracker(config['x_range'], config['y_range'], config['voxel_size'], int(config['num_queries']),
+                              device=device, **tracking_settings(config)) if track else None
+    for seq_dir, scans_of in by_seq.items():
+        if track:
+            poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
+            tracker.reset()
+        for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
+            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]]) if track else None
+            frames = pred.render(settings, scans=scans, module=model, query_track=query_track,
+                                 gt_maps=_cached_maps(part, pred.grid_hw, device)).cpu().numpy()
+            for f, frame in zip(part, frames):
+                written.append(render_frame_path(out_dir, f, dataset))
+                write_png(written[-1], frame)
+    return written

@@ -25,6 +25,7 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
                    K30 largest 8-connected component + minimum-area rectangle of a packed mask,
                    K32 panoptic tp / fp / fn, IoU sums and confusion per frame from two id arrays (points or BEV cells)
     ops_track      K33 the tracker step over consecutive BEV instance maps (global instance ids) and tube association (S_assoc of LSTQ)
+    ops_render     K36 returns per BEV cell and the composed BEV frame (density, instances / tracks, ground-truth contour, boxes)
 """
 from .ops_core import *            # noqa: F401,F403
 from .ops_records import *         # noqa: F401,F403
@@ -41,3 +42,4 @@ from .ops_rasterize import *       # noqa: F401,F403
 from .ops_augment import *         # noqa: F401,F403
 from .ops_eval import *            # noqa: F401,F403
 from .ops_track import *           # noqa: F401,F403
+from .ops_render import *          # noqa: F401,F403

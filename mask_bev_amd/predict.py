@@ -209,6 +209,24 @@ class Predictions:
         ids = query_track.reshape(-1)[scan.clamp_(max=b - 1) * q + pq.clamp(0, q - 1)]
         return torch.where((pq >= 0) & (pq < q), ids, torch.full_like(ids, -1)).to(torch.int32)
 
+    def render(self, settings=None, scans=None, module=None, query_track=None, gt_maps=None, boxes=None, gt_boxes=None,
+               ranges=None) -> torch.Tensor:
+        """K36: one BEV frame per scan, ``(B, ny * scale, nx * scale, 3)`` uint8 on the device, composed there by
+        ``ops.render_bev`` in one launch; ``settings``: a :class:`~mask_bev_amd.render.RenderSettings` (None: its defaults).
+        Always: the instance map, every owned cell blended with its query's palette colour.  ``scans`` (with ``module``, or its
+        ``VoxelGeometry``): underneath, the returns per cell on a logarithmic grey scale (K36a, ``ops.cell_counts``).
+        ``query_track`` (B, Q) int32 of :meth:`track`: colours by global track id, so an object keeps its colour over a
+        sequence; a query without a track is grey.  ``gt_maps`` (B, ny, nx) integer map in the layout of ``instance_map`` (a
+        rasteriser's (B, nx, ny) map: ``.permute(0, 2, 1)``): a one-pixel contour around every ground-truth instance.
+        ``gt_boxes``: per scan an (n, 7) array of label boxes [x, y, z, l, w, h, yaw] in the velodyne frame, outlined in a
+        second colour; ``boxes='pred'``: the outlines of :meth:`boxes` on top — both need ``ranges`` = (x_range, y_range
+        [, voxel_size]) or a rasteriser.  No host synchronisation, except with ``boxes='pred'``, which costs the two of
+        :meth:`boxes` and is off by default.  ``mask_bev_amd.render.write_png`` writes a frame (``image[b]``) without PIL.
+        Raises ``MaskBevHipError`` for predictions made without an instance map."""
+        from .render import render_predictions
+        return render_predictions(self, settings, scans=scans, module=module, query_track=query_track, gt_maps=gt_maps,
+                                  boxes=boxes, gt_boxes=gt_boxes, ranges=ranges)
+
     def boxes(self, x_range, y_range=None, voxel_size=None, method: str = 'moment') -> dict:
         """Oriented BEV boxes of the kept queries, in metres: ``x_range``, ``y_range``, ``voxel_size`` of the grid, or a
         rasteriser (``KittiRasterizer``) in place of ``x_range``.  ``method='moment'``: K25, ``ops.fit_boxes``, the

@@ -45,6 +45,10 @@ files ``point LSTQ .. S_assoc .. S_cls .. (tubes .., tracks .., dropped ..)`` (`
 ``track_min_cells``, ``track_max_tracks``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
 ``lift_max_height``, ``lift_z_floor``) makes every one of these lifts label only the returns above a ground estimate made from
 the scan, lets the 3D boxes stand on it, and prints one ``ground-aware lift: ..`` line in front of the results it changes.
+``--render DIR`` (K36; ``render_scale``, ``render_alpha``, ``render_boxes``) adds a last pass on rank 0 that writes one BEV frame
+per validation scan, composed on the device: ``DIR/sequences/SS/bev/NNNNNN.png`` for ``dataset: semantic-kitti`` (returns per
+cell, the predicted instances coloured by query — by track id with ``track_instances: true`` — and the contour of the mask
+cache's instances where the file exists), ``DIR/NNNNNN.png`` for ``dataset: kitti`` (with the predicted and the label boxes).
 """
 import argparse
 import os
@@ -191,6 +195,11 @@ def test(args, config, model, val, dataset_name, device, rank, world):
             if lifting is not None and config.get('kitti_3d', False):
                 print(evaluate.format_lift_settings(lifting, config['voxel_size']), flush=True)
             print(evaluate.kitti_bev_evaluation(model, config, device, args.data_root), end='', flush=True)
+    if args.render and rank == 0 and val is not None and dataset_name == 'kitti':
+        tree = datasets.KittiFrames(args.data_root, 'val')
+        paths = evaluate.render_frames(model, config, device, [tree.scan(f) for f in tree.frames], args.render, dataset='kitti',
+                                       label_boxes=[tree.labels(f)['boxes'] for f in tree.frames])
+        print(f'wrote {len(paths)} frames under {args.render}', flush=True)
     if dataset_name != 'semantic-kitti' or val is None:
         return
     if lifting is not None and rank == 0:
@@ -224,9 +233,14 @@ def test(args, config, model, val, dataset_name, device, rank, world):
     if args.write_labels and tracked is None:
         paths = evaluate.write_point_labels(model, config, device, val.files, args.write_labels)     # every rank: its own scans
         print(f'wrote {len(paths)} label files under {args.write_labels}', flush=True)
+    if args.render and rank == 0:
+        scans_of = [f for seq in config.get('val_sequences', [8])
+                    for f in sorted((pathlib.Path(args.data_root) / 'sequences' / f'{int(seq):02d}' / 'velodyne').glob('*.bin'))]
+        paths = evaluate.render_frames(model, config, device, scans_of, args.render)
+        print(f'wrote {len(paths)} frames under {args.render}', flush=True)
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--config', '-c', type=str, help='Config file for current run', required=True)
     parser.add_argument('--train', '-t', action='store_true', help='Train the model')
@@ -252,7 +266,17 @@ def main(argv=None):
     parser.add_argument('--write-labels', default=None, metavar='DIR',
                         help='dataset: semantic-kitti with --test: write the per-point instance labels of every validated '
                              'scan to DIR/sequences/SS/predictions/NNNNNN.label')
+    parser.add_argument('--render', default=None, metavar='DIR',
+                        help='with --test: write one BEV frame per validated scan, composed on the GPU, to '
+                             'DIR/sequences/SS/bev/NNNNNN.png (dataset: semantic-kitti) or DIR/NNNNNN.png (dataset: kitti)')
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
+    if args.render and not args.test:
+        parser.error('--render needs --test')
 
     is_training, is_testing = args.train, args.test
     if is_training is False and is_testing is False:
