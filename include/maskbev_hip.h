@@ -1773,8 +1773,8 @@ int mbv_panoptic_frames(const int32_t* pred_query, const uint32_t* gt_word, int6
 /* ------------------------------------------------------------------------------------------------
  * K33a — the tracker step (csrc/track.hip): BEV instance maps of consecutive frames of ONE sequence are associated after
  * ego-motion compensation, so that an object keeps one global id.  Built with -ffp-contract=off; the numpy restatement of
- * the words below is tests/track_ref.py.  There is no motion model: a moving object is matched only while its footprints of
- * consecutive frames overlap.
+ * the words below is tests/track_ref.py.  The motion model (K37, below) is off by default: in this step a moving object is
+ * matched only while its footprints of consecutive frames overlap.
  *
  * Grid           H = ny rows, W = nx columns, the layout of Predictions.instance_map[b]; x_lo, y_lo, voxel f64.  Cell
  *                (iy, ix) has the centre x = x_lo + (ix + 0.5) * voxel, y = y_lo + (iy + 0.5) * voxel.
@@ -1822,6 +1822,65 @@ int mbv_track_frames(const int32_t* instance_maps, const double* prev_from_cur, 
                      double y_lo, double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age, int32_t min_cells,
                      int32_t* state_map, int32_t* live_id, int32_t* live_seen, int32_t* counters, int32_t* query_track,
                      int32_t* track_map, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * K37 — the tracker step with a constant-velocity motion model and gated re-association (csrc/track.hip).  K33a's step with
+ * a prediction in front of it and a second matching stage behind it; mbv_track_frames is unchanged and stays the default.
+ * The numpy restatement of the words below is tests/track_motion_ref.py.  All f64 arithmetic takes one rounding per
+ * operation, in the order written (-ffp-contract=off); division and rint only, no sqrt, no transcendental function.
+ *
+ * State          K33a's, and a motion record owned by the caller, on the device: pos (P, 2) f64, the centroid of every live
+ *                track in metres, x then y, in the coordinates of the frame last processed; vel (P, 2) f64, metres per
+ *                frame in the same coordinates — the ego motion is compensated, so this is motion over ground in sensor
+ *                axes; motion_counters (2) i32 = [gated, reserved 0].  A fresh record is all zeros.
+ * One frame      K33a's inputs, and cur_from_prev (F, 2, 3) f64 = n, the inverse of prev_from_cur = m (n00 n01 n02 / n10 n11
+ *                n12); gain f64 in [0, 1]; gate f64 >= 0 in metres, 0 switches step 3b off; max_shift i32 >= 0 in cells.
+ *
+ * 0. advect  every live track t gets an integer cell shift sx = rint(vel[t].x / voxel), sy = rint(vel[t].y / voxel); if
+ *            !(fabs(sx) <= max_shift && fabs(sy) <= max_shift), tested in f64 before any conversion, both are 0 (NaN and
+ *            inf give 0).  moved (H, W) starts at -1; every cell (iy, ix) of state_map that holds t in [0, n_live) writes t
+ *            to (iy + sy, ix + sx) when that lies inside the grid; where several tracks land on one cell the smallest t
+ *            wins.  A pure integer translation leaves no holes.
+ * 1 – 3.     K33a's warp, count and match word for word, reading moved instead of state_map.  The count also keeps
+ *            sum_ix[q], sum_iy[q] (i64) over the cells of q; for a present query
+ *            c_q.x = x_lo + ((double)sum_ix / (double)area_q + 0.5) * voxel, c_q.y = y_lo + ((double)sum_iy / (double)area_q
+ *            + 0.5) * voxel.
+ * 3b. gate   for every live t: a = pos[t] + vel[t]; pred[t].x = (n00 * a.x + n01 * a.y) + n02, pred[t].y = (n10 * a.x +
+ *            n11 * a.y) + n12; velr[t].x = n00 * vel.x + n01 * vel.y, velr[t].y = n10 * vel.x + n11 * vel.y.  When gate > 0:
+ *            candidates are the pairs (q, t) with q present and unmatched after step 3, t live and untaken, and
+ *            d2 = dx * dx + dy * dy <= gate * gate, dx = c_q.x - pred[t].x, dy = c_q.y - pred[t].y (NaN fails the
+ *            comparison).  Order: d2 ascending as f64; ties to the smaller q, then the smaller t.  Walk the order and take
+ *            a pair when neither its q nor its t is taken.  motion_counters[0] += the pairs taken here.
+ * 4. update  the live list, the ids, seen, dropped, state_map, track_map and query_track follow K33a's step 4 with warped
+ *            from moved (so a coasting track's footprint coasts with it) and a pair of either stage counting as a match.
+ *            The new list's entries: a present query matched to t: pos' = c_q, vel' = velr[t] + gain * (c_q - pred[t]) per
+ *            component (subtract, multiply, add); a born query: pos' = c_q, vel' = 0; an appended unmatched track:
+ *            pos' = pred[t], vel' = velr[t].  A component of vel' that is not finite is stored as 0.0.  pos and vel past
+ *            the new n_live are 0.0.
+ *
+ * query_velocity (F, Q, 2) f64: vel' of a present query's track, 0.0 for a query that is not present
+ * Identity       with gain = 0 and gate = 0 every velocity stays 0, every shift is 0 and moved == state_map on valid
+ *                indices: query_track, track_map, state_map, live_id, live_seen and counters equal mbv_track_frames' bit
+ *                for bit.
+ * Limits         shifts are whole cells, so a coasting track's footprint drifts by up to half a cell per frame against its
+ *                pos; step 3b can hand a lost track to another detection within gate of its prediction.
+ * workspace      K33a's, the advected map, the two index sums, the shifts, and c_q, pred and velr.
+ * mbv_track_frames_motion steps through the F frames in order, five launches per frame (clear, which also clears moved and
+ * the index sums and computes the shifts; advect, one thread per cell, an unsigned atomicMin on a map of all-ones; count,
+ * one thread per cell, the index sums per block in LDS and then 64-bit global integer atomics; match + gate + update, ONE
+ * workgroup, the same mutual-best rounds under both orders; paint), enqueued on the stream, never synchronised.  Integer
+ * atomics only: bit-deterministic.  Every output element and every element of the new state and motion record is written by
+ * the call.  Every index comes from the sizes.
+ * Error codes as mbv_track_frames; in addition MBV_ERR_BAD_ARG: gain outside [0, 1] or not finite, gate < 0 or not finite,
+ * max_shift < 0, a null cur_from_prev or motion_counters, null pos / vel when P > 0, null query_velocity when Q > 0.
+ */
+size_t mbv_track_frames_motion_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P);
+int mbv_track_frames_motion(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev, int32_t F,
+                            int32_t H, int32_t W, double x_lo, double y_lo, double voxel, int32_t Q, int32_t P, double min_iou,
+                            int32_t max_age, int32_t min_cells, double gain, double gate, int32_t max_shift, int32_t* state_map,
+                            int32_t* live_id, int32_t* live_seen, int32_t* counters, double* pos, double* vel,
+                            int32_t* motion_counters, int32_t* query_track, int32_t* track_map, double* query_velocity,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K33b — tube association (csrc/track.hip): the S_assoc term of LSTQ (Aygün et al., 4D Panoptic LiDAR Segmentation) over a

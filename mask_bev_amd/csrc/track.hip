@@ -13,6 +13,12 @@
 //                what the walk would skip.  By induction the rounds end with the walk's result, and each round takes at
 //                least the first remaining pair.  Then the update of the live list with three block scans.
 //   4. paint     one thread per cell: the new state map and the optional map of global ids.
+// K37, the same step with a constant-velocity motion model (mbv_track_frames_motion), five launches per frame: clear (also
+// the advected map, the centroid sums and the cell shift of every live track), advect (one thread per cell, unsigned
+// atomicMin: the smallest track index wins a cell), count<true> (reads the advected map; the index sums of a query's cells
+// per block in LDS, flushed with 64-bit global atomics), match<true> (after the IoU rounds: centroids, predictions, the gate
+// candidates and the same mutual-best rounds under the order (d2, q, t); then the update also of pos / vel) and paint.
+// count and match are one template each: the <false> instantiations are K33a's kernels.
 // K33b: accumulate (grid-stride blocks with LDS tables for the two size tables where they fit), scores (one workgroup per
 // row; the terms of 256 tracks at a time in LDS, summed by one thread in ascending order) and the class sums.
 // Integer atomics only; every f64 sum in a fixed order: two runs are bit-equal.  Every index comes from the sizes: a query, a
@@ -32,12 +38,20 @@ struct TrackWorkspace {
   int32_t* cand;     // (Q * P): q * P + t of the candidate pairs, in no order
   int32_t* q_new;    // (Q): the new local index of a present query, else -1
   int32_t* t_new;    // (P): the new local index of an appended old track, else -1
+  // K37 only
+  uint32_t* moved;   // (H, W): the advected state map; all-ones (-1 as i32) for none
+  int64_t* sum_ix;   // (Q): the sum of ix over the cells of a query
+  int64_t* sum_iy;   // (Q)
+  int32_t* shift;    // (P, 2): sx, sy of every live track in cells
+  double* cq;        // (Q, 2): the centroid of a present query
+  double* pred;      // (P, 2): the predicted centroid of a live track in the current frame
+  double* velr;      // (P, 2): its velocity in the current frame's axes
   size_t bytes;
 };
 
-TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P) {
+TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P, bool motion = false) {
   MbvCarver c(ws);
-  TrackWorkspace w;
+  TrackWorkspace w{};
   w.warped = c.take<int32_t>(cells);
   w.area_q = c.take<int32_t>(Q);
   w.area_t = c.take<int32_t>(P);
@@ -45,6 +59,15 @@ TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P) {
   w.cand = c.take<int32_t>((int64_t)Q * P);
   w.q_new = c.take<int32_t>(Q);
   w.t_new = c.take<int32_t>(P);
+  if (motion) {
+    w.moved = c.take<uint32_t>(cells);
+    w.sum_ix = c.take<int64_t>(Q);
+    w.sum_iy = c.take<int64_t>(Q);
+    w.shift = c.take<int32_t>(2 * (int64_t)P);
+    w.cq = c.take<double>(2 * (int64_t)Q);
+    w.pred = c.take<double>(2 * (int64_t)P);
+    w.velr = c.take<double>(2 * (int64_t)P);
+  }
   w.bytes = c.off;
   return w;
 }
@@ -63,16 +86,70 @@ __global__ void __launch_bounds__(kThreads) k_track_clear(int Q, int P, int32_t*
   for (int64_t i = t; i < P; i += stride) area_t[i] = 0;
 }
 
+__device__ __forceinline__ void add64(int64_t* p, int64_t n) {
+  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)n);
+}
+
+// K37's clear: K33a's tables, the advected map, the centroid sums, and step 0's cell shift of every track
+__global__ void __launch_bounds__(kThreads) k_track_clear_motion(int64_t cells, int Q, int P, double voxel, int max_shift,
+                                                                 const int32_t* __restrict__ counters,
+                                                                 const double* __restrict__ vel, int32_t* __restrict__ area_q,
+                                                                 int32_t* __restrict__ area_t, int32_t* __restrict__ inter,
+                                                                 uint32_t* __restrict__ moved, int64_t* __restrict__ sum_ix,
+                                                                 int64_t* __restrict__ sum_iy, int32_t* __restrict__ shift) {
+  const int64_t stride = (int64_t)gridDim.x * kThreads, n = (int64_t)Q * P;
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  const int n_live = live_count(counters, P);
+  for (int64_t i = t; i < n; i += stride) inter[i] = 0;
+  for (int64_t i = t; i < cells; i += stride) moved[i] = 0xffffffffu;
+  for (int64_t i = t; i < Q; i += stride) {
+    area_q[i] = 0;
+    sum_ix[i] = 0;
+    sum_iy[i] = 0;
+  }
+  for (int64_t i = t; i < P; i += stride) {
+    area_t[i] = 0;
+    double sx = 0.0, sy = 0.0;
+    if (i < n_live) {
+      sx = rint(vel[2 * i] / voxel);
+      sy = rint(vel[2 * i + 1] / voxel);
+      if (!(fabs(sx) <= (double)max_shift && fabs(sy) <= (double)max_shift)) sx = sy = 0.0;   // NaN and inf land here
+    }
+    shift[2 * i] = (int32_t)sx;                                    // |sx| <= max_shift < 2^31
+    shift[2 * i + 1] = (int32_t)sy;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) k_track_advect(const int32_t* __restrict__ state_map, int H, int W, int P,
+                                                           const int32_t* __restrict__ counters,
+                                                           const int32_t* __restrict__ shift, uint32_t* __restrict__ moved) {
+  const int64_t cells = (int64_t)H * W;
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= cells) return;
+  const int t = state_map[i];
+  if (t < 0 || t >= live_count(counters, P)) return;
+  const int iy = (int)(i / W), ix = (int)(i - (int64_t)iy * W);
+  const int64_t tx = (int64_t)ix + shift[2 * t], ty = (int64_t)iy + shift[2 * t + 1];
+  if (tx >= 0 && tx < W && ty >= 0 && ty < H) atomicMin(&moved[ty * W + tx], (uint32_t)t);
+}
+
+template <bool kMotion>
 __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restrict__ instance_map,
                                                           const int32_t* __restrict__ state_map,
                                                           const double* __restrict__ prev_from_cur, int H, int W, double x_lo,
                                                           double y_lo, double voxel, int Q, int P,
                                                           const int32_t* __restrict__ counters, int32_t* __restrict__ warped,
                                                           int32_t* __restrict__ area_q, int32_t* __restrict__ area_t,
-                                                          int32_t* __restrict__ inter) {
+                                                          int32_t* __restrict__ inter, int64_t* __restrict__ sum_ix,
+                                                          int64_t* __restrict__ sum_iy) {
   __shared__ int32_t s_q[kMaxTracks];
   __shared__ int32_t s_t[kMaxTracks];
+  // K37: a block of 256 cells adds at most 256 * 2^20 < 2^31 to a slot, so i32 holds a block's index sums
+  __shared__ int32_t s_x[kMotion ? kMaxTracks : 1];
+  __shared__ int32_t s_y[kMotion ? kMaxTracks : 1];
   const int n_live = live_count(counters, P);
+  if constexpr (kMotion)
+    for (int k = threadIdx.x; k < Q; k += kThreads) s_x[k] = s_y[k] = 0;
   for (int k = threadIdx.x; k < Q; k += kThreads) s_q[k] = 0;
   for (int k = threadIdx.x; k < P; k += kThreads) s_t[k] = 0;
   __syncthreads();
@@ -94,6 +171,12 @@ __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restr
     int q = instance_map[i];
     if (q < 0 || q >= Q) q = -1;
     if (q >= 0) atomicAdd(&s_q[q], 1);
+    if constexpr (kMotion) {
+      if (q >= 0) {
+        atomicAdd(&s_x[q], ix);
+        atomicAdd(&s_y[q], iy);
+      }
+    }
     if (t >= 0) atomicAdd(&s_t[t], 1);
     if (q >= 0 && t >= 0) atomicAdd(&inter[(int64_t)q * P + t], 1);
   }
@@ -101,6 +184,12 @@ __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restr
   for (int k = threadIdx.x; k < Q; k += kThreads) {
     const int32_t n = s_q[k];
     if (n > 0) atomicAdd(&area_q[k], n);
+    if constexpr (kMotion) {
+      if (n > 0) {
+        add64(&sum_ix[k], s_x[k]);
+        add64(&sum_iy[k], s_y[k]);
+      }
+    }
   }
   for (int k = threadIdx.x; k < P; k += kThreads) {
     const int32_t n = s_t[k];
@@ -140,7 +229,28 @@ __device__ __forceinline__ bool pair_before(const MatchTables& m, int32_t a, int
   return a < b;                                                    // q * P + t: the smaller q, then the smaller t
 }
 
-__device__ __forceinline__ void offer_best(const MatchTables& m, int32_t* slot, int32_t pair) {
+// K37's second stage: the tables are in global memory, written by this workgroup before a barrier (no __restrict__)
+struct GateTables {
+  const double* cq;          // (Q, 2)
+  const double* pred;        // (P, 2)
+  int P;
+};
+
+__device__ __forceinline__ double gate_d2(const double* cq, const double* pred, int q, int t) {
+  const double dx = cq[2 * q] - pred[2 * t], dy = cq[2 * q + 1] - pred[2 * t + 1];
+  return dx * dx + dy * dy;
+}
+
+// the order (d2, q, t); a candidate's d2 is never NaN: it passed d2 <= gate * gate
+__device__ __forceinline__ bool pair_before(const GateTables& m, int32_t a, int32_t b) {
+  const int qa = a / m.P, ta = a - qa * m.P, qb = b / m.P, tb = b - qb * m.P;
+  const double da = gate_d2(m.cq, m.pred, qa, ta), db = gate_d2(m.cq, m.pred, qb, tb);
+  if (da != db) return da < db;
+  return a < b;
+}
+
+template <class Tables>
+__device__ __forceinline__ void offer_best(const Tables& m, int32_t* slot, int32_t pair) {
   int32_t cur = *slot;
   while (cur < 0 || pair_before(m, pair, cur)) {
     const int32_t seen = atomicCAS(slot, cur, pair);
@@ -149,13 +259,67 @@ __device__ __forceinline__ void offer_best(const MatchTables& m, int32_t* slot, 
   }
 }
 
+// The mutual-best rounds over cand[0 .. n_cand) under the order of `m`: valid for any strict total order.  Every thread of
+// the workgroup must call it.
+template <class Tables>
+__device__ __forceinline__ void match_rounds(const Tables& m, const int32_t* cand, int n_cand, int Q, int P, int32_t* s_best_q,
+                                             int32_t* s_best_t, int32_t* s_q_match, int32_t* s_t_taken, int32_t* s_open) {
+  const int t = threadIdx.x;
+  for (int round = 0; round < kMaxTracks; ++round) {               // every round takes a pair or is the last
+    if (t < Q) s_best_q[t] = -1;
+    if (t < P) s_best_t[t] = -1;
+    if (t == 0) *s_open = 0;
+    __syncthreads();
+    for (int k = t; k < n_cand; k += kWide) {
+      const int32_t pair = cand[k];
+      const int q = pair / P, tr = pair - q * P;
+      if (s_q_match[q] >= 0 || s_t_taken[tr]) continue;
+      *s_open = 1;
+      offer_best(m, &s_best_q[q], pair);
+      offer_best(m, &s_best_t[tr], pair);
+    }
+    __syncthreads();
+    if (!*s_open) break;                                           // uniform: read after the barrier
+    if (t < Q) {
+      const int32_t pair = s_best_q[t];
+      if (pair >= 0) {
+        const int tr = pair - t * P;
+        if (s_best_t[tr] == pair) {
+          s_q_match[t] = tr;
+          s_t_taken[tr] = 1;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// K37's per-frame arguments of the match kernel; unused (and empty) in K33a's instantiation
+struct MotionArgs {
+  const double* cur_from_prev;     // (6): n of this frame
+  double gain, gate, x_lo, y_lo, voxel;
+  const int64_t* sum_ix;           // (Q)
+  const int64_t* sum_iy;
+  double* cq;                      // workspace (Q, 2)
+  double* pred;                    // workspace (P, 2)
+  double* velr;                    // workspace (P, 2)
+  double* pos;                     // state (P, 2)
+  double* vel;
+  int32_t* motion_counters;        // state (2)
+  double* query_velocity;          // this frame's (Q, 2)
+};
+
+__device__ __forceinline__ double finite_or_zero(double v) { return fabs(v) <= 1.7976931348623157e308 ? v : 0.0; }
+
+template <bool kMotion>
 __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_iou, int max_age, int min_cells,
                                                        const int32_t* __restrict__ g_area_q,
                                                        const int32_t* __restrict__ g_area_t,
                                                        const int32_t* __restrict__ inter, int32_t* __restrict__ cand,
                                                        int32_t* __restrict__ live_id, int32_t* __restrict__ live_seen,
                                                        int32_t* __restrict__ counters, int32_t* __restrict__ query_track,
-                                                       int32_t* __restrict__ q_new, int32_t* __restrict__ t_new) {
+                                                       int32_t* __restrict__ q_new, int32_t* __restrict__ t_new,
+                                                       MotionArgs mo) {
   __shared__ int32_t s_area_q[kMaxTracks];
   __shared__ int32_t s_area_t[kMaxTracks];
   __shared__ int32_t s_best_q[kMaxTracks];                         // the round's best pair of a row
@@ -196,33 +360,43 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
   __syncthreads();
   const int n_cand = s_n_cand;
   MatchTables m{inter, s_area_q, s_area_t, P};
+  match_rounds(m, cand, n_cand, Q, P, s_best_q, s_best_t, s_q_match, s_t_taken, &s_open);
 
-  for (int round = 0; round < kMaxTracks; ++round) {               // every round takes a pair or is the last
-    if (t < Q) s_best_q[t] = -1;
-    if (t < P) s_best_t[t] = -1;
-    if (t == 0) s_open = 0;
-    __syncthreads();
-    for (int k = t; k < n_cand; k += kWide) {
-      const int32_t pair = cand[k];
-      const int q = pair / P, tr = pair - q * P;
-      if (s_q_match[q] >= 0 || s_t_taken[tr]) continue;
-      s_open = 1;
-      offer_best(m, &s_best_q[q], pair);
-      offer_best(m, &s_best_t[tr], pair);
+  // K37, step 3b: the centroids, the predictions, and the gated second stage over what step 3 left open
+  __shared__ int32_t s_gated;
+  if constexpr (kMotion) {
+    const double* n = mo.cur_from_prev;
+    if (t < Q && s_area_q[t] >= min_cells) {
+      const double area = (double)s_area_q[t];
+      mo.cq[2 * t] = mo.x_lo + ((double)mo.sum_ix[t] / area + 0.5) * mo.voxel;
+      mo.cq[2 * t + 1] = mo.y_lo + ((double)mo.sum_iy[t] / area + 0.5) * mo.voxel;
     }
-    __syncthreads();
-    if (!s_open) break;                                            // uniform: read after the barrier
-    if (t < Q) {
-      const int32_t pair = s_best_q[t];
-      if (pair >= 0) {
-        const int tr = pair - t * P;
-        if (s_best_t[tr] == pair) {
-          s_q_match[t] = tr;
-          s_t_taken[tr] = 1;
-        }
+    if (t < n_live) {
+      const double vx = mo.vel[2 * t], vy = mo.vel[2 * t + 1];
+      const double ax = mo.pos[2 * t] + vx, ay = mo.pos[2 * t + 1] + vy;
+      mo.pred[2 * t] = (n[0] * ax + n[1] * ay) + n[2];
+      mo.pred[2 * t + 1] = (n[3] * ax + n[4] * ay) + n[5];
+      mo.velr[2 * t] = n[0] * vx + n[1] * vy;
+      mo.velr[2 * t + 1] = n[3] * vx + n[4] * vy;
+    }
+    if (t == 0) {
+      s_n_cand = 0;
+      s_gated = 0;
+    }
+    __syncthreads();                                               // cq, pred and velr are read by other threads from here
+    if (mo.gate > 0.0) {                                           // uniform
+      const double g2 = mo.gate * mo.gate;
+      for (int64_t k = t; k < table; k += kWide) {
+        const int q = (int)(k / n_live), tr = (int)(k - (int64_t)q * n_live);
+        if (s_area_q[q] < min_cells || s_q_match[q] >= 0 || s_t_taken[tr]) continue;
+        if (gate_d2(mo.cq, mo.pred, q, tr) <= g2) cand[atomicAdd(&s_n_cand, 1)] = q * P + tr;   // NaN fails
       }
+      const bool open_before = t < Q && s_q_match[t] < 0;
+      __syncthreads();
+      GateTables g{mo.cq, mo.pred, P};
+      match_rounds(g, cand, s_n_cand, Q, P, s_best_q, s_best_t, s_q_match, s_t_taken, &s_open);
+      if (open_before && s_q_match[t] >= 0) atomicAdd(&s_gated, 1);
     }
-    __syncthreads();
   }
 
   // the new live list: the present queries in ascending q, then the unmatched old tracks that are young enough
@@ -260,6 +434,38 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
       live_seen[idx] = s_seen[t];
     }
     t_new[t] = idx;
+    if constexpr (kMotion) {
+      if (idx >= 0) {                                              // a coasting track moves on with its prediction
+        mo.pos[2 * idx] = mo.pred[2 * t];
+        mo.pos[2 * idx + 1] = mo.pred[2 * t + 1];
+        mo.vel[2 * idx] = finite_or_zero(mo.velr[2 * t]);
+        mo.vel[2 * idx + 1] = finite_or_zero(mo.velr[2 * t + 1]);
+      }
+    }
+  }
+  if constexpr (kMotion) {
+    // pos and vel of the old list were last read before the barrier of step 3b: every slot of the new one has one writer
+    if (t >= n_new && t < P) mo.pos[2 * t] = mo.pos[2 * t + 1] = mo.vel[2 * t] = mo.vel[2 * t + 1] = 0.0;
+    if (t < Q) {
+      double vx = 0.0, vy = 0.0;
+      if (present) {
+        const double cx = mo.cq[2 * t], cy = mo.cq[2 * t + 1];
+        if (matched >= 0) {
+          vx = finite_or_zero(mo.velr[2 * matched] + mo.gain * (cx - mo.pred[2 * matched]));
+          vy = finite_or_zero(mo.velr[2 * matched + 1] + mo.gain * (cy - mo.pred[2 * matched + 1]));
+        }
+        mo.pos[2 * (pos_q - 1)] = cx;
+        mo.pos[2 * (pos_q - 1) + 1] = cy;
+        mo.vel[2 * (pos_q - 1)] = vx;
+        mo.vel[2 * (pos_q - 1) + 1] = vy;
+      }
+      mo.query_velocity[2 * t] = vx;
+      mo.query_velocity[2 * t + 1] = vy;
+    }
+    if (t == 0) {
+      mo.motion_counters[0] += s_gated;
+      mo.motion_counters[1] = 0;
+    }
   }
   if (t == 0) {
     counters[0] = n_new;
@@ -301,10 +507,6 @@ __device__ __forceinline__ int tube_class_of(uint32_t word, const int32_t* __res
   if (sem >= lut_len) return -1;
   const int c = class_lut[sem];
   return (c < 0 || c >= C) ? -1 : c;
-}
-
-__device__ __forceinline__ void add64(int64_t* p, int64_t n) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)n);
 }
 
 __global__ void __launch_bounds__(kThreads) k_tube_accumulate(const int32_t* __restrict__ pred_track,
@@ -455,14 +657,72 @@ extern "C" int mbv_track_frames(const int32_t* instance_maps, const double* prev
                        w.area_t, w.inter);
     MBV_CHECK_LAUNCH();
     if (cells > 0) {
-      hipLaunchKernelGGL(k_track_count, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, state_map,
+      hipLaunchKernelGGL(k_track_count<false>, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, state_map,
                          prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo, voxel, (int)Q, (int)P, counters, w.warped,
-                         w.area_q, w.area_t, w.inter);
+                         w.area_q, w.area_t, w.inter, (int64_t*)nullptr, (int64_t*)nullptr);
       MBV_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_track_match, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age, (int)min_cells,
-                       w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters, query_track + (int64_t)f * Q, w.q_new,
-                       w.t_new);
+    hipLaunchKernelGGL(k_track_match<false>, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age,
+                       (int)min_cells, w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters,
+                       query_track + (int64_t)f * Q, w.q_new, w.t_new, MotionArgs{});
+    MBV_CHECK_LAUNCH();
+    if (cells > 0) {
+      hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
+                         w.q_new, w.t_new, query_track + (int64_t)f * Q, state_map,
+                         track_map ? track_map + (int64_t)f * cells : nullptr);
+      MBV_CHECK_LAUNCH();
+    }
+  }
+  return MBV_OK;
+}
+
+extern "C" size_t mbv_track_frames_motion_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
+  if (!track_sizes_supported(H, W, Q, P)) return 0;
+  return carve_track(nullptr, (int64_t)H * W, Q, P, true).bytes;
+}
+
+extern "C" int mbv_track_frames_motion(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev,
+                                       int32_t F, int32_t H, int32_t W, double x_lo, double y_lo, double voxel, int32_t Q,
+                                       int32_t P, double min_iou, int32_t max_age, int32_t min_cells, double gain, double gate,
+                                       int32_t max_shift, int32_t* state_map, int32_t* live_id, int32_t* live_seen,
+                                       int32_t* counters, double* pos, double* vel, int32_t* motion_counters,
+                                       int32_t* query_track, int32_t* track_map, double* query_velocity, void* workspace,
+                                       size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (F == 0) return MBV_OK;
+  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || min_cells < 1 || max_age < 0 || max_shift < 0) return MBV_ERR_BAD_ARG;
+  if (!(gain >= 0.0 && gain <= 1.0) || !(gate >= 0.0 && gate <= 1.7976931348623157e308)) return MBV_ERR_BAD_ARG;   // NaN, inf
+  if (!track_sizes_supported(H, W, Q, P)) return MBV_ERR_UNSUPPORTED;
+  const int64_t cells = (int64_t)H * W;
+  if (!prev_from_cur || !cur_from_prev || !counters || !motion_counters || (cells > 0 && (!instance_maps || !state_map)) ||
+      (P > 0 && (!live_id || !live_seen || !pos || !vel)) || (Q > 0 && (!query_track || !query_velocity)))
+    return MBV_ERR_BAD_ARG;
+  TrackWorkspace w = carve_track(workspace, cells, Q, P, true);
+  if (!workspace || workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
+
+  const int64_t most = (int64_t)Q * P > cells ? (int64_t)Q * P : cells;
+  int64_t clear_blocks = (most + kThreads - 1) / kThreads;
+  clear_blocks = clear_blocks < 1 ? 1 : (clear_blocks > 1024 ? 1024 : clear_blocks);
+  const unsigned cell_blocks = (unsigned)((cells + kThreads - 1) / kThreads);
+  for (int f = 0; f < F; ++f) {
+    const int32_t* imap = instance_maps + (int64_t)f * cells;
+    hipLaunchKernelGGL(k_track_clear_motion, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, cells, (int)Q, (int)P,
+                       voxel, (int)max_shift, counters, vel, w.area_q, w.area_t, w.inter, w.moved, w.sum_ix, w.sum_iy, w.shift);
+    MBV_CHECK_LAUNCH();
+    if (cells > 0) {
+      hipLaunchKernelGGL(k_track_advect, dim3(cell_blocks), dim3(kThreads), 0, stream, state_map, (int)H, (int)W, (int)P,
+                         counters, w.shift, w.moved);
+      MBV_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_track_count<true>, dim3(cell_blocks), dim3(kThreads), 0, stream, imap,
+                         reinterpret_cast<const int32_t*>(w.moved), prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo,
+                         voxel, (int)Q, (int)P, counters, w.warped, w.area_q, w.area_t, w.inter, w.sum_ix, w.sum_iy);
+      MBV_CHECK_LAUNCH();
+    }
+    MotionArgs mo{cur_from_prev + (int64_t)f * 6, gain, gate, x_lo, y_lo, voxel, w.sum_ix, w.sum_iy, w.cq, w.pred, w.velr, pos,
+                  vel, motion_counters, query_velocity + (int64_t)f * Q * 2};
+    hipLaunchKernelGGL(k_track_match<true>, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age,
+                       (int)min_cells, w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters,
+                       query_track + (int64_t)f * Q, w.q_new, w.t_new, mo);
     MBV_CHECK_LAUNCH();
     if (cells > 0) {
       hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,

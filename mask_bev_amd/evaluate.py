@@ -11,7 +11,7 @@ from .datasets import KittiFrames, semantic_kitti_files
 from .kitti_eval import eval_kitti
 from .metrics import DevicePanopticQuality, DeviceTubeAssociation, lstq, semantic_kitti_class_lut
 from .predict import BOX_METHODS, GroundSettings, write_semantic_kitti_labels
-from .tracking import InstanceTracker, velodyne_poses
+from .tracking import InstanceTracker, MotionSettings, velodyne_poses
 
 
 def predictions(model, scan_paths, bsz, device, score_threshold=0.0):
@@ -152,9 +152,15 @@ def format_point_panoptic(result, things=((10,),)):
 
 
 def tracking_settings(config):
-    """``track_min_iou`` (0.3), ``track_max_age`` (2), ``track_min_cells`` (4), ``track_max_tracks`` (256): ``InstanceTracker``'s."""
-    return dict(min_iou=float(config.get('track_min_iou', 0.3)), max_age=int(config.get('track_max_age', 2)),
-                min_cells=int(config.get('track_min_cells', 4)), max_tracks=int(config.get('track_max_tracks', 256)))
+    """``track_min_iou`` (0.3), ``track_max_age`` (2), ``track_min_cells`` (4), ``track_max_tracks`` (256): ``InstanceTracker``'s.
+    ``track_motion: true`` adds ``motion``, a ``MotionSettings`` (K37) from ``track_velocity_gain`` (0.5), ``track_gate`` (3.0 m)
+    and ``track_max_speed`` (6.0 m per frame); without the key the result is what it was."""
+    out = dict(min_iou=float(config.get('track_min_iou', 0.3)), max_age=int(config.get('track_max_age', 2)),
+               min_cells=int(config.get('track_min_cells', 4)), max_tracks=int(config.get('track_max_tracks', 256)))
+    if bool(config.get('track_motion', False)):
+        out['motion'] = MotionSettings(gain=float(config.get('track_velocity_gain', 0.5)), gate_m=float(config.get('track_gate', 3.0)),
+                                       max_speed=float(config.get('track_max_speed', 6.0)))
+    return out
 
 
 def sequence_tracking(model, config, device, root, sequences, out_dir=None, score_threshold=0.0, semantic_id=10):
@@ -163,7 +169,8 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
     ``calib.txt``), the lift to the points (K31) and the per-point track ids.  With ``labels/NNNNNN.label`` next to every scan the
     tube association (K33b) per sequence and the panoptic IoU (K32) of this rank alone over the same frames; with ``out_dir`` the
     ``.label`` files carry the track id + 1 as the instance id.  Returns ``None`` — after one line that says why — when a
-    sequence lacks ``poses.txt`` or ``calib.txt``, else ``{'tracks', 'dropped', 'frames', 'written'}`` plus, with labels,
+    sequence lacks ``poses.txt`` or ``calib.txt``, else ``{'tracks', 'dropped', 'frames', 'written'}`` (with ``track_motion: true``
+    the tracker runs K37's motion model and ``'gated'`` is added) plus, with labels,
     ``{'lstq', 's_assoc', 's_cls', 'tubes'}``.  Not pinned: parity with semantic-kitti-api's 4D evaluator, LSTQ on real data."""
     by_seq = {}
     for f, _ in semantic_kitti_files(root, sequences):
@@ -198,8 +205,8 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
                     out['written'].append(prediction_label_path(out_dir, f))
                     write_semantic_kitti_labels(out['written'][-1], labels, semantic_id, instance_ids=tracks)
         counts = tracker.counters()
-        for key in ('tracks', 'dropped', 'frames'):
-            out[key] += counts[key]
+        for key in ('tracks', 'dropped', 'frames') + (('gated',) if 'gated' in counts else ()):
+            out[key] = out.get(key, 0) + counts[key]
         if have_labels:
             res = tubes.compute()                  # per sequence: SemanticKITTI's instance ids are unique inside one only
             assoc_sum += res['s_assoc'] * res['tubes']
@@ -213,8 +220,9 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
 
 def format_point_lstq(result):
     """The ``point LSTQ`` line of ``--test`` from :func:`sequence_tracking`."""
+    gated = f', gated {result["gated"]}' if 'gated' in result else ''                  # K37: with ``track_motion: true`` only
     return (f'point LSTQ {result["lstq"]:.4f} S_assoc {result["s_assoc"]:.4f} S_cls {result["s_cls"]:.4f} '
-            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]})')
+            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]}{gated})')
 
 
 def format_layer_metrics(logged, layer):

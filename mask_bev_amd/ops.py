@@ -24,7 +24,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
                    K29 pairwise overlap of packed masks + COCO per-image matching (mask mAP),
                    K30 largest 8-connected component + minimum-area rectangle of a packed mask,
                    K32 panoptic tp / fp / fn, IoU sums and confusion per frame from two id arrays (points or BEV cells)
-    ops_track      K33 the tracker step over consecutive BEV instance maps (global instance ids) and tube association (S_assoc of LSTQ)
+    ops_track      K33 the tracker step over consecutive BEV instance maps (global instance ids) and tube association (S_assoc of LSTQ);
+                   K37 the same step with a constant-velocity motion model and gated re-association
     ops_render     K36 returns per BEV cell and the composed BEV frame (density, instances / tracks, ground-truth contour, boxes)
 """
 from .ops_core import *            # noqa: F401,F403

@@ -1,8 +1,10 @@
-"""K33a — the tracker step over consecutive BEV instance maps of one sequence, and K33b — tube association, the S_assoc
-term of LSTQ (csrc/track.hip).  Behind ``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions
-are in include/maskbev_hip.h."""
+"""K33a — the tracker step over consecutive BEV instance maps of one sequence, K37 — the same step with a constant-velocity
+motion model and gated re-association (off by default), and K33b — tube association, the S_assoc term of LSTQ
+(csrc/track.hip).  Behind ``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions are in
+include/maskbev_hip.h."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -14,14 +16,55 @@ from .ops_core import _need_gpu, _ptr, _stream, _workspace
 
 
 @dataclass
+class TrackMotion:
+    """K37's motion record of a tracker, on the device (include/maskbev_hip.h): ``pos`` (P, 2) f64 — the centroid of every live
+    track in metres, x then y, in the coordinates of the frame last processed; ``vel`` (P, 2) f64 — metres per frame in the
+    same coordinates (motion over ground in sensor axes); ``motion_counters`` (2) int32 = gated, reserved 0."""
+    pos: torch.Tensor
+    vel: torch.Tensor
+    motion_counters: torch.Tensor
+
+    @staticmethod
+    def fresh(max_tracks: int, device) -> 'TrackMotion':
+        return TrackMotion(torch.zeros((int(max_tracks), 2), dtype=torch.float64, device=device),
+                           torch.zeros((int(max_tracks), 2), dtype=torch.float64, device=device),
+                           torch.zeros((2,), dtype=torch.int32, device=device))
+
+
+@dataclass
+class MotionSettings:
+    """K37's settings (``tracking.MotionSettings`` is this class): ``gain`` in [0, 1] — the share of a frame's innovation
+    (measured centroid minus predicted) that goes into the velocity; ``gate_m`` >= 0 in metres — the centroid-distance gate of
+    the second stage, 0 switches it off; ``max_speed`` >= 0 in metres per frame — a track predicted to move further is not
+    advected: the kernel's ``max_shift`` is ``floor(max_speed / voxel)`` cells.  The defaults are geometry, not measurement:
+    3.0 m is just over the 2.8 m an oncoming car moves per frame at 100 km/h relative and 10 Hz; 6.0 m per frame is 216 km/h
+    at 10 Hz."""
+    gain: float = 0.5
+    gate_m: float = 3.0
+    max_speed: float = 6.0
+
+    def __post_init__(self):
+        self.gain, self.gate_m, self.max_speed = float(self.gain), float(self.gate_m), float(self.max_speed)
+        if not (0.0 <= self.gain <= 1.0 and 0.0 <= self.gate_m < math.inf and 0.0 <= self.max_speed < math.inf):
+            raise ValueError(f'MotionSettings: gain {self.gain} in [0, 1], gate_m {self.gate_m} >= 0 and max_speed '
+                             f'{self.max_speed} >= 0, all finite, expected')
+
+    def max_shift(self, voxel: float) -> int:
+        """``floor(max_speed / voxel)`` cells, at most 2^31 - 1."""
+        return int(min(math.floor(self.max_speed / float(voxel)), 2 ** 31 - 1))
+
+
+@dataclass
 class TrackState:
     """The tracker's persistent state on the device (include/maskbev_hip.h, K33a): ``state_map`` (H, W) int32 — a local
     track index or -1; ``live_id`` / ``live_seen`` (P) int32 — the global id and the frame of the last match of every live
-    track; ``counters`` (4) int32 = n_live, next_id, frame, dropped."""
+    track; ``counters`` (4) int32 = n_live, next_id, frame, dropped.  ``motion``: K37's record, None without the motion
+    model."""
     state_map: torch.Tensor
     live_id: torch.Tensor
     live_seen: torch.Tensor
     counters: torch.Tensor
+    motion: Optional[TrackMotion] = None
 
     @staticmethod
     def fresh(h: int, w: int, max_tracks: int, device) -> 'TrackState':
@@ -34,9 +77,12 @@ class TrackState:
 @dataclass
 class TrackFrames:
     """K33a's outputs for F frames: ``query_track`` (F, Q) int32 — the global id of every query, -1 when it is not present;
-    ``track_map`` (F, H, W) int32 — the global id on the cells of present queries, else -1 (None when not asked for)."""
+    ``track_map`` (F, H, W) int32 — the global id on the cells of present queries, else -1 (None when not asked for);
+    ``query_velocity`` (F, Q, 2) f64 — K37: the velocity of a present query's track in metres per frame, 0 for a query that is
+    not present (None without the motion model)."""
     query_track: torch.Tensor
     track_map: Optional[torch.Tensor]
+    query_velocity: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -76,10 +122,13 @@ class TubeScores:
 @torch.no_grad()
 def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state: TrackState, x_lo: float, y_lo: float,
                  voxel: float, num_queries: int, min_iou: float = 0.3, max_age: int = 2, min_cells: int = 4,
-                 track_map: bool = False) -> TrackFrames:
+                 track_map: bool = False, motion: Optional[MotionSettings] = None,
+                 cur_from_prev: Optional[torch.Tensor] = None) -> TrackFrames:
     """K33a: ``instance_maps`` (F, H, W) int32 — F consecutive frames of ONE sequence, a query in [0, num_queries) or -1 per
     cell; ``prev_from_cur`` (F, 2, 3) f64 — per frame the map of its BEV coordinates into the previous frame's; ``state`` is
-    stepped in place.  Device tensors only; no host synchronisation."""
+    stepped in place.  Device tensors only; no host synchronisation.
+    ``motion``: K37 — the step with the motion model; ``state.motion`` must hold the record.  ``cur_from_prev`` (F, 2, 3) f64
+    is the inverse of ``prev_from_cur``; when it is absent it is computed on the device (:func:`invert_transforms`)."""
     lib = _lib.load()
     _need_gpu(instance_maps, prev_from_cur, state.state_map, state.live_id, state.live_seen, state.counters)
     dev = instance_maps.device
@@ -103,6 +152,9 @@ def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state
     instance_maps, prev_from_cur = instance_maps.contiguous(), prev_from_cur.contiguous()
     out = TrackFrames(torch.empty((f, q), dtype=torch.int32, device=dev),
                       torch.empty((f, h, w), dtype=torch.int32, device=dev) if track_map else None)
+    if motion is not None:
+        return _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state, float(x_lo), float(y_lo),
+                                    float(voxel), q, p, float(min_iou), int(max_age), int(min_cells), motion, out)
     if f == 0:
         return out
     ws = _workspace(lib.mbv_track_frames_workspace_bytes(h, w, q, p), dev)
@@ -110,6 +162,51 @@ def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state
                                float(min_iou), int(max_age), int(min_cells), _ptr(state.state_map), _ptr(state.live_id),
                                _ptr(state.live_seen), _ptr(state.counters), _ptr(out.query_track), _ptr(out.track_map),
                                _ptr(ws), ws.numel(), _stream()), 'mbv_track_frames')
+    return out
+
+
+def invert_transforms(prev_from_cur: torch.Tensor) -> torch.Tensor:
+    """``cur_from_prev`` (F, 2, 3) f64: the first two rows of the inverse of every ``prev_from_cur`` completed to 3 x 3 with the
+    row 0 0 1 — by the adjugate of the 2 x 2 part, elementwise on the input's device, no host synchronisation."""
+    m = prev_from_cur.to(torch.float64)
+    a, b, tx, c, d, ty = m[:, 0, 0], m[:, 0, 1], m[:, 0, 2], m[:, 1, 0], m[:, 1, 1], m[:, 1, 2]
+    det = a * d - b * c
+    n00, n01, n10, n11 = d / det, -b / det, -c / det, a / det
+    return torch.stack([torch.stack([n00, n01, -(n00 * tx + n01 * ty)], dim=1),
+                        torch.stack([n10, n11, -(n10 * tx + n11 * ty)], dim=1)], dim=1).contiguous()
+
+
+def _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state, x_lo, y_lo, voxel, q, p, min_iou, max_age,
+                         min_cells, motion, out) -> TrackFrames:
+    dev = instance_maps.device
+    f, h, w = (int(v) for v in instance_maps.shape)
+    rec = state.motion
+    if rec is None:
+        raise MaskBevHipError('track_frames: motion settings given, but state.motion is None (TrackMotion.fresh)')
+    _need_gpu(rec.pos, rec.vel, rec.motion_counters)
+    for name, x, shape, dt in (('pos', rec.pos, (p, 2), torch.float64), ('vel', rec.vel, (p, 2), torch.float64),
+                               ('motion_counters', rec.motion_counters, (2,), torch.int32)):
+        if tuple(x.shape) != shape or x.dtype != dt or x.device != dev or not x.is_contiguous():
+            raise MaskBevHipError(f'track_frames: state.motion.{name} must be a contiguous {shape} {dt} tensor on {dev}')
+    if not voxel > 0.0:
+        raise MaskBevHipError(f'track_frames: voxel {voxel} > 0 expected')
+    gain, gate, max_shift = motion.gain, motion.gate_m, motion.max_shift(voxel)
+    if cur_from_prev is None:
+        cur_from_prev = invert_transforms(prev_from_cur)
+    _need_gpu(cur_from_prev)
+    if tuple(cur_from_prev.shape) != (f, 2, 3) or cur_from_prev.dtype != torch.float64 or cur_from_prev.device != dev:
+        raise MaskBevHipError(f'track_frames: cur_from_prev must be ({f}, 2, 3) float64 on {dev}, got '
+                              f'{tuple(cur_from_prev.shape)} {cur_from_prev.dtype}')
+    cur_from_prev = cur_from_prev.contiguous()
+    out.query_velocity = torch.empty((f, q, 2), dtype=torch.float64, device=dev)
+    if f == 0:
+        return out
+    ws = _workspace(lib.mbv_track_frames_motion_workspace_bytes(h, w, q, p), dev)
+    check(lib.mbv_track_frames_motion(_ptr(instance_maps), _ptr(prev_from_cur), _ptr(cur_from_prev), f, h, w, x_lo, y_lo, voxel,
+                                      q, p, min_iou, max_age, min_cells, gain, gate, max_shift, _ptr(state.state_map),
+                                      _ptr(state.live_id), _ptr(state.live_seen), _ptr(state.counters), _ptr(rec.pos),
+                                      _ptr(rec.vel), _ptr(rec.motion_counters), _ptr(out.query_track), _ptr(out.track_map),
+                                      _ptr(out.query_velocity), _ptr(ws), ws.numel(), _stream()), 'mbv_track_frames_motion')
     return out
 
 
@@ -166,4 +263,5 @@ def tube_scores(tables: TubeTables) -> TubeScores:
     return out
 
 
-__all__ = ['track_frames', 'tube_accumulate', 'tube_scores', 'TrackState', 'TrackFrames', 'TubeTables', 'TubeScores']
+__all__ = ['track_frames', 'invert_transforms', 'tube_accumulate', 'tube_scores', 'TrackState', 'TrackMotion', 'MotionSettings',
+           'TrackFrames', 'TubeTables', 'TubeScores']

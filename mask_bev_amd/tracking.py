@@ -1,9 +1,16 @@
 """Instance tracking over a sequence (K33a, csrc/track.hip): one stable global id per object from the per-frame BEV
 instance maps of ``MaskBevModule.predict``, after ego-motion compensation with the sequence's poses.
 
-There is no motion model and there are no appearance features: an object is matched to the track whose footprint, warped
-into the current frame by the ego motion, it overlaps best (greedy, exact IoU order).  A parked car keeps its id; a moving
-car keeps it only while its footprints of consecutive frames overlap.
+There are no appearance features: an object is matched to the track whose footprint, warped into the current frame by the
+ego motion, it overlaps best (greedy, exact IoU order).  The motion model is off by default: a parked car keeps its id; a
+moving car keeps it only while its footprints of consecutive frames overlap.
+
+``InstanceTracker(..., motion=MotionSettings())`` turns on K37: every track carries a centroid and a ground-relative
+velocity (constant velocity, a fixed gain), its footprint is shifted by the predicted whole cells before the overlap is
+taken, and what the overlap leaves open is matched by centroid distance within a gate — so a fast car that never overlapped
+itself is picked up in its second frame and keeps its id.  Its limits: shifts are whole cells, so a coasting track's
+footprint drifts by up to half a cell per frame; the gate can hand a lost track to another detection within ``gate_m`` of
+its prediction.  The defaults of ``MotionSettings`` are geometry, not measurement; no LSTQ on real SemanticKITTI is pinned.
 """
 from __future__ import annotations
 
@@ -14,6 +21,7 @@ import torch
 
 from . import ops
 from ._lib import MaskBevHipError
+from .ops_track import MotionSettings
 
 _IDENTITY = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]], dtype=np.float64)
 
@@ -24,6 +32,12 @@ def prev_from_cur_2d(pose_prev, pose_cur) -> np.ndarray:
     dropped: the map is the planar part of the relative motion, exact for a vehicle that only yaws and moves in its plane."""
     rel = np.linalg.inv(np.asarray(pose_prev, dtype=np.float64)) @ np.asarray(pose_cur, dtype=np.float64)
     return np.ascontiguousarray(rel[:2][:, [0, 1, 3]])
+
+
+def cur_from_prev_2d(prev_from_cur) -> np.ndarray:
+    """The (2, 3) f64 inverse of a ``prev_from_cur``: the first two rows of the inverse of the map completed to 3 x 3."""
+    full = np.vstack([np.asarray(prev_from_cur, dtype=np.float64).reshape(2, 3), [0.0, 0.0, 1.0]])
+    return np.ascontiguousarray(np.linalg.inv(full)[:2])
 
 
 def velodyne_poses(poses, calib) -> np.ndarray:
@@ -41,10 +55,12 @@ class InstanceTracker:
     ((ny, nx) cells, cell (iy, ix) centred at ``x_range[0] + (ix + 0.5) * voxel_size``, ``y_range[0] + (iy + 0.5) *
     voxel_size``); ``num_queries`` Q <= ``max_tracks`` P <= 1024.  A query with fewer than ``min_cells`` cells is left out; a
     pair needs an IoU of at least ``min_iou``; a track unmatched for more than ``max_age`` frames is forgotten.  The state
-    lives on the device; :meth:`update` synchronises nothing and :meth:`counters` is the one host copy."""
+    lives on the device; :meth:`update` synchronises nothing and :meth:`counters` is the one host copy.  ``motion``: a
+    :class:`MotionSettings` turns on the constant-velocity motion model and the gated second stage (K37); None, the default,
+    is K33a's step."""
 
     def __init__(self, x_range, y_range, voxel_size: float, num_queries: int, max_tracks: int = 256, min_iou: float = 0.3,
-                 max_age: int = 2, min_cells: int = 4, device='cuda'):
+                 max_age: int = 2, min_cells: int = 4, device='cuda', motion: Optional[MotionSettings] = None):
         self.x_lo, self.y_lo, self.voxel = float(x_range[0]), float(y_range[0]), float(voxel_size)
         self.w = int((x_range[1] - x_range[0]) / voxel_size)
         self.h = int((y_range[1] - y_range[0]) / voxel_size)
@@ -54,60 +70,81 @@ class InstanceTracker:
             raise ValueError(f'InstanceTracker: num_queries {num_queries} <= max_tracks {max_tracks} <= 1024 expected')
         if self.min_cells < 1 or self.max_age < 0 or self.h * self.w > 1024 * 1024:
             raise ValueError('InstanceTracker: min_cells >= 1, max_age >= 0 and at most 2^20 cells expected')
+        if motion is not None and not isinstance(motion, MotionSettings):
+            raise ValueError(f'InstanceTracker: motion must be a MotionSettings or None, got {type(motion).__name__}')
+        if motion is not None and not self.voxel > 0.0:
+            raise ValueError(f'InstanceTracker: voxel_size {voxel_size} > 0 expected with a motion model')
+        self.motion = motion
         self.device = torch.device(device)
         self.reset()
 
     def reset(self) -> None:
         """A fresh sequence: no live track, ids from 0, and the next frame takes the identity transform."""
         self.state = ops.TrackState.fresh(self.h, self.w, self.max_tracks, self.device)
+        if self.motion is not None:
+            self.state.motion = ops.TrackMotion.fresh(self.max_tracks, self.device)
         self._last_pose: Optional[np.ndarray] = None
         self._started = False
 
-    def _transforms(self, b: int, poses, prev_from_cur) -> torch.Tensor:
-        if prev_from_cur is not None:
-            if torch.is_tensor(prev_from_cur):
-                m = prev_from_cur.to(self.device, torch.float64).reshape(b, 2, 3)
-            else:
-                m = torch.from_numpy(np.ascontiguousarray(np.asarray(prev_from_cur, dtype=np.float64).reshape(b, 2, 3))).to(self.device)
+    def _transforms(self, b: int, poses, prev_from_cur):
+        """→ (prev_from_cur on the device, the same on the host or None when it was given as a device tensor)"""
+        if prev_from_cur is not None and torch.is_tensor(prev_from_cur):
+            m = prev_from_cur.to(self.device, torch.float64).reshape(b, 2, 3)
             if not self._started:                          # the first frame after reset(): nothing to warp
                 m = m.clone()
                 m[0] = torch.from_numpy(_IDENTITY).to(self.device)
-            return m
-        out = np.empty((b, 2, 3), dtype=np.float64)
-        if poses is None:
-            out[:] = _IDENTITY                             # a standing sensor
+            return m, None
+        if prev_from_cur is not None:
+            out = np.array(np.asarray(prev_from_cur, dtype=np.float64).reshape(b, 2, 3))
+            if not self._started:
+                out[0] = _IDENTITY
         else:
-            poses = np.asarray(poses, dtype=np.float64).reshape(b, 4, 4)
-            last = self._last_pose
-            for k in range(b):
-                out[k] = _IDENTITY if last is None else prev_from_cur_2d(last, poses[k])
-                last = poses[k]
-            self._last_pose = last
-        return torch.from_numpy(out).to(self.device, non_blocking=True)
+            out = np.empty((b, 2, 3), dtype=np.float64)
+            if poses is None:
+                out[:] = _IDENTITY                         # a standing sensor
+            else:
+                poses = np.asarray(poses, dtype=np.float64).reshape(b, 4, 4)
+                last = self._last_pose
+                for k in range(b):
+                    out[k] = _IDENTITY if last is None else prev_from_cur_2d(last, poses[k])
+                    last = poses[k]
+                self._last_pose = last
+        return torch.from_numpy(out).to(self.device, non_blocking=True), out
 
     @torch.no_grad()
-    def update(self, pred_or_instance_maps, poses=None, prev_from_cur=None, track_map: bool = False):
+    def update(self, pred_or_instance_maps, poses=None, prev_from_cur=None, track_map: bool = False, record: bool = False):
         """``pred_or_instance_maps``: a ``Predictions`` or its (B, ny, nx) int32 ``instance_map`` — B CONSECUTIVE frames of
         the sequence.  ``poses`` (B, 4, 4) f64 sensor poses on the host (the last pose is remembered between calls), or
         ``prev_from_cur`` (B, 2, 3) f64 on the host or the device; with neither, the sensor stands still.  Returns
         ``query_track`` (B, Q) int32 on the device — the global id of every query, -1 where it is not present — or, with
-        ``track_map=True``, the ``ops.TrackFrames`` record that also holds the (B, ny, nx) map of global ids."""
+        ``track_map=True``, the ``ops.TrackFrames`` record that also holds the (B, ny, nx) map of global ids; ``record=True``
+        returns that record without the map — with a motion model it holds ``query_velocity`` (B, Q, 2) f64, metres per
+        frame over ground in the axes of each frame's sensor.  With a motion model the inverse transforms are computed on
+        the host with the transforms themselves, and on the device where ``prev_from_cur`` is a device tensor."""
         maps = getattr(pred_or_instance_maps, 'instance_map', pred_or_instance_maps)
         if maps is None:
             raise MaskBevHipError('InstanceTracker.update: these predictions were made without an instance map')
         if maps.dim() != 3 or tuple(maps.shape[1:]) != (self.h, self.w):
             raise MaskBevHipError(f'InstanceTracker.update: (B, {self.h}, {self.w}) instance maps expected, got {tuple(maps.shape)}')
-        m = self._transforms(int(maps.shape[0]), poses, prev_from_cur)
+        m, host = self._transforms(int(maps.shape[0]), poses, prev_from_cur)
+        n = None
+        if self.motion is not None and host is not None:
+            inv = np.stack([cur_from_prev_2d(x) for x in host]) if len(host) else np.zeros((0, 2, 3), dtype=np.float64)
+            n = torch.from_numpy(inv).to(self.device, non_blocking=True)
         out = ops.track_frames(maps, m, self.state, self.x_lo, self.y_lo, self.voxel, self.num_queries, self.min_iou,
-                               self.max_age, self.min_cells, track_map=track_map)
+                               self.max_age, self.min_cells, track_map=track_map, motion=self.motion, cur_from_prev=n)
         self._started = self._started or maps.shape[0] > 0
-        return out if track_map else out.query_track
+        return out if track_map or record else out.query_track
 
     def counters(self) -> dict:
         """The one host copy: ``{'live', 'tracks', 'frames', 'dropped'}`` — the live tracks, the ids given out so far, the
-        frames seen since :meth:`reset` and the tracks dropped because ``max_tracks`` were live."""
+        frames seen since :meth:`reset` and the tracks dropped because ``max_tracks`` were live; with a motion model also
+        ``'gated'`` — the pairs the second stage took."""
         n_live, next_id, frame, dropped = (int(v) for v in self.state.counters.cpu())
-        return dict(live=n_live, tracks=next_id, frames=frame, dropped=dropped)
+        out = dict(live=n_live, tracks=next_id, frames=frame, dropped=dropped)
+        if self.motion is not None:
+            out['gated'] = int(self.state.motion.motion_counters.cpu()[0])
+        return out
 
 
-__all__ = ['InstanceTracker', 'prev_from_cur_2d', 'velodyne_poses']
+__all__ = ['InstanceTracker', 'MotionSettings', 'prev_from_cur_2d', 'cur_from_prev_2d', 'velodyne_poses']

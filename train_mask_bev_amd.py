@@ -42,7 +42,9 @@ it also prints ``point PQ .. SQ .. RQ .. IoU .. (car; tp .. fp .. fn ..)``, the 
 validation sequences in scan order (K33; needs ``sequences/SS/poses.txt`` and ``calib.txt``, says so in one line and skips
 without them): one global instance id per object, written by ``--write-labels`` in place of the query index, and with label
 files ``point LSTQ .. S_assoc .. S_cls .. (tubes .., tracks .., dropped ..)`` (``track_min_iou``, ``track_max_age``,
-``track_min_cells``, ``track_max_tracks``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
+``track_min_cells``, ``track_max_tracks``; ``track_motion: true`` runs the tracker with its constant-velocity motion model and
+gated re-association, K37 — ``track_velocity_gain``, ``track_gate`` metres, ``track_max_speed`` metres per frame — and the
+parenthesis then ends ``, gated ..``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
 ``lift_max_height``, ``lift_z_floor``) makes every one of these lifts label only the returns above a ground estimate made from
 the scan, lets the 3D boxes stand on it, and prints one ``ground-aware lift: ..`` line in front of the results it changes.
 ``--render DIR`` (K36; ``render_scale``, ``render_alpha``, ``render_boxes``) adds a last pass on rank 0 that writes one BEV frame
