@@ -1883,6 +1883,89 @@ int mbv_track_frames_motion(const int32_t* instance_maps, const double* prev_fro
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K38 — BEV visibility maps and occlusion-aware track ageing.  K38a says which BEV cells a scan could observe at the height
+ * one asks about; K38b is the first consumer: K37's tracker step in which a track that goes unmatched while most of its
+ * footprint was out of sight does not age.  Both are opt-in; mbv_track_frames and mbv_track_frames_motion are unchanged.
+ * The numpy restatements of the words below are tests/visibility_ref.py and tests/track_occlusion_ref.py.
+ *
+ * K38a — mbv_visibility_map (csrc/visibility.hip, built with -ffp-contract=off).  points, point_dim, total_points,
+ * scan_offsets, batch, x_min .. gz, prefilter: as in K31 / K35a / K36a.
+ * origin_cx, origin_cy   i32: the sensor's cell, made on the host; it may lie outside the grid; |value| <= 2^20
+ * origin_z, z_top        f32, in the scan's frame: the sensor's height and the roof height of the objects one asks about
+ * vis           (batch, gy, gx) u8, row = y-cell, column = x-cell (the layout of instance_map): bit 0 PASSED, bit 1 HIT.
+ *               Every element is written.
+ *
+ * 1. targets    a cell is a target iff at least one point TAKES PART in it: K1's cell rule, the device function of K31 / K35a
+ *               / K36a (csrc/point_cell.hpp), the strict pre-filter first under `prefilter`.  Its z_end is the minimum z of
+ *               those points on K31's order-preserving u32 encoding (so -0.0 < +0.0): K35a's cell_min with radius 0 and no
+ *               floor, the same pass (csrc/cell_min.hpp).  A target cell gets HIT.
+ * 2. ray        for a target (ty, tx): dx = tx - origin_cx, dy = ty - origin_cy, n = max(|dx|, |dy|).  Sample k in [0, n) is
+ *               the cell (origin_cy + floor_div(2 * k * dy + n, 2 * n), origin_cx + floor_div(2 * k * dx + n, 2 * n)), in
+ *               64-bit integers, floor_div rounding towards minus infinity.  n = 0 has no samples; the target's own cell
+ *               (k = n) is none.  Samples outside the grid are skipped.
+ * 3. height     sample k certifies its cell iff  (z_end - origin_z) * (float)k <= (z_top - origin_z) * (float)n,  each side
+ *               one f32 subtraction and one f32 multiplication, in that order; a NaN fails.  Certified cells get PASSED.
+ * In words: a beam marks the part of its path on which it ran at or below z_top.  Close to a roof-mounted sensor that part
+ * is empty: the beams are still above the roofs there.
+ *
+ * workspace     the byte count the _workspace_bytes entry returns (0 for sizes out of range): one (batch, gy, gx) u32 plane,
+ *               the encoded cell minima.
+ * Four launches whatever the batch (initialise; one thread per point, integer atomicMin; the rays; the HIT bit).  The rays: a
+ * block of 256 threads owns 256 consecutive cells, scans the ray lengths of its targets in LDS and walks the samples of all
+ * of them with consecutive lanes on consecutive samples, so rays of 0 and of 700 cells load the lanes alike; a certified
+ * cell takes a plain store of the byte 1, and the HIT bit is added by the one thread that owns the cell in the last launch.
+ * Integer atomics and idempotent stores only: the result does not depend on the order of points or rays.  No host
+ * synchronisation, no allocation.
+ * batch == 0: MBV_OK, nothing is written.  total_points == 0: vis is all zeros (one fill; no workspace is needed).
+ * MBV_ERR_UNSUPPORTED: batch > 65535, total_points >= 2^31 - 1, gx or gy > 65536;  MBV_ERR_BAD_ARG: a negative size,
+ * point_dim other than 3 or 4, a grid size < 1, |origin_cx| or |origin_cy| > 2^20, null vis, null points or scan_offsets with
+ * total_points > 0;  MBV_ERR_WORKSPACE: a workspace that is too small.
+ * Limits        z_top is absolute in the sensor frame, not relative to K35's ground; returns outside the grid cast no rays;
+ *               one ray per cell, to its lowest return; the blind ring next to the sensor is neither PASSED nor HIT.
+ *
+ * K38b — mbv_track_frames_occluded (csrc/track.hip): mbv_track_frames_motion with
+ * visibility          (F, H, W) u8 or NULL: K38a's map of every frame (any non-zero byte counts as seen)
+ * live_held           (P) i32 state: the frames a live track has been held since its last match; a fresh tracker: zeros
+ * occlusion_counters  (2) i32 state = [held, reserved 0]
+ * hold_num, hold_den  i32, 0 < hold_num <= hold_den: the share of a footprint that must be hidden
+ * max_hold            i32 >= 0: the most frames in a row a track is held
+ * and these additions to K37's steps:
+ * 2. count   also hidden[t] = the cells where warped == t and visibility[f][iy][ix] == 0 (0 for every t without a map).
+ * 4. update  an unmatched old track t, in ascending t, is OCCLUDED iff visibility != NULL and area_t[t] > 0 and
+ *            (int64)hidden[t] * hold_den >= (int64)area_t[t] * hold_num and live_held[t] < max_hold.  An occluded track takes
+ *            seen' = live_seen[t] + 1 and held' = live_held[t] + 1, and occlusion_counters[0] is incremented; otherwise
+ *            seen' = live_seen[t] and held' = live_held[t].  The age test frame - seen' <= max_age, the capacity rule and
+ *            dropped are K33a's with seen'; an appended track stores seen' and held'.  Matched and born entries get
+ *            held' = 0; live_held past the new n_live is 0.  pos and vel of a held track follow K37's "appended unmatched
+ *            track" line: it coasts.
+ * Identity   with visibility == NULL or max_hold == 0 no track is ever occluded: every output and every state element equals
+ *            mbv_track_frames_motion's bit for bit and live_held stays all 0; with gain = gate = 0 in addition they equal
+ *            mbv_track_frames'.
+ * Limits     a track in the blind ring next to the sensor, or anywhere no beam passed below z_top, counts as hidden and is
+ *            held up to max_hold frames; nothing is claimed about LSTQ on real data.
+ * workspace  K37's and the hidden table.  Five launches per frame, K37's: the count and match kernels are the third
+ * instantiation of the same two templates (hidden is summed per block in LDS, then integer global atomics).  Integer
+ * atomics only: bit-deterministic.  Every output element and every element of the new state is written by the call.
+ * Error codes as mbv_track_frames_motion; in addition MBV_ERR_BAD_ARG: hold_num < 1, hold_num > hold_den, max_hold < 0, null
+ * occlusion_counters, null live_held when P > 0.
+ */
+size_t mbv_visibility_map_workspace_bytes(int32_t batch, int32_t gx, int32_t gy);
+int mbv_visibility_map(const float* points, int32_t point_dim, int64_t total_points, const int32_t* scan_offsets,
+                       int32_t batch, float x_min, float y_min, float z_min, float x_max, float y_max, float z_max, float vx,
+                       float vy, float vz, int32_t gx, int32_t gy, int32_t gz, int32_t prefilter, int32_t origin_cx,
+                       int32_t origin_cy, float origin_z, float z_top, uint8_t* vis, void* workspace, size_t workspace_bytes,
+                       void* stream);
+size_t mbv_track_frames_occluded_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P);
+int mbv_track_frames_occluded(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev,
+                              const uint8_t* visibility, int32_t F, int32_t H, int32_t W, double x_lo, double y_lo,
+                              double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age, int32_t min_cells,
+                              double gain, double gate, int32_t max_shift, int32_t hold_num, int32_t hold_den,
+                              int32_t max_hold, int32_t* state_map, int32_t* live_id, int32_t* live_seen, int32_t* live_held,
+                              int32_t* counters, double* pos, double* vel, int32_t* motion_counters,
+                              int32_t* occlusion_counters, int32_t* query_track, int32_t* track_map, double* query_velocity,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K33b — tube association (csrc/track.hip): the S_assoc term of LSTQ (Aygün et al., 4D Panoptic LiDAR Segmentation) over a
  * whole sequence, from per-element track ids and `.label` words.  Parity with semantic-kitti-api's 4D evaluator is not
  * pinned (it is not installed); the restatement is tests/track_ref.py.

@@ -231,6 +231,12 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_track_frames_motion_workspace_bytes': (c_size_t, [_I, _I, _I, _I]),
     'mbv_track_frames_motion': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _D, _D, _D, _I, _I, _D, _I, _I, _D, _D, _I, _P, _P, _P,
                                                _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'mbv_track_frames_occluded_workspace_bytes': (c_size_t, [_I, _I, _I, _I]),
+    'mbv_track_frames_occluded': (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _I, _I, _D, _I, _I, _D, _D, _I, _I, _I,
+                                                 _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'mbv_visibility_map_workspace_bytes': (c_size_t, [_I, _I, _I]),
+    'mbv_visibility_map': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _I, _I, _F,
+                                          _F, _P, _P, c_size_t, _P]),
     'mbv_tube_accumulate': (ctypes.c_int, [_P, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'mbv_tube_scores': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'mbv_render_box_chunk': (_I, []),

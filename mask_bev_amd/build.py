@@ -43,6 +43,8 @@ FILE_FLAGS = {
     'track.hip': ['-ffp-contract=off'],
     # K36a counts with K1's cell rule `(p - min) / vs`, the copy of point_lift.hip: one rounding per operation
     'render.hip': ['-ffp-contract=off'],
+    # K38a's targets come from K1's cell rule, and its height test is one f32 subtract and one multiply per side, as restated
+    'visibility.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

@@ -37,21 +37,12 @@
 //         fourth table takes the minimum of g per query.  K31 is k_lift_points<false> of the same body.
 #include "common.hpp"
 #include "point_cell.hpp"   // LiftGeom, point_cell: K1's cell rule, the one copy
+#include "cell_min.hpp"     // encode_ordered / decode_ordered, kEncInf and the cell-minimum pass, the one copy
 
 namespace {
 
 constexpr int kThreads = 256, kMaxQueries = 1024, kMaxBins = 256;
 constexpr int kTile = 64, kRowTileRows = 16, kMaxRadius = 32;   // K35a: tiles of the window passes, the largest halo
-constexpr uint32_t kEncInf = 0xff800000u;                       // encode_ordered(+inf)
-
-// f32 → u32 with the order of the floats (negative numbers: all bits flipped; others: the sign bit set) and back
-__device__ __forceinline__ uint32_t encode_ordered(float z) {
-  const uint32_t u = __float_as_uint(z);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float decode_ordered(uint32_t e) {
-  return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
 
 __global__ void __launch_bounds__(kThreads) k_lift_init(int64_t total_points, int64_t bq, int64_t hist_elems,
                                                         int32_t* __restrict__ point_query, int32_t* __restrict__ counts,
@@ -183,29 +174,7 @@ __global__ void __launch_bounds__(kThreads) k_lift_finalize(int64_t bq, int z_bi
 
 // ---- K35a: the elevation grid ---------------------------------------------------------------------------------------------
 
-__global__ void __launch_bounds__(kThreads) k_ground_init(int64_t cells, uint32_t* __restrict__ enc) {
-  const int64_t stride = (int64_t)gridDim.x * kThreads;
-  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < cells; i += stride) enc[i] = kEncInf;
-}
-
-// one thread per point (blocks of 256, grid.y = scan): the cell's minimum takes the point's z when the point takes part
-__global__ void __launch_bounds__(kThreads) k_ground_points(const float* __restrict__ points, int dim, int64_t total_points,
-                                                            const int32_t* __restrict__ scan_offsets, LiftGeom g,
-                                                            int prefilter, float z_floor, uint32_t* __restrict__ enc) {
-  const int b = blockIdx.y;
-  int64_t begin = scan_offsets[b], end = scan_offsets[b + 1];
-  begin = begin < 0 ? 0 : begin;                                   // offsets that point outside the table read nothing
-  end = end > total_points ? total_points : end;
-  const int64_t i = begin + (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= end) return;
-  int64_t cx, cy;
-  float z;
-  // A plain atomic per point.  The cells near the sensor take hundreds of returns each and their few cache lines bound this
-  // launch; a device-scope read in front of the atomic (skip when the stored value is already lower) was measured SLOWER,
-  // 57 us against 34 us at 4 x 120 k points: it doubles the requests to those same lines.
-  if (point_cell(points + i * dim, g, prefilter, cx, cy, z) && z >= z_floor)
-    atomicMin(&enc[((int64_t)b * g.gy + cy) * g.gx + cx], encode_ordered(z));
-}
+// k_ground_init and k_ground_points, the cell minima on the encoding, are in cell_min.hpp: K38a launches them too
 
 // Four cells of a row starting at column x (any sign), +inf outside [0, gx).  VEC: gx is a multiple of 4, x too, and the
 // row is 16-byte aligned, so a quad lies wholly inside or wholly outside.

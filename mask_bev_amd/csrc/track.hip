@@ -19,6 +19,10 @@
 // per block in LDS, flushed with 64-bit global atomics), match<true> (after the IoU rounds: centroids, predictions, the gate
 // candidates and the same mutual-best rounds under the order (d2, q, t); then the update also of pos / vel) and paint.
 // count and match are one template each: the <false> instantiations are K33a's kernels.
+// K38b, occlusion-aware ageing (mbv_track_frames_occluded): K37's five launches with the third instantiation <true, true> of
+// the same two templates.  count also sums hidden[t], the cells of a warped footprint whose visibility byte is 0, in a fifth
+// LDS table; match reads hidden and live_held and, in step 4, lets an unmatched track whose footprint was mostly out of
+// sight keep its age.  With visibility == NULL or max_hold == 0 no track is held and the step is K37's bit for bit.
 // K33b: accumulate (grid-stride blocks with LDS tables for the two size tables where they fit), scores (one workgroup per
 // row; the terms of 256 tracks at a time in LDS, summed by one thread in ascending order) and the class sums.
 // Integer atomics only; every f64 sum in a fixed order: two runs are bit-equal.  Every index comes from the sizes: a query, a
@@ -46,10 +50,12 @@ struct TrackWorkspace {
   double* cq;        // (Q, 2): the centroid of a present query
   double* pred;      // (P, 2): the predicted centroid of a live track in the current frame
   double* velr;      // (P, 2): its velocity in the current frame's axes
+  // K38b only
+  int32_t* hidden;   // (P): the cells of a warped footprint with visibility 0
   size_t bytes;
 };
 
-TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P, bool motion = false) {
+TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P, bool motion = false, bool occlusion = false) {
   MbvCarver c(ws);
   TrackWorkspace w{};
   w.warped = c.take<int32_t>(cells);
@@ -68,6 +74,7 @@ TrackWorkspace carve_track(void* ws, int64_t cells, int Q, int P, bool motion = 
     w.pred = c.take<double>(2 * (int64_t)P);
     w.velr = c.take<double>(2 * (int64_t)P);
   }
+  if (occlusion) w.hidden = c.take<int32_t>(P);
   w.bytes = c.off;
   return w;
 }
@@ -90,13 +97,15 @@ __device__ __forceinline__ void add64(int64_t* p, int64_t n) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)n);
 }
 
-// K37's clear: K33a's tables, the advected map, the centroid sums, and step 0's cell shift of every track
+// K37's clear: K33a's tables, the advected map, the centroid sums, and step 0's cell shift of every track; K38b's hidden
+// table where there is one
 __global__ void __launch_bounds__(kThreads) k_track_clear_motion(int64_t cells, int Q, int P, double voxel, int max_shift,
                                                                  const int32_t* __restrict__ counters,
                                                                  const double* __restrict__ vel, int32_t* __restrict__ area_q,
                                                                  int32_t* __restrict__ area_t, int32_t* __restrict__ inter,
                                                                  uint32_t* __restrict__ moved, int64_t* __restrict__ sum_ix,
-                                                                 int64_t* __restrict__ sum_iy, int32_t* __restrict__ shift) {
+                                                                 int64_t* __restrict__ sum_iy, int32_t* __restrict__ shift,
+                                                                 int32_t* __restrict__ hidden) {
   const int64_t stride = (int64_t)gridDim.x * kThreads, n = (int64_t)Q * P;
   const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const int n_live = live_count(counters, P);
@@ -109,6 +118,7 @@ __global__ void __launch_bounds__(kThreads) k_track_clear_motion(int64_t cells, 
   }
   for (int64_t i = t; i < P; i += stride) {
     area_t[i] = 0;
+    if (hidden) hidden[i] = 0;
     double sx = 0.0, sy = 0.0;
     if (i < n_live) {
       sx = rint(vel[2 * i] / voxel);
@@ -133,7 +143,7 @@ __global__ void __launch_bounds__(kThreads) k_track_advect(const int32_t* __rest
   if (tx >= 0 && tx < W && ty >= 0 && ty < H) atomicMin(&moved[ty * W + tx], (uint32_t)t);
 }
 
-template <bool kMotion>
+template <bool kMotion, bool kOcclusion = false>
 __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restrict__ instance_map,
                                                           const int32_t* __restrict__ state_map,
                                                           const double* __restrict__ prev_from_cur, int H, int W, double x_lo,
@@ -141,13 +151,18 @@ __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restr
                                                           const int32_t* __restrict__ counters, int32_t* __restrict__ warped,
                                                           int32_t* __restrict__ area_q, int32_t* __restrict__ area_t,
                                                           int32_t* __restrict__ inter, int64_t* __restrict__ sum_ix,
-                                                          int64_t* __restrict__ sum_iy) {
+                                                          int64_t* __restrict__ sum_iy,
+                                                          const uint8_t* __restrict__ visibility,
+                                                          int32_t* __restrict__ hidden) {
   __shared__ int32_t s_q[kMaxTracks];
   __shared__ int32_t s_t[kMaxTracks];
   // K37: a block of 256 cells adds at most 256 * 2^20 < 2^31 to a slot, so i32 holds a block's index sums
   __shared__ int32_t s_x[kMotion ? kMaxTracks : 1];
   __shared__ int32_t s_y[kMotion ? kMaxTracks : 1];
+  __shared__ int32_t s_h[kOcclusion ? kMaxTracks : 1];             // K38b: hidden, per block
   const int n_live = live_count(counters, P);
+  if constexpr (kOcclusion)
+    for (int k = threadIdx.x; k < P; k += kThreads) s_h[k] = 0;
   if constexpr (kMotion)
     for (int k = threadIdx.x; k < Q; k += kThreads) s_x[k] = s_y[k] = 0;
   for (int k = threadIdx.x; k < Q; k += kThreads) s_q[k] = 0;
@@ -178,6 +193,9 @@ __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restr
       }
     }
     if (t >= 0) atomicAdd(&s_t[t], 1);
+    if constexpr (kOcclusion) {
+      if (t >= 0 && visibility && visibility[i] == 0) atomicAdd(&s_h[t], 1);
+    }
     if (q >= 0 && t >= 0) atomicAdd(&inter[(int64_t)q * P + t], 1);
   }
   __syncthreads();
@@ -194,6 +212,9 @@ __global__ void __launch_bounds__(kThreads) k_track_count(const int32_t* __restr
   for (int k = threadIdx.x; k < P; k += kThreads) {
     const int32_t n = s_t[k];
     if (n > 0) atomicAdd(&area_t[k], n);
+    if constexpr (kOcclusion) {
+      if (n > 0 && s_h[k] > 0) atomicAdd(&hidden[k], s_h[k]);
+    }
   }
 }
 
@@ -309,9 +330,18 @@ struct MotionArgs {
   double* query_velocity;          // this frame's (Q, 2)
 };
 
+// K38b's per-frame arguments of the match kernel; unused (and empty) in the other instantiations
+struct OcclusionArgs {
+  const int32_t* hidden;           // workspace (P)
+  int32_t* live_held;              // state (P)
+  int32_t* occlusion_counters;     // state (2)
+  int hold_num, hold_den, max_hold;
+  int have_visibility;
+};
+
 __device__ __forceinline__ double finite_or_zero(double v) { return fabs(v) <= 1.7976931348623157e308 ? v : 0.0; }
 
-template <bool kMotion>
+template <bool kMotion, bool kOcclusion = false>
 __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_iou, int max_age, int min_cells,
                                                        const int32_t* __restrict__ g_area_q,
                                                        const int32_t* __restrict__ g_area_t,
@@ -319,7 +349,7 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
                                                        int32_t* __restrict__ live_id, int32_t* __restrict__ live_seen,
                                                        int32_t* __restrict__ counters, int32_t* __restrict__ query_track,
                                                        int32_t* __restrict__ q_new, int32_t* __restrict__ t_new,
-                                                       MotionArgs mo) {
+                                                       MotionArgs mo, OcclusionArgs oc) {
   __shared__ int32_t s_area_q[kMaxTracks];
   __shared__ int32_t s_area_t[kMaxTracks];
   __shared__ int32_t s_best_q[kMaxTracks];                         // the round's best pair of a row
@@ -329,7 +359,8 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
   __shared__ int32_t s_id[kMaxTracks];
   __shared__ int32_t s_seen[kMaxTracks];
   __shared__ int32_t s_scan[kWide];
-  __shared__ int32_t s_n_cand, s_open;
+  __shared__ int32_t s_held[kOcclusion ? kMaxTracks : 1];          // K38b: live_held of the old list
+  __shared__ int32_t s_n_cand, s_open, s_n_held;
   const int t = threadIdx.x;
   const int n_live = live_count(counters, P);
   const int32_t next_id = counters[1], frame = counters[2], dropped = counters[3];
@@ -342,8 +373,12 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
     s_t_taken[t] = 0;
     s_id[t] = t < n_live ? live_id[t] : -1;
     s_seen[t] = t < n_live ? live_seen[t] : -1;
+    if constexpr (kOcclusion) s_held[t] = t < n_live ? oc.live_held[t] : 0;
   }
-  if (t == 0) s_n_cand = 0;
+  if (t == 0) {
+    s_n_cand = 0;
+    s_n_held = 0;
+  }
   __syncthreads();
 
   // the candidate list
@@ -406,6 +441,16 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
   const int32_t n_present = s_scan[kWide - 1];
   const int32_t born = block_scan(present && matched < 0 ? 1 : 0, s_scan);
   const int32_t n_born = s_scan[kWide - 1];
+  // K38b, step 4: an unmatched track whose warped footprint was mostly out of sight keeps its age (seen' and held' are
+  // written back to this thread's own slots of the old list, read again only by this thread)
+  if constexpr (kOcclusion) {
+    if (t < n_live && !s_t_taken[t] && oc.have_visibility && s_area_t[t] > 0 &&
+        (int64_t)oc.hidden[t] * oc.hold_den >= (int64_t)s_area_t[t] * oc.hold_num && s_held[t] < oc.max_hold) {
+      s_seen[t] += 1;
+      s_held[t] += 1;
+      atomicAdd(&s_n_held, 1);
+    }
+  }
   const bool old = t < n_live && !s_t_taken[t] && (int64_t)frame - s_seen[t] <= (int64_t)max_age;
   const int32_t pos_t = block_scan(old ? 1 : 0, s_scan);
   const int32_t n_old = s_scan[kWide - 1];
@@ -417,6 +462,7 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
   if (t >= n_new && t < P) {
     live_id[t] = -1;
     live_seen[t] = -1;
+    if constexpr (kOcclusion) oc.live_held[t] = 0;
   }
   if (t < Q) {
     query_track[t] = id_q;
@@ -424,6 +470,7 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
     if (present) {
       live_id[pos_q - 1] = id_q;
       live_seen[pos_q - 1] = frame;
+      if constexpr (kOcclusion) oc.live_held[pos_q - 1] = 0;
     }
   }
   if (t < P) {
@@ -432,6 +479,7 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
       idx = n_present + pos_t - 1;
       live_id[idx] = s_id[t];
       live_seen[idx] = s_seen[t];
+      if constexpr (kOcclusion) oc.live_held[idx] = s_held[t];
     }
     t_new[t] = idx;
     if constexpr (kMotion) {
@@ -465,6 +513,12 @@ __global__ void __launch_bounds__(kWide) k_track_match(int Q, int P, double min_
     if (t == 0) {
       mo.motion_counters[0] += s_gated;
       mo.motion_counters[1] = 0;
+    }
+  }
+  if constexpr (kOcclusion) {
+    if (t == 0) {
+      oc.occlusion_counters[0] += s_n_held;
+      oc.occlusion_counters[1] = 0;
     }
   }
   if (t == 0) {
@@ -659,12 +713,13 @@ extern "C" int mbv_track_frames(const int32_t* instance_maps, const double* prev
     if (cells > 0) {
       hipLaunchKernelGGL(k_track_count<false>, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, state_map,
                          prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo, voxel, (int)Q, (int)P, counters, w.warped,
-                         w.area_q, w.area_t, w.inter, (int64_t*)nullptr, (int64_t*)nullptr);
+                         w.area_q, w.area_t, w.inter, (int64_t*)nullptr, (int64_t*)nullptr, (const uint8_t*)nullptr,
+                         (int32_t*)nullptr);
       MBV_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_track_match<false>, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age,
                        (int)min_cells, w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters,
-                       query_track + (int64_t)f * Q, w.q_new, w.t_new, MotionArgs{});
+                       query_track + (int64_t)f * Q, w.q_new, w.t_new, MotionArgs{}, OcclusionArgs{});
     MBV_CHECK_LAUNCH();
     if (cells > 0) {
       hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
@@ -675,6 +730,80 @@ extern "C" int mbv_track_frames(const int32_t* instance_maps, const double* prev
   }
   return MBV_OK;
 }
+
+namespace {
+
+// K38b's arguments on the host; null for K37
+struct OcclusionCall {
+  const uint8_t* visibility;       // (F, H, W) or null
+  int32_t* live_held;
+  int32_t* occlusion_counters;
+  int32_t hold_num, hold_den, max_hold;
+};
+
+// K37 (occ == nullptr) and K38b behind one set of checks and launches
+int track_frames_motion(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev, int32_t F,
+                        int32_t H, int32_t W, double x_lo, double y_lo, double voxel, int32_t Q, int32_t P, double min_iou,
+                        int32_t max_age, int32_t min_cells, double gain, double gate, int32_t max_shift, int32_t* state_map,
+                        int32_t* live_id, int32_t* live_seen, int32_t* counters, double* pos, double* vel,
+                        int32_t* motion_counters, int32_t* query_track, int32_t* track_map, double* query_velocity,
+                        const OcclusionCall* occ, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (F == 0) return MBV_OK;
+  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || min_cells < 1 || max_age < 0 || max_shift < 0) return MBV_ERR_BAD_ARG;
+  if (!(gain >= 0.0 && gain <= 1.0) || !(gate >= 0.0 && gate <= 1.7976931348623157e308)) return MBV_ERR_BAD_ARG;   // NaN, inf
+  if (occ && (occ->hold_num <= 0 || occ->hold_num > occ->hold_den || occ->max_hold < 0)) return MBV_ERR_BAD_ARG;
+  if (!track_sizes_supported(H, W, Q, P)) return MBV_ERR_UNSUPPORTED;
+  const int64_t cells = (int64_t)H * W;
+  if (!prev_from_cur || !cur_from_prev || !counters || !motion_counters || (cells > 0 && (!instance_maps || !state_map)) ||
+      (P > 0 && (!live_id || !live_seen || !pos || !vel)) || (Q > 0 && (!query_track || !query_velocity)))
+    return MBV_ERR_BAD_ARG;
+  if (occ && (!occ->occlusion_counters || (P > 0 && !occ->live_held))) return MBV_ERR_BAD_ARG;
+  TrackWorkspace w = carve_track(workspace, cells, Q, P, true, occ != nullptr);
+  if (!workspace || workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
+
+  const int64_t most = (int64_t)Q * P > cells ? (int64_t)Q * P : cells;
+  int64_t clear_blocks = (most + kThreads - 1) / kThreads;
+  clear_blocks = clear_blocks < 1 ? 1 : (clear_blocks > 1024 ? 1024 : clear_blocks);
+  const unsigned cell_blocks = (unsigned)((cells + kThreads - 1) / kThreads);
+  for (int f = 0; f < F; ++f) {
+    const int32_t* imap = instance_maps + (int64_t)f * cells;
+    const uint8_t* vis = occ && occ->visibility ? occ->visibility + (int64_t)f * cells : nullptr;
+    hipLaunchKernelGGL(k_track_clear_motion, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, cells, (int)Q, (int)P,
+                       voxel, (int)max_shift, counters, vel, w.area_q, w.area_t, w.inter, w.moved, w.sum_ix, w.sum_iy, w.shift,
+                       w.hidden);
+    MBV_CHECK_LAUNCH();
+    if (cells > 0) {
+      hipLaunchKernelGGL(k_track_advect, dim3(cell_blocks), dim3(kThreads), 0, stream, state_map, (int)H, (int)W, (int)P,
+                         counters, w.shift, w.moved);
+      MBV_CHECK_LAUNCH();
+      const auto count = occ ? k_track_count<true, true> : k_track_count<true, false>;
+      hipLaunchKernelGGL(count, dim3(cell_blocks), dim3(kThreads), 0, stream, imap,
+                         reinterpret_cast<const int32_t*>(w.moved), prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo,
+                         voxel, (int)Q, (int)P, counters, w.warped, w.area_q, w.area_t, w.inter, w.sum_ix, w.sum_iy, vis,
+                         w.hidden);
+      MBV_CHECK_LAUNCH();
+    }
+    MotionArgs mo{cur_from_prev + (int64_t)f * 6, gain, gate, x_lo, y_lo, voxel, w.sum_ix, w.sum_iy, w.cq, w.pred, w.velr, pos,
+                  vel, motion_counters, query_velocity + (int64_t)f * Q * 2};
+    OcclusionArgs oc{};
+    if (occ) oc = OcclusionArgs{w.hidden, occ->live_held, occ->occlusion_counters, (int)occ->hold_num, (int)occ->hold_den,
+                                (int)occ->max_hold, vis != nullptr};
+    const auto match = occ ? k_track_match<true, true> : k_track_match<true, false>;
+    hipLaunchKernelGGL(match, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age, (int)min_cells, w.area_q,
+                       w.area_t, w.inter, w.cand, live_id, live_seen, counters, query_track + (int64_t)f * Q, w.q_new, w.t_new,
+                       mo, oc);
+    MBV_CHECK_LAUNCH();
+    if (cells > 0) {
+      hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
+                         w.q_new, w.t_new, query_track + (int64_t)f * Q, state_map,
+                         track_map ? track_map + (int64_t)f * cells : nullptr);
+      MBV_CHECK_LAUNCH();
+    }
+  }
+  return MBV_OK;
+}
+
+}  // namespace
 
 extern "C" size_t mbv_track_frames_motion_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
   if (!track_sizes_supported(H, W, Q, P)) return 0;
@@ -688,50 +817,31 @@ extern "C" int mbv_track_frames_motion(const int32_t* instance_maps, const doubl
                                        int32_t* counters, double* pos, double* vel, int32_t* motion_counters,
                                        int32_t* query_track, int32_t* track_map, double* query_velocity, void* workspace,
                                        size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (F == 0) return MBV_OK;
-  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || min_cells < 1 || max_age < 0 || max_shift < 0) return MBV_ERR_BAD_ARG;
-  if (!(gain >= 0.0 && gain <= 1.0) || !(gate >= 0.0 && gate <= 1.7976931348623157e308)) return MBV_ERR_BAD_ARG;   // NaN, inf
-  if (!track_sizes_supported(H, W, Q, P)) return MBV_ERR_UNSUPPORTED;
-  const int64_t cells = (int64_t)H * W;
-  if (!prev_from_cur || !cur_from_prev || !counters || !motion_counters || (cells > 0 && (!instance_maps || !state_map)) ||
-      (P > 0 && (!live_id || !live_seen || !pos || !vel)) || (Q > 0 && (!query_track || !query_velocity)))
-    return MBV_ERR_BAD_ARG;
-  TrackWorkspace w = carve_track(workspace, cells, Q, P, true);
-  if (!workspace || workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
+  return track_frames_motion(instance_maps, prev_from_cur, cur_from_prev, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age,
+                             min_cells, gain, gate, max_shift, state_map, live_id, live_seen, counters, pos, vel,
+                             motion_counters, query_track, track_map, query_velocity, nullptr, workspace, workspace_bytes,
+                             reinterpret_cast<hipStream_t>(stream_));
+}
 
-  const int64_t most = (int64_t)Q * P > cells ? (int64_t)Q * P : cells;
-  int64_t clear_blocks = (most + kThreads - 1) / kThreads;
-  clear_blocks = clear_blocks < 1 ? 1 : (clear_blocks > 1024 ? 1024 : clear_blocks);
-  const unsigned cell_blocks = (unsigned)((cells + kThreads - 1) / kThreads);
-  for (int f = 0; f < F; ++f) {
-    const int32_t* imap = instance_maps + (int64_t)f * cells;
-    hipLaunchKernelGGL(k_track_clear_motion, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, cells, (int)Q, (int)P,
-                       voxel, (int)max_shift, counters, vel, w.area_q, w.area_t, w.inter, w.moved, w.sum_ix, w.sum_iy, w.shift);
-    MBV_CHECK_LAUNCH();
-    if (cells > 0) {
-      hipLaunchKernelGGL(k_track_advect, dim3(cell_blocks), dim3(kThreads), 0, stream, state_map, (int)H, (int)W, (int)P,
-                         counters, w.shift, w.moved);
-      MBV_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_track_count<true>, dim3(cell_blocks), dim3(kThreads), 0, stream, imap,
-                         reinterpret_cast<const int32_t*>(w.moved), prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo,
-                         voxel, (int)Q, (int)P, counters, w.warped, w.area_q, w.area_t, w.inter, w.sum_ix, w.sum_iy);
-      MBV_CHECK_LAUNCH();
-    }
-    MotionArgs mo{cur_from_prev + (int64_t)f * 6, gain, gate, x_lo, y_lo, voxel, w.sum_ix, w.sum_iy, w.cq, w.pred, w.velr, pos,
-                  vel, motion_counters, query_velocity + (int64_t)f * Q * 2};
-    hipLaunchKernelGGL(k_track_match<true>, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age,
-                       (int)min_cells, w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters,
-                       query_track + (int64_t)f * Q, w.q_new, w.t_new, mo);
-    MBV_CHECK_LAUNCH();
-    if (cells > 0) {
-      hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
-                         w.q_new, w.t_new, query_track + (int64_t)f * Q, state_map,
-                         track_map ? track_map + (int64_t)f * cells : nullptr);
-      MBV_CHECK_LAUNCH();
-    }
-  }
-  return MBV_OK;
+extern "C" size_t mbv_track_frames_occluded_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
+  if (!track_sizes_supported(H, W, Q, P)) return 0;
+  return carve_track(nullptr, (int64_t)H * W, Q, P, true, true).bytes;
+}
+
+extern "C" int mbv_track_frames_occluded(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev,
+                                         const uint8_t* visibility, int32_t F, int32_t H, int32_t W, double x_lo, double y_lo,
+                                         double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age, int32_t min_cells,
+                                         double gain, double gate, int32_t max_shift, int32_t hold_num, int32_t hold_den,
+                                         int32_t max_hold, int32_t* state_map, int32_t* live_id, int32_t* live_seen,
+                                         int32_t* live_held, int32_t* counters, double* pos, double* vel,
+                                         int32_t* motion_counters, int32_t* occlusion_counters, int32_t* query_track,
+                                         int32_t* track_map, double* query_velocity, void* workspace, size_t workspace_bytes,
+                                         void* stream_) {
+  const OcclusionCall occ{visibility, live_held, occlusion_counters, hold_num, hold_den, max_hold};
+  return track_frames_motion(instance_maps, prev_from_cur, cur_from_prev, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age,
+                             min_cells, gain, gate, max_shift, state_map, live_id, live_seen, counters, pos, vel,
+                             motion_counters, query_track, track_map, query_velocity, &occ, workspace, workspace_bytes,
+                             reinterpret_cast<hipStream_t>(stream_));
 }
 
 extern "C" int mbv_tube_accumulate(const int32_t* pred_track, const uint32_t* gt_word, int64_t total, const int32_t* class_lut,

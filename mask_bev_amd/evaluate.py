@@ -11,7 +11,7 @@ from .datasets import KittiFrames, semantic_kitti_files
 from .kitti_eval import eval_kitti
 from .metrics import DevicePanopticQuality, DeviceTubeAssociation, lstq, semantic_kitti_class_lut
 from .predict import BOX_METHODS, GroundSettings, write_semantic_kitti_labels
-from .tracking import InstanceTracker, MotionSettings, velodyne_poses
+from .tracking import InstanceTracker, MotionSettings, OcclusionSettings, velodyne_poses
 
 
 def predictions(model, scan_paths, bsz, device, score_threshold=0.0):
@@ -154,12 +154,18 @@ def format_point_panoptic(result, things=((10,),)):
 def tracking_settings(config):
     """``track_min_iou`` (0.3), ``track_max_age`` (2), ``track_min_cells`` (4), ``track_max_tracks`` (256): ``InstanceTracker``'s.
     ``track_motion: true`` adds ``motion``, a ``MotionSettings`` (K37) from ``track_velocity_gain`` (0.5), ``track_gate`` (3.0 m)
-    and ``track_max_speed`` (6.0 m per frame); without the key the result is what it was."""
+    and ``track_max_speed`` (6.0 m per frame); without the key the result is what it was.  ``track_occlusion: true`` adds
+    ``occlusion``, an ``OcclusionSettings`` (K38) from ``track_occlusion_z_top`` (-0.2 m), ``track_hidden_fraction`` ([1, 2]) and
+    ``track_max_hold`` (10 frames); without the key the result is what it was."""
     out = dict(min_iou=float(config.get('track_min_iou', 0.3)), max_age=int(config.get('track_max_age', 2)),
                min_cells=int(config.get('track_min_cells', 4)), max_tracks=int(config.get('track_max_tracks', 256)))
     if bool(config.get('track_motion', False)):
         out['motion'] = MotionSettings(gain=float(config.get('track_velocity_gain', 0.5)), gate_m=float(config.get('track_gate', 3.0)),
                                        max_speed=float(config.get('track_max_speed', 6.0)))
+    if bool(config.get('track_occlusion', False)):
+        out['occlusion'] = OcclusionSettings(z_top=float(config.get('track_occlusion_z_top', -0.2)),
+                                             hidden_fraction=tuple(config.get('track_hidden_fraction', (1, 2))),
+                                             max_hold=int(config.get('track_max_hold', 10)))
     return out
 
 
@@ -170,7 +176,8 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
     tube association (K33b) per sequence and the panoptic IoU (K32) of this rank alone over the same frames; with ``out_dir`` the
     ``.label`` files carry the track id + 1 as the instance id.  Returns ``None`` — after one line that says why — when a
     sequence lacks ``poses.txt`` or ``calib.txt``, else ``{'tracks', 'dropped', 'frames', 'written'}`` (with ``track_motion: true``
-    the tracker runs K37's motion model and ``'gated'`` is added) plus, with labels,
+    the tracker runs K37's motion model and ``'gated'`` is added; with ``track_occlusion: true`` the visibility map of every
+    batch is computed from the scans already read, K38, and ``'held'`` is added) plus, with labels,
     ``{'lstq', 's_assoc', 's_cls', 'tubes'}``.  Not pinned: parity with semantic-kitti-api's 4D evaluator, LSTQ on real data."""
     by_seq = {}
     for f, _ in semantic_kitti_files(root, sequences):
@@ -193,7 +200,8 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
         tracker.reset()
         tubes.reset()
         for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
-            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]])
+            vis = pred.visibility(scans, model, tracker.occlusion) if tracker.occlusion is not None else None
+            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]], visibility=vis)
             lifted = pred.lift(scans, model, **ground)
             ids = pred.point_tracks(lifted, query_track)
             if have_labels:
@@ -205,7 +213,7 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
                     out['written'].append(prediction_label_path(out_dir, f))
                     write_semantic_kitti_labels(out['written'][-1], labels, semantic_id, instance_ids=tracks)
         counts = tracker.counters()
-        for key in ('tracks', 'dropped', 'frames') + (('gated',) if 'gated' in counts else ()):
+        for key in ('tracks', 'dropped', 'frames') + tuple(k for k in ('gated', 'held') if k in counts):
             out[key] = out.get(key, 0) + counts[key]
         if have_labels:
             res = tubes.compute()                  # per sequence: SemanticKITTI's instance ids are unique inside one only
@@ -221,8 +229,9 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
 def format_point_lstq(result):
     """The ``point LSTQ`` line of ``--test`` from :func:`sequence_tracking`."""
     gated = f', gated {result["gated"]}' if 'gated' in result else ''                  # K37: with ``track_motion: true`` only
+    held = f', held {result["held"]}' if 'held' in result else ''                      # K38: with ``track_occlusion: true`` only
     return (f'point LSTQ {result["lstq"]:.4f} S_assoc {result["s_assoc"]:.4f} S_cls {result["s_cls"]:.4f} '
-            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]}{gated})')
+            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]}{gated}{held})')
 
 
 def format_layer_metrics(logged, layer):
@@ -300,7 +309,8 @@ def render_frames(model, config, device, scan_paths, out_dir, dataset='semantic-
             poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
             tracker.reset()
         for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
-            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]]) if track else None
+            vis = pred.visibility(scans, model, tracker.occlusion) if track and tracker.occlusion is not None else None
+            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]], visibility=vis) if track else None
             frames = pred.render(settings, scans=scans, module=model, query_track=query_track,
                                  gt_maps=_cached_maps(part, pred.grid_hw, device)).cpu().numpy()
             for f, frame in zip(part, frames):

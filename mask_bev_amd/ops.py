@@ -16,7 +16,7 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_loss       K8 point sampling, K9 Hungarian, K10 importance sampling, K13 loss rows / costs
     ops_instances  K21 query selection + BEV mask / instance-map extraction at inference; K31 lift of the instance map to
                    the points (per-point labels, points and z-extent per query); K35 ground height per BEV cell and the
-                   lift restricted to the returns above it
+                   lift restricted to the returns above it; K38a BEV visibility map of a scan (PASSED / HIT / unknown)
     ops_rasterize  K22 SemanticKITTI scene -> instance-id map (binning, close + open, paint)
     ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp;
                    K28 KITTI object augmentations: box-table membership, move, removal and pasting of points
@@ -25,7 +25,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
                    K30 largest 8-connected component + minimum-area rectangle of a packed mask,
                    K32 panoptic tp / fp / fn, IoU sums and confusion per frame from two id arrays (points or BEV cells)
     ops_track      K33 the tracker step over consecutive BEV instance maps (global instance ids) and tube association (S_assoc of LSTQ);
-                   K37 the same step with a constant-velocity motion model and gated re-association
+                   K37 the same step with a constant-velocity motion model and gated re-association;
+                   K38b the same step with occlusion-aware ageing from K38a's maps
     ops_render     K36 returns per BEV cell and the composed BEV frame (density, instances / tracks, ground-truth contour, boxes)
 """
 from .ops_core import *            # noqa: F401,F403

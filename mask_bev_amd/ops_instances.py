@@ -159,6 +159,53 @@ def ground_map(scans: Sequence[torch.Tensor], geom, radius: int, z_floor: Option
     return GroundMap(ground, cell_min, radius)
 
 
+def origin_cell(geom, origin) -> Tuple[int, int]:
+    """The BEV cell (cx, cy) of a sensor at ``origin`` = (x, y, z): K1's arithmetic in numpy f32 — ``floor((p - min) / vs)`` as
+    a separate subtraction and division — without the range rejection: the cell may lie outside the grid (KITTI's
+    ``x_range = (0, 80)`` puts a sensor at x = 0 on the edge)."""
+    import numpy as np
+    f = np.float32
+    r, v = geom.pc_range, geom.voxel_size
+    cx = np.floor((f(origin[0]) - f(r[0])) / f(v[0]))
+    cy = np.floor((f(origin[1]) - f(r[1])) / f(v[1]))
+    if not (abs(cx) <= 2 ** 20 and abs(cy) <= 2 ** 20):        # NaN and inf land here
+        raise ValueError(f'origin_cell: the origin {tuple(origin)} lies more than 2^20 cells from the grid\'s corner')
+    return int(cx), int(cy)
+
+
+@torch.no_grad()
+def visibility_map(scans: Sequence[torch.Tensor], geom, origin=(0., 0., 0.), z_top: float = -0.2,
+                   prefilter: bool = True) -> torch.Tensor:
+    """K38a: which BEV cells every scan could observe → (B, gy, gx) uint8, the layout of ``instance_map``: bit 0 PASSED — a
+    beam crossed the cell at or below ``z_top`` on its way to the lowest return of some other cell; bit 1 HIT — the cell holds a
+    return K1's cell rule accepts (``geom``, ``prefilter`` as in :func:`lift_instances`); 0 — unknown: no beam says anything
+    about the cell at that height.  ``origin`` = (x, y, z) of the sensor in the scan's frame; ``z_top`` is absolute in that
+    frame, not relative to the ground: the default -0.2 m is a 1.5 m roof under a sensor 1.73 m above the road — geometry,
+    not measurement.  One ray per cell; returns outside the grid cast none; the ring next to a roof-mounted sensor stays
+    unknown.  Device tensors only; no host synchronisation."""
+    lib = _lib.load()
+    if len(scans) == 0:
+        raise ValueError('visibility_map: empty batch')
+    _need_gpu(*scans)
+    batch, dev = len(scans), scans[0].device
+    points, dim, lens, scan_offsets = _concat_scans('visibility_map', scans, dev)
+    gx, gy, gz = (int(v) for v in geom.grid)
+    ocx, ocy = origin_cell(geom, origin)
+    vis = torch.empty((batch, gy, gx), dtype=torch.uint8, device=dev)
+    nbytes = lib.mbv_visibility_map_workspace_bytes(batch, gx, gy)
+    if nbytes == 0:
+        raise MaskBevHipError(f'visibility_map: a batch of {batch} on a {gy}x{gx} grid is not supported')
+    ws = _workspace(nbytes, dev)
+    r, v = geom.pc_range, geom.voxel_size
+    check(lib.mbv_visibility_map(_ptr(points), dim, sum(lens), _ptr(scan_offsets), batch, r[0], r[1], r[2], r[3], r[4], r[5],
+                                 v[0], v[1], v[2], gx, gy, gz, 1 if prefilter else 0, ocx, ocy, float(origin[2]), float(z_top),
+                                 _ptr(vis), _ptr(ws), ws.numel(), _stream()), 'mbv_visibility_map')
+    return vis
+
+
+VIS_PASSED, VIS_HIT = 1, 2
+
+
 @torch.no_grad()
 def lift_instances(scans: Sequence[torch.Tensor], instance_map: torch.Tensor, geom, num_queries: int, z_bins: int = 64,
                    quantiles: Tuple[float, float] = (0., 1.), prefilter: bool = True, ground=None, clearance: float = 0.3,
@@ -220,4 +267,4 @@ def lift_instances(scans: Sequence[torch.Tensor], instance_map: torch.Tensor, ge
 
 
 __all__ = ['select_queries', 'extract_masks', 'lift_instances', 'PointInstances', 'ground_map', 'GroundMap',
-           'MAX_GROUND_RADIUS']
+           'MAX_GROUND_RADIUS', 'visibility_map', 'origin_cell', 'VIS_PASSED', 'VIS_HIT']

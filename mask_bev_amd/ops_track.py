@@ -1,12 +1,12 @@
 """K33a — the tracker step over consecutive BEV instance maps of one sequence, K37 — the same step with a constant-velocity
 motion model and gated re-association (off by default), and K33b — tube association, the S_assoc term of LSTQ
-(csrc/track.hip).  Behind ``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions are in
+(csrc/track.hip); K38b — K37's step with occlusion-aware ageing from K38a's visibility maps (off by default).  Behind ``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions are in
 include/maskbev_hip.h."""
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -55,16 +55,54 @@ class MotionSettings:
 
 
 @dataclass
+class TrackOcclusion:
+    """K38b's record of a tracker, on the device (include/maskbev_hip.h): ``live_held`` (P) int32 — the frames every live track
+    has been held since its last match; ``occlusion_counters`` (2) int32 = held, reserved 0."""
+    live_held: torch.Tensor
+    occlusion_counters: torch.Tensor
+
+    @staticmethod
+    def fresh(max_tracks: int, device) -> 'TrackOcclusion':
+        return TrackOcclusion(torch.zeros((int(max_tracks),), dtype=torch.int32, device=device),
+                              torch.zeros((2,), dtype=torch.int32, device=device))
+
+
+@dataclass
+class OcclusionSettings:
+    """K38's settings (``tracking.OcclusionSettings`` is this class): ``z_top`` in metres, absolute in the sensor frame — the
+    roof height of the objects one asks about, K38a's; ``hidden_fraction`` = (num, den) with 0 < num <= den — a track that goes
+    unmatched is held when at least num / den of its warped footprint lies on cells of visibility 0; ``max_hold`` >= 0 — the
+    most frames in a row a track is held, 0 holds none; ``origin`` = (x, y, z) of the sensor in the scan's frame.  The defaults
+    are geometry, not measurement: -0.2 m is a 1.5 m roof under a sensor 1.73 m above the road; half of the footprint must be
+    hidden; 10 frames is one second at 10 Hz."""
+    z_top: float = -0.2
+    hidden_fraction: Tuple[int, int] = (1, 2)
+    max_hold: int = 10
+    origin: Tuple[float, float, float] = (0., 0., 0.)
+
+    def __post_init__(self):
+        self.z_top, self.max_hold = float(self.z_top), int(self.max_hold)
+        self.hidden_fraction = (int(self.hidden_fraction[0]), int(self.hidden_fraction[1]))
+        self.origin = tuple(float(v) for v in self.origin)
+        num, den = self.hidden_fraction
+        if not (0 < num <= den < 2 ** 31 and 0 <= self.max_hold < 2 ** 31 and math.isfinite(self.z_top) and len(self.origin) == 3
+                and all(math.isfinite(v) for v in self.origin)):
+            raise ValueError(f'OcclusionSettings: hidden_fraction {self.hidden_fraction} with 0 < num <= den, max_hold '
+                             f'{self.max_hold} >= 0, a finite z_top {self.z_top} and a finite origin {self.origin} (x, y, z) expected')
+
+
+@dataclass
 class TrackState:
     """The tracker's persistent state on the device (include/maskbev_hip.h, K33a): ``state_map`` (H, W) int32 — a local
     track index or -1; ``live_id`` / ``live_seen`` (P) int32 — the global id and the frame of the last match of every live
     track; ``counters`` (4) int32 = n_live, next_id, frame, dropped.  ``motion``: K37's record, None without the motion
-    model."""
+    model.  ``occlusion``: K38b's record, None without occlusion-aware ageing (which needs ``motion`` too)."""
     state_map: torch.Tensor
     live_id: torch.Tensor
     live_seen: torch.Tensor
     counters: torch.Tensor
     motion: Optional[TrackMotion] = None
+    occlusion: Optional[TrackOcclusion] = None
 
     @staticmethod
     def fresh(h: int, w: int, max_tracks: int, device) -> 'TrackState':
@@ -123,12 +161,16 @@ class TubeScores:
 def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state: TrackState, x_lo: float, y_lo: float,
                  voxel: float, num_queries: int, min_iou: float = 0.3, max_age: int = 2, min_cells: int = 4,
                  track_map: bool = False, motion: Optional[MotionSettings] = None,
-                 cur_from_prev: Optional[torch.Tensor] = None) -> TrackFrames:
+                 cur_from_prev: Optional[torch.Tensor] = None, occlusion: Optional[OcclusionSettings] = None,
+                 visibility: Optional[torch.Tensor] = None) -> TrackFrames:
     """K33a: ``instance_maps`` (F, H, W) int32 — F consecutive frames of ONE sequence, a query in [0, num_queries) or -1 per
     cell; ``prev_from_cur`` (F, 2, 3) f64 — per frame the map of its BEV coordinates into the previous frame's; ``state`` is
     stepped in place.  Device tensors only; no host synchronisation.
     ``motion``: K37 — the step with the motion model; ``state.motion`` must hold the record.  ``cur_from_prev`` (F, 2, 3) f64
-    is the inverse of ``prev_from_cur``; when it is absent it is computed on the device (:func:`invert_transforms`)."""
+    is the inverse of ``prev_from_cur``; when it is absent it is computed on the device (:func:`invert_transforms`).
+    ``occlusion``: K38b — the step through ``mbv_track_frames_occluded``; ``state.motion`` and ``state.occlusion`` must hold
+    the records.  Without ``motion`` it runs with gain = gate = 0, K33a's matching.  ``visibility`` (F, H, W) uint8, K38a's
+    maps of the same frames (``ops.visibility_map``); None holds no track: the step is then K37's."""
     lib = _lib.load()
     _need_gpu(instance_maps, prev_from_cur, state.state_map, state.live_id, state.live_seen, state.counters)
     dev = instance_maps.device
@@ -152,9 +194,12 @@ def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state
     instance_maps, prev_from_cur = instance_maps.contiguous(), prev_from_cur.contiguous()
     out = TrackFrames(torch.empty((f, q), dtype=torch.int32, device=dev),
                       torch.empty((f, h, w), dtype=torch.int32, device=dev) if track_map else None)
-    if motion is not None:
+    if visibility is not None and occlusion is None:
+        raise MaskBevHipError('track_frames: a visibility map given without occlusion settings')
+    if motion is not None or occlusion is not None:
         return _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state, float(x_lo), float(y_lo),
-                                    float(voxel), q, p, float(min_iou), int(max_age), int(min_cells), motion, out)
+                                    float(voxel), q, p, float(min_iou), int(max_age), int(min_cells), motion, out, occlusion,
+                                    visibility)
     if f == 0:
         return out
     ws = _workspace(lib.mbv_track_frames_workspace_bytes(h, w, q, p), dev)
@@ -177,12 +222,12 @@ def invert_transforms(prev_from_cur: torch.Tensor) -> torch.Tensor:
 
 
 def _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state, x_lo, y_lo, voxel, q, p, min_iou, max_age,
-                         min_cells, motion, out) -> TrackFrames:
+                         min_cells, motion, out, occlusion=None, visibility=None) -> TrackFrames:
     dev = instance_maps.device
     f, h, w = (int(v) for v in instance_maps.shape)
     rec = state.motion
     if rec is None:
-        raise MaskBevHipError('track_frames: motion settings given, but state.motion is None (TrackMotion.fresh)')
+        raise MaskBevHipError('track_frames: motion or occlusion settings given, but state.motion is None (TrackMotion.fresh)')
     _need_gpu(rec.pos, rec.vel, rec.motion_counters)
     for name, x, shape, dt in (('pos', rec.pos, (p, 2), torch.float64), ('vel', rec.vel, (p, 2), torch.float64),
                                ('motion_counters', rec.motion_counters, (2,), torch.int32)):
@@ -190,7 +235,21 @@ def _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state
             raise MaskBevHipError(f'track_frames: state.motion.{name} must be a contiguous {shape} {dt} tensor on {dev}')
     if not voxel > 0.0:
         raise MaskBevHipError(f'track_frames: voxel {voxel} > 0 expected')
-    gain, gate, max_shift = motion.gain, motion.gate_m, motion.max_shift(voxel)
+    gain, gate, max_shift = (motion.gain, motion.gate_m, motion.max_shift(voxel)) if motion is not None else (0.0, 0.0, 0)
+    occ = state.occlusion
+    if occlusion is not None:
+        if occ is None:
+            raise MaskBevHipError('track_frames: occlusion settings given, but state.occlusion is None (TrackOcclusion.fresh)')
+        _need_gpu(occ.live_held, occ.occlusion_counters)
+        for name, x, shape in (('live_held', occ.live_held, (p,)), ('occlusion_counters', occ.occlusion_counters, (2,))):
+            if tuple(x.shape) != shape or x.dtype != torch.int32 or x.device != dev or not x.is_contiguous():
+                raise MaskBevHipError(f'track_frames: state.occlusion.{name} must be a contiguous {shape} int32 tensor on {dev}')
+        if visibility is not None:
+            _need_gpu(visibility)
+            if tuple(visibility.shape) != (f, h, w) or visibility.dtype != torch.uint8 or visibility.device != dev:
+                raise MaskBevHipError(f'track_frames: visibility must be ({f}, {h}, {w}) uint8 on {dev}, got '
+                                      f'{tuple(visibility.shape)} {visibility.dtype}')
+            visibility = visibility.contiguous()
     if cur_from_prev is None:
         cur_from_prev = invert_transforms(prev_from_cur)
     _need_gpu(cur_from_prev)
@@ -200,6 +259,17 @@ def _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state
     cur_from_prev = cur_from_prev.contiguous()
     out.query_velocity = torch.empty((f, q, 2), dtype=torch.float64, device=dev)
     if f == 0:
+        return out
+    if occlusion is not None:
+        ws = _workspace(lib.mbv_track_frames_occluded_workspace_bytes(h, w, q, p), dev)
+        num, den = occlusion.hidden_fraction
+        check(lib.mbv_track_frames_occluded(_ptr(instance_maps), _ptr(prev_from_cur), _ptr(cur_from_prev), _ptr(visibility), f, h,
+                                            w, x_lo, y_lo, voxel, q, p, min_iou, max_age, min_cells, gain, gate, max_shift, num,
+                                            den, occlusion.max_hold, _ptr(state.state_map), _ptr(state.live_id),
+                                            _ptr(state.live_seen), _ptr(occ.live_held), _ptr(state.counters), _ptr(rec.pos),
+                                            _ptr(rec.vel), _ptr(rec.motion_counters), _ptr(occ.occlusion_counters),
+                                            _ptr(out.query_track), _ptr(out.track_map), _ptr(out.query_velocity), _ptr(ws),
+                                            ws.numel(), _stream()), 'mbv_track_frames_occluded')
         return out
     ws = _workspace(lib.mbv_track_frames_motion_workspace_bytes(h, w, q, p), dev)
     check(lib.mbv_track_frames_motion(_ptr(instance_maps), _ptr(prev_from_cur), _ptr(cur_from_prev), f, h, w, x_lo, y_lo, voxel,
@@ -264,4 +334,5 @@ def tube_scores(tables: TubeTables) -> TubeScores:
 
 
 __all__ = ['track_frames', 'invert_transforms', 'tube_accumulate', 'tube_scores', 'TrackState', 'TrackMotion', 'MotionSettings',
+           'TrackOcclusion', 'OcclusionSettings',
            'TrackFrames', 'TubeTables', 'TubeScores']

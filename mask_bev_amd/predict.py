@@ -185,14 +185,26 @@ class Predictions:
         b, cells = m.shape[0], m.shape[1] * m.shape[2]
         return metric.update(m.reshape(-1).contiguous(), self.query_classes(), words, [cells] * b)
 
-    def track(self, tracker, poses=None, prev_from_cur=None) -> torch.Tensor:
+    def visibility(self, scans, module_or_geometry, settings=None) -> torch.Tensor:
+        """K38a, ``ops.visibility_map``: the (B, ny, nx) uint8 visibility map of ``scans`` — the scans these predictions were
+        made from — in the cell layout of ``instance_map`` (bit 0 PASSED, bit 1 HIT, 0 unknown), with the encoder's voxel
+        geometry (a module, or its ``VoxelGeometry``).  ``settings``: a ``tracking.OcclusionSettings`` — its ``origin`` and
+        ``z_top``; None takes that record's defaults.  No host synchronisation."""
+        from .ops_track import OcclusionSettings
+        settings = OcclusionSettings() if settings is None else settings
+        return ops.visibility_map(scans, voxel_geometry(module_or_geometry), origin=settings.origin, z_top=settings.z_top)
+
+    def track(self, tracker, poses=None, prev_from_cur=None, visibility=None) -> torch.Tensor:
         """Steps a :class:`~mask_bev_amd.tracking.InstanceTracker` through the B frames of these predictions — CONSECUTIVE
         scans of one sequence, in order — and returns ``query_track`` (B, Q) int32: the global track id of every query, -1
         where the query owns too few cells.  ``poses`` (B, 4, 4) f64 sensor poses, or ``prev_from_cur`` (B, 2, 3) f64.  K33a;
-        no host synchronisation."""
+        no host synchronisation.  ``visibility``: :meth:`visibility` of the same scans, for a tracker made with ``occlusion=``
+        (K38b)."""
         if self.instance_map is None:
             raise MaskBevHipError('track: these predictions were made without an instance map')
-        return tracker.update(self.instance_map, poses=poses, prev_from_cur=prev_from_cur)
+        if visibility is None:
+            return tracker.update(self.instance_map, poses=poses, prev_from_cur=prev_from_cur)
+        return tracker.update(self.instance_map, poses=poses, prev_from_cur=prev_from_cur, visibility=visibility)
 
     def point_tracks(self, lifted: 'ops.PointInstances', query_track: torch.Tensor) -> torch.Tensor:
         """The global track id of every point: ``query_track`` (B, Q) from :meth:`track`, gathered by K31's ``point_query``

@@ -11,6 +11,14 @@ taken, and what the overlap leaves open is matched by centroid distance within a
 itself is picked up in its second frame and keeps its id.  Its limits: shifts are whole cells, so a coasting track's
 footprint drifts by up to half a cell per frame; the gate can hand a lost track to another detection within ``gate_m`` of
 its prediction.  The defaults of ``MotionSettings`` are geometry, not measurement; no LSTQ on real SemanticKITTI is pinned.
+
+``InstanceTracker(..., occlusion=OcclusionSettings())`` turns on K38b: ``update(..., visibility=)`` takes K38a's visibility
+maps of the same frames (``ops.visibility_map`` / ``Predictions.visibility``), and a track that goes unmatched while at least
+``hidden_fraction`` of its warped footprint lies on cells no beam certified does not age, for at most ``max_hold`` frames in
+a row — a car behind a truck keeps its id, a false positive that vanishes in the open still dies after ``max_age``.  Its
+limits: ``z_top`` is absolute in the sensor frame, not relative to K35's ground; returns outside the grid cast no rays; the
+blind ring next to a roof-mounted sensor is "unknown", so tracks there are held up to ``max_hold``; one ray per cell, to its
+lowest return.  The defaults are geometry, not measurement, and nothing is claimed about LSTQ on real data.
 """
 from __future__ import annotations
 
@@ -21,7 +29,7 @@ import torch
 
 from . import ops
 from ._lib import MaskBevHipError
-from .ops_track import MotionSettings
+from .ops_track import MotionSettings, OcclusionSettings
 
 _IDENTITY = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]], dtype=np.float64)
 
@@ -57,10 +65,12 @@ class InstanceTracker:
     pair needs an IoU of at least ``min_iou``; a track unmatched for more than ``max_age`` frames is forgotten.  The state
     lives on the device; :meth:`update` synchronises nothing and :meth:`counters` is the one host copy.  ``motion``: a
     :class:`MotionSettings` turns on the constant-velocity motion model and the gated second stage (K37); None, the default,
-    is K33a's step."""
+    is K33a's step.  ``occlusion``: an :class:`OcclusionSettings` turns on occlusion-aware ageing (K38b) for the frames whose
+    visibility map is passed to :meth:`update`; with ``motion`` None it runs on K33a's matching (gain = gate = 0)."""
 
     def __init__(self, x_range, y_range, voxel_size: float, num_queries: int, max_tracks: int = 256, min_iou: float = 0.3,
-                 max_age: int = 2, min_cells: int = 4, device='cuda', motion: Optional[MotionSettings] = None):
+                 max_age: int = 2, min_cells: int = 4, device='cuda', motion: Optional[MotionSettings] = None,
+                 occlusion: Optional[OcclusionSettings] = None):
         self.x_lo, self.y_lo, self.voxel = float(x_range[0]), float(y_range[0]), float(voxel_size)
         self.w = int((x_range[1] - x_range[0]) / voxel_size)
         self.h = int((y_range[1] - y_range[0]) / voxel_size)
@@ -74,15 +84,21 @@ class InstanceTracker:
             raise ValueError(f'InstanceTracker: motion must be a MotionSettings or None, got {type(motion).__name__}')
         if motion is not None and not self.voxel > 0.0:
             raise ValueError(f'InstanceTracker: voxel_size {voxel_size} > 0 expected with a motion model')
-        self.motion = motion
+        if occlusion is not None and not isinstance(occlusion, OcclusionSettings):
+            raise ValueError(f'InstanceTracker: occlusion must be an OcclusionSettings or None, got {type(occlusion).__name__}')
+        if occlusion is not None and not self.voxel > 0.0:
+            raise ValueError(f'InstanceTracker: voxel_size {voxel_size} > 0 expected with occlusion-aware ageing')
+        self.motion, self.occlusion = motion, occlusion
         self.device = torch.device(device)
         self.reset()
 
     def reset(self) -> None:
         """A fresh sequence: no live track, ids from 0, and the next frame takes the identity transform."""
         self.state = ops.TrackState.fresh(self.h, self.w, self.max_tracks, self.device)
-        if self.motion is not None:
+        if self.motion is not None or self.occlusion is not None:       # K38b's entry is K37's: it needs the record too
             self.state.motion = ops.TrackMotion.fresh(self.max_tracks, self.device)
+        if self.occlusion is not None:
+            self.state.occlusion = ops.TrackOcclusion.fresh(self.max_tracks, self.device)
         self._last_pose: Optional[np.ndarray] = None
         self._started = False
 
@@ -112,7 +128,8 @@ class InstanceTracker:
         return torch.from_numpy(out).to(self.device, non_blocking=True), out
 
     @torch.no_grad()
-    def update(self, pred_or_instance_maps, poses=None, prev_from_cur=None, track_map: bool = False, record: bool = False):
+    def update(self, pred_or_instance_maps, poses=None, prev_from_cur=None, track_map: bool = False, record: bool = False,
+               visibility=None):
         """``pred_or_instance_maps``: a ``Predictions`` or its (B, ny, nx) int32 ``instance_map`` — B CONSECUTIVE frames of
         the sequence.  ``poses`` (B, 4, 4) f64 sensor poses on the host (the last pose is remembered between calls), or
         ``prev_from_cur`` (B, 2, 3) f64 on the host or the device; with neither, the sensor stands still.  Returns
@@ -120,7 +137,9 @@ class InstanceTracker:
         ``track_map=True``, the ``ops.TrackFrames`` record that also holds the (B, ny, nx) map of global ids; ``record=True``
         returns that record without the map — with a motion model it holds ``query_velocity`` (B, Q, 2) f64, metres per
         frame over ground in the axes of each frame's sensor.  With a motion model the inverse transforms are computed on
-        the host with the transforms themselves, and on the device where ``prev_from_cur`` is a device tensor."""
+        the host with the transforms themselves, and on the device where ``prev_from_cur`` is a device tensor.
+        ``visibility`` (B, ny, nx) uint8 — K38a's maps of the same frames, for a tracker made with ``occlusion=``; without it
+        no track is held in these frames."""
         maps = getattr(pred_or_instance_maps, 'instance_map', pred_or_instance_maps)
         if maps is None:
             raise MaskBevHipError('InstanceTracker.update: these predictions were made without an instance map')
@@ -128,23 +147,29 @@ class InstanceTracker:
             raise MaskBevHipError(f'InstanceTracker.update: (B, {self.h}, {self.w}) instance maps expected, got {tuple(maps.shape)}')
         m, host = self._transforms(int(maps.shape[0]), poses, prev_from_cur)
         n = None
-        if self.motion is not None and host is not None:
+        if visibility is not None and self.occlusion is None:
+            raise MaskBevHipError('InstanceTracker.update: a visibility map for a tracker made without occlusion=')
+        if (self.motion is not None or self.occlusion is not None) and host is not None:
             inv = np.stack([cur_from_prev_2d(x) for x in host]) if len(host) else np.zeros((0, 2, 3), dtype=np.float64)
             n = torch.from_numpy(inv).to(self.device, non_blocking=True)
         out = ops.track_frames(maps, m, self.state, self.x_lo, self.y_lo, self.voxel, self.num_queries, self.min_iou,
-                               self.max_age, self.min_cells, track_map=track_map, motion=self.motion, cur_from_prev=n)
+                               self.max_age, self.min_cells, track_map=track_map, motion=self.motion, cur_from_prev=n,
+                               occlusion=self.occlusion, visibility=visibility)
         self._started = self._started or maps.shape[0] > 0
         return out if track_map or record else out.query_track
 
     def counters(self) -> dict:
         """The one host copy: ``{'live', 'tracks', 'frames', 'dropped'}`` — the live tracks, the ids given out so far, the
         frames seen since :meth:`reset` and the tracks dropped because ``max_tracks`` were live; with a motion model also
-        ``'gated'`` — the pairs the second stage took."""
+        ``'gated'`` — the pairs the second stage took; with occlusion-aware ageing also ``'held'`` — the times a track was
+        held for a frame."""
         n_live, next_id, frame, dropped = (int(v) for v in self.state.counters.cpu())
         out = dict(live=n_live, tracks=next_id, frames=frame, dropped=dropped)
         if self.motion is not None:
             out['gated'] = int(self.state.motion.motion_counters.cpu()[0])
+        if self.occlusion is not None:
+            out['held'] = int(self.state.occlusion.occlusion_counters.cpu()[0])
         return out
 
 
-__all__ = ['InstanceTracker', 'MotionSettings', 'prev_from_cur_2d', 'cur_from_prev_2d', 'velodyne_poses']
+__all__ = ['InstanceTracker', 'MotionSettings', 'OcclusionSettings', 'prev_from_cur_2d', 'cur_from_prev_2d', 'velodyne_poses']

@@ -44,7 +44,9 @@ without them): one global instance id per object, written by ``--write-labels`` 
 files ``point LSTQ .. S_assoc .. S_cls .. (tubes .., tracks .., dropped ..)`` (``track_min_iou``, ``track_max_age``,
 ``track_min_cells``, ``track_max_tracks``; ``track_motion: true`` runs the tracker with its constant-velocity motion model and
 gated re-association, K37 — ``track_velocity_gain``, ``track_gate`` metres, ``track_max_speed`` metres per frame — and the
-parenthesis then ends ``, gated ..``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
+parenthesis then ends ``, gated ..``; ``track_occlusion: true`` computes a BEV visibility map of every scan and lets a track
+that goes unmatched out of the sensor's sight keep its age, K38 — ``track_occlusion_z_top`` metres in the sensor frame,
+``track_hidden_fraction`` [num, den], ``track_max_hold`` frames — and the parenthesis then ends ``, held ..``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
 ``lift_max_height``, ``lift_z_floor``) makes every one of these lifts label only the returns above a ground estimate made from
 the scan, lets the 3D boxes stand on it, and prints one ``ground-aware lift: ..`` line in front of the results it changes.
 ``--render DIR`` (K36; ``render_scale``, ``render_alpha``, ``render_boxes``) adds a last pass on rank 0 that writes one BEV frame
