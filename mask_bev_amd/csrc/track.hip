@@ -1,28 +1,31 @@
 // K33 — instance tracking over a sequence and tube association (the S_assoc term of LSTQ).  The rules are in
-// include/maskbev_hip.h (K33a, K33b); this file restates nothing, it implements them.
+// include/maskbev_hip.h (K33a, K37, K38b, K33b); this file restates nothing, it implements them.
 //
-// K33a, four launches per frame, all on the caller's stream, no host synchronisation:
-//   1. clear     zeroes area_q, area_t and the (Q, P) intersection table of the workspace.
-//   2. count     one thread per cell (blocks of 256): the f64 warp of the cell centre into the previous frame's grid, one
+// The tracker is ONE step with two optional parts, behind one host driver (track_frames) that the three entries fill a
+// TrackCall for: mbv_track_frames (K33a, neither part), mbv_track_frames_motion (K37, the motion part) and
+// mbv_track_frames_occluded (K38b, both).  Per frame, all on the caller's stream, no host synchronisation:
+//   1. clear     zeroes area_q, area_t and the (Q, P) intersection table of the workspace.  [motion] also fills the advected
+//                map, zeroes the centroid sums and writes the cell shift of every live track; [occlusion] zeroes hidden.
+//   2. advect    [motion only, the fifth launch] one thread per cell, unsigned atomicMin: the smallest track index wins a cell.
+//   3. count     one thread per cell (blocks of 256): the f64 warp of the cell centre into the previous frame's grid, one
 //                rounding per operation (-ffp-contract=off), the warped track index to the workspace; area_q and area_t in
 //                LDS tables (integer LDS atomics, one flush per block), the intersection table with global integer atomics.
-//   3. match     ONE workgroup of 1024: the candidate pairs are compacted into a list; then rounds in which every untaken
+//                [motion] reads the advected map instead of the state map; the index sums of a query's cells per block in
+//                LDS, flushed with 64-bit global atomics.  [occlusion] also sums hidden[t], the cells of a warped footprint
+//                whose visibility byte is 0, in a fifth LDS table.
+//   4. match     ONE workgroup of 1024: the candidate pairs are compacted into a list; then rounds in which every untaken
 //                row and column takes its best candidate under the exact order (IoU by i64 cross-multiplication, then q,
 //                then t) and a pair that is the best of both is taken.  Such a pair is the first of the remaining order
 //                among all pairs that share its query or its track, so the greedy walk takes it too; taking it removes
 //                what the walk would skip.  By induction the rounds end with the walk's result, and each round takes at
-//                least the first remaining pair.  Then the update of the live list with three block scans.
-//   4. paint     one thread per cell: the new state map and the optional map of global ids.
-// K37, the same step with a constant-velocity motion model (mbv_track_frames_motion), five launches per frame: clear (also
-// the advected map, the centroid sums and the cell shift of every live track), advect (one thread per cell, unsigned
-// atomicMin: the smallest track index wins a cell), count<true> (reads the advected map; the index sums of a query's cells
-// per block in LDS, flushed with 64-bit global atomics), match<true> (after the IoU rounds: centroids, predictions, the gate
-// candidates and the same mutual-best rounds under the order (d2, q, t); then the update also of pos / vel) and paint.
-// count and match are one template each: the <false> instantiations are K33a's kernels.
-// K38b, occlusion-aware ageing (mbv_track_frames_occluded): K37's five launches with the third instantiation <true, true> of
-// the same two templates.  count also sums hidden[t], the cells of a warped footprint whose visibility byte is 0, in a fifth
-// LDS table; match reads hidden and live_held and, in step 4, lets an unmatched track whose footprint was mostly out of
-// sight keep its age.  With visibility == NULL or max_hold == 0 no track is held and the step is K37's bit for bit.
+//                least the first remaining pair.  Then the update of the live list with three block scans.  [motion] after
+//                the IoU rounds: centroids, predictions, the gate candidates and the same mutual-best rounds under the order
+//                (d2, q, t); the update also of pos / vel.  [occlusion] reads hidden and live_held and lets an unmatched
+//                track whose footprint was mostly out of sight keep its age; live_held goes through the compaction.
+//   5. paint     one thread per cell: the new state map and the optional map of global ids.
+// clear, count and match are one template each: <false> is K33a's kernel and touches nothing of the motion part; K37 runs
+// <true> / <true, false>; K38b runs <true, true> whatever `visibility` is, and with visibility == NULL or max_hold == 0 holds
+// no track: the step is then K37's bit for bit.
 // K33b: accumulate (grid-stride blocks with LDS tables for the two size tables where they fit), scores (one workgroup per
 // row; the terms of 256 tracks at a time in LDS, summed by one thread in ascending order) and the class sums.
 // Integer atomics only; every f64 sum in a fixed order: two runs are bit-equal.  Every index comes from the sizes: a query, a
@@ -84,49 +87,46 @@ __device__ __forceinline__ int live_count(const int32_t* __restrict__ counters, 
   return n < 0 ? 0 : (n > P ? P : n);
 }
 
-__global__ void __launch_bounds__(kThreads) k_track_clear(int Q, int P, int32_t* __restrict__ area_q,
-                                                          int32_t* __restrict__ area_t, int32_t* __restrict__ inter) {
-  const int64_t stride = (int64_t)gridDim.x * kThreads, n = (int64_t)Q * P;
-  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  for (int64_t i = t; i < n; i += stride) inter[i] = 0;
-  for (int64_t i = t; i < Q; i += stride) area_q[i] = 0;
-  for (int64_t i = t; i < P; i += stride) area_t[i] = 0;
-}
-
 __device__ __forceinline__ void add64(int64_t* p, int64_t n) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)n);
 }
 
-// K37's clear: K33a's tables, the advected map, the centroid sums, and step 0's cell shift of every track; K38b's hidden
-// table where there is one
-__global__ void __launch_bounds__(kThreads) k_track_clear_motion(int64_t cells, int Q, int P, double voxel, int max_shift,
-                                                                 const int32_t* __restrict__ counters,
-                                                                 const double* __restrict__ vel, int32_t* __restrict__ area_q,
-                                                                 int32_t* __restrict__ area_t, int32_t* __restrict__ inter,
-                                                                 uint32_t* __restrict__ moved, int64_t* __restrict__ sum_ix,
-                                                                 int64_t* __restrict__ sum_iy, int32_t* __restrict__ shift,
-                                                                 int32_t* __restrict__ hidden) {
+// <false>: area_q, area_t and the intersection table, and nothing else is read or written.  <true>: also the advected map,
+// the centroid sums and step 0's cell shift of every track; the hidden table where there is one.
+template <bool kMotion>
+__global__ void __launch_bounds__(kThreads) k_track_clear(int64_t cells, int Q, int P, double voxel, int max_shift,
+                                                          const int32_t* __restrict__ counters, const double* __restrict__ vel,
+                                                          int32_t* __restrict__ area_q, int32_t* __restrict__ area_t,
+                                                          int32_t* __restrict__ inter, uint32_t* __restrict__ moved,
+                                                          int64_t* __restrict__ sum_ix, int64_t* __restrict__ sum_iy,
+                                                          int32_t* __restrict__ shift, int32_t* __restrict__ hidden) {
   const int64_t stride = (int64_t)gridDim.x * kThreads, n = (int64_t)Q * P;
   const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  const int n_live = live_count(counters, P);
+  int n_live = 0;
+  if constexpr (kMotion) n_live = live_count(counters, P);
   for (int64_t i = t; i < n; i += stride) inter[i] = 0;
-  for (int64_t i = t; i < cells; i += stride) moved[i] = 0xffffffffu;
+  if constexpr (kMotion)
+    for (int64_t i = t; i < cells; i += stride) moved[i] = 0xffffffffu;
   for (int64_t i = t; i < Q; i += stride) {
     area_q[i] = 0;
-    sum_ix[i] = 0;
-    sum_iy[i] = 0;
+    if constexpr (kMotion) {
+      sum_ix[i] = 0;
+      sum_iy[i] = 0;
+    }
   }
   for (int64_t i = t; i < P; i += stride) {
     area_t[i] = 0;
-    if (hidden) hidden[i] = 0;
-    double sx = 0.0, sy = 0.0;
-    if (i < n_live) {
-      sx = rint(vel[2 * i] / voxel);
-      sy = rint(vel[2 * i + 1] / voxel);
-      if (!(fabs(sx) <= (double)max_shift && fabs(sy) <= (double)max_shift)) sx = sy = 0.0;   // NaN and inf land here
+    if constexpr (kMotion) {
+      if (hidden) hidden[i] = 0;
+      double sx = 0.0, sy = 0.0;
+      if (i < n_live) {
+        sx = rint(vel[2 * i] / voxel);
+        sy = rint(vel[2 * i + 1] / voxel);
+        if (!(fabs(sx) <= (double)max_shift && fabs(sy) <= (double)max_shift)) sx = sy = 0.0;   // NaN and inf land here
+      }
+      shift[2 * i] = (int32_t)sx;                                  // |sx| <= max_shift < 2^31
+      shift[2 * i + 1] = (int32_t)sy;
     }
-    shift[2 * i] = (int32_t)sx;                                    // |sx| <= max_shift < 2^31
-    shift[2 * i + 1] = (int32_t)sy;
   }
 }
 
@@ -681,122 +681,103 @@ bool tube_sizes_supported(int C, int I, int T) {
 
 }  // namespace
 
-extern "C" size_t mbv_track_frames_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
-  if (!track_sizes_supported(H, W, Q, P)) return 0;
-  return carve_track(nullptr, (int64_t)H * W, Q, P).bytes;
-}
-
-extern "C" int mbv_track_frames(const int32_t* instance_maps, const double* prev_from_cur, int32_t F, int32_t H, int32_t W,
-                                double x_lo, double y_lo, double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age,
-                                int32_t min_cells, int32_t* state_map, int32_t* live_id, int32_t* live_seen, int32_t* counters,
-                                int32_t* query_track, int32_t* track_map, void* workspace, size_t workspace_bytes,
-                                void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (F == 0) return MBV_OK;
-  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || min_cells < 1 || max_age < 0) return MBV_ERR_BAD_ARG;
-  if (!track_sizes_supported(H, W, Q, P)) return MBV_ERR_UNSUPPORTED;
-  const int64_t cells = (int64_t)H * W;
-  if (!prev_from_cur || !counters || (cells > 0 && (!instance_maps || !state_map)) || (P > 0 && (!live_id || !live_seen)) ||
-      (Q > 0 && !query_track))
-    return MBV_ERR_BAD_ARG;
-  TrackWorkspace w = carve_track(workspace, cells, Q, P);
-  if (!workspace || workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
-
-  int64_t clear_blocks = ((int64_t)Q * P + kThreads - 1) / kThreads;
-  clear_blocks = clear_blocks < 1 ? 1 : (clear_blocks > 1024 ? 1024 : clear_blocks);
-  const unsigned cell_blocks = (unsigned)((cells + kThreads - 1) / kThreads);
-  for (int f = 0; f < F; ++f) {
-    const int32_t* imap = instance_maps + (int64_t)f * cells;
-    hipLaunchKernelGGL(k_track_clear, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, (int)Q, (int)P, w.area_q,
-                       w.area_t, w.inter);
-    MBV_CHECK_LAUNCH();
-    if (cells > 0) {
-      hipLaunchKernelGGL(k_track_count<false>, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, state_map,
-                         prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo, voxel, (int)Q, (int)P, counters, w.warped,
-                         w.area_q, w.area_t, w.inter, (int64_t*)nullptr, (int64_t*)nullptr, (const uint8_t*)nullptr,
-                         (int32_t*)nullptr);
-      MBV_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_track_match<false>, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age,
-                       (int)min_cells, w.area_q, w.area_t, w.inter, w.cand, live_id, live_seen, counters,
-                       query_track + (int64_t)f * Q, w.q_new, w.t_new, MotionArgs{}, OcclusionArgs{});
-    MBV_CHECK_LAUNCH();
-    if (cells > 0) {
-      hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
-                         w.q_new, w.t_new, query_track + (int64_t)f * Q, state_map,
-                         track_map ? track_map + (int64_t)f * cells : nullptr);
-      MBV_CHECK_LAUNCH();
-    }
-  }
-  return MBV_OK;
-}
-
 namespace {
 
-// K38b's arguments on the host; null for K37
-struct OcclusionCall {
-  const uint8_t* visibility;       // (F, H, W) or null
-  int32_t* live_held;
-  int32_t* occlusion_counters;
-  int32_t hold_num, hold_den, max_hold;
+// One call on the host: K33a's arguments in the order of mbv_track_frames, and the two optional parts.
+struct TrackCall {
+  const int32_t* instance_maps;
+  const double* prev_from_cur;
+  int32_t F, H, W;
+  double x_lo, y_lo, voxel;
+  int32_t Q, P;
+  double min_iou;
+  int32_t max_age, min_cells;
+  int32_t *state_map, *live_id, *live_seen, *counters, *query_track, *track_map;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+  struct Motion {
+    const double* cur_from_prev;
+    double gain, gate;
+    int32_t max_shift;
+    double *pos, *vel;
+    int32_t* motion_counters;
+    double* query_velocity;
+  };
+  struct Occlusion {
+    const uint8_t* visibility;     // (F, H, W) or null
+    int32_t *live_held, *occlusion_counters;
+    int32_t hold_num, hold_den, max_hold;
+  };
+  const Motion* motion;            // null: K33a's step, four launches
+  const Occlusion* occlusion;      // null: nothing of K38b; with it the <true, true> kernels run whatever `visibility` is
 };
 
-// K37 (occ == nullptr) and K38b behind one set of checks and launches
-int track_frames_motion(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev, int32_t F,
-                        int32_t H, int32_t W, double x_lo, double y_lo, double voxel, int32_t Q, int32_t P, double min_iou,
-                        int32_t max_age, int32_t min_cells, double gain, double gate, int32_t max_shift, int32_t* state_map,
-                        int32_t* live_id, int32_t* live_seen, int32_t* counters, double* pos, double* vel,
-                        int32_t* motion_counters, int32_t* query_track, int32_t* track_map, double* query_velocity,
-                        const OcclusionCall* occ, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+// The one driver behind the three entries.
+int track_frames(const TrackCall& c) {
+  const TrackCall::Motion* mo = c.motion;
+  const TrackCall::Occlusion* oc = c.occlusion;
+  const int32_t F = c.F, H = c.H, W = c.W, Q = c.Q, P = c.P;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(c.stream);
   if (F == 0) return MBV_OK;
-  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || min_cells < 1 || max_age < 0 || max_shift < 0) return MBV_ERR_BAD_ARG;
-  if (!(gain >= 0.0 && gain <= 1.0) || !(gate >= 0.0 && gate <= 1.7976931348623157e308)) return MBV_ERR_BAD_ARG;   // NaN, inf
-  if (occ && (occ->hold_num <= 0 || occ->hold_num > occ->hold_den || occ->max_hold < 0)) return MBV_ERR_BAD_ARG;
+  if (F < 0 || H < 0 || W < 0 || Q < 0 || P < 0 || c.min_cells < 1 || c.max_age < 0) return MBV_ERR_BAD_ARG;
+  if (mo && (mo->max_shift < 0 || !(mo->gain >= 0.0 && mo->gain <= 1.0) ||
+             !(mo->gate >= 0.0 && mo->gate <= 1.7976931348623157e308)))                 // NaN, inf
+    return MBV_ERR_BAD_ARG;
+  if (oc && (oc->hold_num <= 0 || oc->hold_num > oc->hold_den || oc->max_hold < 0)) return MBV_ERR_BAD_ARG;
   if (!track_sizes_supported(H, W, Q, P)) return MBV_ERR_UNSUPPORTED;
   const int64_t cells = (int64_t)H * W;
-  if (!prev_from_cur || !cur_from_prev || !counters || !motion_counters || (cells > 0 && (!instance_maps || !state_map)) ||
-      (P > 0 && (!live_id || !live_seen || !pos || !vel)) || (Q > 0 && (!query_track || !query_velocity)))
+  if (!c.prev_from_cur || !c.counters || (cells > 0 && (!c.instance_maps || !c.state_map)) ||
+      (P > 0 && (!c.live_id || !c.live_seen)) || (Q > 0 && !c.query_track))
     return MBV_ERR_BAD_ARG;
-  if (occ && (!occ->occlusion_counters || (P > 0 && !occ->live_held))) return MBV_ERR_BAD_ARG;
-  TrackWorkspace w = carve_track(workspace, cells, Q, P, true, occ != nullptr);
-  if (!workspace || workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
+  if (mo && (!mo->cur_from_prev || !mo->motion_counters || (P > 0 && (!mo->pos || !mo->vel)) || (Q > 0 && !mo->query_velocity)))
+    return MBV_ERR_BAD_ARG;
+  if (oc && (!oc->occlusion_counters || (P > 0 && !oc->live_held))) return MBV_ERR_BAD_ARG;
+  TrackWorkspace w = carve_track(c.workspace, cells, Q, P, mo != nullptr, oc != nullptr);
+  if (!c.workspace || c.workspace_bytes < w.bytes) return MBV_ERR_WORKSPACE;
 
-  const int64_t most = (int64_t)Q * P > cells ? (int64_t)Q * P : cells;
+  // K33a's clear covers the (Q, P) table; with the motion part it covers the advected map too
+  const int64_t most = mo && cells > (int64_t)Q * P ? cells : (int64_t)Q * P;
   int64_t clear_blocks = (most + kThreads - 1) / kThreads;
   clear_blocks = clear_blocks < 1 ? 1 : (clear_blocks > 1024 ? 1024 : clear_blocks);
   const unsigned cell_blocks = (unsigned)((cells + kThreads - 1) / kThreads);
+  const auto clear = mo ? k_track_clear<true> : k_track_clear<false>;
+  const auto count = !mo ? k_track_count<false> : (oc ? k_track_count<true, true> : k_track_count<true, false>);
+  const auto match = !mo ? k_track_match<false> : (oc ? k_track_match<true, true> : k_track_match<true, false>);
   for (int f = 0; f < F; ++f) {
-    const int32_t* imap = instance_maps + (int64_t)f * cells;
-    const uint8_t* vis = occ && occ->visibility ? occ->visibility + (int64_t)f * cells : nullptr;
-    hipLaunchKernelGGL(k_track_clear_motion, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, cells, (int)Q, (int)P,
-                       voxel, (int)max_shift, counters, vel, w.area_q, w.area_t, w.inter, w.moved, w.sum_ix, w.sum_iy, w.shift,
-                       w.hidden);
+    const int32_t* imap = c.instance_maps + (int64_t)f * cells;
+    const double* m = c.prev_from_cur + (int64_t)f * 6;
+    int32_t* query_track = c.query_track + (int64_t)f * Q;
+    const uint8_t* vis = oc && oc->visibility ? oc->visibility + (int64_t)f * cells : nullptr;
+    // the tables of a part that is absent are null in `w`
+    hipLaunchKernelGGL(clear, dim3((unsigned)clear_blocks), dim3(kThreads), 0, stream, cells, (int)Q, (int)P, c.voxel,
+                       mo ? (int)mo->max_shift : 0, c.counters, mo ? mo->vel : nullptr, w.area_q, w.area_t, w.inter, w.moved,
+                       w.sum_ix, w.sum_iy, w.shift, w.hidden);
     MBV_CHECK_LAUNCH();
     if (cells > 0) {
-      hipLaunchKernelGGL(k_track_advect, dim3(cell_blocks), dim3(kThreads), 0, stream, state_map, (int)H, (int)W, (int)P,
-                         counters, w.shift, w.moved);
-      MBV_CHECK_LAUNCH();
-      const auto count = occ ? k_track_count<true, true> : k_track_count<true, false>;
+      if (mo) {
+        hipLaunchKernelGGL(k_track_advect, dim3(cell_blocks), dim3(kThreads), 0, stream, c.state_map, (int)H, (int)W, (int)P,
+                           c.counters, w.shift, w.moved);
+        MBV_CHECK_LAUNCH();
+      }
       hipLaunchKernelGGL(count, dim3(cell_blocks), dim3(kThreads), 0, stream, imap,
-                         reinterpret_cast<const int32_t*>(w.moved), prev_from_cur + (int64_t)f * 6, (int)H, (int)W, x_lo, y_lo,
-                         voxel, (int)Q, (int)P, counters, w.warped, w.area_q, w.area_t, w.inter, w.sum_ix, w.sum_iy, vis,
-                         w.hidden);
+                         mo ? reinterpret_cast<const int32_t*>(w.moved) : c.state_map, m, (int)H, (int)W, c.x_lo, c.y_lo, c.voxel,
+                         (int)Q, (int)P, c.counters, w.warped, w.area_q, w.area_t, w.inter, w.sum_ix, w.sum_iy, vis, w.hidden);
       MBV_CHECK_LAUNCH();
     }
-    MotionArgs mo{cur_from_prev + (int64_t)f * 6, gain, gate, x_lo, y_lo, voxel, w.sum_ix, w.sum_iy, w.cq, w.pred, w.velr, pos,
-                  vel, motion_counters, query_velocity + (int64_t)f * Q * 2};
-    OcclusionArgs oc{};
-    if (occ) oc = OcclusionArgs{w.hidden, occ->live_held, occ->occlusion_counters, (int)occ->hold_num, (int)occ->hold_den,
-                                (int)occ->max_hold, vis != nullptr};
-    const auto match = occ ? k_track_match<true, true> : k_track_match<true, false>;
-    hipLaunchKernelGGL(match, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, min_iou, (int)max_age, (int)min_cells, w.area_q,
-                       w.area_t, w.inter, w.cand, live_id, live_seen, counters, query_track + (int64_t)f * Q, w.q_new, w.t_new,
-                       mo, oc);
+    MotionArgs ma{};
+    if (mo) ma = MotionArgs{mo->cur_from_prev + (int64_t)f * 6, mo->gain, mo->gate, c.x_lo, c.y_lo, c.voxel, w.sum_ix, w.sum_iy,
+                            w.cq, w.pred, w.velr, mo->pos, mo->vel, mo->motion_counters, mo->query_velocity + (int64_t)f * Q * 2};
+    OcclusionArgs oa{};
+    if (oc) oa = OcclusionArgs{w.hidden, oc->live_held, oc->occlusion_counters, (int)oc->hold_num, (int)oc->hold_den,
+                               (int)oc->max_hold, vis != nullptr};
+    hipLaunchKernelGGL(match, dim3(1), dim3(kWide), 0, stream, (int)Q, (int)P, c.min_iou, (int)c.max_age, (int)c.min_cells,
+                       w.area_q, w.area_t, w.inter, w.cand, c.live_id, c.live_seen, c.counters, query_track, w.q_new, w.t_new, ma,
+                       oa);
     MBV_CHECK_LAUNCH();
     if (cells > 0) {
       hipLaunchKernelGGL(k_track_paint, dim3(cell_blocks), dim3(kThreads), 0, stream, imap, cells, (int)Q, (int)P, w.warped,
-                         w.q_new, w.t_new, query_track + (int64_t)f * Q, state_map,
-                         track_map ? track_map + (int64_t)f * cells : nullptr);
+                         w.q_new, w.t_new, query_track, c.state_map, c.track_map ? c.track_map + (int64_t)f * cells : nullptr);
       MBV_CHECK_LAUNCH();
     }
   }
@@ -805,9 +786,29 @@ int track_frames_motion(const int32_t* instance_maps, const double* prev_from_cu
 
 }  // namespace
 
+extern "C" size_t mbv_track_frames_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
+  if (!track_sizes_supported(H, W, Q, P)) return 0;
+  return carve_track(nullptr, (int64_t)H * W, Q, P).bytes;
+}
+
 extern "C" size_t mbv_track_frames_motion_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
   if (!track_sizes_supported(H, W, Q, P)) return 0;
   return carve_track(nullptr, (int64_t)H * W, Q, P, true).bytes;
+}
+
+extern "C" size_t mbv_track_frames_occluded_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
+  if (!track_sizes_supported(H, W, Q, P)) return 0;
+  return carve_track(nullptr, (int64_t)H * W, Q, P, true, true).bytes;
+}
+
+extern "C" int mbv_track_frames(const int32_t* instance_maps, const double* prev_from_cur, int32_t F, int32_t H, int32_t W,
+                                double x_lo, double y_lo, double voxel, int32_t Q, int32_t P, double min_iou, int32_t max_age,
+                                int32_t min_cells, int32_t* state_map, int32_t* live_id, int32_t* live_seen, int32_t* counters,
+                                int32_t* query_track, int32_t* track_map, void* workspace, size_t workspace_bytes,
+                                void* stream_) {
+  return track_frames(TrackCall{instance_maps, prev_from_cur, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age, min_cells,
+                                state_map, live_id, live_seen, counters, query_track, track_map, workspace, workspace_bytes,
+                                stream_, nullptr, nullptr});
 }
 
 extern "C" int mbv_track_frames_motion(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev,
@@ -817,15 +818,10 @@ extern "C" int mbv_track_frames_motion(const int32_t* instance_maps, const doubl
                                        int32_t* counters, double* pos, double* vel, int32_t* motion_counters,
                                        int32_t* query_track, int32_t* track_map, double* query_velocity, void* workspace,
                                        size_t workspace_bytes, void* stream_) {
-  return track_frames_motion(instance_maps, prev_from_cur, cur_from_prev, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age,
-                             min_cells, gain, gate, max_shift, state_map, live_id, live_seen, counters, pos, vel,
-                             motion_counters, query_track, track_map, query_velocity, nullptr, workspace, workspace_bytes,
-                             reinterpret_cast<hipStream_t>(stream_));
-}
-
-extern "C" size_t mbv_track_frames_occluded_workspace_bytes(int32_t H, int32_t W, int32_t Q, int32_t P) {
-  if (!track_sizes_supported(H, W, Q, P)) return 0;
-  return carve_track(nullptr, (int64_t)H * W, Q, P, true, true).bytes;
+  const TrackCall::Motion mo{cur_from_prev, gain, gate, max_shift, pos, vel, motion_counters, query_velocity};
+  return track_frames(TrackCall{instance_maps, prev_from_cur, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age, min_cells,
+                                state_map, live_id, live_seen, counters, query_track, track_map, workspace, workspace_bytes,
+                                stream_, &mo, nullptr});
 }
 
 extern "C" int mbv_track_frames_occluded(const int32_t* instance_maps, const double* prev_from_cur, const double* cur_from_prev,
@@ -837,11 +833,11 @@ extern "C" int mbv_track_frames_occluded(const int32_t* instance_maps, const dou
                                          int32_t* motion_counters, int32_t* occlusion_counters, int32_t* query_track,
                                          int32_t* track_map, double* query_velocity, void* workspace, size_t workspace_bytes,
                                          void* stream_) {
-  const OcclusionCall occ{visibility, live_held, occlusion_counters, hold_num, hold_den, max_hold};
-  return track_frames_motion(instance_maps, prev_from_cur, cur_from_prev, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age,
-                             min_cells, gain, gate, max_shift, state_map, live_id, live_seen, counters, pos, vel,
-                             motion_counters, query_track, track_map, query_velocity, &occ, workspace, workspace_bytes,
-                             reinterpret_cast<hipStream_t>(stream_));
+  const TrackCall::Motion mo{cur_from_prev, gain, gate, max_shift, pos, vel, motion_counters, query_velocity};
+  const TrackCall::Occlusion oc{visibility, live_held, occlusion_counters, hold_num, hold_den, max_hold};
+  return track_frames(TrackCall{instance_maps, prev_from_cur, F, H, W, x_lo, y_lo, voxel, Q, P, min_iou, max_age, min_cells,
+                                state_map, live_id, live_seen, counters, query_track, track_map, workspace, workspace_bytes,
+                                stream_, &mo, &oc});
 }
 
 extern "C" int mbv_tube_accumulate(const int32_t* pred_track, const uint32_t* gt_word, int64_t total, const int32_t* class_lut,

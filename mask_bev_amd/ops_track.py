@@ -1,7 +1,7 @@
-"""K33a — the tracker step over consecutive BEV instance maps of one sequence, K37 — the same step with a constant-velocity
-motion model and gated re-association (off by default), and K33b — tube association, the S_assoc term of LSTQ
-(csrc/track.hip); K38b — K37's step with occlusion-aware ageing from K38a's visibility maps (off by default).  Behind ``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions are in
-include/maskbev_hip.h."""
+"""The tracker step over consecutive BEV instance maps of one sequence (csrc/track.hip) — K33a, with two optional parts, both
+off by default: K37's constant-velocity motion model and gated re-association, and K38b's occlusion-aware ageing from K38a's
+visibility maps (which runs on K37's step) — and K33b, tube association, the S_assoc term of LSTQ.  Behind
+``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions are in include/maskbev_hip.h."""
 from __future__ import annotations
 
 import math
@@ -105,11 +105,14 @@ class TrackState:
     occlusion: Optional[TrackOcclusion] = None
 
     @staticmethod
-    def fresh(h: int, w: int, max_tracks: int, device) -> 'TrackState':
+    def fresh(h: int, w: int, max_tracks: int, device, motion: bool = False, occlusion: bool = False) -> 'TrackState':
+        """``motion`` / ``occlusion``: with the fresh sub-records; ``occlusion`` implies the motion record."""
         return TrackState(torch.full((int(h), int(w)), -1, dtype=torch.int32, device=device),
                           torch.full((int(max_tracks),), -1, dtype=torch.int32, device=device),
                           torch.full((int(max_tracks),), -1, dtype=torch.int32, device=device),
-                          torch.zeros((4,), dtype=torch.int32, device=device))
+                          torch.zeros((4,), dtype=torch.int32, device=device),
+                          TrackMotion.fresh(max_tracks, device) if motion or occlusion else None,
+                          TrackOcclusion.fresh(max_tracks, device) if occlusion else None)
 
 
 @dataclass
@@ -182,10 +185,10 @@ def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state
         raise MaskBevHipError(f'track_frames: prev_from_cur must be ({f}, 2, 3) float64, got {tuple(prev_from_cur.shape)} '
                               f'{prev_from_cur.dtype}')
     q, p = int(num_queries), int(state.live_id.numel())
-    for name, x, shape in (('state_map', state.state_map, (h, w)), ('live_id', state.live_id, (p,)),
-                           ('live_seen', state.live_seen, (p,)), ('counters', state.counters, (4,))):
-        if tuple(x.shape) != shape or x.dtype != torch.int32 or x.device != dev or not x.is_contiguous():
-            raise MaskBevHipError(f'track_frames: state.{name} must be a contiguous {shape} int32 tensor on {dev}')
+    _check_fields('track_frames: state', dev, (('state_map', state.state_map, (h, w), torch.int32),
+                                               ('live_id', state.live_id, (p,), torch.int32),
+                                               ('live_seen', state.live_seen, (p,), torch.int32),
+                                               ('counters', state.counters, (4,), torch.int32)))
     if prev_from_cur.device != dev:
         raise MaskBevHipError('track_frames: tensors on different devices')
     if not (0 <= q <= p <= 1024 and h * w <= 1024 * 1024 and int(min_cells) >= 1 and int(max_age) >= 0):
@@ -196,18 +199,65 @@ def track_frames(instance_maps: torch.Tensor, prev_from_cur: torch.Tensor, state
                       torch.empty((f, h, w), dtype=torch.int32, device=dev) if track_map else None)
     if visibility is not None and occlusion is None:
         raise MaskBevHipError('track_frames: a visibility map given without occlusion settings')
-    if motion is not None or occlusion is not None:
-        return _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state, float(x_lo), float(y_lo),
-                                    float(voxel), q, p, float(min_iou), int(max_age), int(min_cells), motion, out, occlusion,
-                                    visibility)
+    step = (f, h, w, float(x_lo), float(y_lo), float(voxel), q, p, float(min_iou), int(max_age), int(min_cells))
+    rec, occ = state.motion, state.occlusion
+    if motion is not None or occlusion is not None:                     # K38b's entry is K37's: it needs the motion record too
+        if rec is None:
+            raise MaskBevHipError('track_frames: motion or occlusion settings given, but state.motion is None (TrackMotion.fresh)')
+        _need_gpu(rec.pos, rec.vel, rec.motion_counters)
+        _check_fields('track_frames: state.motion', dev, (('pos', rec.pos, (p, 2), torch.float64),
+                                                          ('vel', rec.vel, (p, 2), torch.float64),
+                                                          ('motion_counters', rec.motion_counters, (2,), torch.int32)))
+        if not float(voxel) > 0.0:
+            raise MaskBevHipError(f'track_frames: voxel {float(voxel)} > 0 expected')
+        model = (motion.gain, motion.gate_m, motion.max_shift(float(voxel))) if motion is not None else (0.0, 0.0, 0)
+        if occlusion is not None:
+            if occ is None:
+                raise MaskBevHipError('track_frames: occlusion settings given, but state.occlusion is None (TrackOcclusion.fresh)')
+            _need_gpu(occ.live_held, occ.occlusion_counters)
+            _check_fields('track_frames: state.occlusion', dev, (('live_held', occ.live_held, (p,), torch.int32),
+                                                                 ('occlusion_counters', occ.occlusion_counters, (2,), torch.int32)))
+            if visibility is not None:
+                _need_gpu(visibility)
+                if tuple(visibility.shape) != (f, h, w) or visibility.dtype != torch.uint8 or visibility.device != dev:
+                    raise MaskBevHipError(f'track_frames: visibility must be ({f}, {h}, {w}) uint8 on {dev}, got '
+                                          f'{tuple(visibility.shape)} {visibility.dtype}')
+                visibility = visibility.contiguous()
+        if cur_from_prev is None:
+            cur_from_prev = invert_transforms(prev_from_cur)
+        _need_gpu(cur_from_prev)
+        if tuple(cur_from_prev.shape) != (f, 2, 3) or cur_from_prev.dtype != torch.float64 or cur_from_prev.device != dev:
+            raise MaskBevHipError(f'track_frames: cur_from_prev must be ({f}, 2, 3) float64 on {dev}, got '
+                                  f'{tuple(cur_from_prev.shape)} {cur_from_prev.dtype}')
+        cur_from_prev = cur_from_prev.contiguous()
+        out.query_velocity = torch.empty((f, q, 2), dtype=torch.float64, device=dev)
     if f == 0:
         return out
-    ws = _workspace(lib.mbv_track_frames_workspace_bytes(h, w, q, p), dev)
-    check(lib.mbv_track_frames(_ptr(instance_maps), _ptr(prev_from_cur), f, h, w, float(x_lo), float(y_lo), float(voxel), q, p,
-                               float(min_iou), int(max_age), int(min_cells), _ptr(state.state_map), _ptr(state.live_id),
-                               _ptr(state.live_seen), _ptr(state.counters), _ptr(out.query_track), _ptr(out.track_map),
-                               _ptr(ws), ws.numel(), _stream()), 'mbv_track_frames')
+    frames = (_ptr(instance_maps), _ptr(prev_from_cur))
+    lists = (_ptr(state.state_map), _ptr(state.live_id), _ptr(state.live_seen))
+    if occlusion is not None:
+        name = 'mbv_track_frames_occluded'
+        args = frames + (_ptr(cur_from_prev), _ptr(visibility)) + step + model + occlusion.hidden_fraction + \
+            (occlusion.max_hold,) + lists + (_ptr(occ.live_held), _ptr(state.counters), _ptr(rec.pos), _ptr(rec.vel), _ptr(rec.motion_counters),
+                  _ptr(occ.occlusion_counters), _ptr(out.query_track), _ptr(out.track_map), _ptr(out.query_velocity))
+    elif motion is not None:
+        name = 'mbv_track_frames_motion'
+        args = frames + (_ptr(cur_from_prev),) + step + model + lists + (
+            _ptr(state.counters), _ptr(rec.pos), _ptr(rec.vel), _ptr(rec.motion_counters), _ptr(out.query_track),
+            _ptr(out.track_map), _ptr(out.query_velocity))
+    else:
+        name = 'mbv_track_frames'
+        args = frames + step + lists + (_ptr(state.counters), _ptr(out.query_track), _ptr(out.track_map))
+    ws = _workspace(getattr(lib, name + '_workspace_bytes')(h, w, q, p), dev)
+    check(getattr(lib, name)(*args, _ptr(ws), ws.numel(), _stream()), name)
     return out
+
+
+def _check_fields(what: str, dev, fields) -> None:
+    """Every (name, tensor, shape, dtype) of ``fields`` is a contiguous tensor of that shape and dtype on ``dev``."""
+    for name, x, shape, dt in fields:
+        if tuple(x.shape) != shape or x.dtype != dt or x.device != dev or not x.is_contiguous():
+            raise MaskBevHipError(f'{what}.{name} must be a contiguous {shape} {dt} tensor on {dev}')
 
 
 def invert_transforms(prev_from_cur: torch.Tensor) -> torch.Tensor:
@@ -219,65 +269,6 @@ def invert_transforms(prev_from_cur: torch.Tensor) -> torch.Tensor:
     n00, n01, n10, n11 = d / det, -b / det, -c / det, a / det
     return torch.stack([torch.stack([n00, n01, -(n00 * tx + n01 * ty)], dim=1),
                         torch.stack([n10, n11, -(n10 * tx + n11 * ty)], dim=1)], dim=1).contiguous()
-
-
-def _track_frames_motion(lib, instance_maps, prev_from_cur, cur_from_prev, state, x_lo, y_lo, voxel, q, p, min_iou, max_age,
-                         min_cells, motion, out, occlusion=None, visibility=None) -> TrackFrames:
-    dev = instance_maps.device
-    f, h, w = (int(v) for v in instance_maps.shape)
-    rec = state.motion
-    if rec is None:
-        raise MaskBevHipError('track_frames: motion or occlusion settings given, but state.motion is None (TrackMotion.fresh)')
-    _need_gpu(rec.pos, rec.vel, rec.motion_counters)
-    for name, x, shape, dt in (('pos', rec.pos, (p, 2), torch.float64), ('vel', rec.vel, (p, 2), torch.float64),
-                               ('motion_counters', rec.motion_counters, (2,), torch.int32)):
-        if tuple(x.shape) != shape or x.dtype != dt or x.device != dev or not x.is_contiguous():
-            raise MaskBevHipError(f'track_frames: state.motion.{name} must be a contiguous {shape} {dt} tensor on {dev}')
-    if not voxel > 0.0:
-        raise MaskBevHipError(f'track_frames: voxel {voxel} > 0 expected')
-    gain, gate, max_shift = (motion.gain, motion.gate_m, motion.max_shift(voxel)) if motion is not None else (0.0, 0.0, 0)
-    occ = state.occlusion
-    if occlusion is not None:
-        if occ is None:
-            raise MaskBevHipError('track_frames: occlusion settings given, but state.occlusion is None (TrackOcclusion.fresh)')
-        _need_gpu(occ.live_held, occ.occlusion_counters)
-        for name, x, shape in (('live_held', occ.live_held, (p,)), ('occlusion_counters', occ.occlusion_counters, (2,))):
-            if tuple(x.shape) != shape or x.dtype != torch.int32 or x.device != dev or not x.is_contiguous():
-                raise MaskBevHipError(f'track_frames: state.occlusion.{name} must be a contiguous {shape} int32 tensor on {dev}')
-        if visibility is not None:
-            _need_gpu(visibility)
-            if tuple(visibility.shape) != (f, h, w) or visibility.dtype != torch.uint8 or visibility.device != dev:
-                raise MaskBevHipError(f'track_frames: visibility must be ({f}, {h}, {w}) uint8 on {dev}, got '
-                                      f'{tuple(visibility.shape)} {visibility.dtype}')
-            visibility = visibility.contiguous()
-    if cur_from_prev is None:
-        cur_from_prev = invert_transforms(prev_from_cur)
-    _need_gpu(cur_from_prev)
-    if tuple(cur_from_prev.shape) != (f, 2, 3) or cur_from_prev.dtype != torch.float64 or cur_from_prev.device != dev:
-        raise MaskBevHipError(f'track_frames: cur_from_prev must be ({f}, 2, 3) float64 on {dev}, got '
-                              f'{tuple(cur_from_prev.shape)} {cur_from_prev.dtype}')
-    cur_from_prev = cur_from_prev.contiguous()
-    out.query_velocity = torch.empty((f, q, 2), dtype=torch.float64, device=dev)
-    if f == 0:
-        return out
-    if occlusion is not None:
-        ws = _workspace(lib.mbv_track_frames_occluded_workspace_bytes(h, w, q, p), dev)
-        num, den = occlusion.hidden_fraction
-        check(lib.mbv_track_frames_occluded(_ptr(instance_maps), _ptr(prev_from_cur), _ptr(cur_from_prev), _ptr(visibility), f, h,
-                                            w, x_lo, y_lo, voxel, q, p, min_iou, max_age, min_cells, gain, gate, max_shift, num,
-                                            den, occlusion.max_hold, _ptr(state.state_map), _ptr(state.live_id),
-                                            _ptr(state.live_seen), _ptr(occ.live_held), _ptr(state.counters), _ptr(rec.pos),
-                                            _ptr(rec.vel), _ptr(rec.motion_counters), _ptr(occ.occlusion_counters),
-                                            _ptr(out.query_track), _ptr(out.track_map), _ptr(out.query_velocity), _ptr(ws),
-                                            ws.numel(), _stream()), 'mbv_track_frames_occluded')
-        return out
-    ws = _workspace(lib.mbv_track_frames_motion_workspace_bytes(h, w, q, p), dev)
-    check(lib.mbv_track_frames_motion(_ptr(instance_maps), _ptr(prev_from_cur), _ptr(cur_from_prev), f, h, w, x_lo, y_lo, voxel,
-                                      q, p, min_iou, max_age, min_cells, gain, gate, max_shift, _ptr(state.state_map),
-                                      _ptr(state.live_id), _ptr(state.live_seen), _ptr(state.counters), _ptr(rec.pos),
-                                      _ptr(rec.vel), _ptr(rec.motion_counters), _ptr(out.query_track), _ptr(out.track_map),
-                                      _ptr(out.query_velocity), _ptr(ws), ws.numel(), _stream()), 'mbv_track_frames_motion')
-    return out
 
 
 @torch.no_grad()
@@ -296,7 +287,7 @@ def tube_accumulate(pred_track: torch.Tensor, gt_words: torch.Tensor, class_lut:
                               f'{tuple(gt_words.shape)} {gt_words.dtype}')
     if class_lut.dim() != 1 or class_lut.dtype != torch.int32:
         raise MaskBevHipError('tube_accumulate: class_lut must be a 1-d int32 table')
-    _check_tables('tube_accumulate', tables, dev)
+    _check_fields('tube_accumulate: tables', dev, _tube_fields(tables))
     if gt_words.device != dev or class_lut.device != dev:
         raise MaskBevHipError('tube_accumulate: tensors on different devices')
     n = pred_track.numel()
@@ -309,12 +300,10 @@ def tube_accumulate(pred_track: torch.Tensor, gt_words: torch.Tensor, class_lut:
     return tables
 
 
-def _check_tables(what: str, tables: TubeTables, dev) -> None:
+def _tube_fields(tables: TubeTables):
     rows, t = (tables.num_classes - 1) * tables.id_limit, tables.max_tracks
-    for name, x, shape, dt in (('gt_size', tables.gt_size, (rows,), torch.int64), ('pred_size', tables.pred_size, (t,), torch.int64),
-                               ('pair', tables.pair, (rows, t), torch.int32), ('overflow', tables.overflow, (2,), torch.int64)):
-        if tuple(x.shape) != shape or x.dtype != dt or x.device != dev or not x.is_contiguous():
-            raise MaskBevHipError(f'{what}: tables.{name} must be a contiguous {shape} {dt} tensor on {dev}')
+    return (('gt_size', tables.gt_size, (rows,), torch.int64), ('pred_size', tables.pred_size, (t,), torch.int64),
+            ('pair', tables.pair, (rows, t), torch.int32), ('overflow', tables.overflow, (2,), torch.int64))
 
 
 @torch.no_grad()
@@ -323,7 +312,7 @@ def tube_scores(tables: TubeTables) -> TubeScores:
     lib = _lib.load()
     _need_gpu(tables.gt_size, tables.pred_size, tables.pair, tables.overflow)
     dev = tables.pred_size.device
-    _check_tables('tube_scores', tables, dev)
+    _check_fields('tube_scores: tables', dev, _tube_fields(tables))
     c, rows = tables.num_classes, (tables.num_classes - 1) * tables.id_limit
     out = TubeScores(torch.empty((rows,), dtype=torch.float64, device=dev), torch.empty((c,), dtype=torch.float64, device=dev),
                      torch.empty((c,), dtype=torch.int32, device=dev))

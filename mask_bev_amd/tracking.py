@@ -94,11 +94,8 @@ class InstanceTracker:
 
     def reset(self) -> None:
         """A fresh sequence: no live track, ids from 0, and the next frame takes the identity transform."""
-        self.state = ops.TrackState.fresh(self.h, self.w, self.max_tracks, self.device)
-        if self.motion is not None or self.occlusion is not None:       # K38b's entry is K37's: it needs the record too
-            self.state.motion = ops.TrackMotion.fresh(self.max_tracks, self.device)
-        if self.occlusion is not None:
-            self.state.occlusion = ops.TrackOcclusion.fresh(self.max_tracks, self.device)
+        self.state = ops.TrackState.fresh(self.h, self.w, self.max_tracks, self.device, motion=self.motion is not None,
+                                          occlusion=self.occlusion is not None)
         self._last_pose: Optional[np.ndarray] = None
         self._started = False
 

@@ -11,71 +11,22 @@ import pytest
 import torch
 
 from tests import track_ref as R
+from tests.track_util import call, dev, same_state, walk
 from tests.util_cfg import random_scans, tiny_kwargs
 
 pytestmark = pytest.mark.gpu
-POISON = 0x5a5a5a5a
 BAD_ARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
-
-
-def _dev(a, device):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
-def _call(lib, device, state, maps, ms, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, track_map=True):
-    """mbv_track_frames on F frames into poisoned outputs and workspace; `state` (host dict) is stepped.  The state's own
-    tails (live_id / live_seen past n_live) go in as garbage too.  → (rc, query_track (F, Q), track_map (F, H, W))"""
-    from mask_bev_amd.ops_core import _ptr, _stream
-    maps, ms = np.ascontiguousarray(maps, np.int32), np.ascontiguousarray(ms, np.float64)
-    f, h, w = maps.shape
-    p = state['live_id'].shape[0]
-    n_live = int(min(max(int(state['counters'][0]), 0), p))
-    lid, seen = state['live_id'].copy(), state['live_seen'].copy()
-    lid[n_live:], seen[n_live:] = POISON, POISON
-    d = dict(sm=_dev(state['state_map'], device), lid=_dev(lid, device), seen=_dev(seen, device),
-             cnt=_dev(state['counters'], device), maps=_dev(maps, device), ms=_dev(ms, device))
-    qt = torch.full((f, max(q_num, 1)), POISON, dtype=torch.int32, device=device)
-    tm = torch.full((f, h, w), POISON, dtype=torch.int32, device=device)
-    nbytes = lib.mbv_track_frames_workspace_bytes(h, w, q_num, p)
-    ws = torch.full((max(nbytes, 256),), 0x5a, dtype=torch.uint8, device=device)
-    rc = lib.mbv_track_frames(_ptr(d['maps']), _ptr(d['ms']), f, h, w, x_lo, y_lo, voxel, q_num, p, min_iou, max_age, min_cells,
-                              _ptr(d['sm']), _ptr(d['lid']), _ptr(d['seen']), _ptr(d['cnt']), _ptr(qt),
-                              _ptr(tm) if track_map else None, _ptr(ws), ws.numel(), _stream())
-    torch.cuda.synchronize()
-    if rc == 0:
-        state['state_map'], state['live_id'] = d['sm'].cpu().numpy(), d['lid'].cpu().numpy()
-        state['live_seen'], state['counters'] = d['seen'].cpu().numpy(), d['cnt'].cpu().numpy()
-    return rc, qt.cpu().numpy()[:, :q_num].reshape(f, q_num), tm.cpu().numpy()
-
-
-def _same_state(a, b):
-    for k in ('state_map', 'live_id', 'live_seen', 'counters'):
-        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), (k, a[k], b[k])
-
-
-def _walk(lib, device, frames, h, w, x_lo, y_lo, voxel, q_num, p, min_iou, max_age, min_cells, start=None):
-    """Every frame through the kernel (F = 1) and through the restatement; everything equal after every frame."""
-    got = R.fresh_state(h, w, p) if start is None else R.copy_state(start)
-    ref = R.copy_state(got)
-    for im, m in frames:
-        rc, qt, tm = _call(lib, device, got, im[None], np.asarray(m)[None], x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells)
-        assert rc == 0
-        rqt, rtm = R.step(ref, im, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells)
-        assert qt.dtype == rqt.dtype and np.array_equal(qt[0], rqt), (qt, rqt)
-        assert np.array_equal(tm[0], rtm)
-        _same_state(got, ref)
-    return got
 
 
 def test_k33_scripted_and_constructed_scenes(device):
     from mask_bev_amd import _lib
     lib = _lib.load()
     pr = R.SCRIPT_PARAMS
-    end = _walk(lib, device, R.scripted_scene(), R.H0, R.W0, R.X_LO0, R.Y_LO0, R.VOXEL0, pr['q_num'], pr['p'], pr['min_iou'],
-                pr['max_age'], pr['min_cells'])
+    end, _ = walk(lib, device, R.scripted_scene(), R.H0, R.W0, R.X_LO0, R.Y_LO0, R.VOXEL0, pr['q_num'], pr['p'], pr['min_iou'],
+                  pr['max_age'], pr['min_cells'], entry='plain')
     assert end['counters'].tolist() == [4, 7, 6, 2]                    # by the restatement: 7 ids, 2 drops by capacity
     for frames, pr in R.constructed_cases().values():
-        _walk(lib, device, frames, 6, 8, 0.0, 0.0, 1.0, pr['q_num'], pr['p'], pr['min_iou'], pr['max_age'], pr['min_cells'])
+        walk(lib, device, frames, 6, 8, 0.0, 0.0, 1.0, pr['q_num'], pr['p'], pr['min_iou'], pr['max_age'], pr['min_cells'], entry='plain')
 
 
 @pytest.mark.parametrize('qp', [(8, 8), (4, 4)])
@@ -85,7 +36,7 @@ def test_k33_random_scenes(device, hw, qp):
     lib = _lib.load()
     for seed in range(3):
         frames, x_lo, y_lo = R.random_scene(100 * hw[0] + 10 * qp[0] + seed, hw[0], hw[1], qp[0], frames=5)
-        end = _walk(lib, device, frames, hw[0], hw[1], x_lo, y_lo, 0.5, qp[0], qp[1], 0.3, 1, 4)
+        end, _ = walk(lib, device, frames, hw[0], hw[1], x_lo, y_lo, 0.5, qp[0], qp[1], 0.3, 1, 4, entry='plain')
         assert end['counters'][1] >= 2 and end['counters'][2] == 5
 
 
@@ -99,7 +50,7 @@ def test_k33_table_limits(device):
         im = rng.integers(-1, 300, (64, 64)).astype(np.int32)
         im[8 * k:8 * k + 20, 10:30] = 7 + k                            # and one solid object that moves with the shift
         frames.append((im, np.array([[1.0, 0.0, 0.5], [0.0, 1.0, 0.0]]) if k else R.IDENTITY))
-    end = _walk(lib, device, frames, 64, 64, -16.0, -16.0, 0.5, 300, 1024, 0.05, 2, 4)
+    end, _ = walk(lib, device, frames, 64, 64, -16.0, -16.0, 0.5, 300, 1024, 0.05, 2, 4, entry='plain')
     assert end['counters'][0] > 300 and end['counters'][1] > 400
 
 
@@ -113,11 +64,11 @@ def test_k33_degenerate_frames(device):
     # the first frame of a fresh tracker under a transform that means nothing yet; then an empty map; then the scene again
     far = np.array([[1.0, 0.0, 1e6], [0.0, 1.0, -1e6]])
     nan = np.array([[np.nan, 0.0, 0.0], [0.0, np.inf, 0.0]])
-    mid = _walk(lib, device, [(scene[0][0], far), (empty, R.IDENTITY), scene[1]], *args)
+    mid, _ = walk(lib, device, [(scene[0][0], far), (empty, R.IDENTITY), scene[1]], *args, entry='plain')
     assert mid['counters'][0] > 0
     # everything mapped off the grid, and a NaN / inf transform: no match, all births, the old tracks coast
-    _walk(lib, device, [(scene[2][0], far)], *args, start=mid)
-    _walk(lib, device, [(scene[2][0], nan)], *args, start=mid)
+    walk(lib, device, [(scene[2][0], far)], *args, start=mid, entry='plain')
+    walk(lib, device, [(scene[2][0], nan)], *args, start=mid, entry='plain')
     # values out of range in the instance map and in a corrupted state: results change, addresses never
     bad_map = scene[2][0].copy()
     bad_map[::5, ::3] = q
@@ -128,13 +79,13 @@ def test_k33_degenerate_frames(device):
     broken['state_map'][1::4, ::5] = 2 ** 30
     broken['state_map'][2::4, ::5] = -9
     broken['state_map'][3::4, ::5] = int(mid['counters'][0])          # just past n_live
-    _walk(lib, device, [(bad_map, scene[2][1])], *args, start=broken)
+    walk(lib, device, [(bad_map, scene[2][1])], *args, start=broken, entry='plain')
     for n_live in (-3, p + 5):                                         # a stored n_live outside [0, P] is clamped
         odd = R.copy_state(mid)
         odd['counters'][0] = n_live
         odd['live_id'][:], odd['live_seen'][:] = np.arange(p) + 50, 1
         got, ref = R.copy_state(odd), R.copy_state(odd)
-        rc, qt, tm = _call(lib, device, got, scene[2][0][None], scene[2][1][None], *args[2:5], q, 0.3, 2, 4)
+        rc, qt, tm = call(lib, device, got, scene[2][0][None], scene[2][1][None], *args[2:5], q, 0.3, 2, 4, entry='plain')
         rqt, rtm = R.step(ref, scene[2][0], scene[2][1], *args[2:5], q, 0.3, 2, 4)
         assert rc == 0 and np.array_equal(qt[0], rqt) and np.array_equal(tm[0], rtm)
         for k in ('state_map', 'counters'):
@@ -150,28 +101,28 @@ def test_k33_frames_in_one_call_and_twice(device):
     scene, x_lo, y_lo = R.random_scene(9, h, w, q, frames=3)
     maps, ms = np.stack([f[0] for f in scene]), np.stack([f[1] for f in scene])
     one = R.fresh_state(h, w, p)
-    rc, qt, tm = _call(lib, device, one, maps, ms, x_lo, y_lo, 0.5, q, 0.3, 2, 4)
+    rc, qt, tm = call(lib, device, one, maps, ms, x_lo, y_lo, 0.5, q, 0.3, 2, 4, entry='plain')
     assert rc == 0
     three, parts = R.fresh_state(h, w, p), []
     for k in range(3):
-        rc, a, b = _call(lib, device, three, maps[k:k + 1], ms[k:k + 1], x_lo, y_lo, 0.5, q, 0.3, 2, 4)
+        rc, a, b = call(lib, device, three, maps[k:k + 1], ms[k:k + 1], x_lo, y_lo, 0.5, q, 0.3, 2, 4, entry='plain')
         assert rc == 0
         parts.append((a[0], b[0]))
-    _same_state(one, three)
+    same_state(one, three)
     assert all(np.array_equal(qt[k], parts[k][0]) and np.array_equal(tm[k], parts[k][1]) for k in range(3))
     again = R.fresh_state(h, w, p)
-    rc, qt2, tm2 = _call(lib, device, again, maps, ms, x_lo, y_lo, 0.5, q, 0.3, 2, 4)
+    rc, qt2, tm2 = call(lib, device, again, maps, ms, x_lo, y_lo, 0.5, q, 0.3, 2, 4, entry='plain')
     assert rc == 0 and qt.tobytes() == qt2.tobytes() and tm.tobytes() == tm2.tobytes()
     assert all(one[k].tobytes() == again[k].tobytes() for k in one)
     # without a track map, and the wrapper with the tracker on top: the same ids
     none = R.fresh_state(h, w, p)
-    rc, qt3, _ = _call(lib, device, none, maps, ms, x_lo, y_lo, 0.5, q, 0.3, 2, 4, track_map=False)
+    rc, qt3, _ = call(lib, device, none, maps, ms, x_lo, y_lo, 0.5, q, 0.3, 2, 4, track_map=False, entry='plain')
     assert rc == 0 and np.array_equal(qt, qt3)
-    _same_state(one, none)
+    same_state(one, none)
     from mask_bev_amd.tracking import InstanceTracker
     tracker = InstanceTracker((x_lo, x_lo + w * 0.5), (y_lo, y_lo + h * 0.5), 0.5, q, max_tracks=p, device=device)
-    ids = tracker.update(_dev(maps[:2], device), prev_from_cur=ms[:2])
-    rec = tracker.update(_dev(maps[2:], device), prev_from_cur=_dev(ms[2:], device), track_map=True)
+    ids = tracker.update(dev(maps[:2], device), prev_from_cur=ms[:2])
+    rec = tracker.update(dev(maps[2:], device), prev_from_cur=dev(ms[2:], device), track_map=True)
     assert np.array_equal(ids.cpu().numpy(), qt[:2]) and np.array_equal(rec.query_track.cpu().numpy(), qt[2:])
     assert np.array_equal(rec.track_map.cpu().numpy(), tm[2:])
     c = tracker.counters()
@@ -231,7 +182,7 @@ def test_k33_tube_tables_and_scores(device, cit):
     lut = everything[0][2]
     for pred, words, _ in everything:
         R.tube_accumulate(ref, pred, words, lut, c, i, t)
-        ops.tube_accumulate(_dev(pred, device), _dev(words.view(np.int32), device), _dev(lut, device), tables)
+        ops.tube_accumulate(dev(pred, device), dev(words.view(np.int32), device), dev(lut, device), tables)
     for k in ('gt_size', 'pred_size', 'pair', 'overflow'):
         got = getattr(tables, k).cpu().numpy()
         assert got.dtype == ref[k].dtype and np.array_equal(got, ref[k]), k
@@ -259,7 +210,7 @@ def test_k33_tube_tables_and_scores(device, cit):
     want = float(sum(exact.values(), 0) / len(exact))
     assert res['tubes'] == len(exact) and abs(res['s_assoc'] - want) <= 1e-12 * want and res['overflow'] == [0, 0]
     with pytest.raises(ops.MaskBevHipError):
-        ops.tube_accumulate(torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int32), _dev(lut, device), tables)
+        ops.tube_accumulate(torch.zeros(4, dtype=torch.int32), torch.zeros(4, dtype=torch.int32), dev(lut, device), tables)
 
 
 def test_k33_predict_track_lift_and_tubes(device):
@@ -303,7 +254,7 @@ def test_k33_predict_track_lift_and_tubes(device):
     lut = np.zeros(64, np.int32)
     lut[10], lut[0] = 1, -1
     metric = DeviceTubeAssociation(2, lut, id_limit=8, max_tracks=64)
-    metric.update(ids, _dev(words.view(np.int32), device))
+    metric.update(ids, dev(words.view(np.int32), device))
     res = metric.compute()
     exact, over = R.plain_tube(want_ids, words, lut, 2, 8, 64)
     assert over == [0, 0] and res['tubes'] == len(exact)

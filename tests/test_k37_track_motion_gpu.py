@@ -11,76 +11,13 @@ import torch
 
 from tests import track_motion_ref as M
 from tests import track_ref as R
+from tests import track_util
+from tests.track_util import call, dev, same_state, walk
 from tests.util_cfg import random_scans, tiny_kwargs
 
 pytestmark = pytest.mark.gpu
-POISON = 0x5a5a5a5a
 BAD_ARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
-INT_KEYS = ('state_map', 'live_id', 'live_seen', 'counters', 'motion_counters')
 STEP_PARAMS = {k: v for k, v in M.MOTION_PARAMS.items() if k != 'p'}          # `M.step` takes P from the state
-
-
-def _dev(a, device):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
-def _call(lib, device, state, maps, ms, ns, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, gain, gate, max_shift,
-          track_map=True):
-    """mbv_track_frames_motion on F frames into poisoned outputs and workspace; `state` (host dict) is stepped.  The tails of
-    the state's own tables (past n_live) and the reserved counter go in as garbage too.
-    → (rc, query_track (F, Q), track_map (F, H, W), query_velocity (F, Q, 2))"""
-    from mask_bev_amd.ops_core import _ptr, _stream
-    maps = np.ascontiguousarray(maps, np.int32)
-    ms, ns = np.ascontiguousarray(ms, np.float64), np.ascontiguousarray(ns, np.float64)
-    f, h, w = maps.shape
-    p = state['live_id'].shape[0]
-    n_live = int(min(max(int(state['counters'][0]), 0), p))
-    lid, seen, pos, vel = (state[k].copy() for k in ('live_id', 'live_seen', 'pos', 'vel'))
-    lid[n_live:], seen[n_live:] = POISON, POISON
-    pos[n_live:], vel[n_live:] = 1.25e7, -3.5e-3
-    mc = state['motion_counters'].copy()
-    mc[1] = POISON
-    d = dict(sm=_dev(state['state_map'], device), lid=_dev(lid, device), seen=_dev(seen, device), cnt=_dev(state['counters'], device),
-             pos=_dev(pos, device), vel=_dev(vel, device), mc=_dev(mc, device), maps=_dev(maps, device), ms=_dev(ms, device),
-             ns=_dev(ns, device))
-    qt = torch.full((f, max(q_num, 1)), POISON, dtype=torch.int32, device=device)
-    tm = torch.full((f, h, w), POISON, dtype=torch.int32, device=device)
-    qv = torch.full((f, max(q_num, 1), 2), 7.5e11, dtype=torch.float64, device=device)
-    nbytes = lib.mbv_track_frames_motion_workspace_bytes(h, w, q_num, p)
-    ws = torch.full((max(nbytes, 256),), 0x5a, dtype=torch.uint8, device=device)
-    rc = lib.mbv_track_frames_motion(_ptr(d['maps']), _ptr(d['ms']), _ptr(d['ns']), f, h, w, x_lo, y_lo, voxel, q_num, p, min_iou,
-                                     max_age, min_cells, gain, gate, max_shift, _ptr(d['sm']), _ptr(d['lid']), _ptr(d['seen']),
-                                     _ptr(d['cnt']), _ptr(d['pos']), _ptr(d['vel']), _ptr(d['mc']), _ptr(qt),
-                                     _ptr(tm) if track_map else None, _ptr(qv), _ptr(ws), ws.numel(), _stream())
-    torch.cuda.synchronize()
-    if rc == 0:
-        for key, name in (('state_map', 'sm'), ('live_id', 'lid'), ('live_seen', 'seen'), ('counters', 'cnt'), ('pos', 'pos'),
-                          ('vel', 'vel'), ('motion_counters', 'mc')):
-            state[key] = d[name].cpu().numpy()
-    return rc, qt.cpu().numpy()[:, :q_num].reshape(f, q_num), tm.cpu().numpy(), qv.cpu().numpy()[:, :q_num].reshape(f, q_num, 2)
-
-
-def _same_state(a, b):
-    for k in INT_KEYS:
-        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), (k, a[k], b[k])
-    for k in ('pos', 'vel'):
-        assert a[k].dtype == np.float64 and a[k].tobytes() == b[k].tobytes(), (k, a[k], b[k])
-
-
-def _walk(lib, device, frames, h, w, x_lo, y_lo, voxel, q_num, p, min_iou, max_age, min_cells, gain, gate, max_shift, start=None):
-    """Every frame through the kernels (F = 1) and through the restatement; everything equal after every frame."""
-    got = M.fresh_state(h, w, p) if start is None else M.copy_state(start)
-    ref = M.copy_state(got)
-    for im, m, n in frames:
-        rc, qt, tm, qv = _call(lib, device, got, im[None], np.asarray(m)[None], np.asarray(n)[None], x_lo, y_lo, voxel, q_num,
-                               min_iou, max_age, min_cells, gain, gate, max_shift)
-        assert rc == 0
-        rqt, rtm, rqv = M.step(ref, im, m, n, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, gain, gate, max_shift)
-        assert qt.dtype == rqt.dtype and np.array_equal(qt[0], rqt), (qt, rqt)
-        assert np.array_equal(tm[0], rtm)
-        assert qv.dtype == np.float64 and qv[0].tobytes() == rqv.tobytes(), (qv[0], rqv)
-        _same_state(got, ref)
-    return got
 
 
 def test_k37_scripted_moving_scene(device):
@@ -91,14 +28,14 @@ def test_k37_scripted_moving_scene(device):
     pr = M.MOTION_PARAMS
     for ego in (True, False):
         frames = M.moving_scene(ego)
-        end = _walk(lib, device, frames, M.H1, M.W1, M.X_LO1, M.Y_LO1, M.VOXEL1, **pr)
+        end, _ = walk(lib, device, frames, M.H1, M.W1, M.X_LO1, M.Y_LO1, M.VOXEL1, **pr, entry='motion')
         assert end['counters'].tolist() == [3, 3, 8, 0] and end['motion_counters'].tolist() == [2, 0]
         one = M.fresh_state(M.H1, M.W1, pr['p'])
         maps, ms, ns = (np.stack([f[k] for f in frames]) for k in range(3))
-        rc, qt, tm, qv = _call(lib, device, one, maps, ms, ns, M.X_LO1, M.Y_LO1, M.VOXEL1, pr['q_num'], pr['min_iou'], pr['max_age'],
-                               pr['min_cells'], pr['gain'], pr['gate'], pr['max_shift'])
+        rc, qt, tm, qv = call(lib, device, one, maps, ms, M.X_LO1, M.Y_LO1, M.VOXEL1, pr['q_num'], pr['min_iou'], pr['max_age'],
+                              pr['min_cells'], pr['gain'], pr['gate'], pr['max_shift'], ns=ns, entry='motion')
         assert rc == 0
-        _same_state(one, end)
+        same_state(one, end)
         ref = M.fresh_state(M.H1, M.W1, pr['p'])
         for k, (im, m, n) in enumerate(frames):
             rqt, rtm, rqv = M.step(ref, im, m, n, M.X_LO1, M.Y_LO1, M.VOXEL1, **STEP_PARAMS)
@@ -106,38 +43,22 @@ def test_k37_scripted_moving_scene(device):
         assert sorted(set(qt[qt >= 0].tolist())) == [0, 1, 2]
         # twice: bit-equal
         again = M.fresh_state(M.H1, M.W1, pr['p'])
-        rc, qt2, tm2, qv2 = _call(lib, device, again, maps, ms, ns, M.X_LO1, M.Y_LO1, M.VOXEL1, pr['q_num'], pr['min_iou'],
-                                  pr['max_age'], pr['min_cells'], pr['gain'], pr['gate'], pr['max_shift'], track_map=False)
+        rc, qt2, tm2, qv2 = call(lib, device, again, maps, ms, M.X_LO1, M.Y_LO1, M.VOXEL1, pr['q_num'], pr['min_iou'],
+                                 pr['max_age'], pr['min_cells'], pr['gain'], pr['gate'], pr['max_shift'], ns=ns, entry='motion',
+                                 track_map=False)
         assert rc == 0 and qt.tobytes() == qt2.tobytes() and qv.tobytes() == qv2.tobytes()
-        _same_state(one, again)
-
-
-def _k33_call(lib, device, state, im, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells):
-    from mask_bev_amd.ops_core import _ptr, _stream
-    h, w = im.shape
-    p = state['live_id'].shape[0]
-    d = {k: _dev(state[k], device) for k in ('state_map', 'live_id', 'live_seen', 'counters')}
-    maps, ms = _dev(im[None].astype(np.int32), device), _dev(np.asarray(m, np.float64)[None], device)
-    qt = torch.full((1, max(q_num, 1)), POISON, dtype=torch.int32, device=device)
-    tm = torch.full((1, h, w), POISON, dtype=torch.int32, device=device)
-    ws = torch.full((max(lib.mbv_track_frames_workspace_bytes(h, w, q_num, p), 256),), 0x5a, dtype=torch.uint8, device=device)
-    rc = lib.mbv_track_frames(_ptr(maps), _ptr(ms), 1, h, w, x_lo, y_lo, voxel, q_num, p, min_iou, max_age, min_cells,
-                              _ptr(d['state_map']), _ptr(d['live_id']), _ptr(d['live_seen']), _ptr(d['counters']), _ptr(qt),
-                              _ptr(tm), _ptr(ws), ws.numel(), _stream())
-    torch.cuda.synchronize()
-    assert rc == 0
-    for k in d:
-        state[k] = d[k].cpu().numpy()
-    return qt.cpu().numpy()[0, :q_num], tm.cpu().numpy()[0]
+        same_state(one, again)
 
 
 def _identity(lib, device, frames, h, w, x_lo, y_lo, voxel, q_num, p, min_iou, max_age, min_cells):
     a, b = M.fresh_state(h, w, p), R.fresh_state(h, w, p)
     for im, m in frames:
-        rc, qt, tm, qv = _call(lib, device, a, im[None], np.asarray(m)[None], M.invert(m)[None], x_lo, y_lo, voxel, q_num, min_iou,
-                               max_age, min_cells, 0.0, 0.0, 16)
+        rc, qt, tm, qv = call(lib, device, a, im[None], np.asarray(m)[None], x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells,
+                              0.0, 0.0, 16, ns=M.invert(m)[None], entry='motion')
         assert rc == 0
-        kqt, ktm = _k33_call(lib, device, b, im, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells)
+        rc, (kqt,), (ktm,) = call(lib, device, b, im[None], np.asarray(m)[None], x_lo, y_lo, voxel, q_num, min_iou, max_age,
+                                  min_cells, entry='plain')
+        assert rc == 0
         assert qt[0].tobytes() == kqt.tobytes() and tm[0].tobytes() == ktm.tobytes()
         for k in b:
             assert a[k].tobytes() == b[k].tobytes(), k
@@ -183,8 +104,8 @@ def test_k37_advect_edge_cases(device):
     lib = _lib.load()
     empty, ident = _grid({}), R.IDENTITY
     sq = lambda iy, ix: [(iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1)]
-    walk = lambda start, im, max_shift, gain=0.5: _walk(lib, device, [(im, ident, ident)], *ARGS68, 4, 4, 0.3, 2, 1, gain, 0.0,
-                                                         max_shift, start=start)
+    walk = lambda start, im, max_shift, gain=0.5: track_util.walk(lib, device, [(im, ident, ident)], *ARGS68, 4, 4, 0.3, 2, 1, gain,
+                                                                   0.0, max_shift, start=start, entry='motion')[0]
     # two tracks shifted onto the same cells: the smaller index wins, the other has no cell left; both coast
     end = walk(_hand_state(4, {0: sq(1, 0), 1: sq(1, 2)}, [(1.0, 2.0), (3.0, 2.0)], [(2.0, 0.0), (0.0, 0.0)]), empty, 4)
     assert np.array_equal(end['state_map'], _grid({0: sq(1, 2)})) and end['counters'][0] == 2
@@ -214,7 +135,8 @@ def test_k37_gate_order(device):
     from mask_bev_amd import _lib
     lib = _lib.load()
     ident = R.IDENTITY
-    walk = lambda start, im, gate, q=4: _walk(lib, device, [(im, ident, ident)], *ARGS68, q, 4, 0.3, 2, 1, 0.5, gate, 4, start=start)
+    walk = lambda start, im, gate, q=4: track_util.walk(lib, device, [(im, ident, ident)], *ARGS68, q, 4, 0.3, 2, 1, 0.5, gate, 4,
+                                                         start=start, entry='motion')[0]
     zero = [(0.0, 0.0)]
     # two queries equidistant (d2 = 4 = gate^2, accepted) from one track: the smaller q takes it
     im = _grid({1: [(2, 1)], 3: [(2, 5)]})
@@ -245,7 +167,7 @@ def test_k37_odd_grid_random_moving_scenes(device, seed):
     from mask_bev_amd import _lib
     lib = _lib.load()
     frames, x_lo, y_lo = M.random_moving_scene(40 + seed, 37, 53, 6, frames=5)
-    end = _walk(lib, device, frames, 37, 53, x_lo, y_lo, 0.5, 6, 12, 0.3, 2, 4, 0.5, 3.0, 6)
+    end, _ = walk(lib, device, frames, 37, 53, x_lo, y_lo, 0.5, 6, 12, 0.3, 2, 4, 0.5, 3.0, 6, entry='motion')
     assert end['counters'][1] >= 2 and end['counters'][2] == 5
 
 
@@ -262,7 +184,7 @@ def test_k37_table_limits(device):
         at = rng.random(im.shape) < 0.12
         im[at] = rng.integers(0, 300, int(at.sum()))
         noisy.append((im, m, n))
-    end = _walk(lib, device, noisy, 64, 64, x_lo, y_lo, 0.5, 300, 1024, 0.05, 2, 1, 0.5, 3.0, 6)
+    end, _ = walk(lib, device, noisy, 64, 64, x_lo, y_lo, 0.5, 300, 1024, 0.05, 2, 1, 0.5, 3.0, 6, entry='motion')
     assert end['counters'][0] > 300 and end['counters'][1] > 300 and end['motion_counters'][0] > 50
 
 
@@ -273,12 +195,12 @@ def test_k37_smallest_tables(device):
     # Q = P = 1: an object that moves two cells per frame: the gate takes it in frames 1 and 2 (velocity 1.0, then 1.5 cells
     # per frame, so the footprint shifted by one cell still misses it in frame 2), the overlap in frame 3
     frames = [(_grid({0: [(2, 2 * k), (3, 2 * k)]}), ident, ident) for k in range(4)]
-    end = _walk(lib, device, frames, *ARGS68, 1, 1, 0.3, 2, 1, 0.5, 3.0, 4)
+    end, _ = walk(lib, device, frames, *ARGS68, 1, 1, 0.3, 2, 1, 0.5, 3.0, 4, entry='motion')
     assert end['counters'].tolist() == [1, 1, 4, 0] and end['motion_counters'].tolist() == [2, 0]
     assert end['vel'].tolist() == [[1.75, 0.0]]
     # Q = 0: nothing is ever present; a track written by hand coasts and then dies
     start = _hand_state(2, {0: [(1, 1)]}, [(1.5, 1.5)], [(1.0, 0.0)])
-    end = _walk(lib, device, [(_grid({}), ident, ident)] * 3, *ARGS68, 0, 2, 0.3, 1, 1, 0.5, 3.0, 4, start=start)
+    end, _ = walk(lib, device, [(_grid({}), ident, ident)] * 3, *ARGS68, 0, 2, 0.3, 1, 1, 0.5, 3.0, 4, start=start, entry='motion')
     assert end['counters'].tolist() == [0, 11, 4, 0] and not end['pos'].any()
 
 
@@ -327,7 +249,7 @@ def test_k37_tracker_and_predictions_track(device):
     from mask_bev_amd.tracking import InstanceTracker, MotionSettings, cur_from_prev_2d, prev_from_cur_2d
     pr = M.MOTION_PARAMS
     frames = M.moving_scene(True)
-    maps = _dev(np.stack([f[0] for f in frames]), device)
+    maps = dev(np.stack([f[0] for f in frames]), device)
     poses = np.stack([R.pose_2d(0.8 * k, 0.0, 0.03 * k) for k in range(8)])
     settings = MotionSettings(gain=pr['gain'], gate_m=pr['gate'], max_speed=8.0)            # floor(8 / 0.5) = 16 cells
     make = lambda: InstanceTracker((M.X_LO1, M.X_LO1 + M.W1 * M.VOXEL1), (M.Y_LO1, M.Y_LO1 + M.H1 * M.VOXEL1), M.VOXEL1, pr['q_num'],
@@ -354,7 +276,7 @@ def test_k37_tracker_and_predictions_track(device):
     assert tracker.state.motion.vel.cpu().numpy().tobytes() == ref['vel'].tobytes()
     # the transforms as a device tensor: the inverse is computed on the device, the same ids
     other = make()
-    ms = _dev(np.stack([R.IDENTITY if k == 0 else prev_from_cur_2d(poses[k - 1], poses[k]) for k in range(8)]), device)
+    ms = dev(np.stack([R.IDENTITY if k == 0 else prev_from_cur_2d(poses[k - 1], poses[k]) for k in range(8)]), device)
     out = other.update(maps, prev_from_cur=ms, track_map=True)
     assert np.array_equal(out.query_track.cpu().numpy(), want) and out.query_velocity.shape == (8, pr['q_num'], 2)
     assert np.abs(out.query_velocity.cpu().numpy() - want_v).max() < 1e-9

@@ -10,87 +10,17 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_k37_track_motion_gpu as K37
 from tests import track_motion_ref as M
 from tests import track_occlusion_ref as O
 from tests import track_ref as R
 from tests import visibility_ref as V
+from tests.track_util import call, dev, same_state, walk
 from tests.util_cfg import random_scans, tiny_kwargs
 
 pytestmark = pytest.mark.gpu
-POISON = 0x5a5a5a5a
 BAD_ARG, WORKSPACE, UNSUPPORTED = -1, -2, -3
-INT_KEYS = ('state_map', 'live_id', 'live_seen', 'live_held', 'counters', 'motion_counters', 'occlusion_counters')
 STEP = {k: v for k, v in O.OCC_PARAMS.items() if k != 'p'}
 IDENT = R.IDENTITY
-
-
-def _dev(a, device):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
-def _call(lib, device, state, maps, ms, ns, vis, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, gain, gate, max_shift,
-          hold_num, hold_den, max_hold, track_map=True):
-    """mbv_track_frames_occluded on F frames into poisoned outputs and workspace; `state` (host dict) is stepped.  The tails
-    of the state's own tables (past n_live) and the reserved counters go in as garbage too.  `vis` (F, H, W) uint8 or None.
-    → (rc, query_track (F, Q), track_map (F, H, W), query_velocity (F, Q, 2))"""
-    from mask_bev_amd.ops_core import _ptr, _stream
-    maps = np.ascontiguousarray(maps, np.int32)
-    ms, ns = np.ascontiguousarray(ms, np.float64), np.ascontiguousarray(ns, np.float64)
-    f, h, w = maps.shape
-    p = state['live_id'].shape[0]
-    n_live = int(min(max(int(state['counters'][0]), 0), p))
-    lid, seen, held, pos, vel = (state[k].copy() for k in ('live_id', 'live_seen', 'live_held', 'pos', 'vel'))
-    lid[n_live:], seen[n_live:], held[n_live:] = POISON, POISON, POISON
-    pos[n_live:], vel[n_live:] = 1.25e7, -3.5e-3
-    mc, oc = state['motion_counters'].copy(), state['occlusion_counters'].copy()
-    mc[1], oc[1] = POISON, POISON
-    d = dict(sm=_dev(state['state_map'], device), lid=_dev(lid, device), seen=_dev(seen, device), held=_dev(held, device),
-             cnt=_dev(state['counters'], device), pos=_dev(pos, device), vel=_dev(vel, device), mc=_dev(mc, device),
-             oc=_dev(oc, device), maps=_dev(maps, device), ms=_dev(ms, device), ns=_dev(ns, device))
-    d_vis = None if vis is None else _dev(np.ascontiguousarray(vis, np.uint8), device)
-    qt = torch.full((f, max(q_num, 1)), POISON, dtype=torch.int32, device=device)
-    tm = torch.full((f, h, w), POISON, dtype=torch.int32, device=device)
-    qv = torch.full((f, max(q_num, 1), 2), 7.5e11, dtype=torch.float64, device=device)
-    nbytes = lib.mbv_track_frames_occluded_workspace_bytes(h, w, q_num, p)
-    ws = torch.full((max(nbytes, 256),), 0x5a, dtype=torch.uint8, device=device)
-    rc = lib.mbv_track_frames_occluded(_ptr(d['maps']), _ptr(d['ms']), _ptr(d['ns']), _ptr(d_vis), f, h, w, x_lo, y_lo, voxel, q_num,
-                                       p, min_iou, max_age, min_cells, gain, gate, max_shift, hold_num, hold_den, max_hold,
-                                       _ptr(d['sm']), _ptr(d['lid']), _ptr(d['seen']), _ptr(d['held']), _ptr(d['cnt']),
-                                       _ptr(d['pos']), _ptr(d['vel']), _ptr(d['mc']), _ptr(d['oc']), _ptr(qt),
-                                       _ptr(tm) if track_map else None, _ptr(qv), _ptr(ws), ws.numel(), _stream())
-    torch.cuda.synchronize()
-    if rc == 0:
-        for key, name in (('state_map', 'sm'), ('live_id', 'lid'), ('live_seen', 'seen'), ('live_held', 'held'), ('counters', 'cnt'),
-                          ('pos', 'pos'), ('vel', 'vel'), ('motion_counters', 'mc'), ('occlusion_counters', 'oc')):
-            state[key] = d[name].cpu().numpy()
-    return rc, qt.cpu().numpy()[:, :q_num].reshape(f, q_num), tm.cpu().numpy(), qv.cpu().numpy()[:, :q_num].reshape(f, q_num, 2)
-
-
-def _same_state(a, b):
-    for k in INT_KEYS:
-        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), (k, a[k], b[k])
-    for k in ('pos', 'vel'):
-        assert a[k].dtype == np.float64 and a[k].tobytes() == b[k].tobytes(), (k, a[k], b[k])
-
-
-def _walk(lib, device, frames, h, w, x_lo, y_lo, voxel, p, start=None, **pr):
-    """Every frame through the kernels (F = 1) and through the restatement; everything equal after every frame.  → (the final
-    state, the (Q) query_track of every frame)."""
-    got = O.fresh_state(h, w, p) if start is None else O.copy_state(start)
-    ref = O.copy_state(got)
-    tracks = []
-    for im, m, n, vis in frames:
-        rc, qt, tm, qv = _call(lib, device, got, im[None], np.asarray(m)[None], np.asarray(n)[None], None if vis is None else vis[None],
-                               x_lo, y_lo, voxel, **pr)
-        assert rc == 0
-        rqt, rtm, rqv = O.step(ref, im, m, n, vis, x_lo, y_lo, voxel, **pr)
-        assert qt.dtype == rqt.dtype and np.array_equal(qt[0], rqt), (qt, rqt)
-        assert np.array_equal(tm[0], rtm)
-        assert qv.dtype == np.float64 and qv[0].tobytes() == rqv.tobytes(), (qv[0], rqv)
-        _same_state(got, ref)
-        tracks.append(qt[0].copy())
-    return got, tracks
 
 
 @pytest.fixture(scope='module')
@@ -104,7 +34,7 @@ def test_k38b_random_walk(lib, device, motion):
     """12 frames, 48 x 40, Q = 8, P = 16, random visibility bytes, a turning and moving ego."""
     frames, x_lo, y_lo = O.random_walk(380)
     pr = dict(STEP, **({} if motion else dict(gain=0.0, gate=0.0)))
-    end, _ = _walk(lib, device, frames, 48, 40, x_lo, y_lo, 0.5, O.OCC_PARAMS['p'], **pr)
+    end, _ = walk(lib, device, frames, 48, 40, x_lo, y_lo, 0.5, p=O.OCC_PARAMS['p'], entry='occluded', **pr)
     assert end['counters'][2] == 12 and end['occlusion_counters'][0] > 0 and end['occlusion_counters'][1] == 0
 
 
@@ -120,15 +50,17 @@ def test_k38b_identity_where_nothing_may_be_held(lib, device):
         a0, c = O.fresh_state(48, 40, 16), R.fresh_state(48, 40, 16)
         for im, m, n, vis in frames:
             v = None if off == 'no map' else vis[None]
-            rc, qt, tm, qv = _call(lib, device, a, im[None], m[None], n[None], v, x_lo, y_lo, 0.5, **pr)
-            rc2, qt2, tm2, qv2 = K37._call(lib, device, b, im[None], m[None], n[None], x_lo, y_lo, 0.5, **k37)
+            rc, qt, tm, qv = call(lib, device, a, im[None], m[None], x_lo, y_lo, 0.5, ns=n[None], vis=v, entry='occluded', **pr)
+            rc2, qt2, tm2, qv2 = call(lib, device, b, im[None], m[None], x_lo, y_lo, 0.5, ns=n[None], entry='motion', **k37)
             assert rc == 0 and rc2 == 0
             assert qt.tobytes() == qt2.tobytes() and tm.tobytes() == tm2.tobytes() and qv.tobytes() == qv2.tobytes()
             for key in b:
                 assert a[key].tobytes() == b[key].tobytes(), (off, key)
             assert not a['live_held'].any() and not a['occlusion_counters'].any()
-            rc, qt, tm, qv = _call(lib, device, a0, im[None], m[None], n[None], v, x_lo, y_lo, 0.5, **dict(pr, gain=0.0, gate=0.0))
-            kqt, ktm = K37._k33_call(lib, device, c, im, m, x_lo, y_lo, 0.5, **k33)
+            rc, qt, tm, qv = call(lib, device, a0, im[None], m[None], x_lo, y_lo, 0.5, ns=n[None], vis=v, entry='occluded',
+                                  **dict(pr, gain=0.0, gate=0.0))
+            rc3, (kqt,), (ktm,) = call(lib, device, c, im[None], m[None], x_lo, y_lo, 0.5, entry='plain', **k33)
+            assert rc3 == 0
             assert rc == 0 and qt[0].tobytes() == kqt.tobytes() and tm[0].tobytes() == ktm.tobytes()
             for key in c:
                 assert a0[key].tobytes() == c[key].tobytes(), (off, key)
@@ -148,14 +80,14 @@ def test_k38b_scenario_a_hidden_object_keeps_its_id(lib, device):
     """Present in frames 0 – 2, absent in 3 – 7 with its footprint's visibility 0 and max_age = 2, back in frame 8: the same
     id.  The same maps through mbv_track_frames_motion give a new one."""
     frames = O.gap_scene(False)
-    end, tracks = _walk(lib, device, frames, *ARGS2, 8, **GAP)
+    end, tracks = walk(lib, device, frames, *ARGS2, p=8, entry='occluded', **GAP)
     assert _first_object(tracks) == [1, 1, 1, None, None, None, None, None, 1]
     assert end['occlusion_counters'].tolist() == [5, 0] and end['counters'].tolist() == [2, 2, 9, 0]
     state = M.fresh_state(O.H2, O.W2, 8)
     k37 = {k: v for k, v in GAP.items() if k not in ('hold_num', 'hold_den', 'max_hold')}
     plain = []
     for im, m, n, _ in frames:
-        rc, qt, _, _ = K37._call(lib, device, state, im[None], m[None], n[None], 0.0, 0.0, 1.0, **k37)
+        rc, qt, _, _ = call(lib, device, state, im[None], m[None], 0.0, 0.0, 1.0, ns=n[None], entry='motion', **k37)
         assert rc == 0
         plain.append(qt[0])
     assert _first_object(plain) == [1, 1, 1, None, None, None, None, None, 2] and state['counters'].tolist() == [2, 3, 9, 0]
@@ -164,12 +96,14 @@ def test_k38b_scenario_a_hidden_object_keeps_its_id(lib, device):
 def test_k38b_scenario_b_seen_empty_footprint_dies(lib, device):
     """The same, the footprint PASSED while the object is absent: the track dies exactly as in K33a."""
     frames = O.gap_scene(True)
-    end, tracks = _walk(lib, device, frames, *ARGS2, 8, **GAP)
+    end, tracks = walk(lib, device, frames, *ARGS2, p=8, entry='occluded', **GAP)
     assert _first_object(tracks) == [1, 1, 1, None, None, None, None, None, 2]
     assert end['occlusion_counters'].tolist() == [0, 0] and end['counters'].tolist() == [2, 3, 9, 0]
     k33 = R.fresh_state(O.H2, O.W2, 8)
     for k, (im, m, _, _) in enumerate(frames):
-        kqt, _ = K37._k33_call(lib, device, k33, im, m, 0.0, 0.0, 1.0, 8, GAP['min_iou'], GAP['max_age'], GAP['min_cells'])
+        rc, (kqt,), _ = call(lib, device, k33, im[None], m[None], 0.0, 0.0, 1.0, 8, GAP['min_iou'], GAP['max_age'], GAP['min_cells'],
+                             entry='plain')
+        assert rc == 0
         assert np.array_equal(kqt, tracks[k])
     for key in k33:
         assert np.array_equal(end[key], k33[key]), key
@@ -177,9 +111,9 @@ def test_k38b_scenario_b_seen_empty_footprint_dies(lib, device):
 
 def test_k38b_max_hold_reached_mid_gap(lib, device):
     frames = O.gap_scene(False)
-    end, tracks = _walk(lib, device, frames, *ARGS2, 8, **dict(GAP, max_hold=2))     # held in 3 and 4, aged in 5 and 6, gone in 7
+    end, tracks = walk(lib, device, frames, *ARGS2, p=8, entry='occluded', **dict(GAP, max_hold=2))     # held in 3 and 4, aged in 5 and 6, gone in 7
     assert _first_object(tracks)[-1] == 2 and end['occlusion_counters'].tolist() == [2, 0]
-    end, tracks = _walk(lib, device, frames, *ARGS2, 8, **dict(GAP, max_hold=3))     # held in 3 – 5, aged in 6 and 7, back in 8
+    end, tracks = walk(lib, device, frames, *ARGS2, p=8, entry='occluded', **dict(GAP, max_hold=3))     # held in 3 – 5, aged in 6 and 7, back in 8
     assert _first_object(tracks)[-1] == 1 and end['occlusion_counters'].tolist() == [3, 0]
 
 
@@ -212,7 +146,7 @@ def test_k38b_fraction_boundary(lib, device):
             assert (hidden * den == area * num) == held
             vis = np.full((O.H2, O.W2), 3, np.uint8)
             vis[cells[:hidden, 0], cells[:hidden, 1]] = 0
-            end, _ = _walk(lib, device, [(EMPTY, IDENT, IDENT, vis)], *ARGS2, 4, start=start, **dict(GAP4, hold_num=num, hold_den=den))
+            end, _ = walk(lib, device, [(EMPTY, IDENT, IDENT, vis)], *ARGS2, p=4, entry='occluded', start=start, **dict(GAP4, hold_num=num, hold_den=den))
             assert end['occlusion_counters'].tolist() == [int(held), 0] and end['counters'][0] == int(held)
             assert end['live_held'][0] == int(held) and end['live_seen'][0] == (3 if held else -1)
 
@@ -222,10 +156,10 @@ def test_k38b_footprint_warped_off_the_grid_is_not_held(lib, device):
     start = _hand_state(4, {0: O.FOOT}, frame=5, seen=2)
     far = np.array([[1.0, 0.0, 100.0], [0.0, 1.0, 0.0]])
     vis = np.zeros((O.H2, O.W2), np.uint8)
-    end, _ = _walk(lib, device, [(EMPTY, far, M.invert(far), vis)], *ARGS2, 4, start=start, **GAP4)
+    end, _ = walk(lib, device, [(EMPTY, far, M.invert(far), vis)], *ARGS2, p=4, entry='occluded', start=start, **GAP4)
     assert end['occlusion_counters'].tolist() == [0, 0] and end['counters'].tolist() == [0, 11, 6, 0]
     # the same frame without the jump holds it
-    end, _ = _walk(lib, device, [(EMPTY, IDENT, IDENT, vis)], *ARGS2, 4, start=start, **GAP4)
+    end, _ = walk(lib, device, [(EMPTY, IDENT, IDENT, vis)], *ARGS2, p=4, entry='occluded', start=start, **GAP4)
     assert end['occlusion_counters'].tolist() == [1, 0] and end['counters'].tolist() == [1, 11, 6, 0]
 
 
@@ -238,7 +172,7 @@ def test_k38b_held_tracks_fill_the_list_and_are_dropped(lib, device):
     for q in range(3):
         im[2 + 4 * q:5 + 4 * q, 12:16] = q
     vis = np.zeros((O.H2, O.W2), np.uint8)
-    end, tracks = _walk(lib, device, [(im, IDENT, IDENT, vis)], *ARGS2, 4, start=start, **dict(GAP, q_num=3))
+    end, tracks = walk(lib, device, [(im, IDENT, IDENT, vis)], *ARGS2, p=4, entry='occluded', start=start, **dict(GAP, q_num=3))
     assert end['counters'].tolist() == [4, 17, 6, 3] and end['occlusion_counters'].tolist() == [4, 0]
     assert end['live_id'].tolist() == [14, 15, 16, 10] and end['live_held'].tolist() == [0, 0, 0, 1]
     assert tracks[0].tolist() == [14, 15, 16]
@@ -249,7 +183,7 @@ def test_k38b_held_track_coasts_with_the_motion_model(lib, device):
     start = _hand_state(4, {0: O.FOOT}, frame=5, seen=2, vel=[(1.0, -1.0)])
     vis = np.zeros((O.H2, O.W2), np.uint8)
     pr = dict(GAP4, gain=0.5, gate=2.0, max_shift=4)
-    end, _ = _walk(lib, device, [(EMPTY, IDENT, IDENT, vis)] * 3, *ARGS2, 4, start=start, **pr)
+    end, _ = walk(lib, device, [(EMPTY, IDENT, IDENT, vis)] * 3, *ARGS2, p=4, entry='occluded', start=start, **pr)
     want = np.full((O.H2, O.W2), -1, np.int32)
     want[1:5, 9:14] = 0                                                  # rows 4 – 7 up three, columns 6 – 10 right three
     assert np.array_equal(end['state_map'], want)
@@ -259,16 +193,16 @@ def test_k38b_held_track_coasts_with_the_motion_model(lib, device):
 
 def test_k38b_five_frames_in_one_call(lib, device):
     frames, x_lo, y_lo = O.random_walk(381, frames=5)
-    end, tracks = _walk(lib, device, frames, 48, 40, x_lo, y_lo, 0.5, 16, **STEP)
+    end, tracks = walk(lib, device, frames, 48, 40, x_lo, y_lo, 0.5, p=16, entry='occluded', **STEP)
     one = O.fresh_state(48, 40, 16)
     maps, ms, ns, vis = (np.stack([f[k] for f in frames]) for k in range(4))
-    rc, qt, tm, qv = _call(lib, device, one, maps, ms, ns, vis, x_lo, y_lo, 0.5, **STEP)
+    rc, qt, tm, qv = call(lib, device, one, maps, ms, x_lo, y_lo, 0.5, ns=ns, vis=vis, entry='occluded', **STEP)
     assert rc == 0 and np.array_equal(qt, np.stack(tracks))
-    _same_state(one, end)
+    same_state(one, end)
     again = O.fresh_state(48, 40, 16)
-    rc, qt2, _, qv2 = _call(lib, device, again, maps, ms, ns, vis, x_lo, y_lo, 0.5, track_map=False, **STEP)
+    rc, qt2, _, qv2 = call(lib, device, again, maps, ms, x_lo, y_lo, 0.5, ns=ns, vis=vis, entry='occluded', track_map=False, **STEP)
     assert rc == 0 and qt.tobytes() == qt2.tobytes() and qv.tobytes() == qv2.tobytes()
-    _same_state(one, again)
+    same_state(one, again)
 
 
 def test_k38b_error_codes(lib, device):
@@ -305,9 +239,9 @@ def test_k38b_tracker_and_predictions_track(lib, device):
     from mask_bev_amd.predict import Predictions
     from mask_bev_amd.tracking import InstanceTracker, OcclusionSettings
     frames = O.gap_scene(False)
-    _, want = _walk(lib, device, frames, *ARGS2, 8, **GAP)
+    _, want = walk(lib, device, frames, *ARGS2, p=8, entry='occluded', **GAP)
     want = np.stack(want)
-    maps, vis = _dev(np.stack([f[0] for f in frames]), device), _dev(np.stack([f[3] for f in frames]), device)
+    maps, vis = dev(np.stack([f[0] for f in frames]), device), dev(np.stack([f[3] for f in frames]), device)
     make = lambda **kw: InstanceTracker((0.0, float(O.W2)), (0.0, float(O.H2)), 1.0, 8, max_tracks=8, min_iou=GAP['min_iou'],
                                         max_age=GAP['max_age'], min_cells=GAP['min_cells'], device=device, **kw)
     tracker = make(occlusion=OcclusionSettings(hidden_fraction=(1, 2), max_hold=10))

@@ -1,15 +1,14 @@
 """K37 restated: the tracker step with the constant-velocity motion model and the gated second stage, from the words of
-include/maskbev_hip.h — the yardstick of tests/test_k37_track_motion_gpu.py.  `step` is the numpy version (it shares K33a's
-warp and candidate order with tests/track_ref.py); `plain_advect`, `plain_centroids` and `plain_gate` restate the three new
-pieces independently in plain loops (the gate order with exact fractions).  tests/test_track_motion_cpu.py holds them
-against each other.  Nothing here imports the package."""
-import functools
+include/maskbev_hip.h — the yardstick of tests/test_k37_track_motion_gpu.py.  The frame itself is tests/track_ref.py's `step`
+with its motion part, which takes `advect`, `centroids` and `finite_or_zero` from here; `plain_advect`, `plain_centroids` and
+`plain_gate` restate the three new pieces independently in plain loops (the gate order with exact fractions).
+tests/test_track_motion_cpu.py holds them against each other.  Nothing here imports the package."""
 import math
 from fractions import Fraction
 
 import numpy as np
 
-from tests.track_ref import IDENTITY, _before, pose_2d, prev_from_cur, render, warp
+from tests.track_ref import IDENTITY, pose_2d, prev_from_cur, render
 from tests import track_ref as R
 
 F64 = np.float64
@@ -74,122 +73,10 @@ def finite_or_zero(v):
 
 def step(state, instance_map, m, n, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, gain, gate, max_shift,
          log=None):
-    """One frame of K37 on `state` (changed in place).  → (query_track (Q) int32, track_map (H, W) int32, query_velocity
-    (Q, 2) f64).  `log`, a dict, receives the frame's intermediate tables."""
-    sm, live_id, live_seen, counters = state['state_map'], state['live_id'], state['live_seen'], state['counters']
-    pos, vel = state['pos'], state['vel']
-    h, w = sm.shape
-    p = live_id.shape[0]
-    n_live = int(min(max(int(counters[0]), 0), p))
-    next_id, frame, dropped = int(counters[1]), int(counters[2]), int(counters[3])
-    n = np.asarray(n, F64).reshape(2, 3)
-    gain, gate, voxel = F64(gain), F64(gate), F64(voxel)
-    # 0. advect; 1. warp
-    moved = advect(sm, n_live, vel, voxel, max_shift)
-    warped = warp(moved, n_live, m, x_lo, y_lo, voxel)
-    # 2. count
-    im = instance_map.astype(np.int64)
-    im = np.where((im >= 0) & (im < q_num), im, -1)
-    area_q = np.bincount(im[im >= 0], minlength=q_num).astype(np.int64)
-    area_t = np.bincount(warped[warped >= 0], minlength=p).astype(np.int64)
-    both = (im >= 0) & (warped >= 0)
-    inter = np.bincount(im[both] * p + warped[both], minlength=q_num * p).reshape(q_num, p).astype(np.int64)
-    present = area_q >= min_cells
-    c_q = centroids(im, area_q, x_lo, y_lo, voxel)
-    # 3. match
-    cands = []
-    for q, t in zip(*np.nonzero(inter)):
-        if not present[q]:
-            continue
-        k = int(inter[q, t])
-        u = int(area_q[q] + area_t[t] - k)
-        if F64(k) / F64(u) >= F64(min_iou):
-            cands.append((k, u, int(q), int(t)))
-    cands.sort(key=functools.cmp_to_key(_before))
-    q_match, t_taken = {}, set()
-    for k, u, q, t in cands:
-        if q in q_match or t in t_taken:
-            continue
-        q_match[q] = t
-        t_taken.add(t)
-    # 3b. gate
-    with np.errstate(all='ignore'):
-        a = pos[:n_live] + vel[:n_live]
-        pred = np.stack([(n[0, 0] * a[:, 0] + n[0, 1] * a[:, 1]) + n[0, 2],
-                         (n[1, 0] * a[:, 0] + n[1, 1] * a[:, 1]) + n[1, 2]], axis=1).reshape(n_live, 2)
-        velr = np.stack([n[0, 0] * vel[:n_live, 0] + n[0, 1] * vel[:n_live, 1],
-                         n[1, 0] * vel[:n_live, 0] + n[1, 1] * vel[:n_live, 1]], axis=1).reshape(n_live, 2)
-    gated, open_q, open_t, gate_taken = 0, [], [], []
-    if gate > 0 and n_live > 0:
-        open_q = [q for q in range(q_num) if present[q] and q not in q_match]
-        open_t = [t for t in range(n_live) if t not in t_taken]
-        pairs = []
-        with np.errstate(all='ignore'):
-            g2 = gate * gate
-            for q in open_q:
-                dx, dy = c_q[q, 0] - pred[open_t, 0], c_q[q, 1] - pred[open_t, 1]
-                d2 = dx * dx + dy * dy
-                pairs += [(float(d2[k]), q, t) for k, t in enumerate(open_t) if d2[k] <= g2]
-        pairs.sort()
-        for _, q, t in pairs:
-            if q in q_match or t in t_taken:
-                continue
-            q_match[q] = t
-            t_taken.add(t)
-            gate_taken.append((q, t))
-            gated += 1
-    if log is not None:
-        log.update(moved=moved, c_q=c_q, area_q=area_q, pred=pred, velr=velr, open_q=open_q, open_t=open_t, gate_taken=gate_taken,
-                   gated=gated)
-    # 4. update
-    new_id, new_seen = np.full((p,), -1, np.int32), np.full((p,), -1, np.int32)
-    new_pos, new_vel = np.zeros((p, 2), F64), np.zeros((p, 2), F64)
-    q_new, t_new = np.full((q_num,), -1, np.int64), np.full((p,), -1, np.int64)
-    query_track = np.full((q_num,), -1, np.int32)
-    query_velocity = np.zeros((q_num, 2), F64)
-    n_new = 0
-    for q in range(q_num):
-        if not present[q]:
-            continue
-        if q in q_match:
-            t = q_match[q]
-            gid = int(live_id[t])
-            with np.errstate(all='ignore'):
-                v = finite_or_zero(velr[t] + gain * (c_q[q] - pred[t]))
-        else:
-            gid = next_id
-            next_id += 1
-            v = np.zeros((2,), F64)
-        new_id[n_new], new_seen[n_new] = gid, frame
-        new_pos[n_new], new_vel[n_new] = c_q[q], v
-        query_velocity[q] = v
-        q_new[q] = n_new
-        query_track[q] = gid
-        n_new += 1
-    for t in range(n_live):
-        if t in t_taken:
-            continue
-        if frame - int(live_seen[t]) <= max_age:
-            if n_new < p:
-                new_id[n_new], new_seen[n_new] = live_id[t], live_seen[t]
-                new_pos[n_new], new_vel[n_new] = pred[t], finite_or_zero(velr[t])
-                t_new[t] = n_new
-                n_new += 1
-            else:
-                dropped += 1
-    present, q_new, of_query = np.append(present, False), np.append(q_new, -1), np.append(query_track, -1)   # Q = 0 indexes too
-    pres_cell = (im >= 0) & present[np.maximum(im, 0)]
-    from_q = q_new[np.maximum(im, 0)]
-    from_t = np.where(warped >= 0, t_new[np.maximum(warped, 0)], -1)
-    sm[...] = np.where(pres_cell, from_q, from_t).astype(np.int32)
-    track_map = np.where(pres_cell, of_query[np.maximum(im, 0)], -1).astype(np.int32)
-    live_id[...] = new_id
-    live_seen[...] = new_seen
-    pos[...] = new_pos
-    vel[...] = new_vel
-    counters[...] = np.array([n_new, next_id, frame + 1, dropped], np.int64).astype(np.int32)
-    state['motion_counters'][...] = np.array([int(state['motion_counters'][0]) + gated, 0], np.int64).astype(np.int32)
-    return query_track, track_map, query_velocity
+    """One frame of K37 on `state` (changed in place): tests/track_ref.py's step with the motion part.  → (query_track (Q)
+    int32, track_map (H, W) int32, query_velocity (Q, 2) f64).  `log`, a dict, receives the frame's intermediate tables."""
+    return R.step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells,
+                  motion=(n, gain, gate, max_shift), tables=log)
 
 
 # ---- the new pieces once more, in plain loops -------------------------------------------------------------------------------

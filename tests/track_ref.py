@@ -1,7 +1,10 @@
 """K33 restated: the tracker step (K33a) and tube association (K33b) from the words of include/maskbev_hip.h — the yardstick of
 tests/test_k33_track_gpu.py.  Two versions of each: a numpy one (vectorised warp and counts, the match with i64
 cross-multiplication), and an independent plain-loop one (`plain_*`) that orders the candidates and sums S_assoc with
-`fractions.Fraction`.  tests/test_track_cpu.py holds them against each other.  Nothing here imports the package."""
+`fractions.Fraction`.  tests/test_track_cpu.py holds them against each other.  `step` is the ONLY restatement of the frame:
+its optional `motion` and `occlusion` parts make it K37's and K38b's step, the yardstick of tests/test_k37_track_motion_gpu.py
+and tests/test_k38_track_occlusion_gpu.py too (tests/track_motion_ref.py and tests/track_occlusion_ref.py hold the pieces, the
+plain-loop second opinions and the scenes).  Nothing here imports the package."""
 import functools
 import math
 from fractions import Fraction
@@ -48,15 +51,30 @@ def _before(a, b):
     return -1 if (a[2], a[3]) < (b[2], b[3]) else 1
 
 
-def step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, log=None):
-    """One frame of K33a on `state` (changed in place).  Returns (query_track (Q) int32, track_map (H, W) int32).  `log`, a
-    list, receives the events of the frame as tuples."""
+def step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells, log=None, motion=None, occlusion=None,
+         tables=None):
+    """One frame of the tracker on `state` (changed in place): the only restatement of the frame.  With neither option it is
+    K33a's step and returns (query_track (Q) int32, track_map (H, W) int32).  `motion` = (n, gain, gate, max_shift) adds K37's
+    steps 0 and 3b and the update of `pos` / `vel` / `motion_counters`, and a third return value, query_velocity (Q, 2) f64;
+    its pieces are tests/track_motion_ref.py's.  `occlusion` = (visibility (H, W) uint8 or None, hold_num, hold_den, max_hold),
+    with `motion` only, adds K38b's hidden count and the hold of step 4, on `live_held` / `occlusion_counters`.  `log`, a list,
+    receives the events of the frame as tuples; `tables`, a dict, the frame's intermediate tables."""
     sm, live_id, live_seen, counters = state['state_map'], state['live_id'], state['live_seen'], state['counters']
     h, w = sm.shape
     p = live_id.shape[0]
     n_live = int(min(max(int(counters[0]), 0), p))
     next_id, frame, dropped = int(counters[1]), int(counters[2]), int(counters[3])
-    warped = warp(sm, n_live, m, x_lo, y_lo, voxel)
+    assert occlusion is None or motion is not None, 'K38b runs on K37\'s step'
+    # 0. advect (K37); 1. warp
+    source = sm
+    if motion is not None:
+        from tests import track_motion_ref as M                    # it imports this module: not at the top
+        n, gain, gate, max_shift = motion
+        n, gain, gate = np.asarray(n, np.float64).reshape(2, 3), np.float64(gain), np.float64(gate)
+        pos, vel = state['pos'], state['vel']
+        source = moved = M.advect(sm, n_live, vel, np.float64(voxel), max_shift)
+    warped = warp(source, n_live, m, x_lo, y_lo, voxel)
+    # 2. count; K38b: the hidden cells of every warped footprint
     im = instance_map.astype(np.int64)
     im = np.where((im >= 0) & (im < q_num), im, -1)
     area_q = np.bincount(im[im >= 0], minlength=q_num).astype(np.int64)
@@ -64,25 +82,63 @@ def step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min
     both = (im >= 0) & (warped >= 0)
     inter = np.bincount(im[both] * p + warped[both], minlength=q_num * p).reshape(q_num, p).astype(np.int64)
     present = area_q >= min_cells
+    if occlusion is not None:
+        visibility, hold_num, hold_den, max_hold = occlusion
+        live_held = state['live_held']
+        hidden = np.zeros((p,), np.int64)
+        if visibility is not None:
+            unseen = (warped >= 0) & (np.asarray(visibility) == 0)
+            hidden = np.bincount(warped[unseen], minlength=p).astype(np.int64)
+    # 3. match
     cands = []
     for q, t in zip(*np.nonzero(inter)):
         if not present[q]:
             continue
-        n = int(inter[q, t])
-        u = int(area_q[q] + area_t[t] - n)
-        if np.float64(n) / np.float64(u) >= np.float64(min_iou):
-            cands.append((n, u, int(q), int(t)))
+        k = int(inter[q, t])
+        u = int(area_q[q] + area_t[t] - k)
+        if np.float64(k) / np.float64(u) >= np.float64(min_iou):
+            cands.append((k, u, int(q), int(t)))
     cands.sort(key=functools.cmp_to_key(_before))
     q_match, t_taken = {}, set()
-    for k, (n, u, q, t) in enumerate(cands):
+    for i, (k, u, q, t) in enumerate(cands):
         if q in q_match or t in t_taken:
             continue
         q_match[q] = t
         t_taken.add(t)
         if log is not None:
-            tied = [c for c in cands if c is not cands[k] and c[0] * u == n * c[1] and (c[2] == q or c[3] == t)]
-            log.append(('match', frame, q, t, int(live_id[t]), n, u, int(live_seen[t]), len(tied)))
-    new_id, new_seen = np.full((p,), -1, np.int32), np.full((p,), -1, np.int32)
+            tied = [c for c in cands if c is not cands[i] and c[0] * u == k * c[1] and (c[2] == q or c[3] == t)]
+            log.append(('match', frame, q, t, int(live_id[t]), k, u, int(live_seen[t]), len(tied)))
+    # 3b. gate (K37)
+    if motion is not None:
+        c_q = M.centroids(im, area_q, x_lo, y_lo, np.float64(voxel))
+        with np.errstate(all='ignore'):
+            a = pos[:n_live] + vel[:n_live]
+            pred = np.stack([(n[0, 0] * a[:, 0] + n[0, 1] * a[:, 1]) + n[0, 2],
+                             (n[1, 0] * a[:, 0] + n[1, 1] * a[:, 1]) + n[1, 2]], axis=1).reshape(n_live, 2)
+            velr = np.stack([n[0, 0] * vel[:n_live, 0] + n[0, 1] * vel[:n_live, 1],
+                             n[1, 0] * vel[:n_live, 0] + n[1, 1] * vel[:n_live, 1]], axis=1).reshape(n_live, 2)
+        open_q, open_t, gate_taken = [], [], []
+        if gate > 0 and n_live > 0:
+            open_q = [q for q in range(q_num) if present[q] and q not in q_match]
+            open_t = [t for t in range(n_live) if t not in t_taken]
+            pairs = []
+            with np.errstate(all='ignore'):
+                g2 = gate * gate
+                for q in open_q:
+                    dx, dy = c_q[q, 0] - pred[open_t, 0], c_q[q, 1] - pred[open_t, 1]
+                    d2 = dx * dx + dy * dy
+                    pairs += [(float(d2[k]), q, t) for k, t in enumerate(open_t) if d2[k] <= g2]
+            pairs.sort()
+            for _, q, t in pairs:
+                if q in q_match or t in t_taken:
+                    continue
+                q_match[q] = t
+                t_taken.add(t)
+                gate_taken.append((q, t))
+        new_pos, new_vel = np.zeros((p, 2), np.float64), np.zeros((p, 2), np.float64)
+        query_velocity = np.zeros((q_num, 2), np.float64)
+    # 4. update
+    new_id, new_seen, new_held = np.full((p,), -1, np.int32), np.full((p,), -1, np.int32), np.zeros((p,), np.int32)
     q_new, t_new = np.full((q_num,), -1, np.int64), np.full((p,), -1, np.int64)
     query_track = np.full((q_num,), -1, np.int32)
     n_new = 0
@@ -98,16 +154,32 @@ def step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min
             next_id += 1
             if log is not None:
                 log.append(('birth', frame, q, gid))
+        if motion is not None:
+            v = np.zeros((2,), np.float64)
+            if q in q_match:
+                with np.errstate(all='ignore'):
+                    v = M.finite_or_zero(velr[q_match[q]] + gain * (c_q[q] - pred[q_match[q]]))
+            new_pos[n_new], new_vel[n_new], query_velocity[q] = c_q[q], v, v
         new_id[n_new], new_seen[n_new] = gid, frame
         q_new[q] = n_new
         query_track[q] = gid
         n_new += 1
+    occluded = []
     for t in range(n_live):
         if t in t_taken:
             continue
-        if frame - int(live_seen[t]) <= max_age:
+        seen, held = int(live_seen[t]), 0
+        if occlusion is not None:
+            held = int(live_held[t])
+            if (visibility is not None and area_t[t] > 0 and int(hidden[t]) * int(hold_den) >= int(area_t[t]) * int(hold_num)
+                    and held < max_hold):
+                seen, held = seen + 1, held + 1
+                occluded.append(t)
+        if frame - seen <= max_age:
             if n_new < p:
-                new_id[n_new], new_seen[n_new] = live_id[t], live_seen[t]
+                new_id[n_new], new_seen[n_new], new_held[n_new] = live_id[t], seen, held
+                if motion is not None:
+                    new_pos[n_new], new_vel[n_new] = pred[t], M.finite_or_zero(velr[t])
                 t_new[t] = n_new
                 n_new += 1
                 if log is not None:
@@ -118,6 +190,14 @@ def step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min
                     log.append(('drop', frame, t, int(live_id[t])))
         elif log is not None:
             log.append(('death', frame, t, int(live_id[t])))
+    if tables is not None:
+        tables.update(warped=warped, area_q=area_q, area_t=area_t, t_taken=sorted(t_taken), t_new=t_new.copy(), frame=frame)
+        if motion is not None:
+            tables.update(moved=moved, c_q=c_q, pred=pred, velr=velr, open_q=open_q, open_t=open_t, gate_taken=gate_taken,
+                          gated=len(gate_taken))
+        if occlusion is not None:
+            tables.update(hidden=hidden, occluded=occluded)
+    present, q_new, of_query = np.append(present, False), np.append(q_new, -1), np.append(query_track, -1)   # Q = 0 indexes too
     pres_cell = (im >= 0) & present[np.maximum(im, 0)]
     from_q = q_new[np.maximum(im, 0)]
     from_t = np.where(warped >= 0, t_new[np.maximum(warped, 0)], -1)
@@ -126,11 +206,20 @@ def step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min
         if fell:
             log.append(('fall_through', frame, fell))
     sm[...] = np.where(pres_cell, from_q, from_t).astype(np.int32)
-    track_map = np.where(pres_cell, query_track[np.maximum(im, 0)], -1).astype(np.int32)
+    track_map = np.where(pres_cell, of_query[np.maximum(im, 0)], -1).astype(np.int32)
     live_id[...] = new_id
     live_seen[...] = new_seen
     counters[...] = np.array([n_new, next_id, frame + 1, dropped], np.int64).astype(np.int32)
-    return query_track, track_map
+    if motion is None:
+        return query_track, track_map
+    pos[...] = new_pos
+    vel[...] = new_vel
+    state['motion_counters'][...] = np.array([int(state['motion_counters'][0]) + len(gate_taken), 0], np.int64).astype(np.int32)
+    if occlusion is not None:
+        live_held[...] = new_held
+        state['occlusion_counters'][...] = np.array([int(state['occlusion_counters'][0]) + len(occluded), 0],
+                                                    np.int64).astype(np.int32)
+    return query_track, track_map, query_velocity
 
 
 def plain_step(state, instance_map, m, x_lo, y_lo, voxel, q_num, min_iou, max_age, min_cells):
