@@ -1,7 +1,11 @@
 """K17 (csrc/gemm.hip): the 16-bit MFMA GEMM family against f64 torch expressions of the same products on the
 same (already rounded) inputs.  Tolerances: the kernel accumulates in f32 and rounds once to the output type, so
 the 16-bit outputs are compared at one ulp of that type (bf16 2^-8, fp16 2^-11 relative, + a small absolute term
-for cancellation) and the f32 outputs / atomically accumulated weight gradients at 2e-5 of the operand scale."""
+for cancellation) and the f32 outputs / atomically accumulated weight gradients at 2e-5 of the operand scale.
+
+These are the workload's shapes at loose bars.  tests/test_k17_paths_gpu.py holds K17 to the project's f32 bar against float64
+(max(4e-6, 4 x the float32 CPU evaluation's error); 16-bit stores one rounding more) on the routes production takes, and
+asserts the block tile, the split and the entry point of every case."""
 import math
 
 import pytest
