@@ -1997,6 +1997,87 @@ int mbv_tube_accumulate(const int32_t* pred_track, const uint32_t* gt_word, int6
 int mbv_tube_scores(const int64_t* gt_size, const int64_t* pred_size, const int32_t* pair, int32_t C, int32_t id_limit,
                     int32_t max_tracks, double* assoc, double* class_assoc, int32_t* class_tubes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K39 — tracked BEV footprints fused over time in a rolling world grid (csrc/fuse.hip, built with -ffp-contract=off).  The
+ * tracker (K33a / K37 / K38b) remembers which id an object has; K39a remembers where its cells were: per-cell evidence in a
+ * world-anchored store that scrolls by whole cells, so memory is never re-sampled.  Opt-in; nothing else changes.  The numpy
+ * restatement of the words below is tests/fuse_ref.py.  All f64 arithmetic takes one rounding per operation, in the order
+ * written: (a * x + b * y) + c and (p - lo) / v.
+ *
+ * K39a — mbv_fuse_frames.
+ * Grid           K33a's: H rows, W columns, x_lo, y_lo, voxel = v f64; H * W <= 1024 * 1024; Q <= 1024.
+ * State          owned by the caller, on the device, for ONE sequence: owner (S, S) i32, the global track id that owns a store
+ *                cell, -1 for none; count (S, S) i32, its evidence in [0, cap]; window (4) i64 = [wx0, wy0, frames, reserved
+ *                0].  A fresh state: window all zeros; owner and count may hold anything (frames == 0 clears them).  S is
+ *                even, (S - 4)^2 >= H^2 + W^2 (S >= ceil(hypot(H, W)) + 4: the rotated grid fits whatever the heading) and
+ *                S <= 8192.
+ * World frame    the sensor frame of the first frame after a reset.  World cell (gx, gy) = (floor(X / v), floor(Y / v)) as
+ *                i64 lives at store[gy mod S][gx mod S], the mathematical mod; the window is gx in [wx0, wx0 + S), gy in [wy0,
+ *                wy0 + S).  Store cell (sy, sx) under a corner (wx0, wy0) represents gx = wx0 + ((sx - wx0) mod S), gy likewise.
+ * One frame      instance_maps (F, H, W) i32: the query per cell, a value outside [0, Q) means none; query_track (F, Q) i32
+ *                from the tracker, < 0: the query is not present; world_from_cur = m and cur_from_world = n (F, 2, 3) f64
+ *                row-major, inverses of each other; visibility (F, H, W) u8 or NULL (K38a's, non-zero = seen);
+ *                query_velocity (F, Q, 2) f64 or NULL (K37's); cap >= 1, hit >= 1, miss >= 0, min_count >= 1 i32;
+ *                static_speed f64 >= 0.
+ * Moving         query q is MOVING iff query_velocity != NULL and vx * vx + vy * vy > static_speed * static_speed (a NaN on
+ *                either side fails: not moving).
+ *
+ * 1. window  (cx, cy) = (x_lo + (W * 0.5) * v, y_lo + (H * 0.5) * v); X = (m00 * cx + m01 * cy) + m02, Y likewise;
+ *            wx0' = floor(X / v) - S / 2, wy0' = floor(Y / v) - S / 2.  The frame is INVALID iff any of the twelve entries of m
+ *            and n is not finite or !(|X / v| < 2^40 && |Y / v| < 2^40): state and window stay untouched, fused_ids and
+ *            fused_queries of the frame are -1.  Otherwise a store cell is cleared (owner -1, count 0) iff frames == 0 or the
+ *            world cell it represents under (wx0', wy0') differs from the one under (wx0, wy0).
+ * 2. update  one gather per store cell, its world cell (gx, gy) under the new corner: x = ((double)gx + 0.5) * v, y likewise;
+ *            xs = (n00 * x + n01 * y) + n02, ys = (n10 * x + n11 * y) + n12; fx = floor((xs - x_lo) / v), fy = floor((ys - y_lo)
+ *            / v).  Unless 0 <= fx < W and 0 <= fy < H (NaN and inf fail): hold.  Else q = instance_maps[f][fy][fx]:
+ *              q in [0, Q) and MOVING                         hold
+ *              q in [0, Q), g = query_track[f][q] >= 0, owner == g    count = min(count + hit, cap)
+ *              ...                                 owner != g    count -= hit; if count <= 0: owner = g, count = hit
+ *              no detection (q outside [0, Q) or g < 0), cell seen (visibility == NULL or visibility[f][fy][fx] != 0)
+ *                                                             count -= miss; if count <= 0: owner = -1, count = 0
+ *              no detection, cell not seen                    hold
+ *            (count is stepped in 64-bit integers and stored as i32.)
+ * 3. read    one gather per sensor cell (iy, ix), q = instance_maps[f][iy][ix]: if q in [0, Q) is MOVING and query_track[f][q]
+ *            >= 0, fused_ids = that id and fused_queries = q.  Otherwise x = x_lo + (ix + 0.5) * v, y likewise, X = (m00 * x +
+ *            m01 * y) + m02, Y likewise, gx = floor(X / v), gy = floor(Y / v); if wx0' <= gx < wx0' + S and wy0' <= gy <
+ *            wy0' + S (compared in f64; NaN and inf fail) and the store cell has owner >= 0 and count >= min_count: fused_ids =
+ *            owner and fused_queries = the smallest q in [0, Q) that is not MOVING with query_track[f][q] == owner, -1 when
+ *            there is none.  Otherwise both are -1.  Then window = [wx0', wy0', frames + 1, 0].
+ *
+ * fused_ids      (F, H, W) i32;  fused_queries (F, H, W) i32 or NULL.  Every element is written.
+ * Identity       with cap = hit = miss = min_count = 1, no visibility, no velocity, identity poses and x_lo, y_lo multiples
+ *                of v, fused_ids equals mbv_track_frames' track_map on maps whose present queries are the ones with an id.
+ * Limits         moving objects are passed through, not accumulated; both gathers are nearest-cell, so a footprint seen
+ *                under a turning ego loses and gains border cells; the id of a track that died persists under cells nobody
+ *                sees until the window leaves them; z is ignored.
+ * mbv_fuse_frames steps through the F frames in order, two launches per frame (window + update, one thread per store cell;
+ * read-out, one thread per sensor cell with the frame's Q ids in LDS; its first thread writes the window, which no other
+ * thread of that launch reads), enqueued on the stream, never synchronised, no workspace.  No atomics: both steps are pure
+ * gathers, bit-deterministic.  Every index comes from the sizes: a bad pose, id or stored value changes results, never
+ * addresses (a stored corner is the call's own: |wx0|, |wy0| < 2^41).
+ * F == 0 or H * W == 0: MBV_OK, nothing is written.  MBV_ERR_UNSUPPORTED: S odd, too small or > 8192, Q > 1024, H * W >
+ * 1024 * 1024;  MBV_ERR_BAD_ARG: a negative size, cap < 1, hit < 1, miss < 0, min_count < 1, !(static_speed >= 0), voxel not
+ * finite or <= 0, a null pointer other than visibility, query_velocity, fused_queries (query_track may be null when Q == 0).
+ *
+ * K39b — mbv_masks_from_map: a map of query indices back to the masks every consumer of masks_packed reads.
+ * maps           (F, H, W) i32: a query in [0, Q) per cell; any other value sets nothing
+ * masks_packed   (F * Q, mbv_packed_mask_words(H, W)) u32, mbv_pack_binary_masks layout, row f * Q + q: bit (y * W + x) is
+ *                (maps[f][y][x] == q); tail bits zero
+ * areas          (F, Q) i32: the set bits of every row
+ * Three launches: two fills (masks_packed, areas), then one thread per pixel — a wave ballots every distinct query of its 64
+ * pixels and its first lane stores the two words of that query's row (a word of a row has one writer: plain stores) and
+ * counts the query's cells in an LDS table that is flushed once per block (integer atomicAdd).
+ * Every element of both outputs is written.  F == 0 or Q == 0: MBV_OK, nothing is written.  MBV_ERR_UNSUPPORTED: Q > 1024,
+ * F > 65535, H * W > 1024 * 1024;  MBV_ERR_BAD_ARG: a negative size, H < 1 or W < 1, a null pointer.
+ */
+int mbv_fuse_frames(const int32_t* instance_maps, const int32_t* query_track, const double* world_from_cur,
+                    const double* cur_from_world, const uint8_t* visibility, const double* query_velocity, int32_t F, int32_t H,
+                    int32_t W, int32_t S, double x_lo, double y_lo, double voxel, int32_t Q, int32_t cap, int32_t hit,
+                    int32_t miss, int32_t min_count, double static_speed, int32_t* owner, int32_t* count, int64_t* window,
+                    int32_t* fused_ids, int32_t* fused_queries, void* stream);
+int mbv_masks_from_map(const int32_t* maps, int32_t F, int32_t H, int32_t W, int32_t Q, uint32_t* masks_packed, int32_t* areas,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ from typing import Dict, List, Tuple
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libmaskbev_hip.so')
 
+# Raised when a declared signature changes.  Entries that were only ADDED since (K33b, K35, K38, K39) left it at 59: a stale
+# library without them passes the version check below and fails at the symbol lookup of load(), which names the symbol.
 ABI_VERSION = 59
 
 
@@ -239,6 +241,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
                                           _F, _P, _P, c_size_t, _P]),
     'mbv_tube_accumulate': (ctypes.c_int, [_P, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'mbv_tube_scores': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'mbv_fuse_frames': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, _I, _D, _P, _P, _P,
+                                       _P, _P, _P]),
+    'mbv_masks_from_map': (ctypes.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'mbv_render_box_chunk': (_I, []),
     'mbv_cell_counts': (ctypes.c_int, [_P, _I, _L, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I, _I, _I, _I, _P, _P]),
     'mbv_render_bev': (ctypes.c_int, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, ctypes.c_uint32, _P, _I,

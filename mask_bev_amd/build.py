@@ -45,6 +45,8 @@ FILE_FLAGS = {
     'render.hip': ['-ffp-contract=off'],
     # K38a's targets come from K1's cell rule, and its height test is one f32 subtract and one multiply per side, as restated
     'visibility.hip': ['-ffp-contract=off'],
+    # K39a's f64 transforms of cell centres decide a world cell and a sensor cell: one rounding per operation, as restated
+    'fuse.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

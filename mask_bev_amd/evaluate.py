@@ -11,7 +11,7 @@ from .datasets import KittiFrames, semantic_kitti_files
 from .kitti_eval import eval_kitti
 from .metrics import DevicePanopticQuality, DeviceTubeAssociation, lstq, semantic_kitti_class_lut
 from .predict import BOX_METHODS, GroundSettings, write_semantic_kitti_labels
-from .tracking import InstanceTracker, MotionSettings, OcclusionSettings, velodyne_poses
+from .tracking import FootprintFusion, FusionSettings, InstanceTracker, MotionSettings, OcclusionSettings, velodyne_poses
 
 
 def predictions(model, scan_paths, bsz, device, score_threshold=0.0):
@@ -169,6 +169,34 @@ def tracking_settings(config):
     return out
 
 
+def fusion_settings(config):
+    """``track_fuse: true``: the ``FusionSettings`` (K39) from ``track_fuse_cap`` (8), ``track_fuse_min_count`` (2) and, with
+    ``track_motion: true`` only, ``track_fuse_static_speed`` (0.5 m per frame: a query faster than that is passed through, not
+    accumulated); ``None`` without the key."""
+    if not bool(config.get('track_fuse', False)):
+        return None
+    speed = float(config.get('track_fuse_static_speed', 0.5)) if bool(config.get('track_motion', False)) else None
+    return FusionSettings(cap=int(config.get('track_fuse_cap', 8)), min_count=int(config.get('track_fuse_min_count', 2)),
+                          static_speed=speed)
+
+
+def _fusion(config, device):
+    settings = fusion_settings(config)
+    if settings is None:
+        return None
+    return FootprintFusion(config['x_range'], config['y_range'], config['voxel_size'], int(config['num_queries']), settings,
+                           device=device)
+
+
+def _track(pred, tracker, fusion, poses, vis):
+    """The tracker step of a batch and, with ``fusion``, K39 behind it → (the predictions to lift, label and render from,
+    query_track)."""
+    if fusion is None:
+        return pred, pred.track(tracker, poses=poses, visibility=vis)
+    rec = tracker.update(pred.instance_map, poses=poses, record=True, **({} if vis is None else dict(visibility=vis)))
+    return pred.fused(fusion, rec.query_track, poses=poses, visibility=vis, query_velocity=rec.query_velocity)[0], rec.query_track
+
+
 def sequence_tracking(model, config, device, root, sequences, out_dir=None, score_threshold=0.0, semantic_id=10):
     """``track_instances: true``: one pass over the scans of ``sequences`` in scan order, on ONE rank — predict, the tracker step
     on the BEV instance maps (K33a; reset at every sequence change, the ego motion from the sequence's ``poses.txt`` and
@@ -178,7 +206,9 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
     sequence lacks ``poses.txt`` or ``calib.txt``, else ``{'tracks', 'dropped', 'frames', 'written'}`` (with ``track_motion: true``
     the tracker runs K37's motion model and ``'gated'`` is added; with ``track_occlusion: true`` the visibility map of every
     batch is computed from the scans already read, K38, and ``'held'`` is added) plus, with labels,
-    ``{'lstq', 's_assoc', 's_cls', 'tubes'}``.  Not pinned: parity with semantic-kitti-api's 4D evaluator, LSTQ on real data."""
+    ``{'lstq', 's_assoc', 's_cls', 'tubes'}``.  With ``track_fuse: true`` (K39, :func:`fusion_settings`) the tracker still steps on
+    the model's own maps, but the lift, the written labels, the tube association and the panoptic IoU come from the fused
+    predictions (``Predictions.fused``), and ``'fused': True`` is added.  Not pinned: parity with semantic-kitti-api's 4D evaluator, LSTQ on real data."""
     by_seq = {}
     for f, _ in semantic_kitti_files(root, sequences):
         by_seq.setdefault(f.parent.parent, []).append(f)
@@ -189,6 +219,7 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
     have_labels = all(semantic_kitti_label_path(f).exists() for scans_of in by_seq.values() for f in scans_of)
     tracker = InstanceTracker(config['x_range'], config['y_range'], config['voxel_size'], int(config['num_queries']),
                               device=device, **tracking_settings(config))
+    fusion = _fusion(config, device)
     quality = panoptic_metric(config)
     tubes = DeviceTubeAssociation(quality.num_classes, quality.class_lut('cpu'), id_limit=int(config.get('track_id_limit', 1024)),
                                   max_tracks=int(config.get('track_tube_tracks', 4096)))      # the same classes as `quality`
@@ -199,9 +230,11 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
         poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
         tracker.reset()
         tubes.reset()
+        if fusion is not None:
+            fusion.reset()
         for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
             vis = pred.visibility(scans, model, tracker.occlusion) if tracker.occlusion is not None else None
-            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]], visibility=vis)
+            pred, query_track = _track(pred, tracker, fusion, poses[[int(f.stem) for f in part]], vis)
             lifted = pred.lift(scans, model, **ground)
             ids = pred.point_tracks(lifted, query_track)
             if have_labels:
@@ -219,6 +252,8 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
             res = tubes.compute()                  # per sequence: SemanticKITTI's instance ids are unique inside one only
             assoc_sum += res['s_assoc'] * res['tubes']
             n_tubes += res['tubes']
+    if fusion is not None:
+        out['fused'] = True
     if have_labels:
         s_assoc = assoc_sum / max(n_tubes, 1)
         s_cls = quality.compute(reduce=False)['iou'] if quality.frames else 0.0     # compute() would wait for the other ranks
@@ -230,8 +265,9 @@ def format_point_lstq(result):
     """The ``point LSTQ`` line of ``--test`` from :func:`sequence_tracking`."""
     gated = f', gated {result["gated"]}' if 'gated' in result else ''                  # K37: with ``track_motion: true`` only
     held = f', held {result["held"]}' if 'held' in result else ''                      # K38: with ``track_occlusion: true`` only
+    fused = ', fused' if result.get('fused') else ''                                   # K39: with ``track_fuse: true`` only
     return (f'point LSTQ {result["lstq"]:.4f} S_assoc {result["s_assoc"]:.4f} S_cls {result["s_cls"]:.4f} '
-            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]}{gated}{held})')
+            f'(tubes {result["tubes"]}, tracks {result["tracks"]}, dropped {result["dropped"]}{gated}{held}{fused})')
 
 
 def format_layer_metrics(logged, layer):
@@ -277,7 +313,8 @@ def render_frames(model, config, device, scan_paths, out_dir, dataset='semantic-
     colour (:func:`render_settings`).  ``dataset='semantic-kitti'`` — ``scan_paths`` in scan order: the contour of the mask
     cache's instances where ``mask_cache/NNNNNN.npy`` lies next to a scan; with ``track_instances: true`` the colours are the
     track ids of an ``InstanceTracker`` of this pass's own, reset at every sequence change (K33a; ``poses.txt`` and
-    ``calib.txt`` of the sequence, without them one line says so and the colours are the query indices).  ``dataset='kitti'``:
+    ``calib.txt`` of the sequence, without them one line says so and the colours are the query indices); with ``track_fuse: true``
+    in addition the frames are drawn from the fused predictions (K39).  ``dataset='kitti'``:
     with ``render_boxes`` (default true) the predicted boxes and ``label_boxes`` — per scan an (n, 7) array in the velodyne
     frame — in a second colour.  Returns the paths written."""
     from .render import write_png
@@ -304,13 +341,18 @@ def render_frames(model, config, device, scan_paths, out_dir, dataset='semantic-
         track = False
     tracker = InstanceTracker(config['x_range'], config['y_range'], config['voxel_size'], int(config['num_queries']),
                               device=device, **tracking_settings(config)) if track else None
+    fusion = _fusion(config, device) if track else None
     for seq_dir, scans_of in by_seq.items():
         if track:
             poses = velodyne_poses(B.read_poses(seq_dir / 'poses.txt'), B.read_calib(seq_dir / 'calib.txt'))
             tracker.reset()
+            if fusion is not None:
+                fusion.reset()
         for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
             vis = pred.visibility(scans, model, tracker.occlusion) if track and tracker.occlusion is not None else None
-            query_track = pred.track(tracker, poses=poses[[int(f.stem) for f in part]], visibility=vis) if track else None
+            query_track = None
+            if track:
+                pred, query_track = _track(pred, tracker, fusion, poses[[int(f.stem) for f in part]], vis)
             frames = pred.render(settings, scans=scans, module=model, query_track=query_track,
                                  gt_maps=_cached_maps(part, pred.grid_hw, device)).cpu().numpy()
             for f, frame in zip(part, frames):

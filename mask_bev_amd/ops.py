@@ -26,7 +26,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
                    K32 panoptic tp / fp / fn, IoU sums and confusion per frame from two id arrays (points or BEV cells)
     ops_track      K33 the tracker step over consecutive BEV instance maps (global instance ids) and tube association (S_assoc of LSTQ);
                    K37 the same step with a constant-velocity motion model and gated re-association;
-                   K38b the same step with occlusion-aware ageing from K38a's maps
+                   K38b the same step with occlusion-aware ageing from K38a's maps;
+                   K39 tracked footprints fused over time in a rolling world grid, and a query map back to packed masks
     ops_render     K36 returns per BEV cell and the composed BEV frame (density, instances / tracks, ground-truth contour, boxes)
 """
 from .ops_core import *            # noqa: F401,F403

@@ -1,7 +1,9 @@
 """The tracker step over consecutive BEV instance maps of one sequence (csrc/track.hip) — K33a, with two optional parts, both
 off by default: K37's constant-velocity motion model and gated re-association, and K38b's occlusion-aware ageing from K38a's
 visibility maps (which runs on K37's step) — and K33b, tube association, the S_assoc term of LSTQ.  Behind
-``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  The definitions are in include/maskbev_hip.h."""
+``tracking.InstanceTracker`` and ``metrics.DeviceTubeAssociation``.  K39 (csrc/fuse.hip), behind
+``tracking.FootprintFusion`` and ``Predictions.fused``: the tracked footprints fused over time in a rolling world grid, and a
+query map turned back into packed masks.  The definitions are in include/maskbev_hip.h."""
 from __future__ import annotations
 
 import math
@@ -322,6 +324,137 @@ def tube_scores(tables: TubeTables) -> TubeScores:
     return out
 
 
+@dataclass
+class FusionSettings:
+    """K39a's settings (``tracking.FusionSettings`` is this class): a store cell's evidence ``count`` lives in [0, ``cap``]; a
+    detection of the owner adds ``hit``, a detection of another id takes ``hit`` away (and takes the cell over at 0), a seen
+    cell without a detection loses ``miss``; a cell is read out with ``count >= min_count``.  ``static_speed`` >= 0 in metres
+    per frame: with a ``query_velocity``, a query faster than this is moving — passed through, never accumulated; None, the
+    default, treats every query as static.  The defaults are geometry, not measurement: two frames of agreement show a
+    cell, eight frames of memory bridge 0.8 s at 10 Hz."""
+    cap: int = 8
+    hit: int = 1
+    miss: int = 1
+    min_count: int = 2
+    static_speed: Optional[float] = None
+
+    def __post_init__(self):
+        self.cap, self.hit, self.miss, self.min_count = int(self.cap), int(self.hit), int(self.miss), int(self.min_count)
+        if self.static_speed is not None:
+            self.static_speed = float(self.static_speed)
+        if not (1 <= self.cap < 2 ** 31 and 1 <= self.hit < 2 ** 31 and 0 <= self.miss < 2 ** 31 and 1 <= self.min_count < 2 ** 31
+                and (self.static_speed is None or 0.0 <= self.static_speed < math.inf)):
+            raise ValueError(f'FusionSettings: cap {self.cap} >= 1, hit {self.hit} >= 1, miss {self.miss} >= 0, min_count '
+                             f'{self.min_count} >= 1 and static_speed {self.static_speed} None or finite and >= 0 expected')
+
+
+def fusion_store_size(h: int, w: int) -> int:
+    """The smallest store side K39a accepts for an (h, w) grid: even, with (S - 4)^2 >= h^2 + w^2."""
+    s = math.isqrt(int(h) ** 2 + int(w) ** 2)
+    s += 4 + (s * s < int(h) ** 2 + int(w) ** 2)
+    return s + (s & 1)
+
+
+@dataclass
+class FusionState:
+    """K39a's state of one sequence, on the device (include/maskbev_hip.h): ``owner`` (S, S) int32 — the global track id that
+    owns a store cell, -1 for none; ``count`` (S, S) int32 — its evidence; ``window`` (4) int64 = wx0, wy0, frames, 0."""
+    owner: torch.Tensor
+    count: torch.Tensor
+    window: torch.Tensor
+
+    @staticmethod
+    def fresh(h: int, w: int, device) -> 'FusionState':
+        s = fusion_store_size(h, w)
+        return FusionState(torch.full((s, s), -1, dtype=torch.int32, device=device),
+                           torch.zeros((s, s), dtype=torch.int32, device=device),
+                           torch.zeros((4,), dtype=torch.int64, device=device))
+
+
+@dataclass
+class FusedFrames:
+    """K39a's outputs for F frames: ``ids`` (F, H, W) int32 — the global track id that owns every sensor cell after fusion, -1
+    for none; ``queries`` (F, H, W) int32 — the frame's query of that id (the smallest static one), -1 where the id has no
+    query in this frame: a footprint that is only remembered."""
+    ids: torch.Tensor
+    queries: Optional[torch.Tensor]
+
+
+@torch.no_grad()
+def fuse_frames(instance_maps: torch.Tensor, query_track: torch.Tensor, world_from_cur: torch.Tensor,
+                cur_from_world: torch.Tensor, state: FusionState, x_lo: float, y_lo: float, voxel: float,
+                settings: Optional[FusionSettings] = None, visibility: Optional[torch.Tensor] = None,
+                query_velocity: Optional[torch.Tensor] = None, queries: bool = True) -> FusedFrames:
+    """K39a: ``instance_maps`` (F, H, W) int32 — F consecutive frames of ONE sequence; ``query_track`` (F, Q) int32 — the
+    tracker's ids of the same frames; ``world_from_cur`` / ``cur_from_world`` (F, 2, 3) f64 — every frame's BEV coordinates
+    into the frame of the sequence's first scan, and back; ``state`` is stepped in place.  ``visibility`` (F, H, W) uint8,
+    K38a's maps: without it every cell counts as seen.  ``query_velocity`` (F, Q, 2) f64, K37's: used only with
+    ``settings.static_speed``.  Device tensors only; no host synchronisation."""
+    lib = _lib.load()
+    settings = settings if settings is not None else FusionSettings()
+    _need_gpu(instance_maps, query_track, world_from_cur, cur_from_world, state.owner, state.count, state.window)
+    dev = instance_maps.device
+    if instance_maps.dim() != 3 or instance_maps.dtype != torch.int32:
+        raise MaskBevHipError(f'fuse_frames: instance_maps must be (F, H, W) int32, got {tuple(instance_maps.shape)} '
+                              f'{instance_maps.dtype}')
+    f, h, w = (int(v) for v in instance_maps.shape)
+    if query_track.dim() != 2 or int(query_track.shape[0]) != f or query_track.dtype != torch.int32:
+        raise MaskBevHipError(f'fuse_frames: query_track must be ({f}, Q) int32, got {tuple(query_track.shape)} {query_track.dtype}')
+    q, s = int(query_track.shape[1]), int(state.owner.shape[0])
+    fields = [('instance_maps', instance_maps, (f, h, w), torch.int32), ('query_track', query_track, (f, q), torch.int32),
+              ('world_from_cur', world_from_cur, (f, 2, 3), torch.float64),
+              ('cur_from_world', cur_from_world, (f, 2, 3), torch.float64)]
+    if visibility is not None:
+        fields.append(('visibility', visibility, (f, h, w), torch.uint8))
+    if settings.static_speed is None:
+        query_velocity = None
+    if query_velocity is not None:
+        fields.append(('query_velocity', query_velocity, (f, q, 2), torch.float64))
+    _need_gpu(*(x for _, x, _, _ in fields))
+    for name, x, shape, dt in fields:
+        if tuple(x.shape) != shape or x.dtype != dt or x.device != dev:
+            raise MaskBevHipError(f'fuse_frames: {name} must be a {shape} {dt} tensor on {dev}, got {tuple(x.shape)} {x.dtype}')
+    instance_maps, query_track, world_from_cur, cur_from_world = (x.contiguous() for _, x, _, _ in fields[:4])
+    visibility = visibility.contiguous() if visibility is not None else None
+    query_velocity = query_velocity.contiguous() if query_velocity is not None else None
+    _check_fields('fuse_frames: state', dev, (('owner', state.owner, (s, s), torch.int32), ('count', state.count, (s, s), torch.int32),
+                                              ('window', state.window, (4,), torch.int64)))
+    if not (q <= 1024 and h * w <= 1024 * 1024 and s % 2 == 0 and fusion_store_size(h, w) <= s <= 8192 and float(voxel) > 0.0):
+        raise MaskBevHipError(f'fuse_frames: Q {q} <= 1024, H * W {h * w} <= 2^20, an even store side {s} in '
+                              f'[{fusion_store_size(h, w)}, 8192] or voxel {float(voxel)} > 0 violated')
+    out = FusedFrames(torch.empty((f, h, w), dtype=torch.int32, device=dev),
+                      torch.empty((f, h, w), dtype=torch.int32, device=dev) if queries else None)
+    if f == 0 or h * w == 0:
+        return out
+    speed = settings.static_speed if settings.static_speed is not None else 0.0
+    check(lib.mbv_fuse_frames(_ptr(instance_maps), _ptr(query_track), _ptr(world_from_cur), _ptr(cur_from_world), _ptr(visibility),
+                              _ptr(query_velocity), f, h, w, s, float(x_lo), float(y_lo), float(voxel), q, settings.cap,
+                              settings.hit, settings.miss, settings.min_count, speed, _ptr(state.owner), _ptr(state.count),
+                              _ptr(state.window), _ptr(out.ids), _ptr(out.queries), _stream()), 'mbv_fuse_frames')
+    return out
+
+
+@torch.no_grad()
+def masks_from_map(maps: torch.Tensor, num_queries: int):
+    """K39b: ``maps`` (F, H, W) int32, a query in [0, ``num_queries``) per cell (anything else: none) → (``PackedMasks`` of the
+    F * Q rows f * Q + q in the layout of ``pack_binary_masks``, ``areas`` (F, Q) int32).  No host synchronisation."""
+    from .ops_loss import PackedMasks
+    lib = _lib.load()
+    _need_gpu(maps)
+    if maps.dim() != 3 or maps.dtype != torch.int32:
+        raise MaskBevHipError(f'masks_from_map: maps must be (F, H, W) int32, got {tuple(maps.shape)} {maps.dtype}')
+    f, h, w = (int(v) for v in maps.shape)
+    q = int(num_queries)
+    if not (0 <= q <= 1024 and f <= 65535 and h >= 1 and w >= 1 and h * w <= 1024 * 1024):
+        raise MaskBevHipError(f'masks_from_map: Q {q} <= 1024, F {f} <= 65535 or 1 <= H * W {h * w} <= 2^20 violated')
+    maps = maps.contiguous()
+    words = torch.empty((f * q, lib.mbv_packed_mask_words(h, w)), dtype=torch.int32, device=maps.device)
+    areas = torch.empty((f, q), dtype=torch.int32, device=maps.device)
+    check(lib.mbv_masks_from_map(_ptr(maps), f, h, w, q, _ptr(words), _ptr(areas), _stream()), 'mbv_masks_from_map')
+    return PackedMasks(words, h, w), areas
+
+
 __all__ = ['track_frames', 'invert_transforms', 'tube_accumulate', 'tube_scores', 'TrackState', 'TrackMotion', 'MotionSettings',
            'TrackOcclusion', 'OcclusionSettings',
-           'TrackFrames', 'TubeTables', 'TubeScores']
+           'TrackFrames', 'TubeTables', 'TubeScores',
+           'FusionSettings', 'FusionState', 'FusedFrames', 'fusion_store_size', 'fuse_frames', 'masks_from_map']

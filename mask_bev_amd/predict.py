@@ -206,6 +206,24 @@ class Predictions:
             return tracker.update(self.instance_map, poses=poses, prev_from_cur=prev_from_cur)
         return tracker.update(self.instance_map, poses=poses, prev_from_cur=prev_from_cur, visibility=visibility)
 
+    def fused(self, fusion, query_track: torch.Tensor, poses=None, visibility=None, query_velocity=None):
+        """Steps a :class:`~mask_bev_amd.tracking.FootprintFusion` through the B frames of these predictions — CONSECUTIVE
+        scans of one sequence, in order — with ``query_track`` (B, Q) of :meth:`track` for the same frames (K39a), and turns
+        the fused query map back into masks (K39b).  Returns ``(Predictions, fused_ids)``: the predictions carry
+        ``instance_map`` = the fused query per cell and the ``masks`` / ``areas`` of that map, so :meth:`lift`,
+        :meth:`boxes`, :meth:`boxes3d`, :meth:`kitti_predictions`, ``panoptic_*``, :meth:`point_tracks` and :meth:`render`
+        work on them unchanged; ``labels``, ``scores`` and ``keep`` are these predictions' own, and ``mask_scores`` still
+        describes the UNFUSED masks (a remembered cell has no logit).  ``fused_ids`` (B, ny, nx) int32 is the global track id
+        per cell; a footprint that is only remembered — its track has no query in the frame — is in ``fused_ids`` alone.
+        ``poses`` (B, 4, 4) f64 sensor poses (None: a standing sensor); ``visibility``: :meth:`visibility` of the
+        same scans; ``query_velocity`` (B, Q, 2) f64 of a tracker with a motion model.  No host synchronisation."""
+        if self.instance_map is None:
+            raise MaskBevHipError('fused: these predictions were made without an instance map')
+        out = fusion.update(self.instance_map, query_track, poses=poses, visibility=visibility,
+                            query_velocity=query_velocity)
+        masks, areas = ops.masks_from_map(out.queries, self.labels.shape[1])
+        return Predictions(self.labels, self.scores, self.keep, masks, areas, self.mask_scores, out.queries, self.grid_hw), out.ids
+
     def point_tracks(self, lifted: 'ops.PointInstances', query_track: torch.Tensor) -> torch.Tensor:
         """The global track id of every point: ``query_track`` (B, Q) from :meth:`track`, gathered by K31's ``point_query``
         (``lifted``: :meth:`lift` of the same scans); -1 stays -1.  (N) int32 in the scans' concatenated point order.  No host

@@ -19,6 +19,9 @@ a row — a car behind a truck keeps its id, a false positive that vanishes in t
 limits: ``z_top`` is absolute in the sensor frame, not relative to K35's ground; returns outside the grid cast no rays; the
 blind ring next to a roof-mounted sensor is "unknown", so tracks there are held up to ``max_hold``; one ray per cell, to its
 lowest return.  The defaults are geometry, not measurement, and nothing is claimed about LSTQ on real data.
+
+:class:`FootprintFusion` (K39a) is the tracker's per-cell memory: which id owned which place, in a world-anchored grid that
+scrolls with the ego.  It runs behind the tracker on its ``query_track`` and is off unless used; see the class.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ import torch
 
 from . import ops
 from ._lib import MaskBevHipError
-from .ops_track import MotionSettings, OcclusionSettings
+from .ops_track import FusionSettings, MotionSettings, OcclusionSettings
 
 _IDENTITY = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]], dtype=np.float64)
 
@@ -169,4 +172,89 @@ class InstanceTracker:
         return out
 
 
-__all__ = ['InstanceTracker', 'MotionSettings', 'OcclusionSettings', 'prev_from_cur_2d', 'cur_from_prev_2d', 'velodyne_poses']
+class FootprintFusion:
+    """Tracked footprints fused over time (K39a, csrc/fuse.hip): per-cell memory of which track owned a place, in a
+    world-anchored store that scrolls by whole cells with the ego, so nothing is re-sampled from frame to frame.  The world is
+    the sensor frame of the first pose after :meth:`reset`.  ``x_range``, ``y_range``, ``voxel_size``, ``num_queries``: the
+    tracker's; ``settings``: a :class:`FusionSettings` (None: its defaults).  A detection adds evidence to its cell, a seen
+    empty cell loses it, an unseen cell (``visibility`` 0) holds it: a parked car the detector misses for a frame, or the half
+    of one that went out of sight, stays in the fused map under its id.
+    Limits: moving objects (``settings.static_speed`` with a ``query_velocity``) are passed through, not accumulated; both
+    gathers are nearest-cell, so a footprint seen under a turning ego loses and gains border cells; the id of a track that
+    died persists under cells nobody sees until the window leaves them; z is ignored; the defaults are geometry, not
+    measurement, and no PQ, LSTQ or AP on real data is claimed."""
+
+    def __init__(self, x_range, y_range, voxel_size: float, num_queries: int, settings: Optional[FusionSettings] = None,
+                 device='cuda'):
+        self.x_lo, self.y_lo, self.voxel = float(x_range[0]), float(y_range[0]), float(voxel_size)
+        self.w = int((x_range[1] - x_range[0]) / voxel_size)
+        self.h = int((y_range[1] - y_range[0]) / voxel_size)
+        self.num_queries = int(num_queries)
+        if settings is not None and not isinstance(settings, FusionSettings):
+            raise ValueError(f'FootprintFusion: settings must be a FusionSettings or None, got {type(settings).__name__}')
+        self.settings = settings if settings is not None else FusionSettings()
+        if not (0 <= self.num_queries <= 1024 and self.h * self.w <= 1024 * 1024 and self.voxel > 0.0):
+            raise ValueError('FootprintFusion: num_queries <= 1024, at most 2^20 cells and voxel_size > 0 expected')
+        if ops.fusion_store_size(self.h, self.w) > 8192:
+            raise ValueError(f'FootprintFusion: a {self.h} x {self.w} grid needs a store wider than 8192 cells')
+        self.device = torch.device(device)
+        self.reset()
+
+    def reset(self) -> None:
+        """A fresh sequence: an empty store, and the next pose becomes the world frame."""
+        self.state = ops.FusionState.fresh(self.h, self.w, self.device)
+        self._origin: Optional[np.ndarray] = None
+
+    def transforms(self, b: int, poses=None, world_from_cur=None):
+        """→ (world_from_cur, cur_from_world), both (b, 2, 3) f64 on the host: from ``poses`` (b, 4, 4) f64 sensor poses —
+        ``prev_from_cur_2d(origin, pose)`` with the first pose after :meth:`reset` as the origin, which is remembered — or
+        from ``world_from_cur`` itself; with neither the sensor stands still.  The inverses are taken on the host in f64."""
+        if world_from_cur is not None:
+            if torch.is_tensor(world_from_cur):
+                world_from_cur = world_from_cur.detach().cpu().numpy()
+            m = np.array(np.asarray(world_from_cur, dtype=np.float64).reshape(b, 2, 3))
+        elif poses is None:
+            m = np.tile(_IDENTITY, (b, 1, 1))
+        else:
+            poses = np.asarray(poses, dtype=np.float64).reshape(b, 4, 4)
+            if self._origin is None and b > 0:
+                self._origin = poses[0].copy()
+            m = np.stack([prev_from_cur_2d(self._origin, p) for p in poses]) if b else np.zeros((0, 2, 3))
+        with np.errstate(all='ignore'):
+            n = np.stack([_inverse_or_nan(x) for x in m]) if b else np.zeros((0, 2, 3))
+        return m, n
+
+    @torch.no_grad()
+    def update(self, pred_or_instance_maps, query_track, poses=None, world_from_cur=None, visibility=None, query_velocity=None):
+        """``pred_or_instance_maps``: a ``Predictions`` or its (B, ny, nx) int32 ``instance_map`` — B CONSECUTIVE frames;
+        ``query_track`` (B, Q) int32 of the tracker for the same frames.  ``poses`` (B, 4, 4) f64 sensor poses on the host, or
+        ``world_from_cur`` (B, 2, 3) f64; with neither, the sensor stands still.  ``visibility`` (B, ny, nx) uint8, K38a's;
+        ``query_velocity`` (B, Q, 2) f64, K37's (used with ``settings.static_speed`` only).  Returns ``ops.FusedFrames``:
+        ``ids`` and ``queries`` (B, ny, nx) int32 on the device.  No host synchronisation (a ``world_from_cur`` given as a
+        device tensor is copied to the host for its inverse)."""
+        maps = getattr(pred_or_instance_maps, 'instance_map', pred_or_instance_maps)
+        if maps is None:
+            raise MaskBevHipError('FootprintFusion.update: these predictions were made without an instance map')
+        if maps.dim() != 3 or tuple(maps.shape[1:]) != (self.h, self.w):
+            raise MaskBevHipError(f'FootprintFusion.update: (B, {self.h}, {self.w}) instance maps expected, got {tuple(maps.shape)}')
+        if query_track.dim() != 2 or tuple(query_track.shape) != (int(maps.shape[0]), self.num_queries):
+            raise MaskBevHipError(f'FootprintFusion.update: query_track ({int(maps.shape[0])}, {self.num_queries}) expected, got '
+                                  f'{tuple(query_track.shape)}')
+        m, n = self.transforms(int(maps.shape[0]), poses, world_from_cur)
+        m, n = (torch.from_numpy(np.ascontiguousarray(x)).to(self.device, non_blocking=True) for x in (m, n))
+        return ops.fuse_frames(maps, query_track, m, n, self.state, self.x_lo, self.y_lo, self.voxel, self.settings,
+                               visibility=visibility, query_velocity=query_velocity)
+
+
+def _inverse_or_nan(m) -> np.ndarray:
+    """``cur_from_prev_2d``, with NaN for a map that has no inverse (K39a then takes the frame as invalid)."""
+    if not np.all(np.isfinite(m)):
+        return np.full((2, 3), np.nan)
+    try:
+        return cur_from_prev_2d(m)
+    except np.linalg.LinAlgError:
+        return np.full((2, 3), np.nan)
+
+
+__all__ = ['InstanceTracker', 'MotionSettings', 'OcclusionSettings', 'FusionSettings', 'FootprintFusion', 'prev_from_cur_2d',
+           'cur_from_prev_2d', 'velodyne_poses']

@@ -46,7 +46,10 @@ files ``point LSTQ .. S_assoc .. S_cls .. (tubes .., tracks .., dropped ..)`` (`
 gated re-association, K37 — ``track_velocity_gain``, ``track_gate`` metres, ``track_max_speed`` metres per frame — and the
 parenthesis then ends ``, gated ..``; ``track_occlusion: true`` computes a BEV visibility map of every scan and lets a track
 that goes unmatched out of the sensor's sight keep its age, K38 — ``track_occlusion_z_top`` metres in the sensor frame,
-``track_hidden_fraction`` [num, den], ``track_max_hold`` frames — and the parenthesis then ends ``, held ..``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
+``track_hidden_fraction`` [num, den], ``track_max_hold`` frames — and the parenthesis then ends ``, held ..``; ``track_fuse: true``
+fuses the tracked footprints over time in a rolling world grid, K39 — ``track_fuse_cap``, ``track_fuse_min_count``, and with
+``track_motion`` ``track_fuse_static_speed`` metres per frame — lifts, labels and renders from the fused map, and the parenthesis
+then ends ``, fused``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
 ``lift_max_height``, ``lift_z_floor``) makes every one of these lifts label only the returns above a ground estimate made from
 the scan, lets the 3D boxes stand on it, and prints one ``ground-aware lift: ..`` line in front of the results it changes.
 ``--render DIR`` (K36; ``render_scale``, ``render_alpha``, ``render_boxes``) adds a last pass on rank 0 that writes one BEV frame
