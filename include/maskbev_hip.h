@@ -2078,6 +2078,64 @@ int mbv_fuse_frames(const int32_t* instance_maps, const int32_t* query_track, co
 int mbv_masks_from_map(const int32_t* maps, int32_t F, int32_t H, int32_t W, int32_t Q, uint32_t* masks_packed, int32_t* areas,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K40 — LAMB and (Nesterov) SGD over the flat parameter arena (csrc/optim_flat.hip, built with -ffp-contract=off; the
+ * arithmetic has one definition, csrc/adam.hpp).  Replaces: torch_optimizer.Lamb and torch.optim.SGD built by
+ * MaskBevModule.configure_optimizers (mask_bev/mask_bev_module.py:141-151).  Like K11 every pass streams the arena once with
+ * 16 B per lane, folds the 16-bit shadow refresh and the gradient clear in, allocates nothing, never synchronises with the
+ * host and can be captured in a graph.  All f32 arena arrays are 16-byte aligned, `shadow` (nullable) 8-byte aligned with
+ * shadow_dtype = MBV_DT_BF16 / MBV_DT_F16.  grad is multiplied by grad_scale first; loss_scale / skip_flag / applied_steps
+ * are K11's device scalars (all nullable): grad is divided by *loss_scale on the fly, and a non-zero *skip_flag means the
+ * gradient held inf / nan — parameters, optimizer state and shadow stay as they are and the gradient is cleared.
+ *
+ * LAMB, per parameter tensor (torch_optimizer 0.3.0 Lamb.step):
+ *   m = b1 m + (1 - b1) g        v = b2 v + (1 - b2) g g        u = m / (sqrt(v) + eps) + weight_decay p   (if weight_decay != 0)
+ *   wn = min(||p||, clamp_value)   un = ||u||   trust = 1 if wn == 0 or un == 0 else wn / un
+ *   p -= lr * bias_correction * trust * u,   bias_correction = sqrt(1 - b2^t) / (1 - b1^t) with debias, else 1
+ * The per-tensor norms come from a CHUNK TABLE the caller builds once and keeps on the device: every parameter's padded
+ * arena range [off, off + round_up(numel, 64)) cut into chunks of at most 4096 elements, a parameter's chunks consecutive,
+ * no chunk straddling two parameters; `chunks` holds n_chunks records (16-byte aligned), `param_chunks` n_params pairs
+ * (chunk_begin, chunk_end) of i32 (8-byte aligned).  start and len are multiples of 4, 0 < len <= 4096; a record that breaks
+ * this or reaches past n (the arena's element count) is skipped.  Padding elements must be zero in param, grad and both
+ * moments; they stay zero.  c0 <= c1 select the chunk range [c0, c1) of a launch (a run of parameter groups that share
+ * hyper-parameters).  beta1 / beta2 are f64 so that 1 - beta is rounded to f32 once, from the value the caller means (0.001
+ * for 0.999, where 1.0f - 0.999f is 1.3e-5 off) — what torch does with the Python scalar.
+ * mbv_lamb_moments: reads param, grad, exp_avg, exp_avg_sq; writes exp_avg, exp_avg_sq and u OVER grad (the gradient buffer
+ *   is the stash: mbv_lamb_apply clears it); partials (2, n_chunks) f32 receives, per chunk, the sum of p^2 (row 0) and of
+ *   u^2 (row 1), each reduced by one block in a fixed order — no float atomics, so the sums are bit-reproducible.  On a set
+ *   skip flag it changes nothing.
+ * mbv_lamb_trust: trust[i] (n_params f32) from the partials of parameter i, summed in a fixed order in f64, one block per
+ *   parameter.  After a skipped moments pass its output is meaningless (and unused).
+ * mbv_lamb_apply: reads param, u (in grad) and trust[param of chunk]; writes param, shadow and zeroes grad.  step >= 1 is the
+ *   1-based update count for debias (computed on the host in f64); with debias and applied_steps given, t = *applied_steps + 1
+ *   instead.  On a set skip flag it only zeroes grad.
+ * mbv_sgd_step: ONE pass over n elements, torch/optim/sgd.py's single-tensor order:
+ *   g += weight_decay p (if != 0);  buf = momentum buf + (1 - dampening) g;  g = g + momentum buf if nesterov else buf;
+ *   p -= lr g;  shadow refreshed; zero_grad=1 clears grad.  momentum_buf starts at zero, which equals torch's first-step
+ *   `buf = g` exactly when dampening == 0.  On a set skip flag only zero_grad is honoured.
+ * MBV_ERR_BAD_ARG: a null pointer other than the nullable ones, a misaligned array, a negative size, c0 < 0, c1 < c0,
+ *   c1 > n_chunks, step < 1, a beta outside [0, 1), a shadow whose dtype is neither MBV_DT_BF16 nor MBV_DT_F16.
+ */
+typedef struct mbv_lamb_chunk {
+  int64_t start;  /* first arena element of the chunk */
+  int32_t len;    /* elements */
+  int32_t param;  /* index of its parameter, in arena layout order */
+} mbv_lamb_chunk;
+
+int mbv_lamb_moments(const float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                     const mbv_lamb_chunk* chunks, int32_t n_chunks, int32_t c0, int32_t c1, float* partials, double beta1,
+                     double beta2, float eps, float weight_decay, float grad_scale, const float* loss_scale,
+                     const int32_t* skip_flag, void* stream);
+int mbv_lamb_trust(const float* partials, int32_t n_chunks, const int32_t* param_chunks, int32_t n_params,
+                   float clamp_value, float* trust, void* stream);
+int mbv_lamb_apply(float* param, float* grad, void* shadow, int32_t shadow_dtype, int64_t n, const mbv_lamb_chunk* chunks,
+                   int32_t n_chunks, int32_t c0, int32_t c1, const float* trust, int32_t n_params, float lr, double beta1,
+                   double beta2, int32_t debias, int64_t step, const int32_t* applied_steps, const int32_t* skip_flag,
+                   void* stream);
+int mbv_sgd_step(float* param, float* grad, float* momentum_buf, void* shadow, int32_t shadow_dtype, int64_t n, float lr,
+                 float momentum, float dampening, float weight_decay, int32_t nesterov, float grad_scale, int32_t zero_grad,
+                 const float* loss_scale, const int32_t* skip_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

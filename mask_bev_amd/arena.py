@@ -8,7 +8,8 @@ collapses into a handful of launches (K11, csrc/optim.hip):
                     all-reduce runs over contiguous chunks of it with no bucket copies;
 * ``shadow``  bf16 — the copy of the weights the bf16 GEMMs read, written by the optimizer kernel itself instead
                     of ≈ 450 per-layer cast kernels per step;
-* ``exp_avg``, ``exp_avg_sq`` f32 — Adam moments (owned by :class:`FlatAdam`).
+* ``exp_avg``, ``exp_avg_sq`` f32 — Adam moments (owned by :class:`FlatAdam`; :class:`FlatLamb` owns the same pair,
+                    :class:`FlatSGD` one momentum buffer — K40, csrc/optim_flat.hip).
 
 The arena is laid out in the reference's differential-lr groups — encoder, backbone, head
 (/root/reference: mask_bev/mask_bev_module.py:131-139) — each a contiguous segment, so an optimizer step is one
@@ -190,6 +191,61 @@ class LossScaler:
         self.growth_interval = int(sd.get('growth_interval', self.growth_interval))
 
 
+def _refuse_frozen(arena: ParameterArena, who: str):
+    frozen = [tuple(p.shape) for p, _ in arena.layout if not p.requires_grad]
+    if frozen:          # the single launch updates (and decays) every element of a segment; torch skips frozen ones
+        raise ValueError(f'{who} updates whole arena segments: {len(frozen)} frozen parameter(s) in the arena '
+                         f'(first shape {frozen[0]}); keep frozen parameters out of the arena')
+
+
+def _segment_groups(arena: ParameterArena, groups: List[dict]) -> List[dict]:
+    """torch ``param_groups`` over arena segments: one flat parameter per group, the segment's name kept."""
+    pgs = []
+    for g in groups:
+        a, b = arena.segments[g['segment']]
+        flat = nn.Parameter(arena.param[a:b], requires_grad=True)
+        flat.grad = arena.grad[a:b]
+        pg = {k: v for k, v in g.items() if k != 'segment'}
+        pg['params'] = [flat]
+        pg['segment'] = g['segment']
+        pgs.append(pg)
+    return pgs
+
+
+def _merged_runs(arena: ParameterArena, param_groups: List[dict], hyper) -> List[list]:
+    """[[a, b, hp], ...]: adjacent groups whose ``hyper(pg)`` tuples are equal share one launch over [a, b)."""
+    runs: List[list] = []
+    for pg in param_groups:
+        a, b = arena.segments[pg['segment']]
+        hp = hyper(pg)
+        if runs and runs[-1][2] == hp and runs[-1][1] == a:
+            runs[-1][1] = b
+        else:
+            runs.append([a, b, hp])
+    return runs
+
+
+def _load_per_parameter_state(arena: ParameterArena, state: dict, fields: Dict[str, torch.Tensor], what: str) -> int:
+    """Map a per-parameter torch optimizer state (numbered in module.parameters() order = the order of the arena layout)
+    onto flat buffers: ``fields`` = {state key: flat destination}.  Returns the largest ``step`` found (0 without one)."""
+    if len(state) != len(arena.layout):
+        raise ValueError(f'optimizer state has {len(state)} parameters, the arena {len(arena.layout)}: '
+                         f'cannot map a per-parameter {what} state onto the arena')
+    steps = 0
+    with torch.no_grad():
+        for idx, (p, o) in enumerate(arena.layout):
+            st = state[idx] if idx in state else state[str(idx)]
+            n = p.numel()
+            for key, flat in fields.items():
+                if tuple(st[key].shape) != tuple(p.shape):
+                    raise ValueError(f'optimizer state {idx} has shape {tuple(st[key].shape)}, '
+                                     f'parameter {tuple(p.shape)}')
+                flat[o:o + n].copy_(st[key].reshape(-1))
+            if 'step' in st:
+                steps = max(steps, int(st['step']))
+    return steps
+
+
 class FlatAdam(torch.optim.Optimizer):
     """Adam / AdamW over a :class:`ParameterArena`: one ``mbv_adamw_step`` launch per parameter group.
 
@@ -211,19 +267,8 @@ class FlatAdam(torch.optim.Optimizer):
         self.decoupled = decoupled
         self.zero_grad_in_step = zero_grad
         self.grad_scale = 1.0
-        frozen = [tuple(p.shape) for p, _ in arena.layout if not p.requires_grad]
-        if frozen:          # the single launch updates (and decays) every element of a segment; torch skips frozen ones
-            raise ValueError(f'FlatAdam updates whole arena segments: {len(frozen)} frozen parameter(s) in the arena '
-                             f'(first shape {frozen[0]}); keep frozen parameters out of the arena')
-        pgs = []
-        for g in groups:
-            a, b = arena.segments[g['segment']]
-            flat = nn.Parameter(arena.param[a:b], requires_grad=True)
-            flat.grad = arena.grad[a:b]
-            pg = {k: v for k, v in g.items() if k != 'segment'}
-            pg['params'] = [flat]
-            pg['segment'] = g['segment']
-            pgs.append(pg)
+        _refuse_frozen(arena, 'FlatAdam')
+        pgs = _segment_groups(arena, groups)
         super().__init__(pgs, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.exp_avg = torch.zeros_like(arena.param)
         self.exp_avg_sq = torch.zeros_like(arena.param)
@@ -296,15 +341,8 @@ class FlatAdam(torch.optim.Optimizer):
         self.steps += 1
         stream = torch.cuda.current_stream(ar.device).cuda_stream
         # fuse adjacent groups with the same hyper-parameters into one launch
-        runs: List[list] = []
-        for pg in self.param_groups:
-            a, b = ar.segments[pg['segment']]
-            hp = (float(pg['lr']), float(pg['betas'][0]), float(pg['betas'][1]), float(pg['eps']),
-                  float(pg['weight_decay']))
-            if runs and runs[-1][2] == hp and runs[-1][1] == a:
-                runs[-1][1] = b
-            else:
-                runs.append([a, b, hp])
+        runs = _merged_runs(ar, self.param_groups, lambda pg: (float(pg['lr']), float(pg['betas'][0]), float(pg['betas'][1]),
+                                                               float(pg['eps']), float(pg['weight_decay'])))
         if self._k3_applied:
             # K3's backward already updated these two parameters (and left their gradient range untouched: zero): cut their
             # element ranges out of the launches
@@ -369,21 +407,8 @@ class FlatAdam(torch.optim.Optimizer):
         elif sd.get('state'):
             # a torch.optim.Adam / AdamW state_dict (the reference's checkpoints, or a run saved without the arena):
             # its parameters are numbered in module.parameters() order = the order of the arena layout
-            state = sd['state']
-            if len(state) != len(self.arena.layout):
-                raise ValueError(f'optimizer state has {len(state)} parameters, the arena {len(self.arena.layout)}: '
-                                 'cannot map a per-parameter Adam state onto the arena')
-            steps = 0
-            with torch.no_grad():
-                for idx, (p, o) in enumerate(self.arena.layout):
-                    st = state[idx] if idx in state else state[str(idx)]
-                    if tuple(st['exp_avg'].shape) != tuple(p.shape):
-                        raise ValueError(f'optimizer state {idx} has shape {tuple(st["exp_avg"].shape)}, '
-                                         f'parameter {tuple(p.shape)}')
-                    n = p.numel()
-                    self.exp_avg[o:o + n].copy_(st['exp_avg'].reshape(-1))
-                    self.exp_avg_sq[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
-                    steps = max(steps, int(st['step']))
+            steps = _load_per_parameter_state(self.arena, sd['state'], dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq),
+                                              'Adam')
             self.steps = steps
             if self.scaler is not None:
                 self.scaler.applied_steps.fill_(steps)
@@ -391,3 +416,222 @@ class FlatAdam(torch.optim.Optimizer):
             for k in ('lr', 'betas', 'eps', 'weight_decay'):
                 if k in saved:
                     pg[k] = saved[k]
+
+
+LAMB_CHUNK = 4096    # elements per chunk of the LAMB chunk table (kChunk of csrc/optim_flat.hip)
+
+
+class FlatLamb(torch.optim.Optimizer):
+    """LAMB over a :class:`ParameterArena` (K40, csrc/optim_flat.hip): the rule of ``torch_optimizer.Lamb`` — the Adam
+    direction ``u = m / (sqrt(v) + eps) + weight_decay * p`` scaled per parameter TENSOR by the trust ratio
+    ``min(||p||, clamp_value) / ||u||`` — in three kinds of launch whatever the number of tensors: ``mbv_lamb_moments``
+    (moments, ``u`` and per-chunk partial sums of ``p²`` and ``u²``), ``mbv_lamb_trust`` (one ratio per tensor) and
+    ``mbv_lamb_apply`` (update, 16-bit shadow, gradient clear).  The per-tensor norms come from a chunk table built here
+    once (every parameter's padded range cut into chunks of ``LAMB_CHUNK`` elements) and a partial slab; no float atomics,
+    so a step is bit-reproducible and replays from a graph.
+
+    Same ``param_groups`` contract as :class:`FlatAdam` (the schedulers drive ``lr``; adjacent groups with equal
+    hyper-parameters share a launch), same :class:`LossScaler` and ``grad_scale`` conventions.  ``zero_grad_in_step`` is
+    always true: the moments pass stashes ``u`` in the gradient buffer and the apply pass clears it, so the gradient does
+    not survive a step.  There is no ``fuse_layernorm_affine``: the trust ratio needs the whole tensor's norm, which K3's
+    backward does not have.  ``trust_ratio`` holds the last step's ratio of every arena parameter, in layout order."""
+
+    def __init__(self, arena: ParameterArena, groups: List[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.0, clamp_value: float = 10.0, debias: bool = False,
+                 scaler: Optional[LossScaler] = None):
+        if arena.device.type != 'cuda':
+            raise _lib.MaskBevHipError('FlatLamb runs on the MI355X only (mbv_lamb_moments)')
+        self.arena = arena
+        self.scaler = scaler
+        self.clamp_value = float(clamp_value)
+        self.debias = bool(debias)
+        self.zero_grad_in_step = True
+        self.grad_scale = 1.0
+        _refuse_frozen(arena, 'FlatLamb')
+        super().__init__(_segment_groups(arena, groups), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.exp_avg = torch.zeros_like(arena.param)
+        self.exp_avg_sq = torch.zeros_like(arena.param)
+        self.steps = 0
+        # chunk table: (start, len | param << 32) per chunk = mbv_lamb_chunk; [chunk_begin, chunk_end) per parameter
+        import numpy as np
+        recs, ranges = [], []
+        self._chunk_at: Dict[int, int] = {}            # arena offset of a parameter (or the arena's end) -> its first chunk
+        for i, (p, o) in enumerate(arena.layout):
+            self._chunk_at[o] = len(recs)
+            end = o + _round_up(p.numel(), _ALIGN)
+            begin = len(recs)
+            for s in range(o, end, LAMB_CHUNK):
+                recs.append((s, min(LAMB_CHUNK, end - s), i))
+            ranges.append((begin, len(recs)))
+        self._chunk_at[arena.numel] = len(recs)
+        table = np.zeros(len(recs), dtype=np.dtype([('start', '<i8'), ('len', '<i4'), ('param', '<i4')]))
+        for k, name in enumerate(('start', 'len', 'param')):
+            table[name] = [r[k] for r in recs]
+        self.n_chunks, self.n_params = len(recs), len(ranges)
+        self._chunks = torch.from_numpy(table.view(np.int64).reshape(-1, 2).copy()).to(arena.device)
+        self._param_chunks = torch.tensor(ranges, dtype=torch.int32).reshape(-1, 2).to(arena.device)
+        self._partials = torch.zeros(2, max(1, self.n_chunks), dtype=torch.float32, device=arena.device)
+        self.trust_ratio = torch.ones(self.n_params, dtype=torch.float32, device=arena.device)
+
+    def _chunk_range(self, a: int, b: int) -> Tuple[int, int]:
+        """Chunks of the element range [a, b), whose ends are parameter boundaries (segments are)."""
+        return self._chunk_at[a], self._chunk_at[b]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        ar = self.arena
+        ops.note_parameters_changed()          # cached per-weight records (K20's absmax words) die with this update
+        lib = _lib.load()
+        self.steps += 1
+        stream = torch.cuda.current_stream(ar.device).cuda_stream
+        sc = self.scaler
+        scale = 0 if sc is None else sc.scale.data_ptr()
+        flag = 0 if sc is None else sc.flag.data_ptr()
+        applied = 0 if sc is None else sc.applied_steps.data_ptr()
+        if sc is not None:
+            sc.check(ar.grad)
+        hint = _lib.WORK_HINT.setdefault('lamb_elems', {})
+        # the learning rate only enters the apply pass: the moments passes merge over it
+        for a, b, (b1, b2, eps, wd) in _merged_runs(ar, self.param_groups, lambda pg: (
+                float(pg['betas'][0]), float(pg['betas'][1]), float(pg['eps']), float(pg['weight_decay']))):
+            c0, c1 = self._chunk_range(a, b)
+            hint[(c0, c1)] = b - a
+            with ops.TIMER.span('k_lamb_moments'):
+                check(lib.mbv_lamb_moments(ar.param.data_ptr(), ar.grad.data_ptr(), self.exp_avg.data_ptr(),
+                                           self.exp_avg_sq.data_ptr(), ar.numel, self._chunks.data_ptr(), self.n_chunks,
+                                           c0, c1, self._partials.data_ptr(), b1, b2, eps, wd, float(self.grad_scale),
+                                           scale, flag, stream), 'mbv_lamb_moments')
+        with ops.TIMER.span('k_lamb_trust'):
+            check(lib.mbv_lamb_trust(self._partials.data_ptr(), self.n_chunks, self._param_chunks.data_ptr(), self.n_params,
+                                     self.clamp_value, self.trust_ratio.data_ptr(), stream), 'mbv_lamb_trust')
+        sh = 0 if ar.shadow is None else ar.shadow.data_ptr()
+        for a, b, (lr, b1, b2) in _merged_runs(ar, self.param_groups, lambda pg: (
+                float(pg['lr']), float(pg['betas'][0]), float(pg['betas'][1]))):
+            c0, c1 = self._chunk_range(a, b)
+            hint[(c0, c1)] = b - a
+            with ops.TIMER.span('k_lamb_apply'):
+                check(lib.mbv_lamb_apply(ar.param.data_ptr(), ar.grad.data_ptr(), sh, ar.shadow_flag, ar.numel,
+                                         self._chunks.data_ptr(), self.n_chunks, c0, c1, self.trust_ratio.data_ptr(),
+                                         self.n_params, lr, b1, b2, 1 if self.debias else 0, self.steps, applied, flag,
+                                         stream), 'mbv_lamb_apply')
+        if sc is not None:
+            sc.update()
+        return loss
+
+    def zero_grad(self, set_to_none: bool = False):
+        """Gradients live in the arena and ``step()`` has cleared them."""
+
+    def state_dict(self):
+        sd = super().state_dict()
+        steps = self.steps if self.scaler is None else int(self.scaler.applied_steps.item())
+        sd['flat_state'] = dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, steps=steps, kind='lamb')
+        if self.scaler is not None:
+            sd['loss_scaler'] = self.scaler.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        if self.scaler is not None and sd.get('loss_scaler') is not None:
+            self.scaler.load_state_dict(sd['loss_scaler'])
+        flat = sd.get('flat_state')
+        if flat is not None:
+            if flat.get('kind', 'lamb') != 'lamb':
+                raise ValueError(f"flat optimizer state of kind {flat.get('kind')!r} cannot be loaded into FlatLamb")
+            self.exp_avg.copy_(flat['exp_avg'])
+            self.exp_avg_sq.copy_(flat['exp_avg_sq'])
+            self.steps = int(flat['steps'])
+        elif sd.get('state'):
+            # a per-parameter Lamb state (optimizers.Lamb / torch_optimizer.Lamb: step, exp_avg, exp_avg_sq)
+            self.steps = _load_per_parameter_state(self.arena, sd['state'],
+                                                   dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq), 'Lamb')
+        if self.scaler is not None and (flat is not None or sd.get('state')):
+            self.scaler.applied_steps.fill_(self.steps)
+        for pg, saved in zip(self.param_groups, sd.get('param_groups', [])):
+            for k in ('lr', 'betas', 'eps', 'weight_decay'):
+                if k in saved:
+                    pg[k] = saved[k]
+
+
+class FlatSGD(torch.optim.Optimizer):
+    """SGD with (Nesterov) momentum over a :class:`ParameterArena` (K40): one ``mbv_sgd_step`` launch over the whole arena
+    in ``torch.optim.SGD``'s single-tensor order, with the 16-bit shadow refresh and the gradient clear folded in and the
+    :class:`LossScaler` / ``grad_scale`` conventions of :class:`FlatAdam`.
+
+    ONE group over the whole arena: the reference builds its SGD from ``self.parameters()`` and so ignores
+    ``differential_lr`` (mask_bev_module.py:145-147); that quirk is kept.  One moment buffer, zero-initialised — equal to
+    torch's first-step ``buf = grad`` exactly when ``dampening`` is 0; with a non-zero ``dampening`` the first step's
+    buffer is ``(1 - dampening) * grad``."""
+
+    def __init__(self, arena: ParameterArena, lr: float = 1e-3, momentum: float = 0.99, dampening: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = True, zero_grad: bool = True,
+                 scaler: Optional[LossScaler] = None):
+        if arena.device.type != 'cuda':
+            raise _lib.MaskBevHipError('FlatSGD runs on the MI355X only (mbv_sgd_step)')
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        self.arena = arena
+        self.scaler = scaler
+        self.zero_grad_in_step = zero_grad
+        self.grad_scale = 1.0
+        _refuse_frozen(arena, 'FlatSGD')
+        flat = nn.Parameter(arena.param, requires_grad=True)
+        flat.grad = arena.grad
+        super().__init__([flat], dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov))
+        self.momentum_buffer = torch.zeros_like(arena.param)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        ar = self.arena
+        ops.note_parameters_changed()
+        lib = _lib.load()
+        sc = self.scaler
+        if sc is not None:
+            sc.check(ar.grad)
+        pg = self.param_groups[0]
+        with ops.TIMER.span('k_sgd'):
+            check(lib.mbv_sgd_step(ar.param.data_ptr(), ar.grad.data_ptr(), self.momentum_buffer.data_ptr(),
+                                   0 if ar.shadow is None else ar.shadow.data_ptr(), ar.shadow_flag, ar.numel,
+                                   float(pg['lr']), float(pg['momentum']), float(pg['dampening']),
+                                   float(pg['weight_decay']), 1 if pg['nesterov'] else 0, float(self.grad_scale),
+                                   1 if self.zero_grad_in_step else 0, 0 if sc is None else sc.scale.data_ptr(),
+                                   0 if sc is None else sc.flag.data_ptr(),
+                                   torch.cuda.current_stream(ar.device).cuda_stream), 'mbv_sgd_step')
+        if sc is not None:
+            sc.update()
+        return loss
+
+    def zero_grad(self, set_to_none: bool = False):
+        """Gradients live in the arena: clear in place (``step()`` already did when ``zero_grad=True``)."""
+        if not self.zero_grad_in_step:
+            self.arena.zero_grad()
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd['flat_state'] = dict(momentum_buffer=self.momentum_buffer, kind='sgd')
+        if self.scaler is not None:
+            sd['loss_scaler'] = self.scaler.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        if self.scaler is not None and sd.get('loss_scaler') is not None:
+            self.scaler.load_state_dict(sd['loss_scaler'])
+        flat = sd.get('flat_state')
+        if flat is not None:
+            if flat.get('kind', 'sgd') != 'sgd':
+                raise ValueError(f"flat optimizer state of kind {flat.get('kind')!r} cannot be loaded into FlatSGD")
+            self.momentum_buffer.copy_(flat['momentum_buffer'])
+        elif sd.get('state'):
+            # a torch.optim.SGD state_dict: momentum_buffer per parameter, in module.parameters() order
+            _load_per_parameter_state(self.arena, sd['state'], dict(momentum_buffer=self.momentum_buffer), 'SGD')
+        for k in ('lr', 'momentum', 'dampening', 'weight_decay', 'nesterov'):
+            for saved in sd.get('param_groups', [])[:1]:
+                if k in saved:
+                    self.param_groups[0][k] = saved[k]

@@ -1,4 +1,4 @@
-// AdamW arithmetic shared by K11's optimizer pass (optim.hip) and K3's backward with the update of the (C, ny, nx)
+// Optimizer arithmetic.  AdamW: shared by K11's optimizer pass (optim.hip) and K3's backward with the update of the (C, ny, nx)
 // LayerNorm affine fused into it (scatter_layernorm.hip): ONE definition, so the two paths are bit-identical.
 // Follows torch/optim/adamw.py's single-tensor update order (mask_bev/mask_bev_module.py:131-166 configures it).
 #pragma once
@@ -34,4 +34,48 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   v = v * a.beta2 + (1.0f - a.beta2) * g * g;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
   const float denom = sqrtf(v) / a.bias_correction2_sqrt + a.eps;
   p -= (a.lr / a.bias_correction1) * (m / denom);
+}
+
+// ---- K40: LAMB and (Nesterov) SGD over the arena (optim_flat.hip) ------------------------------------------------------
+// LAMB as torch_optimizer 0.3.0's Lamb.step states it, cut where the per-tensor norms are needed: the moments pass leaves
+// u = m / (sqrt(v) + eps) + wd * p, the apply pass takes p -= (step_size * trust) * u.  Contraction pinned off as above.
+struct LambArgs {
+  // 1 - beta is taken in f64 from the f64 betas of the entry point and rounded once, as torch rounds the Python scalar:
+  // 1.0f - 0.999f is 0.99998713e-3, 1.3e-5 away from the 0.001 the rule means
+  float beta1, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, grad_scale;
+  const float* loss_scale;         // as AdamArgs
+  const int* skip;
+};
+
+__device__ __forceinline__ float lamb_moments_one(float p, float g, float& m, float& v, const LambArgs& a) {
+#pragma clang fp contract(off)
+  g *= a.grad_scale;
+  m = m * a.beta1 + a.one_minus_beta1 * g;        // exp_avg.mul_(beta1).add_(grad, alpha=1 - beta1)
+  v = v * a.beta2 + a.one_minus_beta2 * g * g;    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+  float u = m / (sqrtf(v) + a.eps);               // exp_avg / exp_avg_sq.sqrt().add(eps)
+  if (a.weight_decay != 0.0f) u += a.weight_decay * p;
+  return u;
+}
+
+__device__ __forceinline__ float lamb_apply_one(float p, float u, float scaled_step) {
+#pragma clang fp contract(off)
+  return p - scaled_step * u;                     // p.add_(adam_step, alpha=-step_size * trust_ratio)
+}
+
+// torch/optim/sgd.py's single-tensor order; the momentum buffer starts at zero, which gives torch's first-step `buf = grad`
+// exactly when dampening is 0 (momentum * 0 + grad == grad)
+struct SgdArgs {
+  float lr, momentum, one_minus_dampening, weight_decay, grad_scale;
+  int nesterov, zero_grad, shadow_kind;
+  const float* loss_scale;
+  const int* skip;
+};
+
+__device__ __forceinline__ void sgd_one(float& p, float g, float& buf, const SgdArgs& a) {
+#pragma clang fp contract(off)
+  g *= a.grad_scale;
+  if (a.weight_decay != 0.0f) g += a.weight_decay * p;      // grad.add(param, alpha=weight_decay)
+  buf = buf * a.momentum + a.one_minus_dampening * g;       // buf.mul_(momentum).add_(grad, alpha=1 - dampening)
+  g = a.nesterov ? g + a.momentum * buf : buf;              // grad.add(buf, alpha=momentum) / grad = buf
+  p -= a.lr * g;                                            // param.add_(grad, alpha=-lr)
 }

@@ -1,0 +1,286 @@
+// K40 — LAMB and (Nesterov) SGD over the flat parameter arena (HBM-bound, no MFMA; K11's k_adamw is the model).
+//
+//   mbv_lamb_moments    reads param, grad, exp_avg, exp_avg_sq (16 B/elem), writes exp_avg, exp_avg_sq and the un-scaled update
+//                       u over grad (12 B/elem); per chunk the block-reduced sums of p^2 and u^2 go to a partial slab.
+//   mbv_lamb_trust      per parameter: the partials summed in a fixed order in f64 -> trust ratio (f32).
+//   mbv_lamb_apply      reads param, u (8 B/elem), writes param, the 16-bit shadow and the zeroed gradient (10 B/elem).
+//   mbv_sgd_step        one pass: reads param, grad, momentum buffer (12 B), writes param, buffer, shadow, zeroed grad (14 B).
+//
+// A LAMB step is 28 + 18 = 46 B/elem against k_adamw's 34; SGD is 26.  The per-tensor norms of LAMB come from a CHUNK TABLE
+// built once by the host: every parameter's padded arena range is cut into chunks of kChunk = 4096 elements (a chunk never
+// straddles two parameters; the last chunk of a parameter is shorter, a multiple of 64).  One block works on one chunk at a
+// time, so a chunk's two sums are taken in one fixed order whatever the grid — no float atomics, bit-reproducible, replayable.
+//
+// Reference: torch_optimizer 0.3.0 Lamb.step and torch/optim/sgd.py `_single_tensor_sgd`, as configured at
+// mask_bev/mask_bev_module.py:141-151; the arithmetic itself is in adam.hpp.
+#include "common.hpp"
+#include "adam.hpp"
+
+namespace {
+
+constexpr int kChunk = 4096;            // elements per chunk: 4 float4 per lane of a 256-thread block
+constexpr int kMaxBlocks = 256 * 16;    // 16 blocks per CU, grid-stride beyond (as k_adamw)
+
+struct ChunkRec {                       // = mbv_lamb_chunk (maskbev_hip.h)
+  long start;                           // first arena element, a multiple of 4
+  int len;                              // elements, a multiple of 4, 0 < len <= kChunk
+  int param;                            // index of the parameter the chunk belongs to
+};
+static_assert(sizeof(ChunkRec) == 16, "chunk records are 16 bytes");
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef unsigned short us4 __attribute__((ext_vector_type(4)));
+
+// a record that would reach outside the arena (a corrupted table) is skipped, never followed
+__device__ __forceinline__ bool chunk_ok(const ChunkRec& r, long n) {
+  return r.start >= 0 && r.len > 0 && r.len <= kChunk && ((r.start | r.len) & 3) == 0 && r.start + r.len <= n;
+}
+
+// sums of (a, b) over the 256 threads of the block in one fixed order: xor-butterfly inside a wave, then the four waves
+__device__ __forceinline__ float2 block_sum2(float a, float b, float2* lds) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+  }
+  __syncthreads();                      // the previous chunk's readers are done with lds
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = make_float2(a, b);
+  __syncthreads();
+  return make_float2((lds[0].x + lds[1].x) + (lds[2].x + lds[3].x), (lds[0].y + lds[1].y) + (lds[2].y + lds[3].y));
+}
+
+__global__ void __launch_bounds__(256) k_lamb_moments(const float* __restrict__ param, float* __restrict__ grad,
+                                                      float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, long n,
+                                                      const ChunkRec* __restrict__ chunks, int n_chunks, int c0, int c1,
+                                                      float* __restrict__ partials, LambArgs a) {
+  __shared__ float2 lds[4];
+  if (a.skip && *a.skip) return;        // overflowed step: moments stay, grad keeps the raw gradient (the apply pass drops it)
+  if (a.loss_scale) a.grad_scale /= *a.loss_scale;
+  for (int c = c0 + blockIdx.x; c < c1; c += gridDim.x) {
+    const ChunkRec r = chunks[c];
+    float sp = 0.f, su = 0.f;
+    if (chunk_ok(r, n)) {
+      const long base = r.start >> 2;
+      const int n4 = r.len >> 2;
+      // every array is touched once per step and is far larger than the caches: non-temporal, as k_adamw
+      for (int i = threadIdx.x; i < n4; i += 256) {
+        const f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + base + i);
+        f4 g = __builtin_nontemporal_load(reinterpret_cast<const f4*>(grad) + base + i);
+        f4 m = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg) + base + i);
+        f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg_sq) + base + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float mc = m[k], vc = v[k];
+          const float u = lamb_moments_one(p[k], g[k], mc, vc, a);
+          m[k] = mc; v[k] = vc; g[k] = u;
+          sp += p[k] * p[k];
+          su += u * u;
+        }
+        __builtin_nontemporal_store(m, reinterpret_cast<f4*>(exp_avg) + base + i);
+        __builtin_nontemporal_store(v, reinterpret_cast<f4*>(exp_avg_sq) + base + i);
+        __builtin_nontemporal_store(g, reinterpret_cast<f4*>(grad) + base + i);      // u: read once more, by the apply pass
+      }
+    }
+    const float2 s = block_sum2(sp, su, lds);
+    if (threadIdx.x == 0) {
+      partials[c] = s.x;
+      partials[(long)n_chunks + c] = s.y;
+    }
+  }
+}
+
+// one block per parameter: its chunks' partials in f64, thread t takes chunks t, t + 256, ...; then a fixed tree
+__global__ void __launch_bounds__(256) k_lamb_trust(const float* __restrict__ partials, int n_chunks,
+                                                    const int2* __restrict__ param_chunks, float clamp_value,
+                                                    float* __restrict__ trust) {
+  __shared__ double lp[256], lu[256];
+  const int2 range = param_chunks[blockIdx.x];
+  const int cb = range.x < 0 ? 0 : range.x, ce = range.y > n_chunks ? n_chunks : range.y;
+  double sp = 0.0, su = 0.0;
+  for (int c = cb + threadIdx.x; c < ce; c += 256) {
+    sp += (double)partials[c];
+    su += (double)partials[(long)n_chunks + c];
+  }
+  lp[threadIdx.x] = sp; lu[threadIdx.x] = su;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) { lp[threadIdx.x] += lp[threadIdx.x + w]; lu[threadIdx.x] += lu[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double wn = fmin(sqrt(lp[0]), (double)clamp_value), un = sqrt(lu[0]);
+    trust[blockIdx.x] = (wn == 0.0 || un == 0.0) ? 1.f : (float)(wn / un);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_lamb_apply(float* __restrict__ param, float* __restrict__ grad,
+                                                    unsigned short* __restrict__ shadow, int shadow_kind, long n,
+                                                    const ChunkRec* __restrict__ chunks, int c0, int c1,
+                                                    const float* __restrict__ trust, int n_params, float step_size,
+                                                    float lr, double beta1, double beta2, const int* __restrict__ applied,
+                                                    const int* __restrict__ skip) {
+  const bool skipped = skip && *skip;
+  if (applied) {                        // debias from the device-side count of applied updates (as k_adamw)
+    const double t = (double)(*applied + 1);
+    step_size = (float)((double)lr * sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t)));
+  }
+  const f4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (int c = c0 + blockIdx.x; c < c1; c += gridDim.x) {
+    const ChunkRec r = chunks[c];
+    if (!chunk_ok(r, n) || r.param < 0 || r.param >= n_params) continue;
+    const long base = r.start >> 2;
+    const int n4 = r.len >> 2;
+    if (skipped) {                      // overflowed step: parameters and shadow stay, the gradient is dropped
+      for (int i = threadIdx.x; i < n4; i += 256) __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + base + i);
+      continue;
+    }
+    const float scaled = step_size * trust[r.param];
+    for (int i = threadIdx.x; i < n4; i += 256) {
+      f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + base + i);
+      const f4 u = __builtin_nontemporal_load(reinterpret_cast<const f4*>(grad) + base + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) p[k] = lamb_apply_one(p[k], u[k], scaled);
+      __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + base + i);
+      if (shadow) {
+        us4 s;
+        s.x = shadow_bits(p.x, shadow_kind); s.y = shadow_bits(p.y, shadow_kind);
+        s.z = shadow_bits(p.z, shadow_kind); s.w = shadow_bits(p.w, shadow_kind);
+        reinterpret_cast<us4*>(shadow)[base + i] = s;     // (read again by the next forward: a normal store)
+      }
+      __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + base + i);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_sgd(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ buf,
+                                             unsigned short* __restrict__ shadow, long n, SgdArgs a) {
+  const long n4 = n >> 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long t = (n4 << 2) + first;     // ragged tail (< 4 elements)
+  if (a.loss_scale) a.grad_scale /= *a.loss_scale;
+  const f4 zero = {0.f, 0.f, 0.f, 0.f};
+  if (a.skip && *a.skip) {              // overflowed step: parameters, buffer and shadow stay; the gradient is dropped
+    if (a.zero_grad) {
+      for (long i = first; i < n4; i += stride) __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + i);
+      if (t < n) grad[t] = 0.f;
+    }
+    return;
+  }
+  for (long i = first; i < n4; i += stride) {
+    f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + i);
+    const f4 g = __builtin_nontemporal_load(reinterpret_cast<const f4*>(grad) + i);
+    f4 b = __builtin_nontemporal_load(reinterpret_cast<const f4*>(buf) + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pc = p[k], bc = b[k];
+      sgd_one(pc, g[k], bc, a);
+      p[k] = pc; b[k] = bc;
+    }
+    __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + i);
+    __builtin_nontemporal_store(b, reinterpret_cast<f4*>(buf) + i);
+    if (shadow) {
+      us4 s;
+      s.x = shadow_bits(p.x, a.shadow_kind); s.y = shadow_bits(p.y, a.shadow_kind);
+      s.z = shadow_bits(p.z, a.shadow_kind); s.w = shadow_bits(p.w, a.shadow_kind);
+      reinterpret_cast<us4*>(shadow)[i] = s;
+    }
+    if (a.zero_grad) __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + i);
+  }
+  if (t < n) {
+    float p = param[t], b = buf[t];
+    sgd_one(p, grad[t], b, a);
+    param[t] = p; buf[t] = b;
+    if (shadow) shadow[t] = shadow_bits(p, a.shadow_kind);
+    if (a.zero_grad) grad[t] = 0.f;
+  }
+}
+
+inline bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c) |
+           reinterpret_cast<size_t>(d)) & 15) != 0;
+}
+
+inline unsigned chunk_grid(int c0, int c1) {
+  const int blocks = c1 - c0 < kMaxBlocks ? c1 - c0 : kMaxBlocks;
+  return (unsigned)blocks;
+}
+
+}  // namespace
+
+extern "C" int mbv_lamb_moments(const float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                const mbv_lamb_chunk* chunks, int32_t n_chunks, int32_t c0, int32_t c1, float* partials,
+                                double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                                const float* loss_scale, const int32_t* skip_flag, void* stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !chunks || !partials || n < 0 || n_chunks < 0) return MBV_ERR_BAD_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return MBV_ERR_BAD_ARG;
+  if (c0 < 0 || c1 < c0 || c1 > n_chunks) return MBV_ERR_BAD_ARG;
+  if (misaligned16(param, grad, exp_avg, exp_avg_sq) || misaligned16(chunks) || (reinterpret_cast<size_t>(partials) & 3))
+    return MBV_ERR_BAD_ARG;
+  if (c1 == c0) return MBV_OK;
+  LambArgs a;
+  a.beta1 = (float)beta1; a.beta2 = (float)beta2;
+  a.one_minus_beta1 = (float)(1.0 - beta1); a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = eps; a.weight_decay = weight_decay; a.grad_scale = grad_scale;
+  a.loss_scale = loss_scale; a.skip = skip_flag;
+  hipLaunchKernelGGL(k_lamb_moments, dim3(chunk_grid(c0, c1)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (long)n, reinterpret_cast<const ChunkRec*>(chunks), n_chunks, c0, c1, partials, a);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_lamb_trust(const float* partials, int32_t n_chunks, const int32_t* param_chunks, int32_t n_params,
+                              float clamp_value, float* trust, void* stream) {
+  if (!partials || !param_chunks || !trust || n_chunks < 0 || n_params < 0) return MBV_ERR_BAD_ARG;
+  if ((reinterpret_cast<size_t>(partials) & 3) || (reinterpret_cast<size_t>(param_chunks) & 7) ||
+      (reinterpret_cast<size_t>(trust) & 3))
+    return MBV_ERR_BAD_ARG;
+  if (n_params == 0) return MBV_OK;
+  hipLaunchKernelGGL(k_lamb_trust, dim3((unsigned)n_params), dim3(256), 0, (hipStream_t)stream, partials, n_chunks,
+                     reinterpret_cast<const int2*>(param_chunks), clamp_value, trust);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_lamb_apply(float* param, float* grad, void* shadow, int32_t shadow_dtype, int64_t n,
+                              const mbv_lamb_chunk* chunks, int32_t n_chunks, int32_t c0, int32_t c1, const float* trust,
+                              int32_t n_params, float lr, double beta1, double beta2, int32_t debias, int64_t step,
+                              const int32_t* applied_steps, const int32_t* skip_flag, void* stream) {
+  if (!param || !grad || !chunks || !trust || n < 0 || n_chunks < 0 || n_params < 0 || step < 1) return MBV_ERR_BAD_ARG;
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return MBV_ERR_BAD_ARG;
+  if (c0 < 0 || c1 < c0 || c1 > n_chunks) return MBV_ERR_BAD_ARG;
+  if (misaligned16(param, grad, chunks) || (reinterpret_cast<size_t>(trust) & 3)) return MBV_ERR_BAD_ARG;
+  if (shadow && (reinterpret_cast<size_t>(shadow) & 7)) return MBV_ERR_BAD_ARG;
+  if (shadow && shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
+  if (c1 == c0) return MBV_OK;
+  float step_size = lr;
+  if (debias)
+    step_size = (float)((double)lr * sqrt(1.0 - pow(beta2, (double)step)) / (1.0 - pow(beta1, (double)step)));
+  hipLaunchKernelGGL(k_lamb_apply, dim3(chunk_grid(c0, c1)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     reinterpret_cast<unsigned short*>(shadow), shadow_dtype, (long)n,
+                     reinterpret_cast<const ChunkRec*>(chunks), c0, c1, trust, n_params, step_size, lr, beta1, beta2,
+                     debias ? applied_steps : nullptr, skip_flag);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_sgd_step(float* param, float* grad, float* momentum_buf, void* shadow, int32_t shadow_dtype, int64_t n,
+                            float lr, float momentum, float dampening, float weight_decay, int32_t nesterov,
+                            float grad_scale, int32_t zero_grad, const float* loss_scale, const int32_t* skip_flag,
+                            void* stream) {
+  if (n < 0 || !param || !grad || !momentum_buf) return MBV_ERR_BAD_ARG;
+  if (n == 0) return MBV_OK;
+  if (misaligned16(param, grad, momentum_buf)) return MBV_ERR_BAD_ARG;
+  if (shadow && (reinterpret_cast<size_t>(shadow) & 7)) return MBV_ERR_BAD_ARG;
+  if (shadow && shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
+  SgdArgs a;
+  a.lr = lr; a.momentum = momentum; a.one_minus_dampening = 1.0f - dampening; a.weight_decay = weight_decay;
+  a.grad_scale = grad_scale; a.nesterov = nesterov; a.zero_grad = zero_grad; a.shadow_kind = shadow_dtype;
+  a.loss_scale = loss_scale; a.skip = skip_flag;
+  long blocks = ((n >> 2) + 255) / 256;
+  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_sgd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf,
+                     reinterpret_cast<unsigned short*>(shadow), (long)n, a);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}

@@ -314,6 +314,14 @@ def gemm_work(m: int, n: int, k: int, batch: int, es_in: float, es_out: float, e
     return batch * ((m * k + k * n) * es_in + m * n * es_out) + extra_bytes, 2.0 * batch * m * n * k
 
 
+def _lamb_elems(a, i0: int, i1: int) -> int:
+    """Elements of the chunk range [c0, c1) of a K40 LAMB pass.  The chunk lengths live in a device table: FlatLamb leaves
+    the element count of the run in WORK_HINT; without it, every chunk is priced at its full 4096 elements."""
+    from . import _lib
+    c0, c1 = _i(a[i0]), _i(a[i1])
+    return int(_lib.WORK_HINT.get('lamb_elems', {}).get((c0, c1), (c1 - c0) * 4096))
+
+
 MODELS: Dict[str, Callable[[tuple], Work]] = {
     'mbv_voxelize': _voxelize,
     'mbv_pfn_decorate': lambda a: _decorate(a),
@@ -468,6 +476,13 @@ MODELS: Dict[str, Callable[[tuple], Work]] = {
                                                    + _i(a[5]) * _i(a[6])) * 4.0, 0.0),
     'mbv_cls_loss_fwd': lambda a: ('k_cls_loss', 'hbm', _i(a[4]) * _i(a[5]) * _i(a[6]) * (_i(a[8]) * 4.0 + 4.0), 0.0),
     'mbv_cls_loss_bwd': lambda a: ('k_cls_loss', 'hbm', _i(a[6]) * _i(a[7]) * _i(a[8]) * (_i(a[10]) * 8.0 + 4.0), 0.0),
+    # K40.  LAMB moments: p, g, m, v read, m, v, u written (28 B/elem) + 8 B of partials per chunk; apply: p, u read, p, zeroed
+    # grad written (16 B) + the 16-bit shadow (2 B); trust: the (2, n_chunks) slab read, n_params ratios written.
+    # SGD: p, g, buf read, p, buf written (20 B) + shadow (2 B) + zeroed grad (4 B).
+    'mbv_lamb_moments': lambda a: ('k_lamb_moments', 'hbm', _lamb_elems(a, 7, 8) * 28.0 + (_i(a[8]) - _i(a[7])) * 8.0, 0.0),
+    'mbv_lamb_trust': lambda a: ('k_lamb_trust', 'hbm', _i(a[1]) * 8.0 + _i(a[3]) * 12.0, 0.0),
+    'mbv_lamb_apply': lambda a: ('k_lamb_apply', 'hbm', _lamb_elems(a, 7, 8) * (16.0 + (2.0 if _i(a[2]) else 0.0)), 0.0),
+    'mbv_sgd_step': lambda a: ('k_sgd', 'hbm', _i(a[5]) * (20.0 + (2.0 if _i(a[3]) else 0.0) + (4.0 if _i(a[12]) else 0.0)), 0.0),
 }
 
 
