@@ -1,6 +1,6 @@
 """Parameter arena: every parameter, gradient and optimizer moment of a ``MaskBevModule`` laid out in four flat
 HBM buffers (288 GB of HBM3E makes the extra bf16 shadow free), so that the per-step bookkeeping of ≈ 700 tensors
-collapses into a handful of launches (K11, csrc/optim.hip):
+collapses into a handful of launches (K11 and K40, csrc/optim_flat.hip):
 
 * ``param``   f32 — ``p.data`` of every parameter is a view into it (checkpoint keys and shapes unchanged);
 * ``grad``    f32 — ``p.grad`` is a view; the Linear layers accumulate their weight / bias gradients straight into
@@ -9,16 +9,20 @@ collapses into a handful of launches (K11, csrc/optim.hip):
 * ``shadow``  bf16 — the copy of the weights the bf16 GEMMs read, written by the optimizer kernel itself instead
                     of ≈ 450 per-layer cast kernels per step;
 * ``exp_avg``, ``exp_avg_sq`` f32 — Adam moments (owned by :class:`FlatAdam`; :class:`FlatLamb` owns the same pair,
-                    :class:`FlatSGD` one momentum buffer — K40, csrc/optim_flat.hip).
+                    :class:`FlatSGD` one momentum buffer).
 
 The arena is laid out in the reference's differential-lr groups — encoder, backbone, head
-(/root/reference: mask_bev/mask_bev_module.py:131-139) — each a contiguous segment, so an optimizer step is one
+(mask_bev/mask_bev_module.py:131-139) — each a contiguous segment, so an optimizer step is one
 ``mbv_adamw_step`` launch per group (one launch in total when the groups share a learning rate).
+
+The three optimizers are :class:`FlatOptimizer` subclasses: the base owns the ``step()`` frame, ``zero_grad`` and the
+checkpoint format; a subclass names its state (``KIND`` / ``STATE`` / ``HYPER``) and issues its launches in ``_launch``.
 
 Build it after the module is on its GPU (``module.to(device)`` re-allocates parameters and would detach the views).
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -246,7 +250,110 @@ def _load_per_parameter_state(arena: ParameterArena, state: dict, fields: Dict[s
     return steps
 
 
-class FlatAdam(torch.optim.Optimizer):
+class FlatOptimizer(torch.optim.Optimizer):
+    """What the flat optimizers share: the frame of ``step()`` (closure, cached-record invalidation, step count, the
+    :class:`LossScaler` check before and update after the launches of ``_launch``), ``zero_grad`` and the checkpoint format.
+
+    ``state_dict()['flat_state']`` holds the flat buffers named in ``STATE``, ``kind`` = ``KIND`` and — for the classes that
+    count steps — ``steps``, the number of APPLIED updates (with a scaler that count lives on the device,
+    ``LossScaler.applied_steps``).  ``load_state_dict`` takes that format (a ``kind`` other than the class's own is refused;
+    a state without one, from before the key existed, is accepted), or a per-parameter torch state mapped through the arena
+    layout, and restores the ``HYPER`` keys of the param groups."""
+
+    KIND = ''                   # 'adam' | 'lamb' | 'sgd'
+    STATE: Tuple[str, ...] = ()  # the flat state buffers, each the size of the arena
+    HYPER: Tuple[str, ...] = ()  # param-group keys a checkpoint restores
+    COUNTS_STEPS = True         # keeps ``steps``
+    ENTRY = ''                  # the native entry point named when a CPU arena is refused
+
+    def __init__(self, arena: ParameterArena, param_groups, defaults: dict, scaler: Optional[LossScaler],
+                 zero_grad: bool = True):
+        self.arena = arena
+        self.scaler = scaler
+        self.zero_grad_in_step = zero_grad
+        self.grad_scale = 1.0
+        _refuse_frozen(arena, type(self).__name__)
+        super().__init__(param_groups, defaults)
+        for name in self.STATE:
+            setattr(self, name, torch.zeros_like(arena.param))
+        if self.COUNTS_STEPS:
+            self.steps = 0
+
+    def _require_cuda(self):
+        if self.arena.device.type != 'cuda':
+            raise _lib.MaskBevHipError(f'{type(self).__name__} runs on the MI355X only ({self.ENTRY})')
+
+    def _scaler_ptrs(self) -> Tuple[int, int, int]:
+        """(loss scale, overflow flag, applied-step count) device addresses; zeros without a scaler."""
+        sc = self.scaler
+        return (0, 0, 0) if sc is None else (sc.scale.data_ptr(), sc.flag.data_ptr(), sc.applied_steps.data_ptr())
+
+    def _launch(self, lib, stream: int):
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._require_cuda()
+        ops.note_parameters_changed()          # cached per-weight records (K20's absmax words) die with this update
+        if self.COUNTS_STEPS:
+            self.steps += 1
+        sc = self.scaler
+        if sc is not None:
+            sc.check(self.arena.grad)
+        self._launch(_lib.load(), torch.cuda.current_stream(self.arena.device).cuda_stream)
+        if sc is not None:
+            sc.update()
+        return loss
+
+    def zero_grad(self, set_to_none: bool = False):
+        """Gradients live in the arena: clear in place (``step()`` already did when ``zero_grad_in_step``)."""
+        if not self.zero_grad_in_step:
+            self.arena.zero_grad()
+
+    def state_dict(self):
+        sd = super().state_dict()
+        flat = {name: getattr(self, name) for name in self.STATE}
+        if self.COUNTS_STEPS:
+            flat['steps'] = self.steps if self.scaler is None else int(self.scaler.applied_steps.item())
+        flat['kind'] = self.KIND
+        sd['flat_state'] = flat
+        if self.scaler is not None:
+            sd['loss_scaler'] = self.scaler.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        if self.scaler is not None and sd.get('loss_scaler') is not None:
+            self.scaler.load_state_dict(sd['loss_scaler'])
+        flat, steps = sd.get('flat_state'), None
+        if flat is not None:
+            if flat.get('kind', self.KIND) != self.KIND:
+                raise ValueError(f"flat optimizer state of kind {flat.get('kind')!r} cannot be loaded into "
+                                 f"{type(self).__name__}")
+            for name in self.STATE:
+                getattr(self, name).copy_(flat[name])
+            if self.COUNTS_STEPS:
+                steps = int(flat['steps'])
+        elif sd.get('state'):
+            # a per-parameter state_dict (torch.optim.Adam / AdamW / SGD, optimizers.Lamb / torch_optimizer.Lamb: the
+            # reference's checkpoints, or a run saved without the arena): its parameters are numbered in
+            # module.parameters() order = the order of the arena layout
+            steps = _load_per_parameter_state(self.arena, sd['state'], {name: getattr(self, name) for name in self.STATE},
+                                              type(self).__name__[len('Flat'):])
+        if self.COUNTS_STEPS and steps is not None:
+            self.steps = steps
+            if self.scaler is not None:
+                self.scaler.applied_steps.fill_(steps)
+        for pg, saved in zip(self.param_groups, sd.get('param_groups', [])):
+            for k in self.HYPER:
+                if k in saved:
+                    pg[k] = saved[k]
+
+
+class FlatAdam(FlatOptimizer):
     """Adam / AdamW over a :class:`ParameterArena`: one ``mbv_adamw_step`` launch per parameter group.
 
     ``param_groups`` carry ``lr`` / ``weight_decay`` / ``betas`` / ``eps`` like torch's optimizers, so the
@@ -259,20 +366,15 @@ class FlatAdam(torch.optim.Optimizer):
     ``torch.amp.GradScaler`` skipping ``optimizer.step()`` would leave torch's.  ``state_dict()['flat_state']['steps']``
     is that count."""
 
+    KIND, STATE, HYPER = 'adam', ('exp_avg', 'exp_avg_sq'), ('lr', 'betas', 'eps', 'weight_decay')
+    ENTRY = 'mbv_adamw_step'
+
     def __init__(self, arena: ParameterArena, groups: List[dict], lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 1e-2, decoupled: bool = True, zero_grad: bool = True,
                  scaler: Optional[LossScaler] = None):
-        self.arena = arena
-        self.scaler = scaler
         self.decoupled = decoupled
-        self.zero_grad_in_step = zero_grad
-        self.grad_scale = 1.0
-        _refuse_frozen(arena, 'FlatAdam')
-        pgs = _segment_groups(arena, groups)
-        super().__init__(pgs, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.exp_avg = torch.zeros_like(arena.param)
-        self.exp_avg_sq = torch.zeros_like(arena.param)
-        self.steps = 0
+        super().__init__(arena, _segment_groups(arena, groups), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         scaler, zero_grad)
         self._k3 = None              # (weight, bias, offset_w, offset_b) of a LayerNorm whose update K3's backward performs
         self._k3_applied = False
 
@@ -284,9 +386,11 @@ class FlatAdam(torch.optim.Optimizer):
         per ``step()`` (the graph step does); a second pass before ``step()`` raises.  Not with a loss scaler (an overflowed
         step must skip EVERY update, and the verdict is only known after the whole backward) and not with a gradient
         all-reduce (``grad_scale`` != 1: the reduced gradient does not exist inside the kernel).  ``None`` disarms.
+        The arm is a weak reference on the weight (``weight._mbv_k3_adam``), where K3's backward finds it: several optimizers
+        can be armed at once, each for its own parameters, and a dropped optimizer disarms itself.
         Returns whether the fusion is armed."""
-        if ops.K3_ADAM[0] is self:
-            ops.K3_ADAM[0] = None
+        if self._k3 is not None and self.k3_armed(self._k3[0]):
+            del self._k3[0]._mbv_k3_adam
         self._k3, self._k3_applied = None, False
         if weight is None or bias is None or self.scaler is not None or not self.zero_grad_in_step:
             return False
@@ -294,8 +398,16 @@ class FlatAdam(torch.optim.Optimizer):
         if id(weight) not in off or id(bias) not in off or weight.shape != bias.shape:
             return False
         self._k3 = (weight, bias, off[id(weight)], off[id(bias)])
-        ops.K3_ADAM[0] = self
+        # the two ranges are cut out of k_adamw from now on: nothing would apply or clear what their gradient holds
+        for o in self._k3[2:]:
+            self.arena.grad[o:o + _round_up(weight.numel(), _ALIGN)].zero_()
+        weight._mbv_k3_adam = weakref.ref(self)
         return True
+
+    def k3_armed(self, weight) -> bool:
+        """This optimizer is the live arm of ``weight``: K3's backward hands it the update of that LayerNorm affine."""
+        ref = getattr(weight, '_mbv_k3_adam', None)
+        return ref is not None and ref() is self
 
     def claim(self, weight, bias):
         """Called by K3's backward: the optimizer state of (weight, bias) for the fused update, or None (not the armed
@@ -327,19 +439,8 @@ class FlatAdam(torch.optim.Optimizer):
                 return pg
         return None
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _launch(self, lib, stream):
         ar = self.arena
-        if ar.device.type != 'cuda':
-            raise _lib.MaskBevHipError('FlatAdam runs on the MI355X only (mbv_adamw_step)')
-        ops.note_parameters_changed()          # cached per-weight records (K20's absmax words) die with this update
-        lib = _lib.load()
-        self.steps += 1
-        stream = torch.cuda.current_stream(ar.device).cuda_stream
         # fuse adjacent groups with the same hyper-parameters into one launch
         runs = _merged_runs(ar, self.param_groups, lambda pg: (float(pg['lr']), float(pg['betas'][0]), float(pg['betas'][1]),
                                                                float(pg['eps']), float(pg['weight_decay'])))
@@ -360,9 +461,7 @@ class FlatAdam(torch.optim.Optimizer):
                         if hi < b:
                             cut.append([hi, b, hp])
                 runs = cut
-        sc = self.scaler
-        if sc is not None:
-            sc.check(ar.grad)
+        scale, flag, applied = self._scaler_ptrs()
         for a, b, (lr, b1, b2, eps, wd) in runs:
             if b == a:
                 continue
@@ -372,56 +471,14 @@ class FlatAdam(torch.optim.Optimizer):
                                          self.exp_avg.data_ptr() + 4 * a, self.exp_avg_sq.data_ptr() + 4 * a, sh,
                                          ar.shadow_flag, b - a, lr, b1, b2, eps, wd, self.steps,
                                          float(self.grad_scale), 1 if self.decoupled else 0,
-                                         1 if self.zero_grad_in_step else 0,
-                                         0 if sc is None else sc.scale.data_ptr(),
-                                         0 if sc is None else sc.flag.data_ptr(),
-                                         0 if sc is None else sc.applied_steps.data_ptr(), stream),
+                                         1 if self.zero_grad_in_step else 0, scale, flag, applied, stream),
                       'mbv_adamw_step')
-        if sc is not None:
-            sc.update()
-        return loss
-
-    def zero_grad(self, set_to_none: bool = False):
-        """Gradients live in the arena: clear in place (``step()`` already did when ``zero_grad=True``)."""
-        if not self.zero_grad_in_step:
-            self.arena.zero_grad()
-
-    def state_dict(self):
-        sd = super().state_dict()
-        steps = self.steps if self.scaler is None else int(self.scaler.applied_steps.item())
-        sd['flat_state'] = dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, steps=steps)
-        if self.scaler is not None:
-            sd['loss_scaler'] = self.scaler.state_dict()
-        return sd
-
-    def load_state_dict(self, sd):
-        if self.scaler is not None and sd.get('loss_scaler') is not None:
-            self.scaler.load_state_dict(sd['loss_scaler'])
-        flat = sd.get('flat_state')
-        if flat is not None:
-            self.exp_avg.copy_(flat['exp_avg'])
-            self.exp_avg_sq.copy_(flat['exp_avg_sq'])
-            self.steps = int(flat['steps'])
-            if self.scaler is not None:
-                self.scaler.applied_steps.fill_(self.steps)
-        elif sd.get('state'):
-            # a torch.optim.Adam / AdamW state_dict (the reference's checkpoints, or a run saved without the arena):
-            # its parameters are numbered in module.parameters() order = the order of the arena layout
-            steps = _load_per_parameter_state(self.arena, sd['state'], dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq),
-                                              'Adam')
-            self.steps = steps
-            if self.scaler is not None:
-                self.scaler.applied_steps.fill_(steps)
-        for pg, saved in zip(self.param_groups, sd.get('param_groups', [])):
-            for k in ('lr', 'betas', 'eps', 'weight_decay'):
-                if k in saved:
-                    pg[k] = saved[k]
 
 
 LAMB_CHUNK = 4096    # elements per chunk of the LAMB chunk table (kChunk of csrc/optim_flat.hip)
 
 
-class FlatLamb(torch.optim.Optimizer):
+class FlatLamb(FlatOptimizer):
     """LAMB over a :class:`ParameterArena` (K40, csrc/optim_flat.hip): the rule of ``torch_optimizer.Lamb`` — the Adam
     direction ``u = m / (sqrt(v) + eps) + weight_decay * p`` scaled per parameter TENSOR by the trust ratio
     ``min(||p||, clamp_value) / ||u||`` — in three kinds of launch whatever the number of tensors: ``mbv_lamb_moments``
@@ -436,22 +493,18 @@ class FlatLamb(torch.optim.Optimizer):
     not survive a step.  There is no ``fuse_layernorm_affine``: the trust ratio needs the whole tensor's norm, which K3's
     backward does not have.  ``trust_ratio`` holds the last step's ratio of every arena parameter, in layout order."""
 
+    KIND, STATE, HYPER = 'lamb', ('exp_avg', 'exp_avg_sq'), ('lr', 'betas', 'eps', 'weight_decay')
+    ENTRY = 'mbv_lamb_moments'
+
     def __init__(self, arena: ParameterArena, groups: List[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
                  weight_decay: float = 0.0, clamp_value: float = 10.0, debias: bool = False,
                  scaler: Optional[LossScaler] = None):
-        if arena.device.type != 'cuda':
-            raise _lib.MaskBevHipError('FlatLamb runs on the MI355X only (mbv_lamb_moments)')
         self.arena = arena
-        self.scaler = scaler
+        self._require_cuda()
         self.clamp_value = float(clamp_value)
         self.debias = bool(debias)
-        self.zero_grad_in_step = True
-        self.grad_scale = 1.0
-        _refuse_frozen(arena, 'FlatLamb')
-        super().__init__(_segment_groups(arena, groups), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.exp_avg = torch.zeros_like(arena.param)
-        self.exp_avg_sq = torch.zeros_like(arena.param)
-        self.steps = 0
+        super().__init__(arena, _segment_groups(arena, groups), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         scaler)
         # chunk table: (start, len | param << 32) per chunk = mbv_lamb_chunk; [chunk_begin, chunk_end) per parameter
         import numpy as np
         recs, ranges = [], []
@@ -477,23 +530,9 @@ class FlatLamb(torch.optim.Optimizer):
         """Chunks of the element range [a, b), whose ends are parameter boundaries (segments are)."""
         return self._chunk_at[a], self._chunk_at[b]
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _launch(self, lib, stream):
         ar = self.arena
-        ops.note_parameters_changed()          # cached per-weight records (K20's absmax words) die with this update
-        lib = _lib.load()
-        self.steps += 1
-        stream = torch.cuda.current_stream(ar.device).cuda_stream
-        sc = self.scaler
-        scale = 0 if sc is None else sc.scale.data_ptr()
-        flag = 0 if sc is None else sc.flag.data_ptr()
-        applied = 0 if sc is None else sc.applied_steps.data_ptr()
-        if sc is not None:
-            sc.check(ar.grad)
+        scale, flag, applied = self._scaler_ptrs()
         hint = _lib.WORK_HINT.setdefault('lamb_elems', {})
         # the learning rate only enters the apply pass: the moments passes merge over it
         for a, b, (b1, b2, eps, wd) in _merged_runs(ar, self.param_groups, lambda pg: (
@@ -518,44 +557,9 @@ class FlatLamb(torch.optim.Optimizer):
                                          self._chunks.data_ptr(), self.n_chunks, c0, c1, self.trust_ratio.data_ptr(),
                                          self.n_params, lr, b1, b2, 1 if self.debias else 0, self.steps, applied, flag,
                                          stream), 'mbv_lamb_apply')
-        if sc is not None:
-            sc.update()
-        return loss
-
-    def zero_grad(self, set_to_none: bool = False):
-        """Gradients live in the arena and ``step()`` has cleared them."""
-
-    def state_dict(self):
-        sd = super().state_dict()
-        steps = self.steps if self.scaler is None else int(self.scaler.applied_steps.item())
-        sd['flat_state'] = dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, steps=steps, kind='lamb')
-        if self.scaler is not None:
-            sd['loss_scaler'] = self.scaler.state_dict()
-        return sd
-
-    def load_state_dict(self, sd):
-        if self.scaler is not None and sd.get('loss_scaler') is not None:
-            self.scaler.load_state_dict(sd['loss_scaler'])
-        flat = sd.get('flat_state')
-        if flat is not None:
-            if flat.get('kind', 'lamb') != 'lamb':
-                raise ValueError(f"flat optimizer state of kind {flat.get('kind')!r} cannot be loaded into FlatLamb")
-            self.exp_avg.copy_(flat['exp_avg'])
-            self.exp_avg_sq.copy_(flat['exp_avg_sq'])
-            self.steps = int(flat['steps'])
-        elif sd.get('state'):
-            # a per-parameter Lamb state (optimizers.Lamb / torch_optimizer.Lamb: step, exp_avg, exp_avg_sq)
-            self.steps = _load_per_parameter_state(self.arena, sd['state'],
-                                                   dict(exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq), 'Lamb')
-        if self.scaler is not None and (flat is not None or sd.get('state')):
-            self.scaler.applied_steps.fill_(self.steps)
-        for pg, saved in zip(self.param_groups, sd.get('param_groups', [])):
-            for k in ('lr', 'betas', 'eps', 'weight_decay'):
-                if k in saved:
-                    pg[k] = saved[k]
 
 
-class FlatSGD(torch.optim.Optimizer):
+class FlatSGD(FlatOptimizer):
     """SGD with (Nesterov) momentum over a :class:`ParameterArena` (K40): one ``mbv_sgd_step`` launch over the whole arena
     in ``torch.optim.SGD``'s single-tensor order, with the 16-bit shadow refresh and the gradient clear folded in and the
     :class:`LossScaler` / ``grad_scale`` conventions of :class:`FlatAdam`.
@@ -565,73 +569,29 @@ class FlatSGD(torch.optim.Optimizer):
     torch's first-step ``buf = grad`` exactly when ``dampening`` is 0; with a non-zero ``dampening`` the first step's
     buffer is ``(1 - dampening) * grad``."""
 
+    KIND, STATE, HYPER = 'sgd', ('momentum_buffer',), ('lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
+    COUNTS_STEPS = False
+    ENTRY = 'mbv_sgd_step'
+
     def __init__(self, arena: ParameterArena, lr: float = 1e-3, momentum: float = 0.99, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = True, zero_grad: bool = True,
                  scaler: Optional[LossScaler] = None):
-        if arena.device.type != 'cuda':
-            raise _lib.MaskBevHipError('FlatSGD runs on the MI355X only (mbv_sgd_step)')
+        self.arena = arena
+        self._require_cuda()
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError('Nesterov momentum requires a momentum and zero dampening')
-        self.arena = arena
-        self.scaler = scaler
-        self.zero_grad_in_step = zero_grad
-        self.grad_scale = 1.0
-        _refuse_frozen(arena, 'FlatSGD')
         flat = nn.Parameter(arena.param, requires_grad=True)
         flat.grad = arena.grad
-        super().__init__([flat], dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                      nesterov=nesterov))
-        self.momentum_buffer = torch.zeros_like(arena.param)
+        super().__init__(arena, [flat], dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                             nesterov=nesterov), scaler, zero_grad)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def _launch(self, lib, stream):
         ar = self.arena
-        ops.note_parameters_changed()
-        lib = _lib.load()
-        sc = self.scaler
-        if sc is not None:
-            sc.check(ar.grad)
+        scale, flag, _ = self._scaler_ptrs()
         pg = self.param_groups[0]
         with ops.TIMER.span('k_sgd'):
             check(lib.mbv_sgd_step(ar.param.data_ptr(), ar.grad.data_ptr(), self.momentum_buffer.data_ptr(),
                                    0 if ar.shadow is None else ar.shadow.data_ptr(), ar.shadow_flag, ar.numel,
                                    float(pg['lr']), float(pg['momentum']), float(pg['dampening']),
                                    float(pg['weight_decay']), 1 if pg['nesterov'] else 0, float(self.grad_scale),
-                                   1 if self.zero_grad_in_step else 0, 0 if sc is None else sc.scale.data_ptr(),
-                                   0 if sc is None else sc.flag.data_ptr(),
-                                   torch.cuda.current_stream(ar.device).cuda_stream), 'mbv_sgd_step')
-        if sc is not None:
-            sc.update()
-        return loss
-
-    def zero_grad(self, set_to_none: bool = False):
-        """Gradients live in the arena: clear in place (``step()`` already did when ``zero_grad=True``)."""
-        if not self.zero_grad_in_step:
-            self.arena.zero_grad()
-
-    def state_dict(self):
-        sd = super().state_dict()
-        sd['flat_state'] = dict(momentum_buffer=self.momentum_buffer, kind='sgd')
-        if self.scaler is not None:
-            sd['loss_scaler'] = self.scaler.state_dict()
-        return sd
-
-    def load_state_dict(self, sd):
-        if self.scaler is not None and sd.get('loss_scaler') is not None:
-            self.scaler.load_state_dict(sd['loss_scaler'])
-        flat = sd.get('flat_state')
-        if flat is not None:
-            if flat.get('kind', 'sgd') != 'sgd':
-                raise ValueError(f"flat optimizer state of kind {flat.get('kind')!r} cannot be loaded into FlatSGD")
-            self.momentum_buffer.copy_(flat['momentum_buffer'])
-        elif sd.get('state'):
-            # a torch.optim.SGD state_dict: momentum_buffer per parameter, in module.parameters() order
-            _load_per_parameter_state(self.arena, sd['state'], dict(momentum_buffer=self.momentum_buffer), 'SGD')
-        for k in ('lr', 'momentum', 'dampening', 'weight_decay', 'nesterov'):
-            for saved in sd.get('param_groups', [])[:1]:
-                if k in saved:
-                    self.param_groups[0][k] = saved[k]
+                                   1 if self.zero_grad_in_step else 0, scale, flag, stream), 'mbv_sgd_step')

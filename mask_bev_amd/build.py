@@ -48,6 +48,7 @@ FILE_FLAGS = {
     # K39a's f64 transforms of cell centres decide a world cell and a sensor cell: one rounding per operation, as restated
     'fuse.hip': ['-ffp-contract=off'],
     # K40's LAMB / SGD updates are compared with per-tensor torch restatements: one rounding per operation, as torch does them
+    # (K11's k_adamw shares the unit; its arithmetic pins contraction off itself, adam.hpp)
     'optim_flat.hip': ['-ffp-contract=off'],
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],

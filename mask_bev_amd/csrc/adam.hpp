@@ -1,4 +1,4 @@
-// Optimizer arithmetic.  AdamW: shared by K11's optimizer pass (optim.hip) and K3's backward with the update of the (C, ny, nx)
+// Optimizer arithmetic.  AdamW: shared by K11's optimizer pass (optim_flat.hip) and K3's backward with the update of the (C, ny, nx)
 // LayerNorm affine fused into it (scatter_layernorm.hip): ONE definition, so the two paths are bit-identical.
 // Follows torch/optim/adamw.py's single-tensor update order (mask_bev/mask_bev_module.py:131-166 configures it).
 #pragma once
@@ -20,9 +20,8 @@ __device__ __forceinline__ unsigned short shadow_bits(float p, int kind) {
 }
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamArgs& a) {
-  // contraction pinned OFF: optim.hip is built with hipcc's default (fused multiply-adds where the compiler likes),
-  // scatter_layernorm.hip with -ffp-contract=off (its LayerNorm sums are order-sensitive) — the update must not depend on
-  // which unit runs it; unfused multiply / add is also what torch's single-tensor AdamW computes
+  // contraction pinned OFF here, not by a unit's build flags: the update must not depend on which unit runs it or how that
+  // unit is built; unfused multiply / add is also what torch's single-tensor AdamW computes
 #pragma clang fp contract(off)
   g *= a.grad_scale;
   if (a.decoupled) {

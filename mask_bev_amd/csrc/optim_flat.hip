@@ -1,5 +1,9 @@
-// K40 — LAMB and (Nesterov) SGD over the flat parameter arena (HBM-bound, no MFMA; K11's k_adamw is the model).
+// K11 / K40 — the optimizer passes over the flat parameter arena (HBM-bound, no MFMA).
 //
+//   mbv_adamw_step      one pass of Adam / AdamW: reads param, grad, exp_avg, exp_avg_sq (16 B/elem), writes param, exp_avg,
+//                       exp_avg_sq (12 B/elem), optionally the 16-bit shadow the GEMMs read (2 B/elem) and the zeroed gradient
+//                       (4 B/elem).
+//   mbv_refresh_shadow  f32 -> 16-bit shadow of an arena; mbv_grad_nonfinite / mbv_loss_scale_update: fp16 loss scaling.
 //   mbv_lamb_moments    reads param, grad, exp_avg, exp_avg_sq (16 B/elem), writes exp_avg, exp_avg_sq and the un-scaled update
 //                       u over grad (12 B/elem); per chunk the block-reduced sums of p^2 and u^2 go to a partial slab.
 //   mbv_lamb_trust      per parameter: the partials summed in a fixed order in f64 -> trust ratio (f32).
@@ -11,15 +15,109 @@
 // straddles two parameters; the last chunk of a parameter is shorter, a multiple of 64).  One block works on one chunk at a
 // time, so a chunk's two sums are taken in one fixed order whatever the grid — no float atomics, bit-reproducible, replayable.
 //
-// Reference: torch_optimizer 0.3.0 Lamb.step and torch/optim/sgd.py `_single_tensor_sgd`, as configured at
-// mask_bev/mask_bev_module.py:141-151; the arithmetic itself is in adam.hpp.
+// The unit is built with -ffp-contract=off (K40's updates are compared with per-tensor torch restatements).  That flag
+// cannot change a bit of k_adamw, which used to be built with hipcc's default: its float multiply-adds all sit inside
+// adam_one, which pins contraction off itself, and what remains in the kernel is one division and f64 pow / sqrt.
+//
+// Reference: torch.optim.AdamW / Adam (single-tensor update order of torch/optim/adamw.py), torch_optimizer 0.3.0 Lamb.step
+// and torch/optim/sgd.py `_single_tensor_sgd`, as configured at mask_bev/mask_bev_module.py:131-166; the arithmetic itself is
+// in adam.hpp, the frame the streaming kernels share in arena_stream.hpp.
 #include "common.hpp"
-#include "adam.hpp"
+#include "arena_stream.hpp"
 
 namespace {
 
+// 4 elements per thread per iteration (float4 loads: 16 B/lane, fully coalesced), grid-stride.
+__global__ void __launch_bounds__(256) k_adamw(float* __restrict__ param, float* __restrict__ grad,
+                                               float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                               unsigned short* __restrict__ shadow, long n, AdamArgs a) {
+  const long n4 = n >> 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  if (a.loss_scale) a.grad_scale /= *a.loss_scale;
+  if (a.skip && *a.skip) {         // overflowed step: parameters, moments and the shadow stay; the gradient is dropped
+    if (a.zero_grad) clear_grad(grad, n);
+    return;
+  }
+  if (a.applied) {                 // bias corrections from the device-side count of applied updates
+    const double t = (double)(*a.applied + 1);
+    a.bias_correction1 = (float)(1.0 - pow((double)a.beta1, t));
+    a.bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)a.beta2, t));
+  }
+  // Streaming accesses: every array is read once and written once per step and is far larger than the caches (6.8 GB at the
+  // bench size), so loads and stores carry the non-temporal hint — 1.33 -> 1.25 ms measured; a second row per thread in
+  // flight was slower (1.37 ms).
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + i);
+    const f4 g = __builtin_nontemporal_load(reinterpret_cast<const f4*>(grad) + i);
+    f4 m = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg) + i);
+    f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg_sq) + i);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float pc = p[c], mc = m[c], vc = v[c];
+      adam_one(pc, g[c], mc, vc, a);
+      p[c] = pc; m[c] = mc; v[c] = vc;
+    }
+    __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + i);
+    __builtin_nontemporal_store(m, reinterpret_cast<f4*>(exp_avg) + i);
+    __builtin_nontemporal_store(v, reinterpret_cast<f4*>(exp_avg_sq) + i);
+    if (shadow) store_shadow4(shadow, i, p, a.shadow_kind);
+    if (a.zero_grad) __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4*>(grad) + i);
+  }
+  // ragged tail (< 4 elements)
+  const long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) {
+    float p = param[t], m = exp_avg[t], v = exp_avg_sq[t];
+    adam_one(p, grad[t], m, v, a);
+    param[t] = p; exp_avg[t] = m; exp_avg_sq[t] = v;
+    if (shadow) shadow[t] = shadow_bits(p, a.shadow_kind);
+    if (a.zero_grad) grad[t] = 0.f;
+  }
+}
+
+// f32 -> 16-bit shadow refresh of an arena (after load_state_dict / parameter broadcast).
+__global__ void __launch_bounds__(256) k_shadow(const float* __restrict__ param, unsigned short* __restrict__ shadow,
+                                                long n, int kind) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) shadow[i] = shadow_bits(param[i], kind);
+}
+
+// ---- fp16 loss scaling, all on the device (no host synchronisation, replayable) ---------------------------------
+// flag |= "some gradient element is inf or nan" (what torch.amp.GradScaler's unscale_ reports as found_inf)
+__global__ void __launch_bounds__(256) k_grad_nonfinite(const float* __restrict__ grad, long n, int* __restrict__ flag) {
+  const long n4 = n >> 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const uint4 u = reinterpret_cast<const uint4*>(grad)[i];
+    bad |= ((u.x & 0x7f800000u) == 0x7f800000u) | ((u.y & 0x7f800000u) == 0x7f800000u) |
+           ((u.z & 0x7f800000u) == 0x7f800000u) | ((u.w & 0x7f800000u) == 0x7f800000u);
+  }
+  const long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) bad |= (__float_as_uint(grad[t]) & 0x7f800000u) == 0x7f800000u;
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+// GradScaler.update(): overflow -> scale *= backoff, streak = 0; else streak += 1 and every `interval` clean steps
+// scale *= growth.  Clears the flag for the next step.
+__global__ void k_loss_scale_update(float* __restrict__ scale, int* __restrict__ streak, int* __restrict__ flag,
+                                    float growth, float backoff, int interval, int* __restrict__ applied) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (*flag) {
+    *scale = fmaxf(*scale * backoff, 1.f);
+    *streak = 0;
+  } else {
+    if (applied) ++*applied;       // this step's update was applied: Adam's step count advances
+    if (++*streak >= interval) {
+      const float s = *scale * growth;
+      if (s <= 3.0e38f && s == s) *scale = s;
+      *streak = 0;
+    }
+  }
+  *flag = 0;
+}
+
+// ---- K40: LAMB --------------------------------------------------------------------------------------------------------
 constexpr int kChunk = 4096;            // elements per chunk: 4 float4 per lane of a 256-thread block
-constexpr int kMaxBlocks = 256 * 16;    // 16 blocks per CU, grid-stride beyond (as k_adamw)
 
 struct ChunkRec {                       // = mbv_lamb_chunk (maskbev_hip.h)
   long start;                           // first arena element, a multiple of 4
@@ -27,9 +125,6 @@ struct ChunkRec {                       // = mbv_lamb_chunk (maskbev_hip.h)
   int param;                            // index of the parameter the chunk belongs to
 };
 static_assert(sizeof(ChunkRec) == 16, "chunk records are 16 bytes");
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned short us4 __attribute__((ext_vector_type(4)));
 
 // a record that would reach outside the arena (a corrupted table) is skipped, never followed
 __device__ __forceinline__ bool chunk_ok(const ChunkRec& r, long n) {
@@ -141,30 +236,21 @@ __global__ void __launch_bounds__(256) k_lamb_apply(float* __restrict__ param, f
 #pragma unroll
       for (int k = 0; k < 4; ++k) p[k] = lamb_apply_one(p[k], u[k], scaled);
       __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + base + i);
-      if (shadow) {
-        us4 s;
-        s.x = shadow_bits(p.x, shadow_kind); s.y = shadow_bits(p.y, shadow_kind);
-        s.z = shadow_bits(p.z, shadow_kind); s.w = shadow_bits(p.w, shadow_kind);
-        reinterpret_cast<us4*>(shadow)[base + i] = s;     // (read again by the next forward: a normal store)
-      }
+      if (shadow) store_shadow4(shadow, base + i, p, shadow_kind);
       __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + base + i);
     }
   }
 }
 
+// ---- K40: (Nesterov) SGD ----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ buf,
                                              unsigned short* __restrict__ shadow, long n, SgdArgs a) {
   const long n4 = n >> 2;
   const long stride = (long)gridDim.x * blockDim.x;
   const long first = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long t = (n4 << 2) + first;     // ragged tail (< 4 elements)
   if (a.loss_scale) a.grad_scale /= *a.loss_scale;
-  const f4 zero = {0.f, 0.f, 0.f, 0.f};
   if (a.skip && *a.skip) {              // overflowed step: parameters, buffer and shadow stay; the gradient is dropped
-    if (a.zero_grad) {
-      for (long i = first; i < n4; i += stride) __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + i);
-      if (t < n) grad[t] = 0.f;
-    }
+    if (a.zero_grad) clear_grad(grad, n);
     return;
   }
   for (long i = first; i < n4; i += stride) {
@@ -179,14 +265,10 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ param, float* _
     }
     __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + i);
     __builtin_nontemporal_store(b, reinterpret_cast<f4*>(buf) + i);
-    if (shadow) {
-      us4 s;
-      s.x = shadow_bits(p.x, a.shadow_kind); s.y = shadow_bits(p.y, a.shadow_kind);
-      s.z = shadow_bits(p.z, a.shadow_kind); s.w = shadow_bits(p.w, a.shadow_kind);
-      reinterpret_cast<us4*>(shadow)[i] = s;
-    }
-    if (a.zero_grad) __builtin_nontemporal_store(zero, reinterpret_cast<f4*>(grad) + i);
+    if (shadow) store_shadow4(shadow, i, p, a.shadow_kind);
+    if (a.zero_grad) __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4*>(grad) + i);
   }
+  const long t = (n4 << 2) + first;     // ragged tail (< 4 elements)
   if (t < n) {
     float p = param[t], b = buf[t];
     sgd_one(p, grad[t], b, a);
@@ -196,17 +278,61 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ param, float* _
   }
 }
 
-inline bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c) |
-           reinterpret_cast<size_t>(d)) & 15) != 0;
-}
+inline unsigned chunk_grid(int c0, int c1) { return (unsigned)(c1 - c0 < kMaxBlocks ? c1 - c0 : kMaxBlocks); }
 
-inline unsigned chunk_grid(int c0, int c1) {
-  const int blocks = c1 - c0 < kMaxBlocks ? c1 - c0 : kMaxBlocks;
-  return (unsigned)blocks;
+inline bool bad_shadow(const void* shadow, int32_t shadow_dtype) {       // 8-byte aligned, bf16 or fp16
+  return shadow && ((reinterpret_cast<size_t>(shadow) & 7) || (shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16));
 }
 
 }  // namespace
+
+extern "C" int mbv_adamw_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                              int32_t shadow_dtype, int64_t n, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, int64_t step, float grad_scale, int32_t decoupled, int32_t zero_grad,
+                              const float* loss_scale, const int32_t* skip_flag, const int32_t* applied_steps,
+                              void* stream) {
+  if (n < 0 || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq) return MBV_ERR_BAD_ARG;
+  if (n == 0) return MBV_OK;
+  if (misaligned16(param, grad, exp_avg, exp_avg_sq) || bad_shadow(shadow_bf16, shadow_dtype)) return MBV_ERR_BAD_ARG;
+  AdamArgs a;
+  a.shadow_kind = shadow_dtype; a.loss_scale = loss_scale; a.skip = skip_flag; a.applied = applied_steps;
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+  a.bias_correction1 = (float)(1.0 - pow((double)beta1, (double)step));
+  a.bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  a.grad_scale = grad_scale; a.decoupled = decoupled; a.zero_grad = zero_grad;
+  hipLaunchKernelGGL(k_adamw, dim3(stream_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, reinterpret_cast<unsigned short*>(shadow_bf16), (long)n, a);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_grad_nonfinite(const float* grad, int64_t n, int32_t* flag, void* stream) {
+  if (n < 0 || !grad || !flag || misaligned16(grad)) return MBV_ERR_BAD_ARG;
+  if (n == 0) return MBV_OK;
+  hipLaunchKernelGGL(k_grad_nonfinite, dim3(stream_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, grad, (long)n, flag);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_loss_scale_update(float* loss_scale, int32_t* clean_steps, int32_t* flag, float growth, float backoff,
+                                     int32_t growth_interval, int32_t* applied_steps, void* stream) {
+  if (!loss_scale || !clean_steps || !flag || growth < 1.f || backoff <= 0.f || backoff > 1.f || growth_interval < 1)
+    return MBV_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_loss_scale_update, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_scale, clean_steps, flag,
+                     growth, backoff, growth_interval, applied_steps);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_refresh_shadow(const float* param, void* shadow_bf16, int32_t shadow_dtype, int64_t n, void* stream) {
+  if (n < 0 || !param || !shadow_bf16) return MBV_ERR_BAD_ARG;
+  if (shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
+  if (n == 0) return MBV_OK;
+  hipLaunchKernelGGL(k_shadow, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, param,
+                     reinterpret_cast<unsigned short*>(shadow_bf16), (long)n, shadow_dtype);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
 
 extern "C" int mbv_lamb_moments(const float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                 const mbv_lamb_chunk* chunks, int32_t n_chunks, int32_t c0, int32_t c1, float* partials,
@@ -249,8 +375,7 @@ extern "C" int mbv_lamb_apply(float* param, float* grad, void* shadow, int32_t s
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return MBV_ERR_BAD_ARG;
   if (c0 < 0 || c1 < c0 || c1 > n_chunks) return MBV_ERR_BAD_ARG;
   if (misaligned16(param, grad, chunks) || (reinterpret_cast<size_t>(trust) & 3)) return MBV_ERR_BAD_ARG;
-  if (shadow && (reinterpret_cast<size_t>(shadow) & 7)) return MBV_ERR_BAD_ARG;
-  if (shadow && shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
+  if (bad_shadow(shadow, shadow_dtype)) return MBV_ERR_BAD_ARG;
   if (c1 == c0) return MBV_OK;
   float step_size = lr;
   if (debias)
@@ -269,17 +394,12 @@ extern "C" int mbv_sgd_step(float* param, float* grad, float* momentum_buf, void
                             void* stream) {
   if (n < 0 || !param || !grad || !momentum_buf) return MBV_ERR_BAD_ARG;
   if (n == 0) return MBV_OK;
-  if (misaligned16(param, grad, momentum_buf)) return MBV_ERR_BAD_ARG;
-  if (shadow && (reinterpret_cast<size_t>(shadow) & 7)) return MBV_ERR_BAD_ARG;
-  if (shadow && shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
+  if (misaligned16(param, grad, momentum_buf) || bad_shadow(shadow, shadow_dtype)) return MBV_ERR_BAD_ARG;
   SgdArgs a;
   a.lr = lr; a.momentum = momentum; a.one_minus_dampening = 1.0f - dampening; a.weight_decay = weight_decay;
   a.grad_scale = grad_scale; a.nesterov = nesterov; a.zero_grad = zero_grad; a.shadow_kind = shadow_dtype;
   a.loss_scale = loss_scale; a.skip = skip_flag;
-  long blocks = ((n >> 2) + 255) / 256;
-  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_sgd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf,
+  hipLaunchKernelGGL(k_sgd, dim3(stream_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, param, grad, momentum_buf,
                      reinterpret_cast<unsigned short*>(shadow), (long)n, a);
   MBV_CHECK_LAUNCH();
   return MBV_OK;

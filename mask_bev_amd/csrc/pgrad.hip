@@ -1,119 +1,14 @@
-// K11 — the parameter-arena kernels of the training step (HBM-bound, no MFMA).
+// Parameter-gradient kernels of the backward pass: they accumulate straight into the f32 arena gradient (their Python home
+// is mask_bev_amd/ops_pgrad.py).  Built with hipcc's default flags.
 //
-//   mbv_adamw_step      one pass of Adam / AdamW over a flat f32 parameter arena: reads param, grad, exp_avg,
-//                       exp_avg_sq (16 B/elem), writes param, exp_avg, exp_avg_sq (12 B/elem), optionally the
-//                       bf16 shadow the GEMMs read (2 B/elem) and the zeroed gradient (4 B/elem).
-//   mbv_colsum_accum    bias gradient: out[n] += sum_t g[t, n], accumulated straight into the f32 arena gradient.
-//
-// Reference: torch.optim.AdamW / Adam configured at /root/reference mask_bev/mask_bev_module.py:131-166
-// (single-tensor update order of torch/optim/adamw.py is followed so that results agree to f32 rounding).
+//   mbv_colsum_accum[_group]      bias gradient: out[n] += sum_t g[t, n]; up to 64 column sums per launch.
+//   mbv_act_bwd_colsum            activation backward fused with the bias gradient of the Linear in front of it.
+//   mbv_wgrad_small_f32[_group]   small-token weight gradient in exact f32: acc (O, I) += g^T x; up to 48 per launch.
 #include "common.hpp"
-#include "adam.hpp"
 
 #include <hip/hip_bf16.h>
 
 namespace {
-
-// 4 elements per thread per iteration (float4 loads: 16 B/lane, fully coalesced), grid-stride.
-__global__ void __launch_bounds__(256) k_adamw(float* __restrict__ param, float* __restrict__ grad,
-                                               float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                                               unsigned short* __restrict__ shadow, long n, AdamArgs a) {
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  if (a.loss_scale) a.grad_scale /= *a.loss_scale;
-  if (a.skip && *a.skip) {         // overflowed step: parameters, moments and the shadow stay; the gradient is dropped
-    if (a.zero_grad) {
-      for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
-        reinterpret_cast<float4*>(grad)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      const long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x;
-      if (t < n) grad[t] = 0.f;
-    }
-    return;
-  }
-  if (a.applied) {                 // bias corrections from the device-side count of applied updates
-    const double t = (double)(*a.applied + 1);
-    a.bias_correction1 = (float)(1.0 - pow((double)a.beta1, t));
-    a.bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)a.beta2, t));
-  }
-  // Streaming accesses: every array is read once and written once per step and is far larger than the caches (6.8 GB at the
-  // bench size), so loads and stores carry the non-temporal hint — 1.33 -> 1.25 ms measured; a second row per thread in
-  // flight was slower (1.37 ms).
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  typedef unsigned short us4 __attribute__((ext_vector_type(4)));
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + i);
-    const f4 g = __builtin_nontemporal_load(reinterpret_cast<const f4*>(grad) + i);
-    f4 m = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg) + i);
-    f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg_sq) + i);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float pc = p[c], mc = m[c], vc = v[c];
-      adam_one(pc, g[c], mc, vc, a);
-      p[c] = pc; m[c] = mc; v[c] = vc;
-    }
-    __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + i);
-    __builtin_nontemporal_store(m, reinterpret_cast<f4*>(exp_avg) + i);
-    __builtin_nontemporal_store(v, reinterpret_cast<f4*>(exp_avg_sq) + i);
-    if (shadow) {
-      us4 s;
-      s.x = shadow_bits(p.x, a.shadow_kind); s.y = shadow_bits(p.y, a.shadow_kind);
-      s.z = shadow_bits(p.z, a.shadow_kind); s.w = shadow_bits(p.w, a.shadow_kind);
-      reinterpret_cast<us4*>(shadow)[i] = s;              // (read again by the next forward: a normal store)
-    }
-    if (a.zero_grad) __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4*>(grad) + i);
-  }
-  // ragged tail (< 4 elements)
-  const long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) {
-    float p = param[t], m = exp_avg[t], v = exp_avg_sq[t];
-    adam_one(p, grad[t], m, v, a);
-    param[t] = p; exp_avg[t] = m; exp_avg_sq[t] = v;
-    if (shadow) shadow[t] = shadow_bits(p, a.shadow_kind);
-    if (a.zero_grad) grad[t] = 0.f;
-  }
-}
-
-// f32 -> 16-bit shadow refresh of an arena (after load_state_dict / parameter broadcast).
-__global__ void __launch_bounds__(256) k_shadow(const float* __restrict__ param, unsigned short* __restrict__ shadow,
-                                                long n, int kind) {
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) shadow[i] = shadow_bits(param[i], kind);
-}
-
-// ---- fp16 loss scaling, all on the device (no host synchronisation, replayable) ---------------------------------
-// flag |= "some gradient element is inf or nan" (what torch.amp.GradScaler's unscale_ reports as found_inf)
-__global__ void __launch_bounds__(256) k_grad_nonfinite(const float* __restrict__ grad, long n, int* __restrict__ flag) {
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * blockDim.x;
-  bool bad = false;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const uint4 u = reinterpret_cast<const uint4*>(grad)[i];
-    bad |= ((u.x & 0x7f800000u) == 0x7f800000u) | ((u.y & 0x7f800000u) == 0x7f800000u) |
-           ((u.z & 0x7f800000u) == 0x7f800000u) | ((u.w & 0x7f800000u) == 0x7f800000u);
-  }
-  const long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) bad |= (__float_as_uint(grad[t]) & 0x7f800000u) == 0x7f800000u;
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
-// GradScaler.update(): overflow -> scale *= backoff, streak = 0; else streak += 1 and every `interval` clean steps
-// scale *= growth.  Clears the flag for the next step.
-__global__ void k_loss_scale_update(float* __restrict__ scale, int* __restrict__ streak, int* __restrict__ flag,
-                                    float growth, float backoff, int interval, int* __restrict__ applied) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (*flag) {
-    *scale = fmaxf(*scale * backoff, 1.f);
-    *streak = 0;
-  } else {
-    if (applied) ++*applied;       // this step's update was applied: Adam's step count advances
-    if (++*streak >= interval) {
-      const float s = *scale * growth;
-      if (s <= 3.0e38f && s == s) *scale = s;
-      *streak = 0;
-    }
-  }
-  *flag = 0;
-}
 
 // Column sums of a row-major (T, N) matrix accumulated into out (N,) f32.
 // Block = 4 waves; each wave walks rows r = wave, wave + 4·gridDim.y·…; a lane owns 4 adjacent columns (8 B bf16 /
@@ -417,67 +312,6 @@ __global__ void __launch_bounds__(256) k_wgrad_small_group(const WgradGroupArgs 
 }
 
 }  // namespace
-
-extern "C" int mbv_adamw_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
-                              int32_t shadow_dtype, int64_t n, float lr, float beta1, float beta2, float eps,
-                              float weight_decay, int64_t step, float grad_scale, int32_t decoupled, int32_t zero_grad,
-                              const float* loss_scale, const int32_t* skip_flag, const int32_t* applied_steps,
-                              void* stream) {
-  if (n < 0 || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq) return MBV_ERR_BAD_ARG;
-  if (n == 0) return MBV_OK;
-  if ((reinterpret_cast<size_t>(param) | reinterpret_cast<size_t>(grad) | reinterpret_cast<size_t>(exp_avg) |
-       reinterpret_cast<size_t>(exp_avg_sq)) & 15)
-    return MBV_ERR_BAD_ARG;
-  if (shadow_bf16 && (reinterpret_cast<size_t>(shadow_bf16) & 7)) return MBV_ERR_BAD_ARG;
-  if (shadow_bf16 && shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
-  AdamArgs a;
-  a.shadow_kind = shadow_dtype; a.loss_scale = loss_scale; a.skip = skip_flag; a.applied = applied_steps;
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-  a.bias_correction1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale; a.decoupled = decoupled; a.zero_grad = zero_grad;
-  const long n4 = n >> 2;
-  long blocks = (n4 + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;      // 16 blocks per CU, grid-stride beyond
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_adamw, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, reinterpret_cast<unsigned short*>(shadow_bf16), (long)n, a);
-  MBV_CHECK_LAUNCH();
-  return MBV_OK;
-}
-
-extern "C" int mbv_grad_nonfinite(const float* grad, int64_t n, int32_t* flag, void* stream) {
-  if (n < 0 || !grad || !flag || (reinterpret_cast<size_t>(grad) & 15)) return MBV_ERR_BAD_ARG;
-  if (n == 0) return MBV_OK;
-  long blocks = ((n >> 2) + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_grad_nonfinite, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, (long)n, flag);
-  MBV_CHECK_LAUNCH();
-  return MBV_OK;
-}
-
-extern "C" int mbv_loss_scale_update(float* loss_scale, int32_t* clean_steps, int32_t* flag, float growth, float backoff,
-                                     int32_t growth_interval, int32_t* applied_steps, void* stream) {
-  if (!loss_scale || !clean_steps || !flag || growth < 1.f || backoff <= 0.f || backoff > 1.f || growth_interval < 1)
-    return MBV_ERR_BAD_ARG;
-  hipLaunchKernelGGL(k_loss_scale_update, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_scale, clean_steps, flag,
-                     growth, backoff, growth_interval, applied_steps);
-  MBV_CHECK_LAUNCH();
-  return MBV_OK;
-}
-
-extern "C" int mbv_refresh_shadow(const float* param, void* shadow_bf16, int32_t shadow_dtype, int64_t n, void* stream) {
-  if (n < 0 || !param || !shadow_bf16) return MBV_ERR_BAD_ARG;
-  if (shadow_dtype != MBV_DT_BF16 && shadow_dtype != MBV_DT_F16) return MBV_ERR_BAD_ARG;
-  if (n == 0) return MBV_OK;
-  long blocks = (n + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(k_shadow, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param,
-                     reinterpret_cast<unsigned short*>(shadow_bf16), (long)n, shadow_dtype);
-  MBV_CHECK_LAUNCH();
-  return MBV_OK;
-}
 
 // launch geometry of a column sum: W threads per row, gx column blocks, gy row slices
 static void colsum_geometry(int64_t rows, int32_t n, int target_blocks, int& W, unsigned& gx, long& gy) {

@@ -103,11 +103,10 @@ class GraphedTrainStep:
             self.masks = masks.clone()
         # One GPU: the AdamW update of the encoder's (C, ny, nx) LayerNorm affine happens inside K3's backward (one backward
         # per step here by construction); a data-parallel step needs the all-reduced gradient and keeps the plain form
-        self._k3_fused = False
         if (reducer is None and getattr(module, '_arena', None) is not None
                 and hasattr(optimizer, 'fuse_layernorm_affine')):
             ln = module._encoder._layer_norm
-            self._k3_fused = optimizer.fuse_layernorm_affine(ln.weight, ln.bias)
+            optimizer.fuse_layernorm_affine(ln.weight, ln.bias)
         self._graph_params = list(module._backbone.parameters()) + list(module._panoptic_head.parameters())
         # warm-up on a side stream (allocator / library workspaces / autotuning settle before capture)
         side = torch.cuda.Stream(device=dev)
@@ -265,7 +264,12 @@ class GraphedTrainStep:
             self.arena.zero_grad()
         return self.loss_static
 
+    @property
+    def _k3_fused(self) -> bool:
+        """The optimizer is, now, the live arm of the encoder LayerNorm's fused update (asked, never cached)."""
+        armed = getattr(self.opt, 'k3_armed', None)
+        return bool(armed is not None and armed(self.m._encoder._layer_norm.weight))
+
     def close(self):
         if self._k3_fused:
             self.opt.fuse_layernorm_affine(None)
-            self._k3_fused = False

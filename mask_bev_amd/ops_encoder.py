@@ -415,7 +415,9 @@ class _ScatterLayerNorm(torch.autograd.Function):
             g_w = torch.empty_like(weight)
             g_b = torch.empty_like(weight)
         ws = _workspace(lib.mbv_scatter_layernorm_workspace_bytes(batch), dev)
-        fused = K3_ADAM[0].claim(wp, bp) if (direct and K3_ADAM[0] is not None) else None
+        arm = getattr(wp, '_mbv_k3_adam', None) if direct else None        # weakref to the optimizer armed for wp, if any
+        opt = arm() if arm is not None else None
+        fused = opt.claim(wp, bp) if opt is not None else None
         if fused is not None:
             # the step driver armed the optimizer for this pass (arena.FlatAdam.fuse_layernorm_affine): the AdamW update of
             # the two affine parameters happens inside the launch, their gradients never reach the arena
@@ -458,11 +460,6 @@ class PatchTokens:
 
 def patch_layout_supported(channels: int, ny: int, nx: int, patch: int) -> bool:
     return bool(_lib.load().mbv_scatter_layernorm_patch_supported(channels, ny, nx, patch))
-
-
-# The optimizer that asked for the AdamW update of K3's two affine parameters to be fused into K3's backward (one entry:
-# arena.FlatAdam.fuse_layernorm_affine arms it, FlatAdam.step() reads what was applied); None = the ordinary backward.
-K3_ADAM = [None]
 
 
 def scatter_layernorm(feats: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, p: Pillars, batch: int, ny: int,

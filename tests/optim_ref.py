@@ -1,7 +1,8 @@
 """K40 restated: one LAMB step and one (Nesterov) SGD step of ONE tensor, plain torch at the dtype of the tensors handed in —
 the yardstick of tests/test_optim_cpu.py and tests/test_k40_optim_gpu.py.  Written from the rule as the K40 block of
 include/maskbev_hip.h words it (torch_optimizer 0.3.0 Lamb.step; torch/optim/sgd.py's single-tensor order), not from
-csrc/optim_flat.hip or mask_bev_amd/optimizers.py.  Python scalars stay Python floats (float64) until they meet a tensor."""
+csrc/optim_flat.hip or mask_bev_amd/optimizers.py.  Python scalars stay Python floats (float64) until they meet a tensor.
+The two ``*_unfused`` functions restate one AdamW / SGD step in f32 with one rounding per operation, for exact comparisons."""
 import math
 
 import torch
@@ -34,3 +35,39 @@ def sgd_step(p, g, buf, lr, momentum=0.99, dampening=0.0, weight_decay=0.0, nest
         buf = g.clone() if buf is None else buf.mul(momentum).add(g, alpha=1 - dampening)
         g = g.add(buf, alpha=momentum) if nesterov else buf
     return p.add(g, alpha=-lr), buf
+
+
+def _f32(x):
+    return torch.tensor(x, dtype=torch.float32)
+
+
+def adamw_step_unfused(p, g, m, v, t, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, decoupled=True):
+    """One Adam / AdamW step of an f32 tensor with ONE ROUNDING PER OPERATION in the order mbv_adamw_step's block of
+    include/maskbev_hip.h words it: every multiply and add is its own torch call on f32 tensors (no ``alpha=``, no
+    ``addcmul``, which a backend may fuse), the hyper-parameters are rounded to f32 first, and the bias corrections are taken
+    in float64 from the f32 betas and rounded once.  IEEE multiply / add / divide / sqrt are correctly rounded on the CPU and
+    on the device, so a kernel that keeps this order is equal to it bit for bit.  Returns (p, m, v)."""
+    lr, b1, b2, eps, wd, gs, one = (_f32(x) for x in (lr, betas[0], betas[1], eps, weight_decay, grad_scale, 1.0))
+    bc1 = _f32(1.0 - float(b1) ** t)
+    bc2_sqrt = _f32(math.sqrt(1.0 - float(b2) ** t))
+    g = g * gs
+    if decoupled:
+        p = p * (one - lr * wd)
+    elif weight_decay != 0:
+        g = g + wd * p
+    m = m + (g - m) * (one - b1)
+    v = v * b2 + ((one - b2) * g) * g
+    denom = v.sqrt() / bc2_sqrt + eps
+    return p - (lr / bc1) * (m / denom), m, v
+
+
+def sgd_step_unfused(p, g, buf, lr, momentum=0.99, dampening=0.0, weight_decay=0.0, nesterov=True, grad_scale=1.0):
+    """``sgd_step`` for f32 tensors with one rounding per operation (see ``adamw_step_unfused``) and a buffer that starts at
+    zero, as mbv_sgd_step's does.  Returns (p, buf)."""
+    lr, mom, wd, gs = (_f32(x) for x in (lr, momentum, weight_decay, grad_scale))
+    g = g * gs
+    if weight_decay != 0:
+        g = g + wd * p
+    buf = buf * mom + (_f32(1.0) - _f32(dampening)) * g
+    g = g + mom * buf if nesterov else buf
+    return p - lr * g, buf

@@ -471,6 +471,115 @@ def test_flat_optimizers_refuse_frozen_parameters_and_cpu_arenas(device):
         FlatSGD(cpu_arena)
 
 
+def _adam(arena, **kw):
+    from mask_bev_amd.arena import FlatAdam
+    return FlatAdam(arena, [dict(segment=s, **HP[s]) for s in SEGMENTS], **kw)
+
+
+def test_flat_state_carries_its_kind_and_is_refused_by_the_other_optimizers(device):
+    """One checkpoint format for the three flat optimizers: each writes its own ``kind``, each refuses the other two, and a
+    state without the key (what FlatAdam wrote before it existed) still loads into FlatAdam and FlatLamb."""
+    from mask_bev_amd.arena import FlatSGD
+    make = dict(adam=lambda: _adam(_toy(device)[1]), lamb=lambda: _lamb(_toy(device)[1]),
+                sgd=lambda: FlatSGD(_toy(device)[1], lr=1e-2))
+    toy, arena = _toy(device)
+    stepped = _adam(arena)
+    _feed(toy, _gradients(1)[0])
+    stepped.step()
+    sds = {k: f().state_dict() for k, f in make.items()}
+    sds['adam'] = stepped.state_dict()
+    for k, sd in sds.items():
+        assert sd['flat_state']['kind'] == k
+    assert set(sds['adam']['flat_state']) == {'exp_avg', 'exp_avg_sq', 'steps', 'kind'}
+    for k, f in make.items():
+        for other, sd in sds.items():
+            if other != k:
+                with pytest.raises(ValueError, match=f"kind '{other}' cannot be loaded into Flat"):
+                    f().load_state_dict(sd)
+    legacy = dict(sds['adam'], flat_state={k: v for k, v in sds['adam']['flat_state'].items() if k != 'kind'})
+    assert float(stepped.exp_avg.abs().max()) > 0.0
+    for k in ('adam', 'lamb'):
+        opt = make[k]()
+        opt.load_state_dict(legacy)
+        assert torch.equal(opt.exp_avg, stepped.exp_avg) and torch.equal(opt.exp_avg_sq, stepped.exp_avg_sq)
+        assert opt.steps == 1
+
+
+def test_flat_adam_resumes_from_its_state_dict_bit_for_bit(device):
+    """Two steps, state_dict, a fresh FlatAdam over a fresh arena holding the saved parameters, one more step == three steps
+    without the interruption, in every bit of param, exp_avg, exp_avg_sq and the 16-bit shadow."""
+    grads = _gradients(3)
+
+    def run(toy, arena, opt, steps):
+        for s in steps:
+            _feed(toy, grads[s])
+            opt.step()
+        return opt
+
+    toy_a, arena_a = _toy(device)
+    a = run(toy_a, arena_a, _adam(arena_a), range(3))
+    toy_b, arena_b = _toy(device)
+    b = run(toy_b, arena_b, _adam(arena_b), range(2))
+    toy_c, arena_c = _toy(device)
+    c = _adam(arena_c)
+    c.load_state_dict(b.state_dict())
+    arena_c.param.copy_(arena_b.param)
+    arena_c.refresh_shadow()
+    assert c.steps == 2
+    run(toy_c, arena_c, c, [2])
+    torch.cuda.synchronize()
+    for x, y, name in ((arena_a.param, arena_c.param, 'param'), (a.exp_avg, c.exp_avg, 'exp_avg'),
+                       (a.exp_avg_sq, c.exp_avg_sq, 'exp_avg_sq'), (arena_a.shadow, arena_c.shadow, 'shadow')):
+        assert torch.equal(x, y), name
+    assert float((arena_a.param - _toy(device)[1].param).abs().max()) > 0.0
+
+
+@pytest.mark.parametrize('entry', ['adamw', 'sgd'])
+@pytest.mark.parametrize('n', [1, 3, 4, 5, 1027, 2051])
+def test_streaming_helpers_at_vector_and_tail_boundaries(device, entry, n):
+    """mbv_adamw_step / mbv_sgd_step through the C ABI at the sizes where the shared streaming frame can go wrong: below one
+    float4 (1, 3), exactly one (4), one plus a tail (5), a full block of vectors plus a tail (1027) and two blocks plus a tail
+    (2051).  With the overflow flag clear the result EQUALS tests/optim_ref.py's one-rounding-per-operation f32 restatement
+    (the kernels pin contraction off and use correctly rounded divide / sqrt, so there is nothing to tolerate), the shadow is
+    the RNE bf16 of the new parameter and the gradient is cleared; with the flag set parameters, state and shadow are
+    untouched and the gradient is cleared all the same, ragged tail included."""
+    from mask_bev_amd import _lib
+    lib = _lib.load()
+    gen = torch.Generator().manual_seed(1000 + n)
+    p0, g0 = torch.randn(n, generator=gen), torch.randn(n, generator=gen) * 0.3
+    m0, v0 = torch.randn(n, generator=gen) * 0.1, torch.rand(n, generator=gen) * 0.01
+    st = torch.cuda.current_stream().cuda_stream
+    scale = torch.ones(1, device=device)
+    if entry == 'adamw':
+        hp = dict(lr=3e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05)
+        want = R.adamw_step_unfused(p0, g0, m0, v0, 2, **hp)
+        state0 = (m0, v0)
+    else:
+        hp = dict(lr=1e-2, momentum=0.99, weight_decay=1e-3)
+        want = R.sgd_step_unfused(p0, g0, m0, nesterov=True, **hp)
+        state0 = (m0,)
+    for skip in (1, 0):
+        p, g = p0.to(device), g0.to(device)
+        state = [s.to(device) for s in state0]
+        shadow = torch.full((n,), 7.0, dtype=torch.bfloat16, device=device)
+        flag = torch.full((1,), skip, dtype=torch.int32, device=device)
+        if entry == 'adamw':
+            rc = lib.mbv_adamw_step(p.data_ptr(), g.data_ptr(), state[0].data_ptr(), state[1].data_ptr(), shadow.data_ptr(), 1,
+                                    n, hp['lr'], hp['betas'][0], hp['betas'][1], hp['eps'], hp['weight_decay'], 2, 1.0, 1, 1,
+                                    scale.data_ptr(), flag.data_ptr(), 0, st)
+        else:
+            rc = lib.mbv_sgd_step(p.data_ptr(), g.data_ptr(), state[0].data_ptr(), shadow.data_ptr(), 1, n, hp['lr'],
+                                  hp['momentum'], 0.0, hp['weight_decay'], 1, 1.0, 1, scale.data_ptr(), flag.data_ptr(), st)
+        assert rc == 0
+        torch.cuda.synchronize()
+        assert float(g.abs().max()) == 0.0, skip
+        got = [p.cpu()] + [s.cpu() for s in state]
+        expect = [p0, *state0] if skip else list(want)
+        for i, (x, y) in enumerate(zip(got, expect)):
+            assert torch.equal(x, y), (skip, i, float((x - y).abs().max()))
+        assert torch.equal(shadow.cpu(), torch.full((n,), 7.0, dtype=torch.bfloat16) if skip else want[0].to(torch.bfloat16))
+
+
 @pytest.mark.parametrize('kind', ['lamb', 'sgd'])
 def test_module_trains_with_flat_lamb_and_sgd(device, kind):
     """The whole module under `optimiser_type: lamb | sgd` with bf16 compute, flattened, six captured steps: the flat optimizer

@@ -143,6 +143,9 @@ def test_k40_entry_points_are_declared_bound_and_priced():
         assert name in _lib.SIGNATURES and name in declared and name in W.MODELS, name
     assert _lib.ABI_VERSION == 59
     assert build.FILE_FLAGS['optim_flat.hip'] == ['-ffp-contract=off']
+    # one unit for the optimizer passes (K11's AdamW with K40), one for the parameter-gradient kernels, on default flags
+    assert 'pgrad.hip' in build.sources() and 'optim_flat.hip' in build.sources() and 'optim.hip' not in build.sources()
+    assert 'pgrad.hip' not in build.FILE_FLAGS
     P = ctypes.c_void_p
     n = 3 * 4096 + 64                                        # one parameter: three full chunks and a 64-element one
     _lib.WORK_HINT.pop('lamb_elems', None)
