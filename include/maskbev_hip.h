@@ -483,6 +483,15 @@ int mbv_adamw_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                    float grad_scale, int32_t decoupled, int32_t zero_grad, const float* loss_scale,
                    const int32_t* skip_flag, const int32_t* applied_steps, void* stream);
 
+/* mbv_adamw_step over `count` element ranges [start[i], start[i] + len[i]) of arenas of n elements, one launch per 64 ranges
+ * (start / len: HOST arrays, multiples of 4, inside the arena): the short ranges a step leaves between weights whose update
+ * another kernel performed (K3's backward, mbv_gemm16_tn_group_adam).  Arithmetic and loss-scaling protocol of mbv_adamw_step. */
+int mbv_adamw_step_ranges(float* param, float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                          int32_t shadow_dtype, int64_t n, const int64_t* start, const int64_t* len, int32_t count, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                          int32_t decoupled, int32_t zero_grad, const float* loss_scale, const int32_t* skip_flag,
+                          const int32_t* applied_steps, void* stream);
+
 int mbv_grad_nonfinite(const float* grad, int64_t n, int32_t* flag, void* stream);
 
 int mbv_loss_scale_update(float* loss_scale, int32_t* clean_steps, int32_t* flag, float growth, float backoff,
@@ -908,8 +917,36 @@ int mbv_gemm16_tn_group(const void* const* g, const void* const* x, float* const
                         const int64_t* k, const int64_t* ldg, const int64_t* ldx, int32_t count, int32_t dtype,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* mbv_gemm16_tn_group with the AdamW update of a weight in the epilogue of its gradient's product.
+ * mbv_adam_dev: the hyper-parameters of one parameter group in DEVICE memory (64 bytes, 4-byte aligned) — read when the
+ *   launch RUNS, so a launch captured in a graph follows the learning-rate schedule and the step count.
+ * mbv_adam_args_write: fills a block for update `step` (1-based; the bias corrections are computed on the host exactly as
+ *   mbv_adamw_step computes them) with a one-thread launch on `stream`.  shadow_kind = MBV_DT_BF16 / MBV_DT_F16 (0: unused).
+ * mbv_gemm16_tn_group_adam: as mbv_gemm16_tn_group; adam (HOST array of length count) holds for every entry a DEVICE
+ *   mbv_adam_dev block or null.  An entry with a block whose token sum is ONE work item (m[i] <= 4096: its tile is the whole
+ *   gradient) and whose dw[i] = grad + o lies inside the arena gradient [grad, grad + arena_numel) with o a multiple of 8
+ *   does not touch dw[i]: its owner reads param / exp_avg / exp_avg_sq at o, applies mbv_adamw_step's arithmetic
+ *   (grad_scale 1, no loss scaling) with the gradient from its accumulators and writes them back, with the 16-bit shadow
+ *   (nullable).  All four arenas 16-byte aligned.  fused (HOST, out, length count) is 1 for the entries that did so; every
+ *   other entry — no block, or a deeper token sum — accumulates into dw[i] as in mbv_gemm16_tn_group.  The CALLER keeps a
+ *   fused destination out of the step's mbv_adamw_step and never hands one destination to two entries. */
+typedef struct mbv_adam_dev {
+  float lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt;
+  int32_t decoupled, shadow_kind;
+  int32_t pad[7];
+} mbv_adam_dev;
+
+int mbv_adam_args_write(void* dev_block, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                        int32_t decoupled, int32_t shadow_kind, void* stream);
+
+int mbv_gemm16_tn_group_adam(const void* const* g, const void* const* x, float* const* dw, const int64_t* m,
+                             const int64_t* n, const int64_t* k, const int64_t* ldg, const int64_t* ldx, int32_t count,
+                             int32_t dtype, void* workspace, size_t workspace_bytes, const void* const* adam, float* grad,
+                             float* param, float* exp_avg, float* exp_avg_sq, void* shadow, int64_t arena_numel,
+                             int32_t* fused, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
- * K19 — row-local stage chains of the transformer decoder's query side (csrc/rowchain.hip).
+ * K19— row-local stage chains of the transformer decoder's query side (csrc/rowchain.hip).
  * Replaces, per decoder layer, the few-row Linear / LayerNorm / ReLU / add launches between two attention calls of
  * mask_bev/models/networks/mask2former_head/mask2former_head.py:535-560 (mmdet Mask2FormerTransformerDecoderLayer:
  * cross-attn out-proj + LN, self-attn projections, out-proj + LN, FFN + LN) and the prediction-head MLPs of :428-472.

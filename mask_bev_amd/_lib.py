@@ -12,7 +12,7 @@ from typing import Dict, List, Tuple
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libmaskbev_hip.so')
 
-# Raised when a declared signature changes.  Entries that were only ADDED since (K33b, K35, K38, K39, K40) left it at 59: a stale
+# Raised when a declared signature changes.  Entries that were only ADDED since (K33b, K35, K38, K39, K40, K17's AdamW epilogue) left it at 59: a stale
 # library without them passes the version check below and fails at the symbol lookup of load(), which names the symbol.
 ABI_VERSION = 59
 
@@ -186,7 +186,12 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_patch_embed32_bwd_weight': (ctypes.c_int, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, c_size_t, _P]),
     'mbv_gemm32s_tn_acc': (ctypes.c_int, [_P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, c_size_t, _P]),
     'mbv_gemm16_tn_group': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, c_size_t, _P]),
-    'mbv_select_queries': (ctypes.c_int, [_P, _I, _L, _I, _F, _P, _P, _P, _P]),
+    'mbv_gemm16_tn_group_adam': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, c_size_t, _P, _P, _P, _P, _P, _P,
+                                                _L, _P, _P]),
+    'mbv_adamw_step_ranges': (ctypes.c_int, [_P, _P, _P, _P, _P, _I, _L, _P, _P, _I, _F, _F, _F, _F, _F, _L, _F, _I, _I, _P, _P,
+                                             _P, _P]),
+    'mbv_adam_args_write':(ctypes.c_int, [_P, _F, _F, _F, _F, _F, _L, _I, _I, _P]),
+    'mbv_select_queries':(ctypes.c_int, [_P, _I, _L, _I, _F, _P, _P, _P, _P]),
     'mbv_extract_masks_workspace_bytes': (c_size_t, [_I, _I, _I, _I, _I, _I]),
     'mbv_extract_masks': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, c_size_t, _P]),
     'mbv_rasterize_workspace_bytes': (c_size_t, [_I, _I, _I]),

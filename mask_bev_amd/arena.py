@@ -22,6 +22,7 @@ Build it after the module is on its GPU (``module.to(device)`` re-allocates para
 """
 from __future__ import annotations
 
+import ctypes
 import weakref
 from typing import Dict, Iterable, List, Optional, Tuple
 
@@ -32,6 +33,7 @@ from . import _lib, ops
 from ._lib import check
 
 _ALIGN = 64          # elements: every parameter starts on a 256-byte boundary
+_SHORT_RUN = 1 << 23  # elements: an optimizer run shorter than this shares a launch with its like (FlatAdam._launch)
 
 
 def _round_up(n: int, a: int) -> int:
@@ -377,6 +379,9 @@ class FlatAdam(FlatOptimizer):
                          scaler, zero_grad)
         self._k3 = None              # (weight, bias, offset_w, offset_b) of a LayerNorm whose update K3's backward performs
         self._k3_applied = False
+        self._mx: Dict[int, nn.Parameter] = {}     # arena offset -> weight whose update its weight-gradient GEMM performs
+        self._mx_applied: set = set()              # offsets of those a pass has updated since the last step()
+        self._adam_dev = None        # (param groups, 16) words: one mbv_adam_dev block per group, read by those GEMMs
 
     # -- K3 backward + AdamW of the (C, ny, nx) LayerNorm affine in one launch (csrc/scatter_layernorm.hip, ADAM) ------------
     def fuse_layernorm_affine(self, weight: Optional[nn.Parameter], bias: Optional[nn.Parameter] = None) -> bool:
@@ -432,12 +437,108 @@ class FlatAdam(FlatOptimizer):
                     lr=float(pg['lr']), beta1=float(pg['betas'][0]), beta2=float(pg['betas'][1]), eps=float(pg['eps']),
                     weight_decay=float(pg['weight_decay']), step=self.steps + 1, decoupled=1 if self.decoupled else 0)
 
+    # -- AdamW of Linear weights in the epilogue of their weight-gradient product (csrc/gemm.hip, k_gemm16_tn_group) --------------
+    def fuse_matrices(self, params: Optional[Iterable[nn.Parameter]]) -> bool:
+        """Ask the grouped K17 weight-gradient launch (``ops.launch_tn_group``) to perform the AdamW update of these 2-D
+        weights itself: a product whose token sum is one work item deep holds the complete gradient of its tile in registers,
+        so the gradient never reaches the arena — 16 B per parameter of gradient traffic less per step.  Only weights used
+        ONCE per pass qualify (a second product for an armed weight raises), and the CALLER guarantees one backward pass per
+        ``step()``; a second pass before ``step()`` raises.  Refused with a loss scaler, with ``grad_scale`` != 1 and without
+        ``zero_grad_in_step``, as :meth:`fuse_layernorm_affine` and for its reasons.  ``None`` disarms.  The arm is a weak
+        reference on the weight's gradient view (``p.grad._mbv_adam``), where the launcher finds it.  A product that does not
+        qualify when it runs (deeper token sum, another kernel) leaves its weight to ``mbv_adamw_step`` as ever: what is cut
+        out of that pass is what a launch REPORTED applied.  Returns whether anything is armed."""
+        for p in self._mx.values():
+            g = p.grad
+            ref = getattr(g, '_mbv_adam', None) if g is not None else None
+            if ref is not None and ref() is self:
+                del g._mbv_adam
+        self._mx, self._mx_applied = {}, set()
+        params = list(params or [])
+        if (not params or self.scaler is not None or float(self.grad_scale) != 1.0 or not self.zero_grad_in_step
+                or self.arena.device.type != 'cuda'):
+            return False
+        off = {id(p): o for p, o in self.arena.layout}
+        for p in params:
+            o = off.get(id(p))
+            g = p.grad
+            if (o is None or p.dim() != 2 or p.numel() % 8 or g is None
+                    or g.data_ptr() != self.arena.grad.data_ptr() + 4 * o or self._group_of(o) is None):
+                continue
+            self._mx[o] = p
+            # the range is cut out of k_adamw whenever a launch applied it: nothing would clear what its gradient holds
+            self.arena.grad[o:o + _round_up(p.numel(), _ALIGN)].zero_()
+            g._mbv_adam = weakref.ref(self)
+        if self._mx and self._adam_dev is None:
+            self._adam_dev = torch.zeros(len(self.param_groups), 16, dtype=torch.float32, device=self.arena.device)
+        return bool(self._mx)
+
+    @property
+    def matrices_armed(self) -> bool:
+        return bool(self._mx)
+
+    def _matrix_offset(self, acc: torch.Tensor) -> Optional[int]:
+        o = (acc.data_ptr() - self.arena.grad.data_ptr()) // 4
+        p = self._mx.get(o)
+        return o if p is not None and acc.numel() == p.numel() else None
+
+    def claim_matrix(self, acc: torch.Tensor) -> int:
+        """Called by the launcher for a destination ``acc``: the device address of the hyper-parameter block the fused update
+        of that weight reads, or 0 (not armed / a data-parallel step)."""
+        o = self._matrix_offset(acc)
+        if o is None or float(self.grad_scale) != 1.0:
+            return 0
+        if o in self._mx_applied:
+            raise _lib.MaskBevHipError('FlatAdam: a second weight-gradient product before step() for a weight whose update '
+                                       'is fused into that product (gradient accumulation needs fuse_matrices(None))')
+        pg = self._group_of(o)
+        return self._adam_dev.data_ptr() + 64 * next(i for i, q in enumerate(self.param_groups) if q is pg)
+
+    def write_adam_blocks(self):
+        """The hyper-parameters of the COMING update (``steps + 1``) into every group's device block, on the current stream:
+        before each replay of a graph that holds fused launches, or right in front of an eager one."""
+        if not self._mx:
+            return
+        lib, stream = _lib.load(), torch.cuda.current_stream(self.arena.device).cuda_stream
+        for i, pg in enumerate(self.param_groups):
+            check(lib.mbv_adam_args_write(self._adam_dev.data_ptr() + 64 * i, float(pg['lr']), float(pg['betas'][0]),
+                                          float(pg['betas'][1]), float(pg['eps']), float(pg['weight_decay']), self.steps + 1,
+                                          1 if self.decoupled else 0, self.arena.shadow_flag, stream), 'mbv_adam_args_write')
+
+    def note_matrices_applied(self, accs) -> None:
+        """These destinations' updates were applied by a launch (or by the replay of one): the coming ``step()`` skips them."""
+        for acc in accs:
+            o = acc if isinstance(acc, int) else self._matrix_offset(acc)
+            if o is not None and o in self._mx:
+                self._mx_applied.add(o)
+
+    def take_matrices_applied(self) -> List[int]:
+        """Offsets marked applied, unmarking them: what a graph CAPTURE recorded (nothing ran) and each replay re-announces."""
+        done, self._mx_applied = sorted(self._mx_applied), set()
+        return done
+
     def _group_of(self, offset: int):
         for pg in self.param_groups:
             a, b = self.arena.segments[pg['segment']]
             if a <= offset < b:
                 return pg
         return None
+
+    @staticmethod
+    def _cut(runs: List[list], ranges) -> List[list]:
+        """``runs`` without the element ranges ``[(lo, hi), ...]``: what a fused kernel already updated."""
+        for lo, hi in sorted(ranges, reverse=True):
+            cut = []
+            for a, b, hp in runs:
+                if lo >= b or hi <= a:
+                    cut.append([a, b, hp])
+                else:
+                    if a < lo:
+                        cut.append([a, lo, hp])
+                    if hi < b:
+                        cut.append([hi, b, hp])
+            runs = cut
+        return runs
 
     def _launch(self, lib, stream):
         ar = self.arena
@@ -449,22 +550,32 @@ class FlatAdam(FlatOptimizer):
             # element ranges out of the launches
             self._k3_applied = False
             w, bp, ow, ob = self._k3
-            for lo in sorted((ow, ob), reverse=True):
-                hi = lo + _round_up(w.numel(), _ALIGN)
-                cut = []
-                for a, b, hp in runs:
-                    if lo >= b or hi <= a:
-                        cut.append([a, b, hp])
-                    else:
-                        if a < lo:
-                            cut.append([a, lo, hp])
-                        if hi < b:
-                            cut.append([hi, b, hp])
-                runs = cut
+            runs = self._cut(runs, [(o, o + _round_up(w.numel(), _ALIGN)) for o in (ow, ob)])
+        if self._mx_applied:
+            # ... and the weight-gradient launches these matrices
+            runs = self._cut(runs, [(o, o + _round_up(self._mx[o].numel(), _ALIGN)) for o in self.take_matrices_applied()])
         scale, flag, applied = self._scaler_ptrs()
-        for a, b, (lr, b1, b2, eps, wd) in runs:
-            if b == a:
+        runs = [r for r in runs if r[1] > r[0]]
+        # what the cuts leave between the matrices of a block — biases, LayerNorm affines, position tables — is dozens of short
+        # ranges: those of one hyper-parameter set share a launch (mbv_adamw_step_ranges) instead of taking one each
+        short: Dict[tuple, list] = {}
+        for a, b, hp in runs:
+            if b - a < _SHORT_RUN:
+                short.setdefault(hp, []).append((a, b))
+        for hp, rs in short.items():
+            if len(rs) < 2:
                 continue
+            runs = [r for r in runs if r[2] != hp or (r[0], r[1]) not in rs]
+            lr, b1, b2, eps, wd = hp
+            LA = ctypes.c_int64 * len(rs)
+            with ops.TIMER.span('k_adamw'):
+                check(lib.mbv_adamw_step_ranges(ar.param.data_ptr(), ar.grad.data_ptr(), self.exp_avg.data_ptr(),
+                                                self.exp_avg_sq.data_ptr(), 0 if ar.shadow is None else ar.shadow.data_ptr(),
+                                                ar.shadow_flag, ar.numel, LA(*[a for a, _ in rs]), LA(*[b - a for a, b in rs]),
+                                                len(rs), lr, b1, b2, eps, wd, self.steps, float(self.grad_scale),
+                                                1 if self.decoupled else 0, 1 if self.zero_grad_in_step else 0, scale, flag,
+                                                applied, stream), 'mbv_adamw_step_ranges')
+        for a, b, (lr, b1, b2, eps, wd) in runs:
             sh = 0 if ar.shadow is None else ar.shadow.data_ptr() + 2 * a
             with ops.TIMER.span('k_adamw'):
                 check(lib.mbv_adamw_step(ar.param.data_ptr() + 4 * a, ar.grad.data_ptr() + 4 * a,

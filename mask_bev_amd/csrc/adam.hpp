@@ -15,6 +15,25 @@ struct AdamArgs {
                                    //   Adam's step count must not advance there (a host count would)
 };
 
+// The hyper-parameters of one parameter group in DEVICE memory (= mbv_adam_dev, maskbev_hip.h): what an update that is
+// captured in a graph reads at replay time — the learning rate and the bias corrections change from step to step, kernel
+// arguments do not.  Written by mbv_adam_args_write (optim_flat.hip), read by K17's grouped weight-gradient epilogue.
+struct AdamDev {
+  float lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt;
+  int decoupled, shadow_kind;
+  int pad[7];
+};
+static_assert(sizeof(AdamDev) == 64, "one block per 64 bytes");
+
+__device__ __forceinline__ AdamArgs adam_args_from(const AdamDev& d) {
+  AdamArgs a;
+  a.lr = d.lr; a.beta1 = d.beta1; a.beta2 = d.beta2; a.eps = d.eps; a.weight_decay = d.weight_decay;
+  a.bias_correction1 = d.bias_correction1; a.bias_correction2_sqrt = d.bias_correction2_sqrt;
+  a.grad_scale = 1.0f; a.decoupled = d.decoupled; a.zero_grad = 0; a.shadow_kind = d.shadow_kind;
+  a.loss_scale = nullptr; a.skip = nullptr; a.applied = nullptr;
+  return a;
+}
+
 __device__ __forceinline__ unsigned short shadow_bits(float p, int kind) {
   return kind == MBV_DT_F16 ? __builtin_bit_cast(unsigned short, (_Float16)p) : f32_to_bf16_rne(p);
 }

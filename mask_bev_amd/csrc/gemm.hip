@@ -24,6 +24,7 @@
 // wave-instruction adds two 128-byte row segments, the full-rate shape of MI355X_MICROARCH.md §Global float atomics).
 
 #include "common.hpp"
+#include "adam.hpp"
 #include "gemm_tiles.hpp"
 
 namespace {
@@ -72,10 +73,21 @@ struct GemmArgs {
   int tap[9];           //   k = (tap, channel): the A rows of the K-steps of tap t (tap_steps each) are tap[t] bytes further on
 };
 
+// STORE epilogue of a weight gradient whose AdamW update happens right here (k_gemm16_tn_group): the tile is the complete
+// gradient of its elements, so instead of adding it to c the owner reads param / exp_avg / exp_avg_sq at the same element
+// offsets, runs adam_one (adam.hpp: the arithmetic of k_adamw, bit for bit) with g from the accumulator and writes them back
+// with the 16-bit shadow.  c is neither read nor written.  The views start at the element c starts at (a multiple of 8: the
+// 8-byte shadow stores of a 4-column group are aligned).
+struct AdamEpi {
+  const AdamDev* hp = nullptr;   // hyper-parameters in device memory, read at run time: a captured launch follows the schedule; null: no update
+  float* param = nullptr; float* exp_avg = nullptr; float* exp_avg_sq = nullptr;
+  unsigned short* shadow = nullptr;   // nullable
+};
+
 // One workgroup's share of a product: work item `bid` of the (batch, split, tile_m, tile_n) index, tile_n fastest, so
 // that the items that share an A panel are neighbours (and, after xcd_contiguous, share an L2).
 template <int KB, int NS, int WM, int TM, int TN, bool A_KS, bool B_KS, int OUT, int EPI, typename T>
-__device__ __forceinline__ void gemm16_body(const GemmArgs& p, const int bid, char* smem) {
+__device__ __forceinline__ void gemm16_body(const GemmArgs& p, const int bid, char* smem, const AdamEpi ad = AdamEpi{}) {
   using G = Geo<KB, NS, WM, TM, TN>;
   static_assert(OUT == 1 || TN == 2, "the STORE epilogue turns 64-column wave tiles");
   constexpr int BM = G::BM, BN = G::BN;
@@ -226,6 +238,8 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& p, const int bid, ch
   float bias8[8], csum[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { bias8[e] = 0.f; csum[e] = 0.f; }
+  AdamArgs adam = {};
+  if (ad.hp) adam = adam_args_from(*ad.hp);           // (block-uniform: scalar loads)
   if (p.bias && col_ok) {
     const float4 b0 = *reinterpret_cast<const float4*>(p.bias + gn);
     const float4 b1 = *reinterpret_cast<const float4*>(p.bias + gn + 4);
@@ -244,6 +258,55 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& p, const int bid, ch
         *reinterpret_cast<f32x4*>(stg + r * STG_LD + 32 * j + 8 * g + 4 * h) = v;
       }
     __syncthreads();
+    if (ad.hp) {
+      // The update of this wave's 32 x 64 block, g from the staged accumulators.  A lane owns columns 4 cg .. 4 cg + 3 of each
+      // 32-column half, so every instruction moves whole 128-byte row segments (8 lanes x 16 B); the rows of pass ps + 1 are
+      // requested before pass ps is computed and stored (two passes in flight: the stores could alias the loads for all the
+      // compiler knows, so it would not hoist them itself).  Streaming accesses, as k_adamw; c is not touched.
+      const int gc = n0 + 64 * wn + 4 * cg;
+      const bool okc[2] = {gc < p.gn, gc + 32 < p.gn};           // gn % 8 == 0: a 4-column group is all in or all out
+      f32x4 pp[2][2], mm[2][2], vv[2][2];
+      auto request = [&](int ps, int b) {
+        const int gm = mrow0 + 32 * i + 8 * ps;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          if (gm >= p.gm || !okc[q]) continue;
+          const size_t o = cbase + (size_t)gm * p.ldc + gc + 32 * q;
+          pp[b][q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ad.param + o));
+          mm[b][q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ad.exp_avg + o));
+          vv[b][q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ad.exp_avg_sq + o));
+        }
+      };
+      request(0, 0);
+#pragma unroll
+      for (int ps = 0; ps < 4; ++ps) {
+        const int b = ps & 1;
+        if (ps + 1 < 4) request(ps + 1, b ^ 1);
+        const int row = 8 * ps + prow;
+        const int gm = mrow0 + 32 * i + 8 * ps;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          if (gm >= p.gm || !okc[q]) continue;
+          const size_t o = cbase + (size_t)gm * p.ldc + gc + 32 * q;
+          const f32x4 g4 = *reinterpret_cast<const f32x4*>(stg + row * STG_LD + 32 * q + 4 * cg);
+          f32x4 pq = pp[b][q], mq = mm[b][q], vq = vv[b][q];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float pc = pq[e], mc = mq[e], vc = vq[e];
+            adam_one(pc, g4[e], mc, vc, adam);
+            pq[e] = pc; mq[e] = mc; vq[e] = vc;
+          }
+          __builtin_nontemporal_store(pq, reinterpret_cast<f32x4*>(ad.param + o));
+          __builtin_nontemporal_store(mq, reinterpret_cast<f32x4*>(ad.exp_avg + o));
+          __builtin_nontemporal_store(vq, reinterpret_cast<f32x4*>(ad.exp_avg_sq + o));
+          if (ad.shadow)                                  // read again by the next forward: a normal store
+            *reinterpret_cast<uint2*>(ad.shadow + o) =
+                make_uint2((unsigned)shadow_bits(pq[0], adam.shadow_kind) | ((unsigned)shadow_bits(pq[1], adam.shadow_kind) << 16),
+                           (unsigned)shadow_bits(pq[2], adam.shadow_kind) | ((unsigned)shadow_bits(pq[3], adam.shadow_kind) << 16));
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
       const int row = 8 * ps + prow;
@@ -326,16 +389,22 @@ __global__ void __launch_bounds__(64 * 2 * WM, (Geo<KB, NS, WM, TM, TN>::WPS)) k
 // tiles of ~40 layers do.  Work item = (entry, split, tile_m, tile_n); every entry is cut into token ranges of about
 // the same depth, so the items are about equally long.  splits == 1: the owner adds its tile to dw in place;
 // splits > 1: partial tiles go to the workspace and k_add_parts_group folds them into dw (no atomics either way).
+// A splits == 1 entry whose dw lies in a parameter arena's gradient may carry `adam`: its owner then applies the AdamW
+// update of its tile instead of adding the tile to dw (AdamEpi) — the gradient's round trip through HBM is gone.
 constexpr int kTnGroup = 48;
 struct TnEntry {
   const void* g; const void* x; float* out;     // out: dw (splits == 1) or this entry's parts in the workspace
+  const AdamDev* adam;                          // non-null: splits == 1 and out = grad + (this entry's arena offset)
   int m, n, k, ldg, ldx, ldo;
   int ntn, splits, ksteps, item_begin;
 };
 struct TnGroupArgs {
   TnEntry e[kTnGroup];
+  float* grad; float* param; float* exp_avg; float* exp_avg_sq;      // arena bases of the entries that carry `adam`
+  unsigned short* shadow;                                            // nullable
   int n, total_items;
 };
+static_assert(sizeof(TnGroupArgs) <= 4096, "kernel arguments: 4 KB");
 
 template <int KB, int NS, typename T>
 __global__ void __launch_bounds__(256, (Geo<KB, NS, 2, 2, 2>::WPS)) k_gemm16_tn_group(const TnGroupArgs a) {
@@ -356,7 +425,13 @@ __global__ void __launch_bounds__(256, (Geo<KB, NS, 2, 2, 2>::WPS)) k_gemm16_tn_
   p.out_f32 = 1;
   p.acc_out = e.splits == 1;
   p.tap_steps = 0;
-  gemm16_body<KB, NS, 2, 2, 2, true, true, 0, EPI_NONE, T>(p, item - e.item_begin, smem);
+  AdamEpi ad = {};
+  if (e.adam) {
+    const long off = e.out - a.grad;
+    ad.hp = e.adam; ad.param = a.param + off; ad.exp_avg = a.exp_avg + off; ad.exp_avg_sq = a.exp_avg_sq + off;
+    ad.shadow = a.shadow ? a.shadow + off : nullptr;
+  }
+  gemm16_body<KB, NS, 2, 2, 2, true, true, 0, EPI_NONE, T>(p, item - e.item_begin, smem, ad);
 }
 
 constexpr int kPartsGroup = 96;
@@ -798,16 +873,45 @@ extern "C" size_t mbv_gemm16_tn_group_workspace_bytes(const int64_t* m, const in
   return total;
 }
 
+// The arena of the entries that may take their AdamW update in the epilogue (mbv_gemm16_tn_group_adam); all null: none does.
+struct TnGroupArena {
+  const void* const* adam;     // HOST array (count) of DEVICE mbv_adam_dev blocks; a null element: a plain entry
+  float* grad; float* param; float* exp_avg; float* exp_avg_sq;
+  void* shadow;
+  int64_t numel;
+  int32_t* fused;              // HOST array (count), out: 1 where the update was applied by the launch
+};
+
 // dw[i] (n[i], k[i]) f32, contiguous  +=  g[i] (m[i], n[i])^T . x[i] (m[i], k[i])   for i < count, in one GEMM launch
 // (+ one parts-add launch) per 48 products.  Every array argument is a HOST array of length count.
-extern "C" int mbv_gemm16_tn_group(const void* const* g, const void* const* x, float* const* dw, const int64_t* m,
-                                   const int64_t* n, const int64_t* k, const int64_t* ldg, const int64_t* ldx,
-                                   int32_t count, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+static int tn_group_impl(const void* const* g, const void* const* x, float* const* dw, const int64_t* m,
+                         const int64_t* n, const int64_t* k, const int64_t* ldg, const int64_t* ldx,
+                         int32_t count, int32_t dtype, void* workspace, size_t workspace_bytes, const TnGroupArena& ar,
+                         void* stream) {
   if (count < 0 || dtype < 0 || dtype > 1) return MBV_ERR_BAD_ARG;
   if (count > 0 && (!g || !x || !dw || !m || !n || !k || !ldg || !ldx)) return MBV_ERR_BAD_ARG;
   for (int i = 0; i < count; ++i) {
     if (m[i] < 0) return MBV_ERR_BAD_ARG;
     if (m[i] > 0 && !tn_group_entry_ok(g[i], x[i], dw[i], m[i], n[i], k[i], ldg[i], ldx[i])) return MBV_ERR_UNSUPPORTED;
+    if (ar.fused) ar.fused[i] = 0;
+  }
+  // which entries take their update in the epilogue: asked for, one token range (the tile is the whole gradient), and a
+  // dw that lies inside the arena gradient on an 8-element boundary (16-byte rows of the shadow)
+  auto fuses = [&](int i) {
+    if (!ar.adam || !ar.adam[i] || m[i] == 0) return false;
+    int splits, ksteps;
+    tn_group_split(m[i], splits, ksteps);
+    return splits == 1;
+  };
+  for (int i = 0; i < count; ++i) {
+    if (!fuses(i)) continue;
+    if (!ar.grad || !ar.param || !ar.exp_avg || !ar.exp_avg_sq || !ar.fused) return MBV_ERR_BAD_ARG;
+    if ((reinterpret_cast<size_t>(ar.grad) | reinterpret_cast<size_t>(ar.param) | reinterpret_cast<size_t>(ar.exp_avg) |
+         reinterpret_cast<size_t>(ar.exp_avg_sq) | reinterpret_cast<size_t>(ar.shadow)) & 15)
+      return MBV_ERR_BAD_ARG;
+    if (reinterpret_cast<size_t>(ar.adam[i]) & 3) return MBV_ERR_BAD_ARG;
+    const int64_t off = dw[i] - ar.grad;
+    if (dw[i] < ar.grad || off + n[i] * k[i] > ar.numel || (off & 7)) return MBV_ERR_BAD_ARG;
   }
   if (mbv_gemm16_tn_group_workspace_bytes(m, n, k, count) > workspace_bytes) return MBV_ERR_WORKSPACE;
   if (workspace_bytes && (!workspace || (reinterpret_cast<size_t>(workspace) & 15))) return MBV_ERR_WORKSPACE;
@@ -818,6 +922,8 @@ extern "C" int mbv_gemm16_tn_group(const void* const* g, const void* const* x, f
     TnGroupArgs a;
     PartsGroupArgs pa;
     a.n = 0; pa.n = 0;
+    a.grad = ar.grad; a.param = ar.param; a.exp_avg = ar.exp_avg; a.exp_avg_sq = ar.exp_avg_sq;
+    a.shadow = reinterpret_cast<unsigned short*>(ar.shadow);
     long long items = 0, pblocks = 0;
     for (int j = 0; j < cnt; ++j) {
       const int i = base + j;
@@ -827,6 +933,8 @@ extern "C" int mbv_gemm16_tn_group(const void* const* g, const void* const* x, f
       e.m = (int)m[i]; e.n = (int)n[i]; e.k = (int)k[i]; e.ldg = (int)ldg[i]; e.ldx = (int)ldx[i]; e.ldo = (int)k[i];
       e.ntn = (int)((k[i] + 127) / 128);
       tn_group_split(m[i], e.splits, e.ksteps);
+      e.adam = fuses(i) ? reinterpret_cast<const AdamDev*>(ar.adam[i]) : nullptr;
+      if (e.adam) ar.fused[i] = 1;
       e.item_begin = (int)items;
       items += (long long)((n[i] + 127) / 128) * e.ntn * e.splits;
       if (e.splits == 1) {
@@ -855,4 +963,26 @@ extern "C" int mbv_gemm16_tn_group(const void* const* g, const void* const* x, f
     }
   }
   return MBV_OK;
+}
+
+extern "C" int mbv_gemm16_tn_group(const void* const* g, const void* const* x, float* const* dw, const int64_t* m,
+                                   const int64_t* n, const int64_t* k, const int64_t* ldg, const int64_t* ldx,
+                                   int32_t count, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  return tn_group_impl(g, x, dw, m, n, k, ldg, ldx, count, dtype, workspace, workspace_bytes, TnGroupArena{}, stream);
+}
+
+// mbv_gemm16_tn_group whose entries with adam[i] != null and a token sum of one work item (m[i] <= 4096) apply the AdamW
+// update of dw[i]'s parameter in their epilogue: dw[i] = grad + offset, and param / exp_avg / exp_avg_sq / shadow (nullable)
+// are updated at the same offset from hyper-parameters read from the DEVICE block adam[i] (mbv_adam_args_write); dw[i] is
+// neither read nor written.  fused[i] (HOST, out) tells which entries did; the others accumulate into dw[i] as ever.
+extern "C" int mbv_gemm16_tn_group_adam(const void* const* g, const void* const* x, float* const* dw, const int64_t* m,
+                                        const int64_t* n, const int64_t* k, const int64_t* ldg, const int64_t* ldx,
+                                        int32_t count, int32_t dtype, void* workspace, size_t workspace_bytes,
+                                        const void* const* adam, float* grad, float* param, float* exp_avg,
+                                        float* exp_avg_sq, void* shadow, int64_t arena_numel, int32_t* fused, void* stream) {
+  if (count > 0 && (!adam || !fused)) return MBV_ERR_BAD_ARG;
+  TnGroupArena ar;
+  ar.adam = adam; ar.grad = grad; ar.param = param; ar.exp_avg = exp_avg; ar.exp_avg_sq = exp_avg_sq; ar.shadow = shadow;
+  ar.numel = arena_numel; ar.fused = fused;
+  return tn_group_impl(g, x, dw, m, n, k, ldg, ldx, count, dtype, workspace, workspace_bytes, ar, stream);
 }

@@ -74,6 +74,60 @@ __global__ void __launch_bounds__(256) k_adamw(float* __restrict__ param, float*
   }
 }
 
+// k_adamw over up to kAdamRanges SHORT element ranges of the arena in one launch: what is left of a segment between the
+// weights that took their update elsewhere (K3's backward, K17's grouped weight gradient) is dozens of ranges of a few hundred
+// to a few hundred thousand elements — biases, LayerNorm affines, position tables — and one launch each is 3 us of kernel
+// behind 8 us of launch.  Block b works on chunk (b - block_begin[i]) of range i, kRangeChunk4 float4 items; starts and
+// lengths are multiples of 4 elements (arena parameters start on 64-element boundaries), so there is no ragged tail.
+constexpr int kAdamRanges = 64;
+constexpr int kRangeChunk4 = 1024;      // float4 items per block: 4 per thread
+struct AdamRanges {
+  long start4[kAdamRanges];             // first float4 item
+  int len4[kAdamRanges];                // float4 items
+  int block_begin[kAdamRanges];
+  int n;
+};
+
+__global__ void __launch_bounds__(256) k_adamw_ranges(float* __restrict__ param, float* __restrict__ grad,
+                                                      float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                                      unsigned short* __restrict__ shadow, const AdamRanges r, AdamArgs a) {
+  int i = 0;
+  while (i + 1 < r.n && (int)blockIdx.x >= r.block_begin[i + 1]) ++i;       // block-uniform
+  const long base = r.start4[i];
+  const int c0 = ((int)blockIdx.x - r.block_begin[i]) * kRangeChunk4;
+  const int c1 = c0 + kRangeChunk4 < r.len4[i] ? c0 + kRangeChunk4 : r.len4[i];
+  if (a.loss_scale) a.grad_scale /= *a.loss_scale;
+  if (a.skip && *a.skip) {         // overflowed step, as k_adamw: only the gradient clear is honoured
+    if (a.zero_grad)
+      for (int j = c0 + threadIdx.x; j < c1; j += 256)
+        __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4*>(grad) + base + j);
+    return;
+  }
+  if (a.applied) {
+    const double t = (double)(*a.applied + 1);
+    a.bias_correction1 = (float)(1.0 - pow((double)a.beta1, t));
+    a.bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)a.beta2, t));
+  }
+  for (int j = c0 + threadIdx.x; j < c1; j += 256) {
+    const long idx = base + j;
+    f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + idx);
+    const f4 g = __builtin_nontemporal_load(reinterpret_cast<const f4*>(grad) + idx);
+    f4 m = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg) + idx);
+    f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(exp_avg_sq) + idx);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float pc = p[c], mc = m[c], vc = v[c];
+      adam_one(pc, g[c], mc, vc, a);
+      p[c] = pc; m[c] = mc; v[c] = vc;
+    }
+    __builtin_nontemporal_store(p, reinterpret_cast<f4*>(param) + idx);
+    __builtin_nontemporal_store(m, reinterpret_cast<f4*>(exp_avg) + idx);
+    __builtin_nontemporal_store(v, reinterpret_cast<f4*>(exp_avg_sq) + idx);
+    if (shadow) store_shadow4(shadow, idx, p, a.shadow_kind);
+    if (a.zero_grad) __builtin_nontemporal_store(f4{0.f, 0.f, 0.f, 0.f}, reinterpret_cast<f4*>(grad) + idx);
+  }
+}
+
 // f32 -> 16-bit shadow refresh of an arena (after load_state_dict / parameter broadcast).
 __global__ void __launch_bounds__(256) k_shadow(const float* __restrict__ param, unsigned short* __restrict__ shadow,
                                                 long n, int kind) {
@@ -278,6 +332,18 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ param, float* _
   }
 }
 
+// one thread fills a parameter group's hyper-parameter block (plain stores): stream-ordered in front of the launches that read it
+__global__ void k_adam_args_write(AdamDev* __restrict__ dst, AdamDev v) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
+}
+
+// Adam's bias corrections of update `step` (1-based), in f64 on the host and rounded once: the ONE place they are computed for
+// kernels that take them by value (k_adamw) and for the device block (mbv_adam_args_write), so the two are equal bit for bit
+inline void adam_bias_corrections(float beta1, float beta2, int64_t step, float& bc1, float& bc2_sqrt) {
+  bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+}
+
 inline unsigned chunk_grid(int c0, int c1) { return (unsigned)(c1 - c0 < kMaxBlocks ? c1 - c0 : kMaxBlocks); }
 
 inline bool bad_shadow(const void* shadow, int32_t shadow_dtype) {       // 8-byte aligned, bf16 or fp16
@@ -297,11 +363,63 @@ extern "C" int mbv_adamw_step(float* param, float* grad, float* exp_avg, float* 
   AdamArgs a;
   a.shadow_kind = shadow_dtype; a.loss_scale = loss_scale; a.skip = skip_flag; a.applied = applied_steps;
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-  a.bias_correction1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bias_correction2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  adam_bias_corrections(beta1, beta2, step, a.bias_correction1, a.bias_correction2_sqrt);
   a.grad_scale = grad_scale; a.decoupled = decoupled; a.zero_grad = zero_grad;
   hipLaunchKernelGGL(k_adamw, dim3(stream_blocks(n >> 2)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                      exp_avg_sq, reinterpret_cast<unsigned short*>(shadow_bf16), (long)n, a);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+// mbv_adamw_step over `count` element ranges [start[i], start[i] + len[i]) of arenas of n elements (HOST arrays; starts and
+// lengths multiples of 4, ranges inside the arena), one launch per 64 ranges: for the many short ranges a step leaves between
+// weights updated elsewhere.  Same arithmetic, same loss-scaling protocol.
+extern "C" int mbv_adamw_step_ranges(float* param, float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                     int32_t shadow_dtype, int64_t n, const int64_t* start, const int64_t* len, int32_t count,
+                                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                                     float grad_scale, int32_t decoupled, int32_t zero_grad, const float* loss_scale,
+                                     const int32_t* skip_flag, const int32_t* applied_steps, void* stream) {
+  if (n < 0 || count < 0 || step < 1 || !param || !grad || !exp_avg || !exp_avg_sq) return MBV_ERR_BAD_ARG;
+  if (count > 0 && (!start || !len)) return MBV_ERR_BAD_ARG;
+  if (misaligned16(param, grad, exp_avg, exp_avg_sq) || bad_shadow(shadow_bf16, shadow_dtype)) return MBV_ERR_BAD_ARG;
+  for (int i = 0; i < count; ++i)
+    if (start[i] < 0 || len[i] < 0 || ((start[i] | len[i]) & 3) || start[i] + len[i] > n || len[i] > 0x7fffffffLL)
+      return MBV_ERR_BAD_ARG;
+  AdamArgs a;
+  a.shadow_kind = shadow_dtype; a.loss_scale = loss_scale; a.skip = skip_flag; a.applied = applied_steps;
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+  adam_bias_corrections(beta1, beta2, step, a.bias_correction1, a.bias_correction2_sqrt);
+  a.grad_scale = grad_scale; a.decoupled = decoupled; a.zero_grad = zero_grad;
+  for (int base = 0; base < count; base += kAdamRanges) {
+    AdamRanges r;
+    r.n = 0;
+    long blocks = 0;
+    for (int i = base; i < count && i < base + kAdamRanges; ++i) {
+      if (len[i] == 0) continue;
+      r.start4[r.n] = start[i] >> 2; r.len4[r.n] = (int)(len[i] >> 2); r.block_begin[r.n] = (int)blocks;
+      blocks += ((len[i] >> 2) + kRangeChunk4 - 1) / kRangeChunk4;
+      ++r.n;
+    }
+    if (r.n == 0) continue;
+    if (blocks > 0x7fffffffLL) return MBV_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_adamw_ranges, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                       exp_avg_sq, reinterpret_cast<unsigned short*>(shadow_bf16), r, a);
+    MBV_CHECK_LAUNCH();
+  }
+  return MBV_OK;
+}
+
+// The hyper-parameters of update `step` into a 64-byte device block (mbv_adam_dev) that mbv_gemm16_tn_group_adam's fused
+// entries read when they RUN: called eagerly before each replay of a graph that holds such a launch.
+extern "C" int mbv_adam_args_write(void* dev_block, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                   int64_t step, int32_t decoupled, int32_t shadow_kind, void* stream) {
+  if (!dev_block || step < 1 || (reinterpret_cast<size_t>(dev_block) & 3)) return MBV_ERR_BAD_ARG;
+  if (shadow_kind != 0 && shadow_kind != MBV_DT_BF16 && shadow_kind != MBV_DT_F16) return MBV_ERR_BAD_ARG;
+  AdamDev v = {};
+  v.lr = lr; v.beta1 = beta1; v.beta2 = beta2; v.eps = eps; v.weight_decay = weight_decay;
+  adam_bias_corrections(beta1, beta2, step, v.bias_correction1, v.bias_correction2_sqrt);
+  v.decoupled = decoupled; v.shadow_kind = shadow_kind;
+  hipLaunchKernelGGL(k_adam_args_write, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<AdamDev*>(dev_block), v);
   MBV_CHECK_LAUNCH();
   return MBV_OK;
 }

@@ -37,7 +37,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import ops
+from . import ops, switches
 from .ddp import RangeReady
 from .mask_bev_module import MaskBevModule
 
@@ -129,6 +129,14 @@ class GraphedTrainStep:
             for p in self._graph_params:
                 p.grad = None
         self.x_static.grad = None
+        # One GPU: the AdamW update of the Swin blocks' qkv / proj / fc1 / fc2 matrices happens in the epilogue of their grouped
+        # weight-gradient product (each is used once per pass by construction; only products one work item deep take it).
+        # Armed AFTER the warm-up passes — they run without optimizer steps and would apply the update three times — and the
+        # captured launches read their hyper-parameters from device blocks that step() refreshes before every replay.
+        self._mx_fused = []
+        if (reducer is None and self.arena is not None and hasattr(optimizer, 'fuse_matrices')
+                and switches.get('adam_in_wgrad')):
+            optimizer.fuse_matrices(self._swin_matrices())
         # Two graphs sharing one memory pool: (1) forward, loss, backward of the head and of the LAST backbone stage;
         # (2) backward of the earlier stages.  Between the two replays a data-parallel step launches the all-reduce
         # of the gradients graph 1 completed (head + last stage = 38 % of the bytes), which then runs on RCCL's
@@ -141,7 +149,16 @@ class GraphedTrainStep:
         with torch.cuda.graph(self.graph_late, pool=self.graph.pool()):
             self._backward_early_stages()
         torch.cuda.synchronize()
+        if getattr(optimizer, 'matrices_armed', False):
+            # what the captured launches WILL apply on every replay (the capture itself ran nothing: unmarked again)
+            self._mx_fused = optimizer.take_matrices_applied()
         self._ranges_head, self._ranges_late = self._arena_ranges()
+
+    def _swin_matrices(self):
+        swin = self.m._backbone._backbone
+        return [w for stage in swin.stages for blk in stage.blocks
+                for w in (blk.attn.w_msa.qkv.weight, blk.attn.w_msa.proj.weight, blk.ffn.layers[0][0].weight,
+                          blk.ffn.layers[1].weight)]
 
     @staticmethod
     def _rows(x):
@@ -186,6 +203,9 @@ class GraphedTrainStep:
 
     def step(self, batch) -> torch.Tensor:
         m = self.m
+        if self._mx_fused and not self.opt.matrices_armed:
+            raise ops.MaskBevHipError('GraphedTrainStep: the captured weight-gradient launches apply AdamW updates the optimizer '
+                                      'no longer expects (fuse_matrices was disarmed, or close() called): build a new step')
         scans, labels, masks, _ = m._unpack(batch)
         with m._autocast():                                # eager: K1 → K2 → K3 (into the static buffer)
             x = self._rows(m._encoder(scans, patch=self._patch, out=self.x_static.detach()))
@@ -211,6 +231,8 @@ class GraphedTrainStep:
         mark = (lambda name, nbytes=0: tr[-1].append((name, time.perf_counter(), int(nbytes)))) if tr is not None \
             else (lambda *a: None)
         nb = lambda ranges: 4 * sum(b - a for a, b in ranges)
+        if self._mx_fused:
+            self.opt.write_adam_blocks()                   # this update's learning rate and bias corrections, read by the replay
         mark('graph 1 replay')
         self.graph.replay()                                # backbone, head, loss; backward of head + last stage
         handles = None
@@ -256,6 +278,8 @@ class GraphedTrainStep:
             x.backward(self.x_static.grad)                 # eager: backward of K3 / K2
             if self.reducer is not None:
                 self.reducer.reduce_all()
+        if self._mx_fused:
+            self.opt.note_matrices_applied(self._mx_fused)  # the replays updated these: cut out of the optimizer pass
         self.opt.step()
         if self.arena is None:
             for p in self.m._encoder.parameters():         # graph-owned gradients are overwritten by the replay
@@ -273,3 +297,5 @@ class GraphedTrainStep:
     def close(self):
         if self._k3_fused:
             self.opt.fuse_layernorm_affine(None)
+        if getattr(self.opt, 'matrices_armed', False):
+            self.opt.fuse_matrices(None)         # (graphs that hold fused launches: step() refuses from now on)

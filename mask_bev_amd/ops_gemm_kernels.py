@@ -179,11 +179,16 @@ def gemm16_tn(g: torch.Tensor, x: torch.Tensor, out_dtype: Optional[torch.dtype]
     return out
 
 
-def gemm16_tn_group(items) -> None:
+def gemm16_tn_group(items, adam=None, optimizer=None):
     """``acc (N, K) f32 += g (M, N)^T @ x (M, K)`` for every ``(g, x, acc)`` of ``items`` in one K17 launch per 48 (all of
-    one 16-bit dtype, contiguous ``acc``)."""
+    one 16-bit dtype, contiguous ``acc``).
+
+    ``adam`` (with ``optimizer``, a :class:`~mask_bev_amd.arena.FlatAdam`): per item the device address of the hyper-parameter
+    block of its parameter group, or 0 — an item with a block whose token sum is one work item deep takes the AdamW update
+    of its weight in the product's epilogue instead of adding to ``acc`` (mbv_gemm16_tn_group_adam).  Returns one flag per
+    item: whether the launch applied its update."""
     if not items:
-        return
+        return []
     lib = _lib.load()
     n = len(items)
     dt = items[0][0].dtype
@@ -196,10 +201,19 @@ def gemm16_tn_group(items) -> None:
         LA(*[x.shape[1] for _, x, _ in items])
     nbytes = lib.mbv_gemm16_tn_group_workspace_bytes(m, nn, k, n)
     ws = _workspace(nbytes, items[0][0].device) if nbytes else None
-    check(lib.mbv_gemm16_tn_group(PA(*[g.data_ptr() for g, _, _ in items]), PA(*[x.data_ptr() for _, x, _ in items]),
-                                  PA(*[a.data_ptr() for _, _, a in items]), m, nn, k,
-                                  LA(*[g.stride(0) for g, _, _ in items]), LA(*[x.stride(0) for _, x, _ in items]),
-                                  n, _GEMM16_DT[dt], _ptr(ws), int(nbytes), _stream()), 'mbv_gemm16_tn_group')
+    ptrs = (PA(*[g.data_ptr() for g, _, _ in items]), PA(*[x.data_ptr() for _, x, _ in items]),
+            PA(*[a.data_ptr() for _, _, a in items]), m, nn, k,
+            LA(*[g.stride(0) for g, _, _ in items]), LA(*[x.stride(0) for _, x, _ in items]),
+            n, _GEMM16_DT[dt], _ptr(ws), int(nbytes))
+    if adam is None or optimizer is None or not any(adam):
+        check(lib.mbv_gemm16_tn_group(*ptrs, _stream()), 'mbv_gemm16_tn_group')
+        return [False] * n
+    ar = optimizer.arena
+    fused = (ctypes.c_int32 * n)()
+    check(lib.mbv_gemm16_tn_group_adam(*ptrs, PA(*[int(b or 0) for b in adam]), ar.grad.data_ptr(), ar.param.data_ptr(),
+                                       optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), _ptr(ar.shadow),
+                                       ar.numel, fused, _stream()), 'mbv_gemm16_tn_group_adam')
+    return [bool(f) for f in fused]
 
 
 def _gemm32s_ok(*ts: torch.Tensor) -> bool:

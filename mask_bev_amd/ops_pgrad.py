@@ -151,9 +151,34 @@ def launch_tn_group(items) -> None:
     """The grouped launch(es) for a pass's products: deepest token sums first (their work items are the longest of a
     launch), one call per 16-bit dtype."""
     items = sorted(items, key=lambda it: -it[0].shape[0])
+    # destinations an optimizer armed (FlatAdam.fuse_matrices): the launch applies their AdamW update in its epilogue.  An
+    # armed destination takes ONE product per pass — a tied weight would be updated twice — so a second one raises.
+    opt, blocks, seen = None, {}, set()
+    for it in items:
+        arm = _adam_arm(it[2])
+        if arm is None or (opt is not None and arm is not opt):
+            continue
+        if it[2].data_ptr() in seen:
+            raise MaskBevHipError('launch_tn_group: two products for one destination whose AdamW update is fused into its '
+                                  'weight-gradient GEMM (a tied weight needs FlatAdam.fuse_matrices(None))')
+        block = arm.claim_matrix(it[2])
+        if block:
+            opt = arm
+            seen.add(it[2].data_ptr())
+            blocks[it[2].data_ptr()] = block
+    if opt is not None and not torch.cuda.is_current_stream_capturing():
+        opt.write_adam_blocks()          # an eager pass: by value, right in front of the launch that reads them
     for dt in {it[0].dtype for it in items}:
         for wave in _distinct_destination_waves([it for it in items if it[0].dtype == dt]):
-            gemm16_tn_group(wave)
+            fused = gemm16_tn_group(wave, [blocks.get(it[2].data_ptr(), 0) for it in wave], opt)
+            if opt is not None:
+                opt.note_matrices_applied([it[2] for it, f in zip(wave, fused) if f])
+
+
+def _adam_arm(acc: torch.Tensor):
+    """The optimizer that armed arena gradient ``acc`` for the fused update (a weak reference on the tensor object), or None."""
+    ref = getattr(acc, '_mbv_adam', None)
+    return None if ref is None or not switches.get('adam_in_wgrad') else ref()
 
 
 def _distinct_destination_waves(items):
@@ -299,8 +324,13 @@ def _wgrad_into(acc: torch.Tensor, g2: torch.Tensor, x2: torch.Tensor, bias_acc:
         per_layer = _k17_wants('wgrad', t) and (x2.shape[1] <= switches.get('tn_max_in') or gemm16_policy() == 'all')   # 2048-wide patch rows: the library wins (77 vs 95 us)
         # few-token 16-bit products (the decoder's 400-row output projections: a 256 x 256 result over 400 rows) are a
         # handful of work items of the grouped launch; alone, the library ran them as ONE 256 x 256 tile — 30 us each
-        few = t <= 512 and gemm16_policy() == 'auto'       # (Swin stage 4's 1024-token layers stay with the library: measured)
-        if (persistent and (per_layer or few or (switches.get('tn_group') == 'all' and t >= 512))
+        few = t <= 512 and gemm16_policy() == 'auto'       # (1024-token layers stay with the library unless `armed`: measured)
+        # a destination whose AdamW update the grouped launch performs (FlatAdam.fuse_matrices) joins it whenever its token sum
+        # is one work item deep, also where the GEMM alone is the library's (Swin stage 4's 1024 tokens, 3072-wide fc2 rows):
+        # the comparison is now GEMM + 34 B per parameter of optimizer pass against a GEMM with a 26-byte epilogue
+        armed = (switches.get('adam_wgrad_min_tokens') <= t <= 4096 and gemm16_policy() == 'auto'
+                 and acc.is_contiguous() and _adam_arm(acc) is not None)
+        if (persistent and (per_layer or few or armed or (switches.get('tn_group') == 'all' and t >= 512))
                 and _defer_tn_wgrad(g2, x2, acc)):
             return False                         # K17, grouped with the pass's other weight gradients at its end
         if per_layer:

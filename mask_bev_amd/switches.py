@@ -23,6 +23,8 @@ _DEFAULTS: Dict[str, Any] = {
     'early_targets': True,        # the loss's batch-only preparation forks where the head's forward began
     'wgrad_group': True,          # grouped small-token weight gradients / column sums at the end of a backward pass
     'tn_group': '1',              # '0' | '1' | 'all': which K17 weight gradients join the grouped launch
+    'adam_in_wgrad': True,        # one GPU, graph step: AdamW of the Swin blocks' matrices in the epilogue of their grouped weight gradient
+    'adam_wgrad_min_tokens': 1024,  # fewest tokens of such a product that joins the group for it (4096: Swin stage 4 stays with the library)
     'nn_colsum_defer': True,      # a fused data gradient's bias column sums join the pass's grouped column-sum launch
     # --- kernels selected over a library / ATen form ----------------------------------------------------------------
     'gemm16': 'auto',             # '0' | 'auto' | 'all': which Linear work runs on K17

@@ -241,6 +241,17 @@ def _tn_group(a) -> Work:
     return ('k_gemm16_tn_group', 'mfma', by, fl)        # bench.py prices the family against the roofline that bounds it
 
 
+def _tn_group_adam(a) -> Work:
+    """mbv_gemm16_tn_group_adam: an entry that applies its AdamW update (a block in `adam`, one work item of token depth) moves
+    param + two moments in and out and the 16-bit shadow out, 26 B per element, instead of the gradient's 8."""
+    n = _i(a[8])
+    m, o, k, adam = a[3], a[4], a[5], a[12]
+    fused = [bool(adam[j]) and 0 < m[j] <= 4096 for j in range(n)]
+    by = sum(m[j] * (o[j] + k[j]) * 2.0 + o[j] * k[j] * (26.0 if fused[j] else 8.0) for j in range(n))
+    fl = sum(2.0 * m[j] * o[j] * k[j] for j in range(n))
+    return ('k_gemm16_tn_group', 'mfma', by, fl)
+
+
 def _sz(flag) -> float:
     return 4.0 if _i(flag) == 0 else 2.0
 
@@ -410,6 +421,7 @@ MODELS: Dict[str, Callable[[tuple], Work]] = {
     'mbv_wgrad_small_f32_group': lambda a: _wgrad_group(a),
     'mbv_colsum_accum_group': lambda a: _colsum_group(a),
     'mbv_gemm16_tn_group': lambda a: _tn_group(a),
+    'mbv_gemm16_tn_group_adam': lambda a: _tn_group_adam(a),
     # K20 (f32 products from IEEE-half pairs): the ALGORITHMIC flops of the f32 product, 2 m n k, against the 16-bit MFMA peak
     # (the kernel issues three matrix instructions per product term: a frac of 1/3 would be the pipe's own ceiling)
     'mbv_gemm32s_nt': lambda a: ('k_gemm32s<NT>', 'mfma', ((_i(a[5]) * _i(a[7]) + _i(a[6]) * _i(a[7])) * 4.0
