@@ -2173,6 +2173,38 @@ int mbv_sgd_step(float* param, float* grad, float* momentum_buf, void* shadow, i
                  float momentum, float dampening, float weight_decay, int32_t nesterov, float grad_scale, int32_t zero_grad,
                  const float* loss_scale, const int32_t* skip_flag, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K41 — gradient clipping by global norm for the flat optimizers (csrc/optim_flat.hip).  Replaces:
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2), which Lightning's Trainer(gradient_clip_val=...) runs
+ * between backward and optimizer.step().  Two launches measure the norm of the gradient the optimizer will apply,
+ * g * grad_scale / *loss_scale, and leave ONE device float, loss_scale / clip_coefficient, which mbv_adamw_step,
+ * mbv_adamw_step_ranges, mbv_lamb_moments and mbv_sgd_step take as their `loss_scale` argument: the gradient buffer is never
+ * rewritten.  No atomics, no host synchronisation, nothing allocated; both can be captured in a graph.
+ *
+ * mbv_grad_norm_partials: start / len are HOST arrays of count <= 8 element ranges of the arena gradient `grad` (n elements,
+ *   16-byte aligned); starts and lengths are multiples of 4, ranges lie inside [0, n).  Every range is cut into chunks of 4096
+ *   elements (the last one shorter); the chunks of range r follow those of range r - 1.  partials (n_partials f64, 8-byte
+ *   aligned) receives per chunk the sum of (double)g * (double)g: each thread accumulates its float4s in f64, one block reduces
+ *   a chunk in a fixed order — the result does not depend on the grid and is bit-reproducible; a gradient element whose square
+ *   overflows f32 is summed right.  n_partials must equal the sum of ceil(len[r] / 4096).  Padding elements inside a range are
+ *   summed: they must be zero (ParameterArena's are).
+ * mbv_grad_clip_coef: range_chunks is a HOST array of count + 1 chunk boundaries into partials (range_chunks[0] = 0,
+ *   non-decreasing, range_chunks[count] = n_partials).  One block sums every range and the total in f64 in a fixed order, then
+ *     L = loss_scale ? *loss_scale : 1      total = sqrt(sum) * grad_scale / L      coef = min(1, max_norm / (total + 1e-6))
+ *   (all f64 from the f32 inputs; torch's rule) and writes rec (16 f32, 4-byte aligned):  rec[0] = L / coef, rec[1] = total,
+ *   rec[2] = coef, rec[3 + r] = sqrt(sum of range r) * grad_scale / L, the rest zero.  max_norm = +inf measures and never
+ *   clips: coef is exactly 1 and rec[0] exactly L.  A NaN total gives a NaN coefficient, as torch's.  loss_scale is K11's
+ *   device scalar (nullable).
+ * n == 0 or count == 0: MBV_OK (mbv_grad_clip_coef then writes norm 0, coefficient 1).  MBV_ERR_UNSUPPORTED: count > 8, more
+ *   than 2^31 - 1 chunks;  MBV_ERR_BAD_ARG: a null or misaligned pointer (other than loss_scale), a negative size, a range
+ *   outside the arena, a start or length that is no multiple of 4, n_partials or range_chunks that do not match,
+ *   max_norm <= 0 or NaN.
+ */
+int mbv_grad_norm_partials(const float* grad, int64_t n, const int64_t* start, const int64_t* len, int32_t count,
+                           double* partials, int32_t n_partials, void* stream);
+int mbv_grad_clip_coef(const double* partials, int32_t n_partials, const int32_t* range_chunks, int32_t count, float max_norm,
+                       float grad_scale, const float* loss_scale, float* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

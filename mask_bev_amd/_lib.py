@@ -12,7 +12,7 @@ from typing import Dict, List, Tuple
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG_DIR, 'libmaskbev_hip.so')
 
-# Raised when a declared signature changes.  Entries that were only ADDED since (K33b, K35, K38, K39, K40, K17's AdamW epilogue) left it at 59: a stale
+# Raised when a declared signature changes.  Entries that were only ADDED since (K33b, K35, K38, K39, K40, K17's AdamW epilogue, K41) left it at 59: a stale
 # library without them passes the version check below and fails at the symbol lookup of load(), which names the symbol.
 ABI_VERSION = 59
 
@@ -257,6 +257,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_lamb_trust': (ctypes.c_int, [_P, _I, _P, _I, _F, _P, _P]),
     'mbv_lamb_apply': (ctypes.c_int, [_P, _P, _P, _I, _L, _P, _I, _I, _I, _P, _I, _F, _D, _D, _I, _L, _P, _P, _P]),
     'mbv_sgd_step': (ctypes.c_int, [_P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P]),
+    'mbv_grad_norm_partials': (ctypes.c_int, [_P, _L, _P, _P, _I, _P, _I, _P]),
+    'mbv_grad_clip_coef': (ctypes.c_int, [_P, _I, _P, _I, _F, _F, _P, _P, _P]),
 }
 
 _lib = None

@@ -34,6 +34,7 @@ from ._lib import check
 
 _ALIGN = 64          # elements: every parameter starts on a 256-byte boundary
 _SHORT_RUN = 1 << 23  # elements: an optimizer run shorter than this shares a launch with its like (FlatAdam._launch)
+CLIP_RANGES = 8       # element ranges one mbv_grad_norm_partials call sums (kNormRanges of csrc/optim_flat.hip)
 
 
 def _round_up(n: int, a: int) -> int:
@@ -260,7 +261,26 @@ class FlatOptimizer(torch.optim.Optimizer):
     count steps — ``steps``, the number of APPLIED updates (with a scaler that count lives on the device,
     ``LossScaler.applied_steps``).  ``load_state_dict`` takes that format (a ``kind`` other than the class's own is refused;
     a state without one, from before the key existed, is accepted), or a per-parameter torch state mapped through the arena
-    layout, and restores the ``HYPER`` keys of the param groups."""
+    layout, and restores the ``HYPER`` keys of the param groups.
+
+    **Gradient clipping by global norm (K41).**  ``max_grad_norm`` (``None`` = off: nothing is allocated and every launch is
+    what it was; a positive float or ``float('inf')`` = on, fixed for the optimizer's lifetime) makes ``step()`` measure the
+    2-norm of the gradient the optimizer is about to apply — ``grad * grad_scale / loss scale``, so the fp16 loss scale and
+    the data-parallel ``1 / world`` are accounted for — over the arena's segments in two launches (``mbv_grad_norm_partials``,
+    ``mbv_grad_clip_coef``) with ``torch.nn.utils.clip_grad_norm_``'s rule ``coef = min(1, max_norm / (norm + 1e-6))``.
+    They leave one device float, ``loss scale / coef``, which the update kernels take in place of the loss scale:
+
+    * the gradient buffer is never scaled in place — with ``zero_grad=False``, ``p.grad`` after ``step()`` holds the
+      UN-clipped gradient, where torch's utility scales ``p.grad`` itself;
+    * ``float('inf')`` measures and never clips: the update is bit for bit the one without clipping;
+    * the threshold crosses the C ABI as an f32: 0.01 is applied as float32(0.01), 2e-8 relative from the double torch's
+      utility would use, while the ``max_grad_norm`` property returns the value as given;
+    * an overflowed fp16 step is skipped as before; it reports ``grad_norm = inf`` and the loss-scale protocol is untouched;
+    * a non-finite norm WITHOUT a scaler poisons the parameters, as ``clip_grad_norm_(error_if_nonfinite=False)`` followed
+      by ``step()`` does.
+
+    ``grad_norm``, ``clip_coef`` and ``grad_norms()`` are views of the device record of the last step: reading them costs no
+    host synchronisation until the caller asks for a value."""
 
     KIND = ''                   # 'adam' | 'lamb' | 'sgd'
     STATE: Tuple[str, ...] = ()  # the flat state buffers, each the size of the arena
@@ -269,26 +289,91 @@ class FlatOptimizer(torch.optim.Optimizer):
     ENTRY = ''                  # the native entry point named when a CPU arena is refused
 
     def __init__(self, arena: ParameterArena, param_groups, defaults: dict, scaler: Optional[LossScaler],
-                 zero_grad: bool = True):
+                 zero_grad: bool = True, max_grad_norm: Optional[float] = None):
         self.arena = arena
         self.scaler = scaler
         self.zero_grad_in_step = zero_grad
         self.grad_scale = 1.0
         _refuse_frozen(arena, type(self).__name__)
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f'max_grad_norm must be positive (inf measures without clipping), got {max_grad_norm}')
+            if len(arena.segments) > CLIP_RANGES:
+                raise ValueError(f'gradient clipping sums at most {CLIP_RANGES} arena segments, the arena has '
+                                 f'{len(arena.segments)}')
+        self._max_grad_norm = max_grad_norm
         super().__init__(param_groups, defaults)
         for name in self.STATE:
             setattr(self, name, torch.zeros_like(arena.param))
         if self.COUNTS_STEPS:
             self.steps = 0
+        if max_grad_norm is not None:
+            # K41: the segments as element ranges, their chunk boundaries in the partial slab, and the 16-float device record
+            spans = list(arena.segments.values())
+            bounds = [0]
+            for a, b in spans:
+                bounds.append(bounds[-1] + (b - a + LAMB_CHUNK - 1) // LAMB_CHUNK)
+            self._clip_start = (ctypes.c_int64 * len(spans))(*[a for a, _ in spans])
+            self._clip_len = (ctypes.c_int64 * len(spans))(*[b - a for a, b in spans])
+            self._clip_bounds = (ctypes.c_int32 * len(bounds))(*bounds)
+            self._clip_partials = torch.zeros(max(1, bounds[-1]), dtype=torch.float64, device=arena.device)
+            self._clip_rec = torch.zeros(16, dtype=torch.float32, device=arena.device)
+            self._clip_rec[2] = 1.0             # before the first step: norm 0, coefficient 1
 
     def _require_cuda(self):
         if self.arena.device.type != 'cuda':
             raise _lib.MaskBevHipError(f'{type(self).__name__} runs on the MI355X only ({self.ENTRY})')
 
+    # -- K41: clipping by global norm ----------------------------------------------------------------------------------
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        """The clipping threshold given at construction (``None``: no clipping, no norm)."""
+        return self._max_grad_norm
+
+    def _clip_record(self) -> torch.Tensor:
+        if self._max_grad_norm is None:
+            raise _lib.MaskBevHipError(f'{type(self).__name__} was built without max_grad_norm: no gradient norm is measured')
+        return self._clip_rec
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """0-d device tensor: the last step's total norm of the gradient as applied (un-scaled, data-parallel mean)."""
+        return self._clip_record()[1]
+
+    @property
+    def clip_coef(self) -> torch.Tensor:
+        """0-d device tensor: the last step's coefficient ``min(1, max_grad_norm / (grad_norm + 1e-6))``."""
+        return self._clip_record()[2]
+
+    def grad_norms(self) -> Dict[str, torch.Tensor]:
+        """Segment name -> 0-d device tensor: the last step's gradient norm of each arena segment."""
+        rec = self._clip_record()
+        return {name: rec[3 + i] for i, name in enumerate(self.arena.segments)}
+
+    def _measure_norm(self, lib, stream: int):
+        """The two K41 launches over the arena's segments: the record's divisor is what ``_scaler_ptrs`` hands on."""
+        ar, sc = self.arena, self.scaler
+        n_partials = self._clip_bounds[len(self._clip_bounds) - 1]
+        with ops.TIMER.span('k_grad_norm_partials'):
+            check(lib.mbv_grad_norm_partials(ar.grad.data_ptr(), ar.numel, self._clip_start, self._clip_len,
+                                             len(self._clip_start), self._clip_partials.data_ptr(), n_partials, stream),
+                  'mbv_grad_norm_partials')
+        with ops.TIMER.span('k_grad_clip_coef'):
+            check(lib.mbv_grad_clip_coef(self._clip_partials.data_ptr(), n_partials, self._clip_bounds, len(self._clip_start),
+                                         self._max_grad_norm, float(self.grad_scale),
+                                         0 if sc is None else sc.scale.data_ptr(), self._clip_rec.data_ptr(), stream),
+                  'mbv_grad_clip_coef')
+
     def _scaler_ptrs(self) -> Tuple[int, int, int]:
-        """(loss scale, overflow flag, applied-step count) device addresses; zeros without a scaler."""
+        """(loss scale, overflow flag, applied-step count) device addresses; zeros without a scaler.  With clipping the
+        first is the record's divisor ``loss scale / clip coefficient``, which the kernels divide by where they divided by
+        the loss scale."""
         sc = self.scaler
-        return (0, 0, 0) if sc is None else (sc.scale.data_ptr(), sc.flag.data_ptr(), sc.applied_steps.data_ptr())
+        flag, applied = (0, 0) if sc is None else (sc.flag.data_ptr(), sc.applied_steps.data_ptr())
+        if self._max_grad_norm is not None:
+            return self._clip_rec.data_ptr(), flag, applied
+        return (0 if sc is None else sc.scale.data_ptr()), flag, applied
 
     def _launch(self, lib, stream: int):
         raise NotImplementedError
@@ -306,7 +391,10 @@ class FlatOptimizer(torch.optim.Optimizer):
         sc = self.scaler
         if sc is not None:
             sc.check(self.arena.grad)
-        self._launch(_lib.load(), torch.cuda.current_stream(self.arena.device).cuda_stream)
+        lib, stream = _lib.load(), torch.cuda.current_stream(self.arena.device).cuda_stream
+        if self._max_grad_norm is not None:
+            self._measure_norm(lib, stream)
+        self._launch(lib, stream)
         if sc is not None:
             sc.update()
         return loss
@@ -373,10 +461,10 @@ class FlatAdam(FlatOptimizer):
 
     def __init__(self, arena: ParameterArena, groups: List[dict], lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 1e-2, decoupled: bool = True, zero_grad: bool = True,
-                 scaler: Optional[LossScaler] = None):
+                 scaler: Optional[LossScaler] = None, max_grad_norm: Optional[float] = None):
         self.decoupled = decoupled
         super().__init__(arena, _segment_groups(arena, groups), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
-                         scaler, zero_grad)
+                         scaler, zero_grad, max_grad_norm)
         self._k3 = None              # (weight, bias, offset_w, offset_b) of a LayerNorm whose update K3's backward performs
         self._k3_applied = False
         self._mx: Dict[int, nn.Parameter] = {}     # arena offset -> weight whose update its weight-gradient GEMM performs
@@ -390,14 +478,17 @@ class FlatAdam(FlatOptimizer):
         reach the arena — 16 B per parameter of gradient traffic less per step.  The CALLER guarantees one backward pass
         per ``step()`` (the graph step does); a second pass before ``step()`` raises.  Not with a loss scaler (an overflowed
         step must skip EVERY update, and the verdict is only known after the whole backward) and not with a gradient
-        all-reduce (``grad_scale`` != 1: the reduced gradient does not exist inside the kernel).  ``None`` disarms.
+        all-reduce (``grad_scale`` != 1: the reduced gradient does not exist inside the kernel), and for the same reason not
+        with ``max_grad_norm``: the clip coefficient needs the norm of the WHOLE gradient, which exists only after the
+        backward, and a gradient consumed here never reaches the arena to be measured.  ``None`` disarms.
         The arm is a weak reference on the weight (``weight._mbv_k3_adam``), where K3's backward finds it: several optimizers
         can be armed at once, each for its own parameters, and a dropped optimizer disarms itself.
         Returns whether the fusion is armed."""
         if self._k3 is not None and self.k3_armed(self._k3[0]):
             del self._k3[0]._mbv_k3_adam
         self._k3, self._k3_applied = None, False
-        if weight is None or bias is None or self.scaler is not None or not self.zero_grad_in_step:
+        if (weight is None or bias is None or self.scaler is not None or not self.zero_grad_in_step
+                or self._max_grad_norm is not None):
             return False
         off = {id(p): o for p, o in self.arena.layout}
         if id(weight) not in off or id(bias) not in off or weight.shape != bias.shape:
@@ -444,7 +535,8 @@ class FlatAdam(FlatOptimizer):
         so the gradient never reaches the arena — 16 B per parameter of gradient traffic less per step.  Only weights used
         ONCE per pass qualify (a second product for an armed weight raises), and the CALLER guarantees one backward pass per
         ``step()``; a second pass before ``step()`` raises.  Refused with a loss scaler, with ``grad_scale`` != 1 and without
-        ``zero_grad_in_step``, as :meth:`fuse_layernorm_affine` and for its reasons.  ``None`` disarms.  The arm is a weak
+        ``zero_grad_in_step``, as :meth:`fuse_layernorm_affine` and for its reasons, and with ``max_grad_norm`` (the update
+        would run before the norm of the whole gradient exists, on a gradient the norm never sees).  ``None`` disarms.  The arm is a weak
         reference on the weight's gradient view (``p.grad._mbv_adam``), where the launcher finds it.  A product that does not
         qualify when it runs (deeper token sum, another kernel) leaves its weight to ``mbv_adamw_step`` as ever: what is cut
         out of that pass is what a launch REPORTED applied.  Returns whether anything is armed."""
@@ -456,7 +548,7 @@ class FlatAdam(FlatOptimizer):
         self._mx, self._mx_applied = {}, set()
         params = list(params or [])
         if (not params or self.scaler is not None or float(self.grad_scale) != 1.0 or not self.zero_grad_in_step
-                or self.arena.device.type != 'cuda'):
+                or self._max_grad_norm is not None or self.arena.device.type != 'cuda'):
             return False
         off = {id(p): o for p, o in self.arena.layout}
         for p in params:
@@ -609,13 +701,13 @@ class FlatLamb(FlatOptimizer):
 
     def __init__(self, arena: ParameterArena, groups: List[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
                  weight_decay: float = 0.0, clamp_value: float = 10.0, debias: bool = False,
-                 scaler: Optional[LossScaler] = None):
+                 scaler: Optional[LossScaler] = None, max_grad_norm: Optional[float] = None):
         self.arena = arena
         self._require_cuda()
         self.clamp_value = float(clamp_value)
         self.debias = bool(debias)
         super().__init__(arena, _segment_groups(arena, groups), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
-                         scaler)
+                         scaler, max_grad_norm=max_grad_norm)
         # chunk table: (start, len | param << 32) per chunk = mbv_lamb_chunk; [chunk_begin, chunk_end) per parameter
         import numpy as np
         recs, ranges = [], []
@@ -686,7 +778,7 @@ class FlatSGD(FlatOptimizer):
 
     def __init__(self, arena: ParameterArena, lr: float = 1e-3, momentum: float = 0.99, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = True, zero_grad: bool = True,
-                 scaler: Optional[LossScaler] = None):
+                 scaler: Optional[LossScaler] = None, max_grad_norm: Optional[float] = None):
         self.arena = arena
         self._require_cuda()
         if nesterov and (momentum <= 0 or dampening != 0):
@@ -694,7 +786,7 @@ class FlatSGD(FlatOptimizer):
         flat = nn.Parameter(arena.param, requires_grad=True)
         flat.grad = arena.grad
         super().__init__(arena, [flat], dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                             nesterov=nesterov), scaler, zero_grad)
+                                             nesterov=nesterov), scaler, zero_grad, max_grad_norm)
 
     def _launch(self, lib, stream):
         ar = self.arena

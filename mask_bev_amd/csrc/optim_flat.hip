@@ -10,7 +10,12 @@
 //   mbv_lamb_apply      reads param, u (8 B/elem), writes param, the 16-bit shadow and the zeroed gradient (10 B/elem).
 //   mbv_sgd_step        one pass: reads param, grad, momentum buffer (12 B), writes param, buffer, shadow, zeroed grad (14 B).
 //
-// A LAMB step is 28 + 18 = 46 B/elem against k_adamw's 34; SGD is 26.  The per-tensor norms of LAMB come from a CHUNK TABLE
+//   mbv_grad_norm_partials   K41: reads grad (4 B/elem); per chunk the block-reduced f64 sum of g^2 goes to a partial slab (8 B).
+//   mbv_grad_clip_coef       K41: the partials summed in a fixed order in f64 -> a 16-float record: the divisor
+//                            loss_scale / clip_coefficient the passes above take in place of the loss scale, the total norm,
+//                            the coefficient and the norm of every range.  The gradient itself is never rewritten.
+//
+// A LAMB step is 28 + 18 = 46 B/elem against k_adamw's 34; SGD is 26; clipping adds 4.  The per-tensor norms of LAMB come from a CHUNK TABLE
 // built once by the host: every parameter's padded arena range is cut into chunks of kChunk = 4096 elements (a chunk never
 // straddles two parameters; the last chunk of a parameter is shorter, a multiple of 64).  One block works on one chunk at a
 // time, so a chunk's two sums are taken in one fixed order whatever the grid — no float atomics, bit-reproducible, replayable.
@@ -332,6 +337,105 @@ __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ param, float* _
   }
 }
 
+// ---- K41: gradient clipping by global norm ------------------------------------------------------------------------------
+constexpr int kNormRanges = 8;
+struct NormRanges {
+  long start4[kNormRanges];             // first float4 item of the range
+  long len4[kNormRanges];               // float4 items
+  int chunk_begin[kNormRanges + 1];     // first chunk of the range in `partials`; [n] = all chunks
+  int n;
+};
+
+// sum of a over the 256 threads of the block in f64, in block_sum2's fixed order: xor-butterfly inside a wave, then the four waves
+__device__ __forceinline__ double block_sum_f64(double a, double* lds) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+  __syncthreads();                      // the previous chunk's readers are done with lds
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
+// partials[c] = sum of (double)g * (double)g over chunk c; one block per chunk at a time, so the sum's order is the chunk's own
+// whatever the grid.  The four float4 of a lane are loaded before any is used (plain loads: k_adamw reads the gradient next).
+__global__ void __launch_bounds__(256) k_grad_norm_partials(const float* __restrict__ grad, const NormRanges r,
+                                                            double* __restrict__ partials) {
+  __shared__ double lds[4];
+  const int total = r.chunk_begin[r.n];
+  for (int c = blockIdx.x; c < total; c += gridDim.x) {
+    int i = 0;
+    while (i + 1 < r.n && c >= r.chunk_begin[i + 1]) ++i;                    // block-uniform
+    const long first = (long)(c - r.chunk_begin[i]) * (kChunk / 4);         // float4 items into the range
+    const long left = r.len4[i] - first;
+    const int n4 = left < kChunk / 4 ? (int)left : kChunk / 4;
+    const f4* src = reinterpret_cast<const f4*>(grad) + r.start4[i] + first;
+    f4 g[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = (int)threadIdx.x + 256 * k;
+      g[k] = j < n4 ? src[j] : f4{0.f, 0.f, 0.f, 0.f};
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double d = (double)g[k][e];
+        s += d * d;
+      }
+    s = block_sum_f64(s, lds);
+    if (threadIdx.x == 0) partials[c] = s;
+  }
+}
+
+struct ClipRanges {
+  int chunk[kNormRanges + 1];           // chunk boundaries of the ranges in `partials`
+  int n;
+};
+
+// partials[c0, c1) summed by the one block: thread t takes chunks t, t + 256, ..., then a fixed tree (as k_lamb_trust)
+__device__ __forceinline__ double tree_sum_f64(const double* __restrict__ partials, int c0, int c1, double* lds) {
+  double s = 0.0;
+  for (int c = c0 + (int)threadIdx.x; c < c1; c += 256) s += partials[c];
+  __syncthreads();                      // the previous sum's readers are done with lds
+  lds[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) lds[threadIdx.x] += lds[threadIdx.x + w];
+    __syncthreads();
+  }
+  return lds[0];
+}
+
+// rec (16 f32) = { L / coef, total norm, coef, norm of range 0 .. 7, 0 ... } with torch.nn.utils.clip_grad_norm_'s rule on the
+// gradient the optimizer applies (g * grad_scale / L); every norm in f64, rounded to f32 once
+__global__ void __launch_bounds__(256) k_grad_clip_coef(const double* __restrict__ partials, const ClipRanges r,
+                                                        double max_norm, double grad_scale,
+                                                        const float* __restrict__ loss_scale, float* __restrict__ rec) {
+  __shared__ double lds[256];
+  const double L = loss_scale ? (double)*loss_scale : 1.0;
+  const double unit = grad_scale / L;
+  double norms[kNormRanges];
+#pragma unroll
+  for (int i = 0; i < kNormRanges; ++i)
+    norms[i] = i < r.n ? sqrt(tree_sum_f64(partials, r.chunk[i], r.chunk[i + 1], lds)) * unit : 0.0;
+  const double sum = r.n > 0 ? tree_sum_f64(partials, r.chunk[0], r.chunk[r.n], lds) : 0.0;
+  if (threadIdx.x != 0) return;
+  const double total = sqrt(sum) * unit;
+  double coef = 1.0;                    // max_norm = +inf measures and never clips: rec[0] is L bit for bit
+  if (max_norm <= 1.7976931348623157e308) {
+    coef = max_norm / (total + 1e-6);
+    if (coef > 1.0) coef = 1.0;         // a NaN norm stays a NaN coefficient, as torch's clamp leaves it
+  }
+  rec[0] = (float)(L / coef);
+  rec[1] = (float)total;
+  rec[2] = (float)coef;
+#pragma unroll
+  for (int i = 0; i < kNormRanges; ++i) rec[3 + i] = (float)norms[i];
+#pragma unroll
+  for (int i = 3 + kNormRanges; i < 16; ++i) rec[i] = 0.f;
+}
+
 // one thread fills a parameter group's hyper-parameter block (plain stores): stream-ordered in front of the launches that read it
 __global__ void k_adam_args_write(AdamDev* __restrict__ dst, AdamDev v) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
@@ -502,6 +606,55 @@ extern "C" int mbv_lamb_apply(float* param, float* grad, void* shadow, int32_t s
                      reinterpret_cast<unsigned short*>(shadow), shadow_dtype, (long)n,
                      reinterpret_cast<const ChunkRec*>(chunks), c0, c1, trust, n_params, step_size, lr, beta1, beta2,
                      debias ? applied_steps : nullptr, skip_flag);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+// K41: per-chunk sums of squares of `count` <= 8 element ranges of the gradient (HOST arrays, as mbv_adamw_step_ranges)
+extern "C" int mbv_grad_norm_partials(const float* grad, int64_t n, const int64_t* start, const int64_t* len, int32_t count,
+                                      double* partials, int32_t n_partials, void* stream) {
+  if (n < 0 || count < 0 || n_partials < 0 || !grad || misaligned16(grad)) return MBV_ERR_BAD_ARG;
+  if (count > kNormRanges) return MBV_ERR_UNSUPPORTED;
+  if (count > 0 && (!start || !len)) return MBV_ERR_BAD_ARG;
+  NormRanges r;
+  r.n = 0;
+  long chunks = 0;
+  for (int i = 0; i < count; ++i) {
+    if (start[i] < 0 || len[i] < 0 || ((start[i] | len[i]) & 3) || start[i] > n || len[i] > n - start[i]) return MBV_ERR_BAD_ARG;
+    if (len[i] == 0) continue;
+    r.start4[r.n] = start[i] >> 2; r.len4[r.n] = len[i] >> 2; r.chunk_begin[r.n] = (int)chunks;
+    chunks += (len[i] + kChunk - 1) / kChunk;
+    if (chunks > 0x7fffffffLL) return MBV_ERR_UNSUPPORTED;
+    ++r.n;
+  }
+  r.chunk_begin[r.n] = (int)chunks;
+  if (chunks != n_partials) return MBV_ERR_BAD_ARG;
+  if (chunks == 0) return MBV_OK;
+  if (!partials || (reinterpret_cast<size_t>(partials) & 7)) return MBV_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_grad_norm_partials, dim3(chunk_grid(0, (int)chunks)), dim3(256), 0, (hipStream_t)stream, grad, r,
+                     partials);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+// K41: the partials of mbv_grad_norm_partials -> the 16-float record the optimizer kernels take in place of the loss scale
+extern "C" int mbv_grad_clip_coef(const double* partials, int32_t n_partials, const int32_t* range_chunks, int32_t count,
+                                  float max_norm, float grad_scale, const float* loss_scale, float* rec, void* stream) {
+  if (n_partials < 0 || count < 0 || !rec || (reinterpret_cast<size_t>(rec) & 3)) return MBV_ERR_BAD_ARG;
+  if (!(max_norm > 0.f)) return MBV_ERR_BAD_ARG;                             // <= 0 or NaN
+  if (count > kNormRanges) return MBV_ERR_UNSUPPORTED;
+  if (loss_scale && (reinterpret_cast<size_t>(loss_scale) & 3)) return MBV_ERR_BAD_ARG;
+  ClipRanges r = {};
+  if (count > 0) {
+    if (!range_chunks || range_chunks[0] != 0 || range_chunks[count] != n_partials) return MBV_ERR_BAD_ARG;
+    for (int i = 0; i < count; ++i)
+      if (range_chunks[i + 1] < range_chunks[i]) return MBV_ERR_BAD_ARG;
+    for (int i = 0; i <= count; ++i) r.chunk[i] = range_chunks[i];
+    r.n = count;
+  }
+  if (r.n > 0 && n_partials > 0 && (!partials || (reinterpret_cast<size_t>(partials) & 7))) return MBV_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_grad_clip_coef, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, r, (double)max_norm,
+                     (double)grad_scale, loss_scale, rec);
   MBV_CHECK_LAUNCH();
   return MBV_OK;
 }

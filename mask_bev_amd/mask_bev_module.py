@@ -91,6 +91,9 @@ class MaskBevModule(_Base):
         # build extension (not a reference key): arithmetic type of the GEMM-shaped layers
         self._compute_dtype = {'fp32': None, 'bf16': torch.bfloat16, 'fp16': torch.float16}[
             kwargs.get('compute_dtype', 'fp32')]
+        # build extension under Lightning's name (Trainer(gradient_clip_val=...)): clip the gradient's global 2-norm, None = off
+        clip = kwargs.get('gradient_clip_val', None)
+        self._gradient_clip_val = None if clip is None else float(clip)
 
         voxel_size_z = z_range[1] - z_range[0]
         head_in_dims = [2 ** i * backbone_embed_dim for i in range(4)]
@@ -164,16 +167,18 @@ class MaskBevModule(_Base):
         groups = [dict(segment='encoder', lr=self._lr * scale), dict(segment='backbone', lr=self._lr * scale),
                   dict(segment='head', lr=self._lr)]
         scaler = getattr(self, '_loss_scaler', None)
+        clip = getattr(self, '_gradient_clip_val', None)      # the flat optimizers clip themselves (K41)
         if self._optimiser_type == OptimizerType.LAMB:        # torch_optimizer defaults: betas (0.9, 0.999), eps 1e-6, clamp 10
-            return FlatLamb(self._arena, groups, lr=self._lr, weight_decay=self._weight_decay, scaler=scaler)
+            return FlatLamb(self._arena, groups, lr=self._lr, weight_decay=self._weight_decay, scaler=scaler,
+                            max_grad_norm=clip)
         if self._optimiser_type == OptimizerType.SGD:         # built from self.parameters(): no differential lr, as the reference
             return FlatSGD(self._arena, lr=self._lr, momentum=0.99, weight_decay=self._weight_decay, nesterov=True,
-                           scaler=scaler)
+                           scaler=scaler, max_grad_norm=clip)
         if self._optimiser_type == OptimizerType.ADAM_W:      # torch defaults: betas (0.9, 0.999), eps 1e-8
             return FlatAdam(self._arena, groups, lr=self._lr, weight_decay=self._weight_decay, decoupled=True,
-                            scaler=scaler)
+                            scaler=scaler, max_grad_norm=clip)
         return FlatAdam(self._arena, groups, lr=self._lr, weight_decay=self._weight_decay, decoupled=False,
-                        scaler=scaler)
+                        scaler=scaler, max_grad_norm=clip)
 
     def configure_optimizers(self):
         if getattr(self, '_arena', None) is not None:         # every optimiser_type has its flat form (K11, K40)

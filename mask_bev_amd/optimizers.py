@@ -2,10 +2,15 @@
 
 ``Lamb`` restates ``torch_optimizer.Lamb`` (0.3.0), which ``optimiser_type: lamb`` names (mask_bev/mask_bev_module.py:148-151):
 plain torch, any device.  It is what ``MaskBevModule.configure_optimizers`` returns for a module without a parameter arena;
-with an arena the same rule runs as three flat launches (``arena.FlatLamb``, K40)."""
+with an arena the same rule runs as three flat launches (``arena.FlatLamb``, K40).
+
+``clip_gradients`` is the launcher's one call for gradient clipping by global norm whatever the optimizer; ``ClipStats`` keeps
+an epoch's sums of what a clipping flat optimizer reports, on the device."""
 from __future__ import annotations
 
 import math
+
+from typing import Optional
 
 import torch
 
@@ -65,3 +70,38 @@ class Lamb(torch.optim.Optimizer):
                 trust = torch.where((wn == 0) | (un == 0), torch.ones_like(wn), wn / un)
                 p.sub_(u * (step_size * trust))
         return loss
+
+
+def clip_gradients(optimizer, parameters, max_norm: Optional[float]) -> Optional[torch.Tensor]:
+    """Clip the global 2-norm of the gradients of ``parameters`` at ``max_norm`` before ``optimizer.step()``.  ``None`` for
+    ``max_norm is None`` (nothing to do) and for a flat optimizer (``arena.FlatOptimizer``), which clips inside its own
+    ``step()`` when built with ``max_grad_norm`` (K41) — the loss scale and ``grad_scale`` it folds in are unknown here.
+    Otherwise ``torch.nn.utils.clip_grad_norm_`` scales the gradients in place and its total norm is returned."""
+    from .arena import FlatOptimizer
+    if max_norm is None or isinstance(optimizer, FlatOptimizer):
+        return None
+    return torch.nn.utils.clip_grad_norm_(parameters, float(max_norm))
+
+
+class ClipStats:
+    """An epoch's sums of a clipping flat optimizer's ``grad_norm`` / ``clip_coef`` (0-d device tensors that the next step
+    overwrites), kept on the device and read once.  A step whose norm is not finite — an overflowed fp16 step, which the
+    optimizer skipped — enters neither the mean nor the clipped count: it is counted as skipped."""
+
+    def __init__(self):
+        self.sums = None                 # [sum of the finite norms, steps with a finite norm, of those: coefficient < 1]
+
+    def add(self, grad_norm: torch.Tensor, clip_coef: torch.Tensor) -> None:
+        finite = torch.isfinite(grad_norm)
+        row = torch.stack([torch.where(finite, grad_norm, torch.zeros_like(grad_norm)).double(), finite.double(),
+                           (finite & (clip_coef < 1)).double()])
+        self.sums = row if self.sums is None else self.sums + row
+
+    def summary(self, n_steps: int):
+        """(mean of the finite norms, clipped steps, applied steps, skipped steps); the one host read."""
+        total, applied, clipped = (0.0, 0.0, 0.0) if self.sums is None else self.sums.tolist()
+        return total / max(1.0, applied), int(clipped), int(applied), n_steps - int(applied)
+
+    def line(self, n_steps: int) -> str:
+        mean, clipped, applied, skipped = self.summary(n_steps)
+        return f'grad_norm {mean:.4g} clipped {clipped}/{applied}' + (f' skipped {skipped}' if skipped else '')

@@ -495,6 +495,11 @@ MODELS: Dict[str, Callable[[tuple], Work]] = {
     'mbv_lamb_trust': lambda a: ('k_lamb_trust', 'hbm', _i(a[1]) * 8.0 + _i(a[3]) * 12.0, 0.0),
     'mbv_lamb_apply': lambda a: ('k_lamb_apply', 'hbm', _lamb_elems(a, 7, 8) * (16.0 + (2.0 if _i(a[2]) else 0.0)), 0.0),
     'mbv_sgd_step': lambda a: ('k_sgd', 'hbm', _i(a[5]) * (20.0 + (2.0 if _i(a[3]) else 0.0) + (4.0 if _i(a[12]) else 0.0)), 0.0),
+    # K41.  (grad, n, start, len, count, partials, n_partials, stream): the ranges of the gradient read once (4 B/elem), one f64
+    # partial written per chunk; (partials, n_partials, ...): the partials read, the 64 B record written.
+    'mbv_grad_norm_partials': lambda a: ('k_grad_norm_partials', 'hbm',
+                                         4.0 * sum(int(a[3][i]) for i in range(_i(a[4]))) + 8.0 * _i(a[6]), 0.0),
+    'mbv_grad_clip_coef': lambda a: ('k_grad_clip_coef', 'hbm', 8.0 * _i(a[1]) + 64.0, 0.0),
 }
 
 

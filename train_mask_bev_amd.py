@@ -75,6 +75,7 @@ os.environ.setdefault('OMP_NUM_THREADS', str(6))          # /root/reference: tra
 
 from mask_bev.mask_bev_module import MaskBevModule          # noqa: E402  (the reference's import line, :12)
 from mask_bev_amd import datasets, evaluate                 # noqa: E402
+from mask_bev_amd.optimizers import ClipStats, clip_gradients   # noqa: E402
 
 
 def get_metric_from_name(path, regex):
@@ -111,9 +112,13 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
     # EarlyStopping(check_metric, patience=30) of the reference's Trainer (train_mask_bev.py:100): stop after 30
     # epochs without an improvement of the monitored metric (Lightning's default min_delta = 0, mode = 'min')
     es_best, es_wait, es_patience = float('inf'), 0, 30
+    # a flat optimizer with clipping (K41) keeps the last step's gradient norm and clip coefficient on the device
+    clipping = getattr(optimizer, 'max_grad_norm', None) is not None
+    clip_val = config.get('gradient_clip_val', None)
     for epoch in range(args.max_epochs):
         model.current_epoch = epoch
         t0, loss_sum, n_steps = time.perf_counter(), None, 0
+        clip_stats = ClipStats()
         n_batches = int(len(data) * float(config.get('limit_train_batches', 1.0))) if isinstance(
             config.get('limit_train_batches', 1.0), float) else int(config.get('limit_train_batches'))
         for i in range(max(1, n_batches)):
@@ -132,12 +137,15 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
                 model.scale_loss(loss).backward()
                 if reducer is not None:
                     reducer.finish(optimizer)
+                clip_gradients(optimizer, model.parameters(), clip_val)     # per-tensor optimizers; a flat one clips itself
                 optimizer.step()
                 optimizer.zero_grad(set_to_none=False)
             # accumulate on the device: the graphed step returns ONE static tensor that every replay overwrites,
             # so keeping references would average N aliases of the last batch's loss (the reference monitors the
             # epoch mean of train_loss, mask_bev_module.py:296 `self.log('train_loss', ..., on_epoch=True)`)
             loss_sum = loss.detach().clone() if loss_sum is None else loss_sum + loss.detach()
+            if clipping:           # views of the optimizer's record, which the next step overwrites: summed on the device too
+                clip_stats.add(optimizer.grad_norm, optimizer.clip_coef)
             n_steps += 1
             step_count += 1
             if 0 < args.max_steps <= step_count:
@@ -156,6 +164,7 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
             dt = time.perf_counter() - t0
             print(f'epoch {epoch}: train_loss {train_loss:.6f}'
                   + (f' val_loss {val_loss:.6f}' if val_loss is not None else '')
+                  + (' ' + clip_stats.line(n_steps) if clipping else '')
                   + f'  {n_steps * int(config.get("batch_size", 1)) * world / dt:.1f} scans/s', flush=True)
             save_checkpoint(model, optimizer, checkpoint_folder_path / 'last.ckpt', epoch, check_metric, monitored)
             if monitored < best:
@@ -259,6 +268,8 @@ def build_parser():
     parser.add_argument('--max-steps', type=int, default=-1, help='stop after this many optimizer steps (-1: no limit)')
     parser.add_argument('--steps-per-epoch', type=int, default=100, help='synthetic data: batches per epoch')
     parser.add_argument('--compute-dtype', default=None, choices=[None, 'fp32', 'bf16', 'fp16'])
+    parser.add_argument('--gradient-clip-val', type=float, default=None,
+                        help='clip the global 2-norm of the gradient at this value (overrides the YAML gradient_clip_val)')
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly (no HIP-graph replay)')
     parser.add_argument('--checkpoint-root', default='checkpoints')
     parser.add_argument('--build-object-bank', action='store_true',
@@ -298,6 +309,8 @@ def main(argv=None):
         config: dict = yaml.safe_load(f)
     if args.compute_dtype:
         config['compute_dtype'] = args.compute_dtype
+    if args.gradient_clip_val is not None:
+        config['gradient_clip_val'] = args.gradient_clip_val
 
     limit_val_batches = config.get('limit_val_batches', 1.0)
     check_metric = 'val_loss' if (limit_val_batches > 0 and not args.synthetic
