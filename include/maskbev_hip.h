@@ -2205,6 +2205,57 @@ int mbv_grad_norm_partials(const float* grad, int64_t n, const int64_t* start, c
 int mbv_grad_clip_coef(const double* partials, int32_t n_partials, const int32_t* range_chunks, int32_t count, float max_norm,
                        float grad_scale, const float* loss_scale, float* rec, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K42 — reconciling the kept queries of one decoder output with each other (csrc/resolve.hip): greedy mask NMS and
+ * Mask2Former's overlap filter (`panoptic_postprocess`: the per-pixel argmax over the kept queries, a segment dropped when it
+ * wins less than OVERLAP_THRESHOLD of its own mask).  The reference's consumers keep every `argmax > 0` query
+ * (mask_bev/mask_bev_module.py:286-294, mask_bev/evaluation/kitti_eval.py:27-44).  Integer arithmetic only (comparisons in
+ * int64), per frame, no host synchronisation, no workspace, capturable in a graph.  Thresholds are ratios num / den with
+ * 1 <= num <= den <= 65535.
+ *
+ * The rule, between K21a / K21b and their consumers:
+ *   N  candidates = queries with keep set, in descending f32 score, ties to the smaller q.  Walking that order, a candidate
+ *      not yet suppressed is a survivor; a survivor i suppresses every later, not yet suppressed candidate j with
+ *      labels[i] == labels[j] (only with same_label), union = area_i + area_j - inter_ij > 0 and
+ *      inter_ij * den >= num * union (equality suppresses): suppressed_by[j] = i, -1 for everybody else;
+ *      keep1 = keep & (suppressed_by < 0).  Not transitive: a suppressed candidate suppresses nobody.
+ *   M  mbv_extract_masks again on the same logits with keep1, for instance_map only.
+ *   F  owned[q] = cells of that map equal to q (0 for q outside keep1); a q of keep1 is dropped iff owned[q] < min_cells or
+ *      owned[q] * den < num * areas[q]; one pass, not iterated; the cells of a dropped query become -1 and are not handed to
+ *      the next best query.  keep2 is the final keep.
+ *   X  (optional) mbv_masks_from_map of the filtered map: disjoint masks, areas == owned on kept queries.
+ *
+ * K42a mbv_mask_self_overlap — words (B * Q, nwords) u32, mbv_pack_binary_masks layout with tail bits zero, row b * Q + q;
+ *   keep (B, Q) u8; inter (B, Q, Q) i32: inter[b][i][j] = popcount(row i & row j) where both are kept — symmetric, the
+ *   diagonal is a kept mask's own popcount — and 0 wherever either is not kept.  Rows that are not kept are never read.
+ *   Two launches: a fill of inter, then one workgroup per (32 x 32 tile of the frame's KEPT rows in ascending q, tile pairs
+ *   with row tile <= column tile only; 512 words of the contraction).  The kept count exists only on the device: the grid
+ *   is sized from Q and a workgroup whose tile lies beyond the kept rows leaves after reading keep.  The 64 rows of a pair
+ *   of tiles stream through LDS 128 words at a time (16-byte loads where nwords and the base allow), popcounts are taken 64
+ *   bits at a time, and the splits of the contraction are joined with integer atomics into both triangles: exact, so
+ *   their order does not matter.
+ * K42b mbv_mask_nms — stage N from K42a's table (areas = its diagonal), scores (B, Q) f32, labels (B, Q) i32, keep (B, Q)
+ *   u8 → keep_out (B, Q) u8 and suppressed_by (B, Q) i32.  One workgroup per frame: the order by counting in LDS, then the
+ *   walk, the later candidates tested in parallel between barriers.  A score that does not order (NaN) is skipped by the walk
+ *   and stays kept.  keep_out may be keep.
+ * K42c mbv_overlap_filter — stage F: instance_map (B, H, W) i32 in and out, areas (B, Q) i32, keep (B, Q) u8 (keep1) →
+ *   owned (B, Q) i32, keep_out (B, Q) u8.  num == 0 leaves only the min_cells test.  Three launches: a fill of owned, a
+ *   per-workgroup cell histogram in LDS flushed with integer atomics for the queries of keep, then the decision per
+ *   workgroup in LDS and the rewrite of its cells: a cell whose value is in [0, Q) and not in keep_out becomes -1 (a query
+ *   outside keep included), any other value stays.  keep_out must not be keep: other workgroups still read it.
+ * Every element of every output is written by a kernel.  Indices come from the sizes: a label, score or map value out of
+ * range changes results, never addresses.
+ * B * Q == 0: MBV_OK before any pointer is looked at, nothing is written.  MBV_ERR_UNSUPPORTED: Q > 1024, B > 65535,
+ * nwords > 32768, H * W > 1024 * 1024;  MBV_ERR_BAD_ARG: a null pointer, a negative size, H < 1 or W < 1, min_cells < 0, a
+ * ratio outside 1 <= num <= den <= 65535 (K42c: 0 <= num).
+ */
+int mbv_mask_self_overlap(const uint32_t* words, const uint8_t* keep, int32_t B, int32_t Q, int64_t nwords, int32_t* inter,
+                          void* stream);
+int mbv_mask_nms(const int32_t* inter, const float* scores, const int32_t* labels, const uint8_t* keep, int32_t B, int32_t Q,
+                 int32_t num, int32_t den, int32_t same_label, uint8_t* keep_out, int32_t* suppressed_by, void* stream);
+int mbv_overlap_filter(int32_t* instance_map, const int32_t* areas, const uint8_t* keep, int32_t B, int32_t H, int32_t W,
+                       int32_t Q, int32_t num, int32_t den, int32_t min_cells, int32_t* owned, uint8_t* keep_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,8 @@ FILE_FLAGS = {
     # K40's LAMB / SGD updates are compared with per-tensor torch restatements: one rounding per operation, as torch does them
     # (K11's k_adamw shares the unit; its arithmetic pins contraction off itself, adam.hpp)
     'optim_flat.hip': ['-ffp-contract=off'],
+    # (K42's resolve.hip is integer arithmetic throughout, like instances.hip's neighbours mask_map.hip and
+    # mask_components.hip: the common flags, no entry here)
     # the LDS-DMA helper writes M0 inside its asm statement and says so in the clobber list (cdna_hip_programming.md §5.7)
     'gemm.hip': ['-Wno-inline-asm'],
 }

@@ -1,5 +1,6 @@
 """What ``--test`` runs after the validation loss, one pass over the scans per feature: KITTI BEV / 3D AP (K25-K27, K30, K31),
 per-point labels (K31), their panoptic quality (K32), tracking with LSTQ (K33), BEV frames as PNG files (K36); the settings and printed lines of each.  With
+``predict_resolve: true`` every one of these passes predicts with mask NMS and the overlap filter among the kept queries (K42).  With
 ``lift_ground: true`` every lift labels only the returns above a ground estimate made from the scan itself (K35)."""
 import pathlib
 
@@ -10,17 +11,41 @@ from . import batch as B
 from .datasets import KittiFrames, semantic_kitti_files
 from .kitti_eval import eval_kitti
 from .metrics import DevicePanopticQuality, DeviceTubeAssociation, lstq, semantic_kitti_class_lut
-from .predict import BOX_METHODS, GroundSettings, write_semantic_kitti_labels
+from .predict import BOX_METHODS, GroundSettings, ResolveSettings, write_semantic_kitti_labels
 from .tracking import FootprintFusion, FusionSettings, InstanceTracker, MotionSettings, OcclusionSettings, velodyne_poses
 
 
-def predictions(model, scan_paths, bsz, device, score_threshold=0.0):
-    """``(paths, scans, pred)`` per batch of ``bsz`` of ``scan_paths``: the scans on the device and ``model.predict`` of them."""
+def resolve_settings(config):
+    """``predict_resolve: true``: the :class:`~mask_bev_amd.predict.ResolveSettings` (K42: mask NMS and the overlap filter among
+    the kept queries) from ``predict_nms_iou`` ([1, 2]; null: no NMS), ``predict_min_overlap`` ([4, 5]; null: only the cell
+    count), ``predict_min_cells`` (1) and ``predict_exclusive_masks`` (false); ``None`` without the key.  The defaults are the
+    conventional mask-NMS IoU and Mask2Former's OVERLAP_THRESHOLD, not tuned here."""
+    if not bool(config.get('predict_resolve', False)):
+        return None
+    ratio = lambda key, default: None if config.get(key, default) is None else tuple(config.get(key, default))
+    return ResolveSettings(nms_iou=ratio('predict_nms_iou', (1, 2)), min_overlap=ratio('predict_min_overlap', (4, 5)),
+                           min_cells=config.get('predict_min_cells', 1),
+                           exclusive=bool(config.get('predict_exclusive_masks', False)))
+
+
+def format_resolve_settings(settings):
+    """The line ``--test`` prints in front of the results that ``predict_resolve: true`` changes."""
+    ratio = lambda r: 'off' if r is None else f'{r[0]}/{r[1]}'
+    return (f'resolved predictions: nms_iou {ratio(settings.nms_iou)}, min_overlap {ratio(settings.min_overlap)}, '
+            f'min_cells {settings.min_cells}' + (', exclusive masks' if settings.exclusive else ''))
+
+
+def predictions(model, scan_paths, bsz, device, score_threshold=0.0, resolve=None):
+    """``(paths, scans, pred)`` per batch of ``bsz`` of ``scan_paths``: the scans on the device and ``model.predict`` of them —
+    the one place ``--test`` predicts; ``resolve``: :func:`resolve_settings` of the configuration (K42)."""
     bsz = max(1, int(bsz))
     for start in range(0, len(scan_paths), bsz):
         part = scan_paths[start:start + bsz]
         scans = [torch.from_numpy(B.read_velodyne_bin(f)).to(device) for f in part]
-        yield part, scans, model.predict(scans, score_threshold)
+        if resolve is None:
+            yield part, scans, model.predict(scans, score_threshold)
+        else:
+            yield part, scans, model.predict(scans, score_threshold, resolve=resolve)
 
 
 def semantic_kitti_label_path(scan_path):
@@ -90,7 +115,8 @@ def kitti_bev_evaluation(model, config, device, root, split='val', score_thresho
     ground = _ground(config)
     tree = KittiFrames(root, split)
     labels, scan_paths, boxes = [tree.labels(f) for f in tree.frames], [tree.scan(f) for f in tree.frames], []
-    for _, scans, pred in predictions(model, scan_paths, config.get('batch_size', 1), device, score_threshold):
+    for _, scans, pred in predictions(model, scan_paths, config.get('batch_size', 1), device, score_threshold,
+                                        resolve=resolve_settings(config)):
         lift = dict(scans=scans, module=model, extent=extent) if with_3d else {}
         if with_3d and ground:
             lift.update(ground=ground['ground'], bottom='ground')
@@ -105,7 +131,8 @@ def write_point_labels(model, config, device, files, out_dir, score_threshold=0.
     returns above the estimated ground are labelled (:func:`lift_settings`).  Returns the paths written."""
     written = []
     ground = _ground(config)
-    for part, scans, pred in predictions(model, [f for f, _ in files], config.get('batch_size', 1), device, score_threshold):
+    for part, scans, pred in predictions(model, [f for f, _ in files], config.get('batch_size', 1), device, score_threshold,
+                                        resolve=resolve_settings(config)):
         for f, labels in zip(part, pred.lift(scans, model, **ground).per_scan()):
             written.append(prediction_label_path(out_dir, f))
             write_semantic_kitti_labels(written[-1], labels, semantic_id)
@@ -137,7 +164,8 @@ def point_panoptic_evaluation(model, config, device, files, score_threshold=0.0)
         return None
     metric = panoptic_metric(config)
     ground = _ground(config)
-    for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
+    for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold,
+                                        resolve=resolve_settings(config)):
         words = [read_label_words(semantic_kitti_label_path(f), device) for f in part]
         pred.panoptic_points(pred.lift(scans, model, **ground), words, metric)
     return metric
@@ -232,7 +260,8 @@ def sequence_tracking(model, config, device, root, sequences, out_dir=None, scor
         tubes.reset()
         if fusion is not None:
             fusion.reset()
-        for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
+        for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold,
+                                        resolve=resolve_settings(config)):
             vis = pred.visibility(scans, model, tracker.occlusion) if tracker.occlusion is not None else None
             pred, query_track = _track(pred, tracker, fusion, poses[[int(f.stem) for f in part]], vis)
             lifted = pred.lift(scans, model, **ground)
@@ -323,7 +352,8 @@ def render_frames(model, config, device, scan_paths, out_dir, dataset='semantic-
         with_boxes = bool(config.get('render_boxes', True))
         ranges = (config['x_range'], config['y_range'], config['voxel_size'])
         start = 0
-        for part, scans, pred in predictions(model, list(scan_paths), config.get('batch_size', 1), device, score_threshold):
+        for part, scans, pred in predictions(model, list(scan_paths), config.get('batch_size', 1), device, score_threshold,
+                                        resolve=resolve_settings(config)):
             gt = None if (label_boxes is None or not with_boxes) else list(label_boxes[start:start + len(part)])
             start += len(part)
             frames = pred.render(settings, scans=scans, module=model, boxes='pred' if with_boxes else None, gt_boxes=gt,
@@ -348,7 +378,8 @@ def render_frames(model, config, device, scan_paths, out_dir, dataset='semantic-
             tracker.reset()
             if fusion is not None:
                 fusion.reset()
-        for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold):
+        for part, scans, pred in predictions(model, scans_of, config.get('batch_size', 1), device, score_threshold,
+                                        resolve=resolve_settings(config)):
             vis = pred.visibility(scans, model, tracker.occlusion) if track and tracker.occlusion is not None else None
             query_track = None
             if track:

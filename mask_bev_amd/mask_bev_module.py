@@ -309,11 +309,12 @@ class MaskBevModule(_Base):
         return self._step(val_batch, batch_idx, 'val')
 
     # ------------------------------------------------------------------ inference (build extension, predict.py)
-    def predict(self, scans, score_threshold: float = 0.0):
+    def predict(self, scans, score_threshold: float = 0.0, resolve=None):
         """Instances of a list of device scans: eager forward in eval mode under no_grad (the previous mode is restored),
-        then K21 on the last decoder output → :class:`~mask_bev_amd.predict.Predictions`."""
+        then K21 on the last decoder output → :class:`~mask_bev_amd.predict.Predictions`.  ``resolve``: a
+        :class:`~mask_bev_amd.predict.ResolveSettings` — mask NMS and the overlap filter among the kept queries (K42)."""
         from .predict import predict
-        return predict(self, scans, score_threshold)
+        return predict(self, scans, score_threshold, resolve=resolve)
 
     def predict_step(self, batch, batch_idx=0):
         """Lightning's name: ``batch`` is a list of scans or a ``(scans, targets[, metadata])`` batch."""

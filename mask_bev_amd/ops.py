@@ -16,7 +16,8 @@ tests patch ``ops.mask_logits`` / ``ops.hungarian`` here):
     ops_loss       K8 point sampling, K9 Hungarian, K10 importance sampling, K13 loss rows / costs
     ops_instances  K21 query selection + BEV mask / instance-map extraction at inference; K31 lift of the instance map to
                    the points (per-point labels, points and z-extent per query); K35 ground height per BEV cell and the
-                   lift restricted to the returns above it; K38a BEV visibility map of a scan (PASSED / HIT / unknown)
+                   lift restricted to the returns above it; K38a BEV visibility map of a scan (PASSED / HIT / unknown);
+                   K42 the kept queries reconciled with each other: self-overlap of the kept masks, greedy mask NMS, overlap filter
     ops_rasterize  K22 SemanticKITTI scene -> instance-id map (binning, close + open, paint)
     ops_augment    K23 training augmentations: per-point op program, compaction / sort, instance-map warp;
                    K28 KITTI object augmentations: box-table membership, move, removal and pasting of points

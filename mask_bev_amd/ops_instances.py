@@ -2,7 +2,8 @@
 areas, mask scores and instance map of one decoder output, straight from the (h, w) logits with no (B, Q, H, W)
 intermediate.  K31 — the lift of that instance map to the points of the scans (csrc/point_lift.hip): per-point query labels,
 points per query and their z-extent.  K35 — a ground height per BEV cell from the scans themselves and the lift restricted to the
-returns above it (same file).  Class convention: index 0 = empty, > 0 = object; a pixel is set when its interpolated
+returns above it (same file).  K42 — the kept queries reconciled with each other (csrc/resolve.hip): the pairwise overlap of the
+kept masks, greedy mask NMS and Mask2Former's overlap filter on the instance map.  Class convention: index 0 = empty, > 0 = object; a pixel is set when its interpolated
 logit is > 0 (sigmoid > 0.5)."""
 from __future__ import annotations
 
@@ -76,6 +77,110 @@ def extract_masks(logits: torch.Tensor, scores: torch.Tensor, keep: torch.Tensor
                                 _ptr(mscores), _ptr(imap), _ptr(ws), nbytes if ws is not None else 0, _stream()),
           'mbv_extract_masks')
     return dict(masks=PackedMasks(words, H, W) if masks else None, areas=areas, mask_scores=mscores, instance_map=imap)
+
+
+def _ratio(what: str, ratio, num_min: int = 1) -> Tuple[int, int]:
+    """An integer ratio (num, den) with num_min <= num <= den <= 65535, or MaskBevHipError."""
+    try:
+        num, den = ratio
+        ok = int(num) == num and int(den) == den and num_min <= int(num) <= int(den) <= 65535 and int(den) >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise MaskBevHipError(f'{what}: an integer ratio (num, den) with {num_min} <= num <= den <= 65535 expected, got {ratio!r}')
+    return int(num), int(den)
+
+
+def _frame_table(what: str, name: str, t: torch.Tensor, shape, dtype, dev) -> torch.Tensor:
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev:
+        raise MaskBevHipError(f'{what}: {name} must be {tuple(shape)} {dtype} on {dev}, got '
+                              f'{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__} {getattr(t, "dtype", "")}')
+    return t.contiguous()
+
+
+@torch.no_grad()
+def mask_self_overlap(masks: PackedMasks, keep: torch.Tensor) -> torch.Tensor:
+    """K42a: ``masks`` — the B * Q packed maps of :func:`extract_masks` (row b * Q + q), ``keep`` (B, Q) bool → ``inter``
+    (B, Q, Q) int32: the popcount of row i AND row j where both are kept (the diagonal: a kept mask's area), 0 wherever either is
+    not.  Only kept rows are read, every unordered pair once.  Q <= 1024.  Exact; no host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(masks.words, keep)
+    words = masks.words
+    if keep.dim() != 2 or keep.dtype != torch.bool or keep.device != words.device:
+        raise MaskBevHipError(f'mask_self_overlap: keep must be (B, Q) bool on the masks\' device, got {tuple(keep.shape)} '
+                              f'{keep.dtype}')
+    b, q = (int(v) for v in keep.shape)
+    nwords = lib.mbv_packed_mask_words(int(masks.h), int(masks.w))
+    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous() or tuple(words.shape) != (b * q, nwords):
+        raise MaskBevHipError(f'mask_self_overlap: words must be a contiguous ({b * q}, {nwords}) int32 tensor for {b} x {q} '
+                              f'maps on a {masks.h}x{masks.w} grid, got {tuple(words.shape)} {words.dtype}')
+    if q > 1024 or b > 65535 or nwords > 32768:
+        raise MaskBevHipError(f'mask_self_overlap: Q {q} <= 1024, B {b} <= 65535 or H * W <= 2^20 violated')
+    keep = keep.contiguous()
+    inter = torch.empty((b, q, q), dtype=torch.int32, device=words.device)
+    check(lib.mbv_mask_self_overlap(_ptr(words), _ptr(keep), b, q, nwords, _ptr(inter), _stream()), 'mbv_mask_self_overlap')
+    return inter
+
+
+@torch.no_grad()
+def mask_nms(inter: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, keep: torch.Tensor, iou=(1, 2),
+             same_label: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """K42b, greedy mask NMS: ``inter`` (B, Q, Q) int32 of :func:`mask_self_overlap`, ``scores`` (B, Q) f32, ``labels`` (B, Q)
+    int32 and ``keep`` (B, Q) bool of :func:`select_queries`; ``iou`` = (num, den).  The kept queries in descending score (ties:
+    the smaller q first); a survivor i suppresses every later, not yet suppressed j (of its label, with ``same_label``) with
+    ``inter * den >= num * union`` and ``union > 0`` — equality suppresses, a suppressed query suppresses nobody.  Returns
+    ``(keep (B, Q) bool, suppressed_by (B, Q) int32)``, -1 where nobody did.  Exact integers; no host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(inter, scores, labels, keep)
+    if keep.dim() != 2:
+        raise MaskBevHipError(f'mask_nms: keep must be (B, Q) bool, got {tuple(keep.shape)}')
+    b, q = (int(v) for v in keep.shape)
+    dev = keep.device
+    num, den = _ratio('mask_nms: iou', iou)
+    keep = _frame_table('mask_nms', 'keep', keep, (b, q), torch.bool, dev)
+    inter = _frame_table('mask_nms', 'inter', inter, (b, q, q), torch.int32, dev)
+    scores = _frame_table('mask_nms', 'scores', scores, (b, q), torch.float32, dev)
+    labels = _frame_table('mask_nms', 'labels', labels, (b, q), torch.int32, dev)
+    if q > 1024 or b > 65535:
+        raise MaskBevHipError(f'mask_nms: Q {q} <= 1024 or B {b} <= 65535 violated')
+    keep_out = torch.empty((b, q), dtype=torch.bool, device=dev)
+    suppressed_by = torch.empty((b, q), dtype=torch.int32, device=dev)
+    check(lib.mbv_mask_nms(_ptr(inter), _ptr(scores), _ptr(labels), _ptr(keep), b, q, num, den, 1 if same_label else 0,
+                           _ptr(keep_out), _ptr(suppressed_by), _stream()), 'mbv_mask_nms')
+    return keep_out, suppressed_by
+
+
+@torch.no_grad()
+def overlap_filter(instance_map: torch.Tensor, areas: torch.Tensor, keep: torch.Tensor, min_overlap=(4, 5),
+                   min_cells: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """K42c, Mask2Former's overlap filter: ``instance_map`` (B, H, W) int32 contiguous — CHANGED IN PLACE —, ``areas`` (B, Q)
+    int32 and ``keep`` (B, Q) bool.  ``owned[q]`` = cells of the map equal to q (0 for q outside ``keep``); a kept q is dropped
+    iff ``owned < min_cells`` or ``owned * den < num * area`` (``min_overlap`` = (num, den); None: the first test only).  One
+    pass; the cells of every query that is not kept afterwards become -1.  Returns ``(keep (B, Q) bool, owned (B, Q) int32)``.
+    Exact integers; no host synchronisation."""
+    lib = _lib.load()
+    _need_gpu(instance_map, areas, keep)
+    if keep.dim() != 2:
+        raise MaskBevHipError(f'overlap_filter: keep must be (B, Q) bool, got {tuple(keep.shape)}')
+    b, q = (int(v) for v in keep.shape)
+    dev = keep.device
+    num, den = (0, 1) if min_overlap is None else _ratio('overlap_filter: min_overlap', min_overlap)
+    if int(min_cells) != min_cells or not 0 <= int(min_cells) < 2 ** 31:
+        raise MaskBevHipError(f'overlap_filter: min_cells must be an integer >= 0, got {min_cells!r}')
+    if (instance_map.dim() != 3 or instance_map.dtype != torch.int32 or instance_map.shape[0] != b
+            or instance_map.device != dev or not instance_map.is_contiguous()):
+        raise MaskBevHipError(f'overlap_filter: instance_map must be a contiguous ({b}, H, W) int32 tensor on keep\'s device '
+                              f'(it is changed in place), got {tuple(instance_map.shape)} {instance_map.dtype}')
+    h, w = int(instance_map.shape[1]), int(instance_map.shape[2])
+    keep = _frame_table('overlap_filter', 'keep', keep, (b, q), torch.bool, dev)
+    areas = _frame_table('overlap_filter', 'areas', areas, (b, q), torch.int32, dev)
+    if q > 1024 or b > 65535 or not 1 <= h * w <= 1024 * 1024:
+        raise MaskBevHipError(f'overlap_filter: Q {q} <= 1024, B {b} <= 65535 or 1 <= H * W {h * w} <= 2^20 violated')
+    keep_out = torch.empty((b, q), dtype=torch.bool, device=dev)
+    owned = torch.empty((b, q), dtype=torch.int32, device=dev)
+    check(lib.mbv_overlap_filter(_ptr(instance_map), _ptr(areas), _ptr(keep), b, h, w, q, num, den, int(min_cells), _ptr(owned),
+                                 _ptr(keep_out), _stream()), 'mbv_overlap_filter')
+    return keep_out, owned
 
 
 @dataclass
@@ -266,5 +371,5 @@ def lift_instances(scans: Sequence[torch.Tensor], instance_map: torch.Tensor, ge
                           z_extent[..., 3], tuple(lens), z_ground)
 
 
-__all__ = ['select_queries', 'extract_masks', 'lift_instances', 'PointInstances', 'ground_map', 'GroundMap',
+__all__ = ['select_queries', 'extract_masks', 'mask_self_overlap', 'mask_nms', 'overlap_filter','lift_instances', 'PointInstances', 'ground_map', 'GroundMap',
            'MAX_GROUND_RADIUS', 'visibility_map', 'origin_cell', 'VIS_PASSED', 'VIS_HIT']

@@ -48,6 +48,44 @@ class GroundSettings:
         return cells
 
 
+@dataclass
+class ResolveSettings:
+    """K42: how the kept queries of one decoder output are reconciled with each other (``extract_instances(...,
+    resolve=)``).  Thresholds are integer ratios (num, den) with 1 <= num <= den <= 65535; everything is exact integer
+    arithmetic on the device.  ``nms_iou`` — greedy mask NMS: in descending score a surviving query suppresses every later one
+    (of its label, with ``same_label``) whose mask IoU with it is >= num / den (None: no NMS);  ``min_overlap`` — Mask2Former's
+    overlap filter: after the instance map is rebuilt from the survivors, a query that owns less than num / den of its own mask
+    in it is dropped (None: only ``min_cells``);  ``min_cells`` — and one that owns fewer cells than this;  ``exclusive`` —
+    ``masks`` and ``areas`` become the cells every query won (disjoint), not its thresholded mask.  1/2 and 4/5 are the
+    conventional mask-NMS IoU and Mask2Former's OVERLAP_THRESHOLD; neither is tuned or measured on real data here."""
+    nms_iou: Optional[Tuple[int, int]] = (1, 2)
+    min_overlap: Optional[Tuple[int, int]] = (4, 5)
+    min_cells: int = 1
+    same_label: bool = True
+    exclusive: bool = False
+
+    def __post_init__(self):
+        for name in ('nms_iou', 'min_overlap'):
+            r = getattr(self, name)
+            if r is None:
+                continue
+            try:
+                num, den = r
+                ok = (not isinstance(num, bool) and not isinstance(den, bool) and int(num) == num and int(den) == den
+                      and 1 <= int(num) <= int(den) <= 65535)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f'ResolveSettings: {name} must be None or an integer ratio (num, den) with '
+                                 f'1 <= num <= den <= 65535, got {r!r}')
+            setattr(self, name, (int(num), int(den)))
+        mc = self.min_cells
+        if isinstance(mc, bool) or not isinstance(mc, (int, np.integer)) or not 0 <= int(mc) < 2 ** 31:
+            raise ValueError(f'ResolveSettings: min_cells must be an integer >= 0, got {mc!r}')
+        self.min_cells = int(mc)
+        self.same_label, self.exclusive = bool(self.same_label), bool(self.exclusive)
+
+
 def unpack_bits(words: torch.Tensor, h: int, w: int) -> torch.Tensor:
     """Bit-packed maps (N, words) int32 in the mbv_pack_binary_masks layout (pixel y*w + x at bit (y*w + x) % 32 of word
     (y*w + x) // 32) → (N, h, w) bool, on the words' device."""
@@ -65,7 +103,14 @@ class Predictions:
     label;  keep (B, Q) bool — label > 0 and score >= the threshold;  masks — :class:`ops.PackedMasks` of the B*Q maps at
     (H, W) (row b*Q + q), or None;  areas (B, Q) int32 — set pixels;  mask_scores (B, Q) f32 — mean sigmoid over the set
     pixels (0 for an empty mask);  instance_map (B, H, W) int32 — per pixel the kept query with a set bit maximising
-    score * sigmoid, -1 for none (or None)."""
+    score * sigmoid, -1 for none (or None).
+
+    With ``resolve=`` (K42, :class:`ResolveSettings`) ``keep`` is what survived mask NMS and the overlap filter and
+    ``instance_map`` the map of those queries alone;  suppressed_by (B, Q) int32 — the surviving query that suppressed this one
+    in the NMS, -1 for nobody;  owned (B, Q) int32 — the cells a query won in the map rebuilt after the NMS (0 outside it), also
+    for a query the filter then dropped.  Both are None without ``resolve``.  ``masks`` and ``areas`` stay the thresholded
+    masks unless ``exclusive``; then they are the cells won (``areas == owned`` on kept queries), while ``mask_scores`` still
+    describes the UNRESOLVED masks."""
     labels: torch.Tensor
     scores: torch.Tensor
     keep: torch.Tensor
@@ -74,6 +119,8 @@ class Predictions:
     mask_scores: Optional[torch.Tensor]
     instance_map: Optional[torch.Tensor]
     grid_hw: Tuple[int, int]
+    suppressed_by: Optional[torch.Tensor] = None
+    owned: Optional[torch.Tensor] = None
 
     def _map(self, fn) -> 'Predictions':
         vals = {}
@@ -391,19 +438,48 @@ def write_semantic_kitti_labels(path, point_query, semantic_id: int = 10, instan
     out.tofile(str(path))
 
 
+def _resolve_settings(resolve, masks: bool, instance_map: bool) -> Optional[ResolveSettings]:
+    if resolve is None:
+        return None
+    if not isinstance(resolve, ResolveSettings):
+        raise TypeError(f'resolve must be a ResolveSettings or None, got {type(resolve).__name__}')
+    if not (masks and instance_map):
+        raise ValueError('resolve needs masks=True and instance_map=True: the rule reads the masks and rebuilds the map')
+    return resolve
+
+
 def extract_instances(cls: torch.Tensor, mask_logits: torch.Tensor, grid_hw, score_threshold: float = 0.0,
-                      masks: bool = True, instance_map: bool = True) -> Predictions:
+                      masks: bool = True, instance_map: bool = True, resolve: Optional[ResolveSettings] = None) -> Predictions:
     """K21a + K21b on one decoder output: cls (B, Q, K+1) f32 / bf16 / fp16 and mask_logits (B, Q, h, w) f32 on the device,
     grid_hw = (H, W) the BEV grid.  ``masks=False`` skips the packed masks, areas and mask scores; ``instance_map=False``
-    the map.  Device tensors only (a CPU tensor raises MaskBevHipError)."""
+    the map.  Device tensors only (a CPU tensor raises MaskBevHipError).
+
+    ``resolve`` (K42, a :class:`ResolveSettings`; needs both flags): K21b's first pass makes masks, areas and mask scores only;
+    K42a + K42b suppress duplicates among the kept queries; a second K21b pass over the survivors makes the instance map; K42c
+    drops the queries that own too little of their mask in it and clears their cells; with ``exclusive`` K39b turns the map
+    back into masks.  No host synchronisation; all of it can be captured in a graph."""
     ops._need_gpu(cls, mask_logits)
     if cls.dim() != 3 or mask_logits.dim() != 4 or tuple(cls.shape[:2]) != tuple(mask_logits.shape[:2]):
         raise MaskBevHipError(f'extract_instances: cls (B, Q, K+1) and mask logits (B, Q, h, w) expected, got '
                               f'{tuple(cls.shape)} and {tuple(mask_logits.shape)}')
+    resolve = _resolve_settings(resolve, masks, instance_map)
+    grid = (int(grid_hw[0]), int(grid_hw[1]))
     labels, scores, keep = ops.select_queries(cls, score_threshold)
-    out = ops.extract_masks(mask_logits, scores, keep, grid_hw, masks=masks, instance_map=instance_map)
-    return Predictions(labels, scores, keep, out['masks'], out['areas'], out['mask_scores'], out['instance_map'],
-                       (int(grid_hw[0]), int(grid_hw[1])))
+    if resolve is None:
+        out = ops.extract_masks(mask_logits, scores, keep, grid_hw, masks=masks, instance_map=instance_map)
+        return Predictions(labels, scores, keep, out['masks'], out['areas'], out['mask_scores'], out['instance_map'], grid)
+    out = ops.extract_masks(mask_logits, scores, keep, grid_hw, masks=True, instance_map=False)
+    pm, areas = out['masks'], out['areas']
+    if resolve.nms_iou is not None:
+        inter = ops.mask_self_overlap(pm, keep)
+        keep, suppressed_by = ops.mask_nms(inter, scores, labels, keep, resolve.nms_iou, resolve.same_label)
+    else:
+        suppressed_by = torch.full_like(labels, -1, dtype=torch.int32)
+    imap = ops.extract_masks(mask_logits, scores, keep, grid_hw, masks=False, instance_map=True)['instance_map']
+    keep, owned = ops.overlap_filter(imap, areas, keep, resolve.min_overlap, resolve.min_cells)
+    if resolve.exclusive:
+        pm, areas = ops.masks_from_map(imap, int(labels.shape[1]))
+    return Predictions(labels, scores, keep, pm, areas, out['mask_scores'], imap, grid, suppressed_by, owned)
 
 
 def grid_hw(module) -> Tuple[int, int]:
@@ -428,16 +504,19 @@ class _EvalMode:
         return False
 
 
-def predict(module, scans, score_threshold: float = 0.0, masks: bool = True, instance_map: bool = True) -> Predictions:
+def predict(module, scans, score_threshold: float = 0.0, masks: bool = True, instance_map: bool = True,
+            resolve: Optional[ResolveSettings] = None) -> Predictions:
     """Eager inference on a list of (N_i, pc_dim) device scans: forward in eval mode under no_grad, K21 on the last
-    decoder output (MaskBevModule.predict)."""
+    decoder output (MaskBevModule.predict); ``resolve``: K42, as in :func:`extract_instances`."""
+    resolve = _resolve_settings(resolve, masks, instance_map)
     with _EvalMode(module), torch.no_grad():
         cls, mk, _ = module(scans)
-        return extract_instances(cls[-1], mk[-1], grid_hw(module), score_threshold, masks, instance_map)
+        return extract_instances(cls[-1], mk[-1], grid_hw(module), score_threshold, masks, instance_map, resolve)
 
 
 class GraphedPredictStep:
-    """``step(scans) -> Predictions`` with backbone + head + K21 replayed from one HIP graph.
+    """``step(scans) -> Predictions`` with backbone + head + K21 (and, with ``resolve=``, K42: every stage of
+    :func:`extract_instances` inside the graph) replayed from one HIP graph.
 
     The encoder runs eagerly in eval mode and writes into the graph's static input (the 16-bit patch rows of
     ``module._patch_handoff()``, or the f32 map with its registered absmax record in fp32 compute).  The returned
@@ -450,11 +529,11 @@ class GraphedPredictStep:
     during training).  Construct it before any eager backward on the default stream, like the training graph."""
 
     def __init__(self, module, example_scans, score_threshold: float = 0.0, masks: bool = True,
-                 instance_map: bool = True, warmup_iters: int = 2):
+                 instance_map: bool = True, warmup_iters: int = 2, resolve: Optional[ResolveSettings] = None):
         m = self.m = module
         self.batch = len(example_scans)
         self.score_threshold = float(score_threshold)
-        self._flags = (masks, instance_map)
+        self._flags = (masks, instance_map, _resolve_settings(resolve, masks, instance_map))
         self._grid = grid_hw(m)
         dev = example_scans[0].device
         with _EvalMode(m), torch.no_grad():

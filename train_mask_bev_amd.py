@@ -49,7 +49,10 @@ that goes unmatched out of the sensor's sight keep its age, K38 — ``track_occl
 ``track_hidden_fraction`` [num, den], ``track_max_hold`` frames — and the parenthesis then ends ``, held ..``; ``track_fuse: true``
 fuses the tracked footprints over time in a rolling world grid, K39 — ``track_fuse_cap``, ``track_fuse_min_count``, and with
 ``track_motion`` ``track_fuse_static_speed`` metres per frame — lifts, labels and renders from the fused map, and the parenthesis
-then ends ``, fused``).  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
+then ends ``, fused``).  ``predict_resolve: true`` (K42; ``predict_nms_iou`` [num, den], ``predict_min_overlap`` [num, den],
+``predict_min_cells``, ``predict_exclusive_masks``) reconciles the kept queries of every prediction of these passes with each
+other — greedy mask NMS, then Mask2Former's overlap filter on the rebuilt instance map — and prints one ``resolved predictions:
+..`` line in front of the results it changes; the defaults 1/2 and 4/5 are conventions, not tuned here.  ``lift_ground: true`` (K35; ``lift_ground_radius`` metres, ``lift_ground_clearance``,
 ``lift_max_height``, ``lift_z_floor``) makes every one of these lifts label only the returns above a ground estimate made from
 the scan, lets the 3D boxes stand on it, and prints one ``ground-aware lift: ..`` line in front of the results it changes.
 ``--render DIR`` (K36; ``render_scale``, ``render_alpha``, ``render_boxes``) adds a last pass on rank 0 that writes one BEV frame
@@ -193,6 +196,7 @@ def test(args, config, model, val, dataset_name, device, rank, world):
     """The reference runs trainer.validate then trainer.test (train_mask_bev.py:118-119); MaskBevModule defines no test_step
     (SURVEY Appendix B), so the test pass has nothing of its own to run: validation, then the extras of mask_bev_amd/evaluate.py."""
     lifting = evaluate.lift_settings(config)   # None unless `lift_ground: true` (K35)
+    resolving = evaluate.resolve_settings(config)   # None unless `predict_resolve: true` (K42)
     layers = tuple(range(model.num_layers))    # the reference attaches its metrics to all ten decoder outputs (:85-98)
     if val is not None:
         # what trainer.validate logs there: COCO mask AP (K29), mIoU and class AP of every decoder layer
@@ -205,6 +209,8 @@ def test(args, config, model, val, dataset_name, device, rank, world):
         if val is not None:
             for layer in layers:
                 print(evaluate.format_layer_metrics(model.logged, layer), flush=True)
+        if resolving is not None and val is not None:
+            print(evaluate.format_resolve_settings(resolving), flush=True)
         if dataset_name == 'kitti' and val is not None:
             # what the reference's mask_to_pred + eval_kitti are for: boxes from the predicted masks, KITTI BEV AP
             # (`kitti_3d: true`: with the heights lifted from the scans, and the 3D AP lines)
