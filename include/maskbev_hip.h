@@ -2206,6 +2206,46 @@ int mbv_grad_clip_coef(const double* partials, int32_t n_partials, const int32_t
                        float grad_scale, const float* loss_scale, float* rec, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K43 — averaged weights over the flat arena (csrc/optim_flat.hip).  Replaces: mmengine's EMAHook / timm's ModelEmaV2
+ * (torch._foreach_lerp_ over every parameter plus a host-side decay warm-up) and SWA's equal-weight mean
+ * (torch.optim.swa_utils.AveragedModel).  `avg` is one more f32 buffer the size of the arena.  No host synchronisation,
+ * nothing allocated, capturable in a graph: the counters live in a 16-byte device record and advance on the device.
+ *
+ * mbv_weight_average_update: TWO launches on `stream`.
+ *   tick (one thread), with u = state->updates, c = state->calls:
+ *     applied = applied_steps ? (*applied_steps != state->seen) : true;   if applied_steps: state->seen = *applied_steps
+ *       (applied_steps is K11's count of applied updates, LossScaler's: mbv_loss_scale_update does not advance it on an
+ *       overflowed step, and has already cleared the overflow flag when this runs)
+ *     w = 0;  if applied: c += 1; if c % every == 0:
+ *       MBV_AVERAGE_MEAN:  w = 1.0f / (float)(u + 1)
+ *       MBV_AVERAGE_EMA:   d = warmup ? min(decay, (float)(1 + u) / (float)(10 + u)) : decay;   w = 1.0f - d
+ *       u += 1
+ *     state->weight = w        (f32 throughout, the divides correctly rounded)
+ *   stream (k_sgd's frame: 16-byte non-temporal accesses, grid-stride, ragged tail), every element of [0, n):
+ *     w == 0: nothing is read or written;   w == 1: avg = param;   else avg = avg + w * (param - avg), three f32 roundings,
+ *     no contraction.  Reads param and avg, writes avg: at most 12 B per element.  param is never written.
+ *   The first update of a mean (u = 0) and of an EMA with decay 0 has w = 1: avg takes param bit for bit.
+ * mbv_weight_average_swap: param[i] <-> avg[i], and shadow[i] = bf16 / half (RNE) of the new param[i] when shadow is given:
+ *   one pass, 16 B per element + 2 B.  Bits are moved: two calls restore param, avg and the shadow exactly.
+ * n == 0: MBV_OK, nothing launched (the record does not advance).  MBV_ERR_BAD_ARG: a null param, avg or state, param == avg,
+ *   n < 0, param or avg not 16-byte aligned, state or applied_steps not 4-byte aligned, decay outside [0, 1) or NaN, every < 1,
+ *   a mode other than the two, a shadow that is not 8-byte aligned or whose dtype is neither MBV_DT_BF16 nor MBV_DT_F16.
+ */
+#define MBV_AVERAGE_EMA 0
+#define MBV_AVERAGE_MEAN 1
+typedef struct mbv_weight_average_state {
+  int32_t updates; /* u: averaging updates applied */
+  int32_t calls;   /* c: applied optimizer steps seen */
+  int32_t seen;    /* *applied_steps at the last call */
+  float weight;    /* w of the last call; 0 = it did nothing */
+} mbv_weight_average_state;
+
+int mbv_weight_average_update(const float* param, float* avg, int64_t n, mbv_weight_average_state* state,
+                              const int32_t* applied_steps, int32_t mode, float decay, int32_t warmup, int32_t every,
+                              void* stream);
+int mbv_weight_average_swap(float* param, float* avg, void* shadow, int32_t shadow_dtype, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K42 — reconciling the kept queries of one decoder output with each other (csrc/resolve.hip): greedy mask NMS and
  * Mask2Former's overlap filter (`panoptic_postprocess`: the per-pixel argmax over the kept queries, a segment dropped when it
  * wins less than OVERLAP_THRESHOLD of its own mask).  The reference's consumers keep every `argmax > 0` query

@@ -259,6 +259,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     'mbv_sgd_step': (ctypes.c_int, [_P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _I, _F, _I, _P, _P, _P]),
     'mbv_grad_norm_partials': (ctypes.c_int, [_P, _L, _P, _P, _I, _P, _I, _P]),
     'mbv_grad_clip_coef': (ctypes.c_int, [_P, _I, _P, _I, _F, _F, _P, _P, _P]),
+    'mbv_weight_average_update': (ctypes.c_int, [_P, _P, _L, _P, _P, _I, _F, _I, _I, _P]),
+    'mbv_weight_average_swap': (ctypes.c_int, [_P, _P, _P, _I, _L, _P]),
     'mbv_mask_self_overlap': (ctypes.c_int, [_P, _P, _I, _I, _L, _P, _P]),
     'mbv_mask_nms': (ctypes.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     'mbv_overlap_filter': (ctypes.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

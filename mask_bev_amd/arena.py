@@ -18,10 +18,14 @@ The arena is laid out in the reference's differential-lr groups — encoder, bac
 The three optimizers are :class:`FlatOptimizer` subclasses: the base owns the ``step()`` frame, ``zero_grad`` and the
 checkpoint format; a subclass names its state (``KIND`` / ``STATE`` / ``HYPER``) and issues its launches in ``_launch``.
 
+:class:`WeightAverage` (K43) keeps one more flat f32 buffer beside them: an exponential moving average or running mean of
+``param``, updated in one streaming pass behind the optimizer step and exchanged with ``param`` for evaluation.
+
 Build it after the module is on its GPU (``module.to(device)`` re-allocates parameters and would detach the views).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import weakref
 from typing import Dict, Iterable, List, Optional, Tuple
@@ -798,3 +802,183 @@ class FlatSGD(FlatOptimizer):
                                    float(pg['lr']), float(pg['momentum']), float(pg['dampening']),
                                    float(pg['weight_decay']), 1 if pg['nesterov'] else 0, float(self.grad_scale),
                                    1 if self.zero_grad_in_step else 0, scale, flag, stream), 'mbv_sgd_step')
+
+
+AVERAGE_MODES = {'ema': 0, 'mean': 1}     # MBV_AVERAGE_EMA / MBV_AVERAGE_MEAN (maskbev_hip.h)
+
+
+class WeightAverage:
+    """An averaged copy of a :class:`ParameterArena`'s parameters (K43, csrc/optim_flat.hip): the exponential moving average
+    the Mask2Former family is evaluated and checkpointed on (mmengine's ``EMAHook``, timm's ``ModelEmaV2``) or SWA's
+    equal-weight running mean.  ``avg`` is ONE more flat f32 buffer, initialised to a copy of ``arena.param``; an update is one
+    C call (two launches) whatever the number of tensors, with no host synchronisation, and can be captured in a graph: the
+    counters and the blend weight live in a 16-byte device record that the update itself advances.
+
+    The rule of one ``update()`` (call it after ``optimizer.step()``), in f32 with one rounding per operation, for
+    ``u`` = updates applied and ``c`` = applied optimizer steps seen so far:
+
+    * with a :class:`LossScaler` the step counts only if the scaler's ``applied_steps`` moved since the last call — an
+      overflowed fp16 step, which the optimizer skipped, leaves ``avg`` and both counters alone;
+    * ``c += 1``; unless ``c % every == 0`` nothing else happens (the pass returns at once: launch latency only);
+    * ``mode='mean'``: ``w = 1 / (u + 1)``;  ``mode='ema'``: ``w = 1 - d``, ``d = decay``, or with ``warmup``
+      ``d = min(decay, (1 + u) / (10 + u))`` (timm's / ``torch.optim.swa_utils.get_ema_multi_avg_fn``'s warm-up);
+    * ``avg = avg + w * (param - avg)`` (``avg = param`` exactly when ``w == 1``); ``u += 1``.
+
+    ``decay`` crosses the C ABI as an f32: 0.9999 is applied as float32(0.9999), 2e-9 from the double, and ``w`` is
+    ``1.0f - float32(decay)``; the ``decay`` attribute returns the value as given.  An f32 average with a small ``w`` stops
+    moving once ``|param - avg|`` falls below about ``2**-24 / w`` of ``|avg|`` (``w = 1e-4``: 6e-4 relative) — true of every
+    f32 EMA; compensated summation is not attempted.
+
+    ``swap()`` exchanges ``param`` and ``avg`` in one pass that also rewrites the 16-bit shadow, and drops the cached
+    per-weight records (``ops.note_parameters_changed``): the module then computes with the averaged weights, and a second
+    ``swap()`` restores everything bit for bit.  ``applied()`` is the context manager for that.  While the average is swapped
+    in, ``update()`` and ``state_dict()`` raise — ``param`` does not hold the live weights then.
+
+    Module BUFFERS are not averaged (the PFN BatchNorm's running statistics, < 2 KB, not in the arena): evaluation under the
+    average reads the live ones — mmengine's ``update_buffers=False`` default.
+
+    A CPU arena is served by plain torch f32 operations, one per rounding (``swap`` = three copies and ``refresh_shadow``)."""
+
+    KIND = 'weight_average'
+
+    def __init__(self, arena: ParameterArena, mode: str = 'ema', decay: float = 0.9999, warmup: bool = True, every: int = 1,
+                 scaler: Optional[LossScaler] = None):
+        if mode not in AVERAGE_MODES:
+            raise ValueError(f"weight average mode must be 'ema' or 'mean', got {mode!r}")
+        self.arena = arena
+        self.scaler = scaler
+        self._set_hyper(mode, decay, warmup, every)
+        self.avg = arena.param.detach().clone()
+        # (updates, calls, seen, weight as f32 bits) = mbv_weight_average_state
+        self._rec = torch.zeros(4, dtype=torch.int32, device=arena.device)
+        self.is_applied = False
+        self.reset()
+
+    def _set_hyper(self, mode, decay, warmup, every):
+        decay, every = float(decay), int(every)
+        d32 = float(torch.tensor(decay, dtype=torch.float32))
+        if not 0.0 <= d32 < 1.0:
+            raise ValueError(f'weight average decay must lie in [0, 1) as a float32, got {decay}')
+        if every < 1:
+            raise ValueError(f'weight average every must be at least 1, got {every}')
+        if mode not in AVERAGE_MODES:
+            raise ValueError(f"weight average mode must be 'ema' or 'mean', got {mode!r}")
+        self.mode, self.decay, self.warmup, self.every = mode, decay, bool(warmup), every
+
+    # -- the record -----------------------------------------------------------------------------------------------------
+    @property
+    def num_updates(self) -> torch.Tensor:
+        """0-d device tensor (int32): averaging updates applied so far."""
+        return self._rec[0]
+
+    @property
+    def last_weight(self) -> torch.Tensor:
+        """0-d device tensor (f32): the blend weight of the last ``update()``; 0 = it did nothing."""
+        return self._rec.view(torch.float32)[3]
+
+    @torch.no_grad()
+    def reset(self):
+        """``avg = param``, no updates and no calls so far; with a scaler, steps applied before now are not counted."""
+        self._refuse_applied('reset()')
+        self.avg.copy_(self.arena.param)
+        self._rec.zero_()
+        if self.scaler is not None:
+            self._rec[2:3].copy_(self.scaler.applied_steps)        # device to device: no host synchronisation
+
+    def _refuse_applied(self, what: str):
+        if self.is_applied:
+            raise _lib.MaskBevHipError(f'WeightAverage.{what} while the average is swapped in: arena.param holds the averaged '
+                                       f'weights, not the live ones (swap() back first)')
+
+    # -- update ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def update(self):
+        self._refuse_applied('update()')
+        ar, sc = self.arena, self.scaler
+        if ar.device.type != 'cuda':
+            return self._update_torch()
+        lib = _lib.load()
+        with ops.TIMER.span('k_average_blend'):
+            check(lib.mbv_weight_average_update(ar.param.data_ptr(), self.avg.data_ptr(), ar.numel, self._rec.data_ptr(),
+                                                0 if sc is None else sc.applied_steps.data_ptr(), AVERAGE_MODES[self.mode],
+                                                self.decay, 1 if self.warmup else 0, self.every,
+                                                torch.cuda.current_stream(ar.device).cuda_stream),
+                  'mbv_weight_average_update')
+
+    def _update_torch(self):
+        """The rule on a CPU arena: torch f32 scalars and tensors, one operation per rounding."""
+        f32 = lambda v: torch.tensor(float(v), dtype=torch.float32)
+        u, c, seen = (int(v) for v in self._rec[:3])
+        applied = True
+        if self.scaler is not None:
+            now = int(self.scaler.applied_steps)
+            applied, seen = now != seen, now
+        w = f32(0.0)
+        if applied:
+            c += 1
+            if c % self.every == 0:
+                if self.mode == 'mean':
+                    w = f32(1.0) / f32(u + 1)
+                else:
+                    d = f32(self.decay)
+                    if self.warmup:
+                        d = torch.minimum(d, f32(1 + u) / f32(10 + u))
+                    w = f32(1.0) - d
+                u += 1
+        self._rec[0], self._rec[1], self._rec[2] = u, c, seen
+        self._rec.view(torch.float32)[3] = w
+        w = float(w)
+        if w == 1.0:
+            self.avg.copy_(self.arena.param)
+        elif w != 0.0:
+            self.avg.add_((self.arena.param - self.avg).mul_(w))
+
+    # -- evaluation under the average -----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def swap(self):
+        """Exchange ``arena.param`` and ``avg`` (and rewrite the 16-bit shadow); flips ``is_applied``."""
+        ar = self.arena
+        if ar.device.type != 'cuda':
+            live = ar.param.clone()
+            ar.param.copy_(self.avg)
+            self.avg.copy_(live)
+            ar.refresh_shadow()
+        elif ar.numel:
+            lib = _lib.load()
+            with ops.TIMER.span('k_average_swap'):
+                check(lib.mbv_weight_average_swap(ar.param.data_ptr(), self.avg.data_ptr(),
+                                                  0 if ar.shadow is None else ar.shadow.data_ptr(), ar.shadow_flag, ar.numel,
+                                                  torch.cuda.current_stream(ar.device).cuda_stream),
+                      'mbv_weight_average_swap')
+            ops.note_parameters_changed()
+        self.is_applied = not self.is_applied
+
+    @contextlib.contextmanager
+    def applied(self):
+        """``with average.applied():`` — the module computes with the averaged weights inside, with the live ones after, also
+        when the body raises."""
+        self._refuse_applied('applied()')
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    # -- checkpoint -----------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        self._refuse_applied('state_dict()')
+        u, c, seen = (int(v) for v in self._rec[:3].tolist())
+        return dict(kind=self.KIND, avg=self.avg, updates=u, calls=c, seen=seen, mode=self.mode, decay=self.decay,
+                    warmup=self.warmup, every=self.every)
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        self._refuse_applied('load_state_dict()')
+        if sd.get('kind') != self.KIND:
+            raise ValueError(f"state of kind {sd.get('kind')!r} cannot be loaded into {type(self).__name__}")
+        if tuple(sd['avg'].shape) != tuple(self.avg.shape):
+            raise ValueError(f"averaged weights of {tuple(sd['avg'].shape)} elements, the arena has {tuple(self.avg.shape)}")
+        self._set_hyper(sd.get('mode', self.mode), sd.get('decay', self.decay), sd.get('warmup', self.warmup),
+                        sd.get('every', self.every))
+        self.avg.copy_(sd['avg'])
+        self._rec.copy_(torch.tensor([int(sd['updates']), int(sd['calls']), int(sd['seen']), 0], dtype=torch.int32))

@@ -97,3 +97,22 @@ __device__ __forceinline__ void sgd_one(float& p, float g, float& buf, const Sgd
   g = a.nesterov ? g + a.momentum * buf : buf;              // grad.add(buf, alpha=momentum) / grad = buf
   p -= a.lr * g;                                            // param.add_(grad, alpha=-lr)
 }
+
+// ---- K43: weight averaging over the arena (optim_flat.hip) ---------------------------------------------------------------
+// The device record of a WeightAverage (= mbv_weight_average_state, maskbev_hip.h): the counters a captured update advances
+// itself, and the blend weight its tick leaves for the streaming pass that follows it on the stream.
+struct AverageRec {
+  int updates;                     // u: averaging updates applied so far
+  int calls;                       // c: applied optimizer steps seen
+  int seen;                        // the LossScaler's applied_steps at the last call
+  float weight;                    // w of this call; 0 = nothing to do
+};
+static_assert(sizeof(AverageRec) == 16, "the record is four words");
+
+// avg.lerp_(p, w) written out: three roundings, and w == 1 takes p itself (avg + (p - avg) need not be p)
+__device__ __forceinline__ float average_one(float avg, float p, float w) {
+#pragma clang fp contract(off)
+  if (w == 1.0f) return p;
+  const float d = p - avg;
+  return avg + w * d;
+}

@@ -32,10 +32,11 @@ static inline bool misaligned16(const void* a, const void* b = nullptr, const vo
            reinterpret_cast<size_t>(d)) & 15) != 0;
 }
 
-// blocks of 256 threads for n4 items of one thread-iteration each: capped at kMaxBlocks, at least one (the ragged tail)
-static inline unsigned stream_blocks(long n4) {
+// blocks of 256 threads for n4 items of one thread-iteration each: capped at `cap` (kMaxBlocks unless a kernel has measured
+// another), at least one (the ragged tail)
+static inline unsigned stream_blocks(long n4, long cap = kMaxBlocks) {
   long blocks = (n4 + 255) / 256;
-  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+  if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return (unsigned)blocks;
 }

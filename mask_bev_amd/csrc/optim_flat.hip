@@ -15,7 +15,14 @@
 //                            loss_scale / clip_coefficient the passes above take in place of the loss scale, the total norm,
 //                            the coefficient and the norm of every range.  The gradient itself is never rewritten.
 //
-// A LAMB step is 28 + 18 = 46 B/elem against k_adamw's 34; SGD is 26; clipping adds 4.  The per-tensor norms of LAMB come from a CHUNK TABLE
+//   mbv_weight_average_update   K43: two launches.  One thread decides from a 16-byte device record whether this call blends
+//                               and with what weight (EMA with optional decay warm-up, or the equal-weight running mean; an
+//                               overflowed fp16 step, read off K11's applied-step count, and the steps between `every` do
+//                               not); then one pass reads param and avg (8 B/elem) and writes avg (4 B/elem), or returns at
+//                               once on weight 0.  param, grad and the shadow are not touched.
+//   mbv_weight_average_swap     K43: param <-> avg in one pass (16 B/elem) that also rewrites the shadow (2 B/elem).
+//
+// A LAMB step is 28 + 18 = 46 B/elem against k_adamw's 34; SGD is 26; clipping adds 4; averaging adds 12.  The per-tensor norms of LAMB come from a CHUNK TABLE
 // built once by the host: every parameter's padded arena range is cut into chunks of kChunk = 4096 elements (a chunk never
 // straddles two parameters; the last chunk of a parameter is shorter, a multiple of 64).  One block works on one chunk at a
 // time, so a chunk's two sums are taken in one fixed order whatever the grid — no float atomics, bit-reproducible, replayable.
@@ -436,6 +443,89 @@ __global__ void __launch_bounds__(256) k_grad_clip_coef(const double* __restrict
   for (int i = 3 + kNormRanges; i < 16; ++i) rec[i] = 0.f;
 }
 
+// ---- K43: EMA / running mean of the parameters -----------------------------------------------------------------------------
+enum { kAverageEma = 0, kAverageMean = 1 };                // = MBV_AVERAGE_EMA / MBV_AVERAGE_MEAN
+
+// The grid cap of K43's two streams: 256 blocks per CU, not kMaxBlocks' 16.  Measured at the bench arena (200.8 M elements,
+// profiles/k43, scratch/ubench/k43_blend_grid.hip): the blend under the 4096-block cap runs 48 grid-stride trips per thread
+// and reaches 4.6 - 4.7 TB/s of model bytes, 0.76 of k_sgd in the same run; the same kernel under a 65536-block cap (3 trips)
+// reaches 6.3 TB/s, and with one float4 per thread 6.4.  More loads per thread in flight (2 or 4 float4 rows) and plain
+// instead of non-temporal accesses changed nothing under the low cap.  The older kernels keep kMaxBlocks: their launches
+// are not this change's to alter.
+constexpr long kAverageMaxBlocks = 256 * 256;
+
+// The decision of one update, by one thread, in a launch of its own: the streaming pass behind it on the stream reads the
+// weight this leaves (one kernel in which a block advances the counters while others still read them would race).  With
+// K11's applied-step count the step counts only if the count moved since the last call: k_loss_scale_update has cleared the
+// overflow flag by now, but it does not advance the count on an overflow.
+__global__ void k_average_tick(AverageRec* __restrict__ rec, const int* __restrict__ applied_steps, int mode, float decay,
+                               int warmup, int every) {
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  AverageRec r = *rec;
+  bool applied = true;
+  if (applied_steps) {
+    const int a = *applied_steps;
+    applied = a != r.seen;
+    r.seen = a;
+  }
+  r.weight = 0.f;
+  if (applied) {
+    r.calls += 1;
+    if (r.calls % every == 0) {
+      if (mode == kAverageMean) {
+        r.weight = 1.0f / (float)(r.updates + 1);
+      } else {
+        float d = decay;
+        if (warmup) d = fminf(decay, (float)(1 + r.updates) / (float)(10 + r.updates));
+        r.weight = 1.0f - d;
+      }
+      r.updates += 1;
+    }
+  }
+  *rec = r;
+}
+
+// avg = avg + w (p - avg) over n elements, k_sgd's frame; reads param and avg, writes avg (12 B/elem); w == 0 costs the launch only
+__global__ void __launch_bounds__(256) k_average_blend(const float* __restrict__ param, float* __restrict__ avg, long n,
+                                                       const AverageRec* __restrict__ rec) {
+  const float w = rec->weight;          // uniform: one scalar load
+  if (w == 0.f) return;
+  const long n4 = n >> 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long i = first; i < n4; i += stride) {
+    const f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + i);
+    f4 a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(avg) + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = average_one(a[k], p[k], w);
+    __builtin_nontemporal_store(a, reinterpret_cast<f4*>(avg) + i);
+  }
+  const long t = (n4 << 2) + first;     // ragged tail (< 4 elements)
+  if (t < n) avg[t] = average_one(avg[t], param[t], w);
+}
+
+// param <-> avg, and the 16-bit shadow of what param now holds: 16 B/elem (+ 2 B); bits are moved, so twice is the identity
+__global__ void __launch_bounds__(256) k_average_swap(float* __restrict__ param, float* __restrict__ avg,
+                                                      unsigned short* __restrict__ shadow, int shadow_kind, long n) {
+  const long n4 = n >> 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long i = first; i < n4; i += stride) {
+    const f4 p = __builtin_nontemporal_load(reinterpret_cast<const f4*>(param) + i);
+    const f4 a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(avg) + i);
+    __builtin_nontemporal_store(a, reinterpret_cast<f4*>(param) + i);
+    __builtin_nontemporal_store(p, reinterpret_cast<f4*>(avg) + i);
+    if (shadow) store_shadow4(shadow, i, a, shadow_kind);
+  }
+  const long t = (n4 << 2) + first;     // ragged tail (< 4 elements)
+  if (t < n) {
+    const float p = param[t], a = avg[t];
+    param[t] = a; avg[t] = p;
+    if (shadow) shadow[t] = shadow_bits(a, shadow_kind);
+  }
+}
+
 // one thread fills a parameter group's hyper-parameter block (plain stores): stream-ordered in front of the launches that read it
 __global__ void k_adam_args_write(AdamDev* __restrict__ dst, AdamDev v) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
@@ -655,6 +745,36 @@ extern "C" int mbv_grad_clip_coef(const double* partials, int32_t n_partials, co
   if (r.n > 0 && n_partials > 0 && (!partials || (reinterpret_cast<size_t>(partials) & 7))) return MBV_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_grad_clip_coef, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, r, (double)max_norm,
                      (double)grad_scale, loss_scale, rec);
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+// K43: one averaging update = the tick and the streaming pass, in that order on the stream
+extern "C" int mbv_weight_average_update(const float* param, float* avg, int64_t n, mbv_weight_average_state* state,
+                                         const int32_t* applied_steps, int32_t mode, float decay, int32_t warmup,
+                                         int32_t every, void* stream) {
+  if (n < 0 || !param || !avg || !state || param == avg) return MBV_ERR_BAD_ARG;
+  if (mode != kAverageEma && mode != kAverageMean) return MBV_ERR_BAD_ARG;
+  if (!(decay >= 0.f && decay < 1.f) || every < 1) return MBV_ERR_BAD_ARG;                 // NaN included
+  if ((reinterpret_cast<size_t>(state) & 3) || (reinterpret_cast<size_t>(applied_steps) & 3)) return MBV_ERR_BAD_ARG;
+  if (n == 0) return MBV_OK;
+  if (misaligned16(param, avg)) return MBV_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_average_tick, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<AverageRec*>(state),
+                     applied_steps, mode, decay, warmup, every);
+  MBV_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_average_blend, dim3(stream_blocks(n >> 2, kAverageMaxBlocks)), dim3(256), 0, (hipStream_t)stream, param, avg, (long)n,
+                     reinterpret_cast<const AverageRec*>(state));
+  MBV_CHECK_LAUNCH();
+  return MBV_OK;
+}
+
+extern "C" int mbv_weight_average_swap(float* param, float* avg, void* shadow, int32_t shadow_dtype, int64_t n,
+                                       void* stream) {
+  if (n < 0 || !param || !avg || param == avg) return MBV_ERR_BAD_ARG;
+  if (n == 0) return MBV_OK;
+  if (misaligned16(param, avg) || bad_shadow(shadow, shadow_dtype)) return MBV_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_average_swap, dim3(stream_blocks(n >> 2, kAverageMaxBlocks)), dim3(256), 0, (hipStream_t)stream, param, avg,
+                     reinterpret_cast<unsigned short*>(shadow), shadow_dtype, (long)n);
   MBV_CHECK_LAUNCH();
   return MBV_OK;
 }

@@ -66,10 +66,13 @@ class GraphedTrainStep:
     """``step(batch) -> loss`` with the static-shape part of the step replayed from a HIP graph."""
 
     def __init__(self, module: MaskBevModule, optimizer: torch.optim.Optimizer, example_batch, warmup_iters: int = 3,
-                 reducer=None):
+                 reducer=None, average=None):
         self.m = module
         self.opt = optimizer
         self.reducer = reducer
+        # K43: a WeightAverage updated right behind the optimizer step.  Both fused arms below stay on: they finish their
+        # parameter updates inside the backward, before that point
+        self.average = average
         self.trace = None       # a list -> every step appends [(mark, host time, bytes), ...] (bench.py --dry-run-collectives)
         scans, labels, masks, _ = module._unpack(example_batch)
         dev = labels.device
@@ -281,6 +284,8 @@ class GraphedTrainStep:
         if self._mx_fused:
             self.opt.note_matrices_applied(self._mx_fused)  # the replays updated these: cut out of the optimizer pass
         self.opt.step()
+        if self.average is not None:
+            self.average.update()
         if self.arena is None:
             for p in self.m._encoder.parameters():         # graph-owned gradients are overwritten by the replay
                 p.grad = None

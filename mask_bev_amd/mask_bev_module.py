@@ -94,6 +94,14 @@ class MaskBevModule(_Base):
         # build extension under Lightning's name (Trainer(gradient_clip_val=...)): clip the gradient's global 2-norm, None = off
         clip = kwargs.get('gradient_clip_val', None)
         self._gradient_clip_val = None if clip is None else float(clip)
+        # build extension (K43): an averaged copy of the arena's weights, None = off; see make_weight_average
+        mode = kwargs.get('weight_average', None)
+        if mode not in (None, 'ema', 'mean'):
+            raise ValueError(f"weight_average must be 'ema', 'mean' or absent, got {mode!r}")
+        self._weight_average = mode
+        self._weight_average_args = dict(decay=float(kwargs.get('weight_average_decay', 0.9999)),
+                                         warmup=bool(kwargs.get('weight_average_warmup', True)),
+                                         every=int(kwargs.get('weight_average_every', 1)))
 
         voxel_size_z = z_range[1] - z_range[0]
         head_in_dims = [2 ** i * backbone_embed_dim for i in range(4)]
@@ -160,6 +168,18 @@ class MaskBevModule(_Base):
         bf16 / fp32 compute.  The matching un-scaling happens inside the flat optimizer's ``step()``."""
         scaler = getattr(self, '_loss_scaler', None)
         return loss if scaler is None else scaler.scale_loss(loss)
+
+    def make_weight_average(self):
+        """Build extension (K43): a :class:`~mask_bev_amd.arena.WeightAverage` over the module's arena as the keywords
+        ``weight_average`` (``'ema'`` | ``'mean'``), ``weight_average_decay``, ``weight_average_warmup`` and
+        ``weight_average_every`` describe it, following the module's loss scaler when it has one (fp16 compute: an
+        overflowed step is not averaged).  ``None`` when the feature is off or the parameters are not in an arena.  Module
+        buffers (the PFN BatchNorm's running statistics) are not averaged."""
+        if getattr(self, '_weight_average', None) is None or getattr(self, '_arena', None) is None:
+            return None
+        from .arena import WeightAverage
+        return WeightAverage(self._arena, mode=self._weight_average, scaler=getattr(self, '_loss_scaler', None),
+                             **self._weight_average_args)
 
     def _flat_optimizer(self):
         from .arena import FlatAdam, FlatLamb, FlatSGD

@@ -500,6 +500,10 @@ MODELS: Dict[str, Callable[[tuple], Work]] = {
     'mbv_grad_norm_partials': lambda a: ('k_grad_norm_partials', 'hbm',
                                          4.0 * sum(int(a[3][i]) for i in range(_i(a[4]))) + 8.0 * _i(a[6]), 0.0),
     'mbv_grad_clip_coef': lambda a: ('k_grad_clip_coef', 'hbm', 8.0 * _i(a[1]) + 64.0, 0.0),
+    # K43.  (param, avg, n, state, ...): param and avg read, avg written — an UPPER bound, the host cannot know whether this
+    # call's weight is 0; (param, avg, shadow, shadow_dtype, n, stream): both read, both written, + the 16-bit shadow.
+    'mbv_weight_average_update': lambda a: ('k_average_blend', 'hbm', _i(a[2]) * 12.0, 0.0),
+    'mbv_weight_average_swap': lambda a: ('k_average_swap', 'hbm', _i(a[4]) * (16.0 + (2.0 if _i(a[2]) else 0.0)), 0.0),
 }
 
 

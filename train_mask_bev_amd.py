@@ -33,6 +33,13 @@ files, and saved with ``save_scene_bank: true``), and each batch's instance maps
 ``--build-scene-bank`` writes the banks of the train and validation sequences and exits; ``--build-mask-cache`` [``--overwrite``]
 writes the reference's ``mask_cache/NNNNNN.npy`` files from them and exits.
 
+``weight_average: ema | mean`` (or ``--weight-average``; K43, ``weight_average_decay``, ``weight_average_warmup``,
+``weight_average_every``, ``weight_average_start_epoch``) keeps an averaged copy of the arena's weights, updated on the device
+behind every optimizer step from the start epoch on: validation — and so the monitored ``val_loss`` and the choice of the best
+checkpoint — runs on the averaged weights, every checkpoint gains a ``weight_average`` entry beside the live ``state_dict``,
+and ``--test`` loads the averaged weights when the key is set and the checkpoint has the entry, saying so in one
+``weight average: ..`` line.  Module buffers are not averaged.  Without the key nothing changes.
+
 ``--test`` extras: ``dataset: kitti`` prints the Car BEV AP block, with ``kitti_3d: true`` (optional ``kitti_3d_extent:
 [q_lo, q_hi]``) also the ``3d   AP:`` lines from heights lifted out of the scans (K31, K26b); ``dataset: semantic-kitti`` with
 ``--write-labels DIR`` writes the per-point instance labels of every validated scan (K31) to
@@ -61,6 +68,7 @@ cell, the predicted instances coloured by query — by track id with ``track_ins
 cache's instances where the file exists), ``DIR/NNNNNN.png`` for ``dataset: kitti`` (with the predicted and the label boxes).
 """
 import argparse
+import contextlib
 import os
 import pathlib
 import re
@@ -85,17 +93,22 @@ def get_metric_from_name(path, regex):
     return float(regex.search(str(path)).group(1))
 
 
-def save_checkpoint(model, optimizer, path, epoch, metric_name, metric):
-    torch.save({'state_dict': model.state_dict(), 'hyper_parameters': dict(getattr(model, 'hparams', {})),
-                'optimizer_states': [optimizer.state_dict()], 'epoch': epoch, metric_name: metric}, path)
+def save_checkpoint(model, optimizer, path, epoch, metric_name, metric, average=None):
+    ckpt = {'state_dict': model.state_dict(), 'hyper_parameters': dict(getattr(model, 'hparams', {})),
+            'optimizer_states': [optimizer.state_dict()], 'epoch': epoch, metric_name: metric}
+    if average is not None:
+        # 'state_dict' stays the LIVE weights, which the optimizer state belongs to; the averaged ones travel beside them
+        ckpt['weight_average'] = average.state_dict()
+    torch.save(ckpt, path)
 
 
-def validate(model, val, epoch, device, world):
+def validate(model, val, epoch, device, world, average=None):
     if val is None:
         return None
     model.eval()
     tot = 0.0
-    with torch.no_grad():
+    # with a weight average (K43) the monitored val_loss is the averaged weights': swapped in for the pass, back after it
+    with torch.no_grad(), (average.applied() if average is not None else contextlib.nullcontext()):
         for i in range(len(val)):
             tot += float(model.validation_step(val.batch(epoch, i), i))
     model.train()
@@ -106,7 +119,8 @@ def validate(model, val, epoch, device, world):
     return float(v)
 
 
-def train(args, config, model, optimizer, scheduler, reducer, data, val, device, rank, world, checkpoint_folder_path, check_metric):
+def train(args, config, model, optimizer, scheduler, reducer, data, val, device, rank, world, checkpoint_folder_path, check_metric,
+          average=None):
     model.train()
     if rank == 0:
         checkpoint_folder_path.mkdir(parents=True, exist_ok=True)
@@ -118,8 +132,16 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
     # a flat optimizer with clipping (K41) keeps the last step's gradient norm and clip coefficient on the device
     clipping = getattr(optimizer, 'max_grad_norm', None) is not None
     clip_val = config.get('gradient_clip_val', None)
+    # a weight average (K43) starts at `weight_average_start_epoch` (SWA: average the tail of the run only): before it there
+    # are no updates, validation reads the live weights and the checkpoints carry no average
+    average_start, averaging = int(config.get('weight_average_start_epoch', 0)), None
     for epoch in range(args.max_epochs):
         model.current_epoch = epoch
+        if average is not None and epoch == average_start:
+            average.reset()
+            averaging = average
+            if graphed is not None:
+                graphed.average = average
         t0, loss_sum, n_steps = time.perf_counter(), None, 0
         clip_stats = ClipStats()
         n_batches = int(len(data) * float(config.get('limit_train_batches', 1.0))) if isinstance(
@@ -131,7 +153,7 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
                     from mask_bev_amd.graph import GraphedTrainStep
                     if reducer is not None:
                         reducer.no_sync(True)
-                    graphed = GraphedTrainStep(model, optimizer, batch, reducer=reducer)
+                    graphed = GraphedTrainStep(model, optimizer, batch, reducer=reducer, average=averaging)
                 loss = graphed.step(batch)
             else:
                 if reducer is not None:
@@ -142,6 +164,8 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
                     reducer.finish(optimizer)
                 clip_gradients(optimizer, model.parameters(), clip_val)     # per-tensor optimizers; a flat one clips itself
                 optimizer.step()
+                if averaging is not None:
+                    averaging.update()
                 optimizer.zero_grad(set_to_none=False)
             # accumulate on the device: the graphed step returns ONE static tensor that every replay overwrites,
             # so keeping references would average N aliases of the last batch's loss (the reference monitors the
@@ -157,7 +181,7 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
         if world > 1:
             from mask_bev_amd.ddp import reduce_scalars
             train_loss = reduce_scalars({'train_loss': torch.tensor(train_loss, device=device)})['train_loss']
-        val_loss = validate(model, val, epoch, device, world)
+        val_loss = validate(model, val, epoch, device, world, averaging)
         monitored = val_loss if (check_metric == 'val_loss' and val_loss is not None) else train_loss
         if isinstance(scheduler, torch.optim.lr_scheduler.ReduceLROnPlateau):
             scheduler.step(train_loss)                          # monitor 'train_loss', interval 'epoch'
@@ -169,14 +193,14 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
                   + (f' val_loss {val_loss:.6f}' if val_loss is not None else '')
                   + (' ' + clip_stats.line(n_steps) if clipping else '')
                   + f'  {n_steps * int(config.get("batch_size", 1)) * world / dt:.1f} scans/s', flush=True)
-            save_checkpoint(model, optimizer, checkpoint_folder_path / 'last.ckpt', epoch, check_metric, monitored)
+            save_checkpoint(model, optimizer, checkpoint_folder_path / 'last.ckpt', epoch, check_metric, monitored, averaging)
             if monitored < best:
                 best = monitored
                 for old in checkpoint_folder_path.glob(f'{exp_name}-epoch=*'):
                     old.unlink()
                 save_checkpoint(model, optimizer, checkpoint_folder_path /
                                 f'{exp_name}-epoch={epoch:02d}-{check_metric}={monitored:.6f}.ckpt', epoch,
-                                check_metric, monitored)
+                                check_metric, monitored, averaging)
         if monitored < es_best:
             es_best, es_wait = monitored, 0
         else:
@@ -190,6 +214,24 @@ def train(args, config, model, optimizer, scheduler, reducer, data, val, device,
             break
     if graphed is not None:
         graphed.close()
+
+
+def load_averaged_weights(model, average, checkpoint_path, rank):
+    """--test with `weight_average` set: the checkpoint's averaged weights (K43) take the place of the live ones in the model,
+    when the checkpoint has them.  Buffers stay the live ones.  Prints what was loaded in one line."""
+    if average is None:
+        return False
+    entry = torch.load(checkpoint_path, map_location='cpu', weights_only=False).get('weight_average')
+    if entry is None:
+        return False
+    average.load_state_dict(entry)
+    with torch.no_grad():
+        model._arena.param.copy_(average.avg)
+    model._arena.refresh_shadow()
+    if rank == 0:
+        print(f'weight average: {average.mode}, ' + (f'decay {average.decay:g}, ' if average.mode == 'ema' else '')
+              + f'{int(average.num_updates)} updates', flush=True)
+    return True
 
 
 def test(args, config, model, val, dataset_name, device, rank, world):
@@ -276,6 +318,8 @@ def build_parser():
     parser.add_argument('--compute-dtype', default=None, choices=[None, 'fp32', 'bf16', 'fp16'])
     parser.add_argument('--gradient-clip-val', type=float, default=None,
                         help='clip the global 2-norm of the gradient at this value (overrides the YAML gradient_clip_val)')
+    parser.add_argument('--weight-average', default=None, choices=['ema', 'mean'],
+                        help='keep an averaged copy of the weights, validate and checkpoint it (overrides the YAML weight_average)')
     parser.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly (no HIP-graph replay)')
     parser.add_argument('--checkpoint-root', default='checkpoints')
     parser.add_argument('--build-object-bank', action='store_true',
@@ -317,6 +361,8 @@ def main(argv=None):
         config['compute_dtype'] = args.compute_dtype
     if args.gradient_clip_val is not None:
         config['gradient_clip_val'] = args.gradient_clip_val
+    if args.weight_average is not None:
+        config['weight_average'] = args.weight_average
 
     limit_val_batches = config.get('limit_val_batches', 1.0)
     check_metric = 'val_loss' if (limit_val_batches > 0 and not args.synthetic
@@ -364,6 +410,7 @@ def main(argv=None):
     model.flatten_parameters()         # fp16 compute: this also creates the device-side loss scaler
     opt_cfg = model.configure_optimizers()
     optimizer, scheduler = opt_cfg['optimizer'], opt_cfg['lr_scheduler']
+    average = model.make_weight_average()      # None unless `weight_average: ema | mean` (K43)
 
     reducer = None
     if world > 1:
@@ -397,8 +444,9 @@ def main(argv=None):
 
     if is_training:
         train(args, config, model, optimizer, scheduler, reducer, data, val, device, rank, world, checkpoint_folder_path,
-              check_metric)
+              check_metric, average)
     if is_testing:
+        load_averaged_weights(model, average, config['checkpoint'], rank)
         test(args, config, model, val, dataset_name, device, rank, world)
     if world > 1:
         dist.destroy_process_group()
