@@ -1,6 +1,6 @@
 """Shared pieces of the per-kernel float64 suites (test_k4_paths_gpu.py, test_k6_paths_gpu.py, test_k7_paths_gpu.py, and the
 encoder front: test_k2_paths_gpu.py — PillarFeatureNet, with its dense reference tests/pfn_ref.py — and test_k3_paths_gpu.py —
-scatter + LayerNorm; and the normalisation kernels: test_k12_paths_gpu.py, test_k18_paths_gpu.py, with tests/norm_ref.py): the relative max-norm error, the printed ``err … bar …`` line, roundings of a float64 tensor to a 16-bit
+scatter + LayerNorm; and the normalisation kernels: test_k12_paths_gpu.py, test_k18_paths_gpu.py, with tests/norm_ref.py; and the decoder's row chains: test_k19_paths_gpu.py, with tests/decoder_ref.py): the relative max-norm error, the printed ``err … bar …`` line, roundings of a float64 tensor to a 16-bit
 type and the project's f32 bar."""
 import torch
 
